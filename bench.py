@@ -13,11 +13,17 @@ update ON THE HOST (north star), next pose back to the GPU.
           32-double record per iteration over RCCL (library-owned communicator); strong scaling.  `python bench.py --gpus N`
           starts its own N rank processes (no GPU is touched by the parent); under torch.distributed.run it is one rank.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-The timed region (barrier + synchronize, K steps, synchronize + barrier, MAX over ranks) is repeated --repeats times from the
-same start pose; ms_per_step is the MEDIAN repetition (p10 / p90 beside it).  Rank 0 prints ONE JSON line.
-Nothing here reads /root/reference.
+A plain run does what the headline needs and nothing else: set up, pre-warm, pick the host CPU, W warm-up steps, SETTLE_REGIONS
+untimed regions, ONE timed region of exactly K steps (barrier + synchronize, K steps, synchronize + barrier, MAX over ranks), the
+outputs, the JSON line.
+--full adds everything reported beside the headline: --repeats timed regions (default 50; ms_per_step is then the MEDIAN
+repetition, p10 / p90 beside it) with HIP events on some of them (roofline), the untuned figure, the pose against the CPU oracle,
+the CPU baseline, the bandwidth-bound and reference-API kernels, fp64, the other legs and, for N > 1, the collectives timed beside
+the headline's.  --dump-outputs DIR writes the last timed step's result (the pose a caller of rpe_gn_refine receives, with the
+step norm and cost where the path returns them) as DIR/<name>.npy; the inputs are seeded, the same on every run.
+Rank 0 prints ONE JSON line.  Nothing here reads the reference project.
 """
 from __future__ import annotations
 
@@ -39,6 +45,8 @@ BYTES_PER_CORR = 24 + 2      # Xw 12 + Xc 12 + short inlier mask 2 (SURVEY.md 8d
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 THRE_3D = 0.2                # Parameters.yml thre_3d
 PROFILE_INDEX = "profiles/r06_bench_profiles.json"   # rocprofv3 / PMC summaries of THIS command, one entry per steps-per-launch
+PREWARM_MAX_STEPS = 2000     # steps per launch of the pre-warm, of each host-CPU trial and of the settle regions (the default --steps)
+SETTLE_REGIONS = 24          # untimed regions right before a plain run's one timed region
 
 
 # ------------------------------------------------------------------------------------------------ launcher (no GPU, no torch)
@@ -148,6 +156,18 @@ def rot_err(Ra, Rb):
     return math.atan2(s, (np.trace(D) - 1) / 2)
 
 
+def dump_outputs(out_dir: str, pose, last: dict):
+    """--dump-outputs: what the timed path returned after its last step, as float64 .npy files -- pose.npy (12: R row-major, then t,
+    as rpe_gn_refine writes it back), step_norm.npy (|delta| of the last step) and, where the path returns it, cost.npy (the last
+    step's cost).  The inputs are seeded (make_shard, initial_pose), so two builds run with the same arguments can be compared."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"pose": np.asarray(pose, np.float64).reshape(12)}
+    arrays.update({k: np.array([v], np.float64) for k, v in last.items() if v is not None})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 ORIG_AFFINITY = None
 
 
@@ -189,7 +209,11 @@ def cpu_baseline(sc, seconds: float):
         # the bench's host thread is pinned to one CPU; the worker threads of the all-core legs get the process's original CPU set back
         pinned = os.sched_getaffinity(0)
         wide = ORIG_AFFINITY or pinned
-        threads = max(1, min(64, len(wide)))
+        try:   # a job given fewer CPUs than it can see says so in OMP_NUM_THREADS
+            granted = int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0])
+        except ValueError:
+            granted = 64
+        threads = max(1, min(64, len(wide), granted))
 
         def all_cores(f):
             os.sched_setaffinity(0, wide)
@@ -282,19 +306,19 @@ def percentile(xs, q):
     return xs[min(len(xs) - 1, max(0, int(round(q * (len(xs) - 1)))))]
 
 
-def collective_plan(world: int, want: str, share_gpu: bool) -> dict:
+def collective_plan(world: int, want: str, share_gpu: bool, full: bool = True) -> dict:
     """What `bench.py --gpus N` does about the per-iteration all-reduce, decided BEFORE any GPU is touched (the dry-run launcher test
     prints it).  The north star's collective -- one RCCL all-reduce of the normal-equation scalars per Gauss-Newton iteration over xGMI,
-    here on a communicator the library owns -- is the headline whenever RCCL can be set up; other ways of adding the 32-double records
-    are timed beside it.  RPE_BENCH_COLLECTIVE = auto (default: RCCL headline, host-side exchange beside) | rccl | host |
-    p2p (the in-kernel mailboxes as headline) | auto_p2p (RCCL headline, mailboxes beside)."""
+    here on a communicator the library owns -- is the headline whenever RCCL can be set up; with --full (`full`), other ways of adding
+    the 32-double records are timed beside it.  RPE_BENCH_COLLECTIVE = auto (default: RCCL headline, host-side exchange beside) | rccl |
+    host | p2p (the in-kernel mailboxes as headline) | auto_p2p (RCCL headline, mailboxes beside)."""
     if want not in ("auto", "rccl", "host", "p2p", "auto_p2p"):
         sys.exit(f"bench.py: unknown RPE_BENCH_COLLECTIVE={want}")
     if world <= 1:
         return {"headline": "none", "timed_beside": [], "rccl_init": False, "rccl_ranks_expected": 0, "distinct_gpu_check": False,
                 "scaling": "weak", "weak_scaling_extra": False}
     headline = {"auto": "rccl", "rccl": "rccl", "host": "host", "p2p": "p2p", "auto_p2p": "rccl"}[want]
-    beside = {"auto": ["host"], "rccl": [], "host": [], "p2p": [], "auto_p2p": ["p2p"]}[want]
+    beside = {"auto": ["host"], "rccl": [], "host": [], "p2p": [], "auto_p2p": ["p2p"]}[want] if full else []
     rccl_init = want != "host" and not (want == "p2p" and os.environ.get("RPE_BENCH_STRICT_COLLECTIVE") == "1")
     return {"headline": headline, "timed_beside": beside, "rccl_init": rccl_init, "rccl_ranks_expected": world if rccl_init else 0,
             "fallback": "host-side exchange, then torch.distributed, if RCCL cannot be set up", "distinct_gpu_check": not share_gpu,
@@ -521,7 +545,7 @@ def worker(args, affinity):
             print(json.dumps({"dry_run": True, "rank": rank, "local_rank": local_rank, "world": world, "gpus": args.gpus, "steps": args.steps,
                               "master": os.environ.get("MASTER_ADDR", "") + ":" + os.environ.get("MASTER_PORT", ""),
                               "collective_plan": collective_plan(world, os.environ.get("RPE_BENCH_COLLECTIVE", "auto"),
-                                                                 os.environ.get("RPE_BENCH_SHARE_GPU") == "1")}), flush=True)
+                                                                 os.environ.get("RPE_BENCH_SHARE_GPU") == "1", args.full)}), flush=True)
         sys.exit(int(os.environ.get("RPE_BENCH_DRY_EXIT", "0")) if rank == int(os.environ.get("RPE_BENCH_DRY_EXIT_RANK", "-1")) else 0)
     import ctypes as C
     import numpy as np
@@ -593,7 +617,7 @@ def worker(args, affinity):
         # can be set up; the host-side exchange (and, on request, the in-kernel peer-to-peer mailboxes) are timed in the same run and
         # reported beside it in config.collective_step_us.
         want = os.environ.get("RPE_BENCH_COLLECTIVE", "auto")
-        plan = collective_plan(world if world > 1 else (2 if force_dist else 1), want, os.environ.get("RPE_BENCH_SHARE_GPU") == "1")
+        plan = collective_plan(world if world > 1 else (2 if force_dist else 1), want, os.environ.get("RPE_BENCH_SHARE_GPU") == "1", args.full)
         if world == 1 and force_dist:   # the collective path exercised with one rank (tests)
             plan.update(rccl_ranks_expected=1 if plan["rccl_init"] else 0, distinct_gpu_check=False)
         p2p = native = rccl_ok = hostex = False
@@ -657,7 +681,7 @@ def worker(args, affinity):
                         print("[bench] the RCCL step's record differs from the all-reduced local records: communicator dropped", file=sys.stderr, flush=True)
                     ctx.comm_destroy()
                     rccl_ok = False
-            if rccl_ok:
+            if rccl_ok and args.full:
                 coll_times["rccl_us"] = timed(400) * 1e6   # rpe_gn_steps_dist = kernel + ncclAllReduce of its run records + publish kernel per step
                 # ... and the same steps chained on the device (rpe_gn_steps_dist_device: solve + exp-map in the kernels, the host enqueues
                 # 400 x {kernel, ncclAllReduce} and waits once) -- timed beside: the headline keeps the exp-map on the host (north star)
@@ -676,7 +700,8 @@ def worker(args, affinity):
                     ctx.p2p_destroy()
                     p2p = False
             if p2p:
-                coll_times["p2p_us"] = timed(400) * 1e6
+                if args.full:
+                    coll_times["p2p_us"] = timed(400) * 1e6
                 if plan["headline"] != "p2p":
                     dist.barrier()
                     ctx.p2p_destroy()   # timed beside; the headline runs on RCCL
@@ -705,7 +730,8 @@ def worker(args, affinity):
                         print(f"[bench] rank {rank}: refinement over the host-side exchange failed: {e}", file=sys.stderr, flush=True)
                         return False
                 good = all_ok(refine_ok(200))   # the ranks agree after every phase, so they always enter the same torch collective next
-                if good:
+                host_us = None
+                if good and args.full:
                     dist.barrier()
                     t0_ = time.perf_counter()
                     ran = refine_ok(400)
@@ -752,6 +778,8 @@ def worker(args, affinity):
         _args = (ctx._h, 1, _kinds.ctypes.data_as(C.c_void_p), None, L.USE_MASK, _pose.ctypes.data_as(C.c_void_p))
         _tail = (C.c_double(0.0), C.byref(_its), C.byref(_stepn), C.byref(_cost))
 
+        last = {}   # what the path returned besides the pose in its last call (--dump-outputs)
+
         def run_steps(p, k):
             if k <= 0:
                 return p
@@ -759,12 +787,14 @@ def worker(args, affinity):
                 _pose[:] = p
                 L.check(_refine(*_args, k, *_tail))
                 assert _its.value == k
+                last.update(step_norm=_stepn.value, cost=_cost.value)
                 return _pose.copy()
             if native:
-                ctx.gn_steps_dist(L.RES_P2P, p, k, L.USE_MASK)
+                last.update(step_norm=ctx.gn_steps_dist(L.RES_P2P, p, k, L.USE_MASK))
                 return p
             for _ in range(k):
-                p = gn.step(p)[0]
+                p, step_norm, _ = gn.step(p)
+            last.update(step_norm=step_norm)
             return p
 
         # untimed pre-warm, independent of --warmup: the first process on a freshly booted box runs its kernels slower for about a
@@ -773,10 +803,11 @@ def worker(args, affinity):
             pose = run_steps(pose, int(os.environ.get("RPE_BENCH_PREWARM_STEPS", "20000")))   # a FIXED count: every rank issues the same number of collective steps
         else:
             # launches of the TIMED length, so that every launch of the resident kernel in this process serves args.steps iterations
-            # and a rocprofv3 --kernel-trace --stats average over the run is the average timed launch (only the --warmup launch differs)
+            # and a rocprofv3 --kernel-trace --stats average over the run is the average timed launch (only the --warmup launch differs);
+            # at most PREWARM_MAX_STEPS per launch, so that a long timed region does not stretch the pre-warm past its time
             t_pre = time.perf_counter()
             while time.perf_counter() - t_pre < float(os.environ.get("RPE_BENCH_PREWARM_S", "1.5")):
-                pose = run_steps(pose12(R0, t0), args.steps)
+                pose = run_steps(pose12(R0, t0), min(args.steps, PREWARM_MAX_STEPS))
         # which host CPU polls fastest differs from box to box (GPU-local cores usually, the other socket's on some boxes, by 5-10 %).
         # The choice is the LIBRARY's (rpe_tune_host_thread: a few candidates of both kinds, a short refinement each, the calling
         # thread left pinned to the fastest) -- any C++ caller of rpe_gn_refine gets the same with one call or RPE_HOST_CPU=auto.
@@ -784,12 +815,23 @@ def worker(args, affinity):
             try:
                 if ORIG_AFFINITY:
                     os.sched_setaffinity(0, ORIG_AFFINITY)   # every CPU the process may use is a candidate again
-                tune = ctx.tune_host_thread(L.RES_P2P, pose12(R0, t0), flags=L.USE_MASK, steps=args.steps, reps=max(3, min(12, 6000 // args.steps)))
+                tune_steps = min(args.steps, PREWARM_MAX_STEPS)   # every candidate CPU runs reps x tune_steps: bounded like the pre-warm
+                tune = ctx.tune_host_thread(L.RES_P2P, pose12(R0, t0), flags=L.USE_MASK, steps=tune_steps, reps=max(3, min(12, 6000 // tune_steps)))
                 affinity = dict(affinity, pinned=True, cpu=tune["cpu"], tuned_by="rpe_tune_host_thread (library call; RPE_HOST_CPU=auto does the same for any caller)",
                                 calibration_us_per_step={str(k): round(v, 3) for k, v in tune["trials"].items()})
             except Exception as e:  # noqa: BLE001
                 affinity = dict(affinity, calibration_error=repr(e))
         run_steps(pose12(R0, t0), args.warmup)
+        if not args.full:
+            # the first region after the warm-up runs slower than the ones after it (on one box: 7.0-8.6 us per 20-step region
+            # against a median of 6.5-6.8 over 50): a plain run times ONE region, so untimed regions of the same form go first, as
+            # many as stood before the median of --full's 50 (a fixed count: every rank runs the same collectives)
+            for _ in range(SETTLE_REGIONS):
+                if world > 1:
+                    dist.barrier()
+                torch.cuda.synchronize()
+                run_steps(pose12(R0, t0), min(args.steps, PREWARM_MAX_STEPS))
+                torch.cuda.synchronize()
         if os.environ.get("RPE_BENCH_INJECT_LOST_GRID"):   # tests: a workgroup withholds its sums in the timed region's refinements
             ctx.inject_resident_fault(int(os.environ["RPE_BENCH_INJECT_LOST_GRID"]), 0.0)
 
@@ -799,9 +841,10 @@ def worker(args, affinity):
         per_rep_records = (launches_per_rep + time_every - 1) // time_every
         budget = 4096
         # HIP events on a launch are instrumentation with a cost of their own (about 8 us per launch: 0.4 us per step of a 20-step
-        # region): --event-reps of the repetitions carry them (for roofline.avg_launch_us), interleaved with the plain ones
-        timed_reps = max(1, min(args.repeats, args.event_reps, budget // max(per_rep_records, 1)))
-        event_every = max(1, args.repeats // timed_reps)
+        # region): with --full, --event-reps of the repetitions carry them (for roofline.avg_launch_us), interleaved with the plain ones;
+        # a plain run times its steps without them
+        timed_reps = max(1, min(args.repeats, args.event_reps, budget // max(per_rep_records, 1))) if args.full else 0
+        event_every = max(1, args.repeats // max(timed_reps, 1))
         samples, k_cnt, k_total_ms, k_min_ms = [], 0, 0.0, 1e30
         for rep in range(args.repeats):
             timing = rep % event_every == 0 and rep // event_every < timed_reps
@@ -828,7 +871,9 @@ def worker(args, affinity):
                 if cnt:
                     k_min_ms = min(k_min_ms, mn_ms)
                 ctx.timing_enable(0, 1)
-        ev_avg_ms, ev_min_ms = ctx.timing_calibrate(200)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, pose, last)
+        ev_avg_ms, ev_min_ms = ctx.timing_calibrate(200) if args.full else (None, None)
         elapsed = percentile(samples, 0.5)
         res_state1 = ctx.resident_state()
         resident_lost_in_run = res_state1["lost"] - res_state0["lost"]
@@ -836,7 +881,7 @@ def worker(args, affinity):
 
         # where a step's time goes, seen from the host thread (resident loop only): waiting for the GPU vs its own work
         loop_prof = None
-        if not dist_path and hasattr(L.lib(), "rpe_debug_loop_profile"):
+        if args.full and not dist_path and hasattr(L.lib(), "rpe_debug_loop_profile"):
             try:
                 gpu_us, host_us, cnt = C.c_double(0), C.c_double(0), C.c_longlong(0)
                 L.lib().rpe_debug_loop_profile(ctx._h, 1, None, None, None)
@@ -851,7 +896,7 @@ def worker(args, affinity):
 
     # extra on the collective path (every rank takes part): the sharded device-resident loop
     sharded_loop = None
-    if world > 1 and p2p and not args.no_extras:
+    if world > 1 and p2p and args.full and not args.no_extras:
         try:
             K = 500
             ctx.gn_refine_device([(L.RES_P2P, 1.0)], pose12(R0, t0), L.USE_MASK, 50, 0.0)
@@ -869,7 +914,7 @@ def worker(args, affinity):
     # weak-scaling figure beside the strong-scaling headline (every rank takes part): a frame-sized shard (configs[1]: 307 200) on every
     # rank, the same way of adding the records as the headline
     weak = None
-    if world > 1 and not args.no_extras and (hostex or (rccl_ok and not p2p)):
+    if world > 1 and args.full and not args.no_extras and (hostex or (rccl_ok and not p2p)):
         try:
             wn = 307200
             wsc = make_shard(1000 + rank, wn)
@@ -976,8 +1021,9 @@ def worker(args, affinity):
                          "traffic_over_algorithmic": (traffic / bytes_per_launch) if traffic else None,
                          "kernel": kernel_name, "algorithmic_bytes_per_launch": bytes_per_launch, "algorithmic_bytes_per_step": BYTES_PER_CORR * n,
                          "steps_per_launch": steps_per_launch,
-                         "avg_launch_us": k_avg_s * 1e6, "avg_launch_us_per_step": k_avg_s * 1e6 / steps_per_launch, "min_launch_us": (k_min_ms * 1e3) if k_cnt else None,
-                         "launches_timed": k_cnt, "empty_event_pair_us": ev_avg_ms * 1e3,
+                         "avg_launch_us": (k_avg_s * 1e6) if k_cnt else None, "avg_launch_us_per_step": (k_avg_s * 1e6 / steps_per_launch) if k_cnt else None,
+                         "min_launch_us": (k_min_ms * 1e3) if k_cnt else None,
+                         "launches_timed": k_cnt, "empty_event_pair_us": (ev_avg_ms * 1e3) if ev_avg_ms is not None else None,
                          "profile_same_steps_per_launch": profile_same, "profiles_other_steps_per_launch": profile_other or None,
                          "note": "HIP events on the kernel's own stream (hipExtLaunchKernelGGL start / stop = the dispatch's begin / end timestamps, what "
                                  "rocprofv3 reports); one launch per step, 26 B x correspondences of this rank per launch" if not resident else
@@ -990,7 +1036,9 @@ def worker(args, affinity):
                                  "profile of this command whose launches served the same number of steps as this run's; null when no such profile is "
                                  "committed (the per-step values of the other profiles are listed with their own steps_per_launch)"},
         }
-        if world == 1:
+        if world == 1 and not args.full:
+            out["cpu_baseline"] = None
+        elif world == 1:
             try:   # pose parity: converged GN pose vs the CPU oracle's closed form (shinji, fp64, same fp32 inputs, same inlier set)
                 sys.path.insert(0, os.path.join(ROOT, "tests"))
                 import oracle_lib as O
@@ -1384,7 +1432,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=50, help="repetitions of the timed K-step region; the median is reported")
+    ap.add_argument("--full", action="store_true", help="also measure everything reported beside the headline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float64)")
+    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the timed K-step region; the median is reported (default 1, 50 with --full)")
     ap.add_argument("--event-reps", type=int, default=16, help="how many of the repetitions also time their launches with HIP events (roofline.avg_launch_us)")
     ap.add_argument("--n-per-gpu", type=int, default=N_FRAME, help="correspondences at N = 1 (configs[1])")
     ap.add_argument("--n-total", type=int, default=0, help="total correspondences at N > 1 (default configs[4]: 10 000 000)")
@@ -1394,12 +1444,14 @@ def main():
     ap.add_argument("--untuned-probe", action="store_true", help="internal: print the K-step figure of a process with NO host-side tuning (no pinning, default environment) and exit")
     ap.add_argument("--no-hbm", action="store_true", help="skip the live bandwidth-bound block (roofline_hbm: 1 M point-to-plane steady / cold, 10 M / 20 M point-to-point)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 50 if args.full else 1
     if args.gpus < 1 or args.steps < 1 or args.repeats < 1:
         sys.exit("bench.py: --gpus, --steps and --repeats must be positive")
     if args.untuned_probe:
         untuned_probe(args)
         return
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_extras and os.environ.get("RPE_BENCH_NO_UNTUNED") != "1":
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_extras and os.environ.get("RPE_BENCH_NO_UNTUNED") != "1":
         # the untuned figure beside the headline: a child process with the caller's own environment and no pinning, run BEFORE this
         # process initialises the GPU (the two never use it at the same time)
         try:

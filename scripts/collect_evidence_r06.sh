@@ -8,19 +8,19 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-drv="--gpus 1 --steps 20 --warmup 5"
+drv="--gpus 1 --steps 20 --warmup 5 --full"
 timeout 1800 python3 -m pytest $root/tests -m gpu -q > $out/pytest_gpu.txt 2>&1   # (the suite as the driver runs it: multi-process cases on, soak off)
 tail -4 $out/pytest_gpu.txt
 timeout 900 python3 $root/bench.py $drv > $out/bench_driver_cmd.json 2> $out/bench_stderr.txt
 tail -c 300 $out/bench_driver_cmd.json; echo
-timeout 900 python3 $root/bench.py > $out/bench_default_2000steps.json 2>> $out/bench_stderr.txt
+timeout 900 python3 $root/bench.py --full > $out/bench_default_2000steps.json 2>> $out/bench_stderr.txt
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_driver -- python3 $root/bench.py $drv > $out/bench_driver_under_rocprof.txt 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_driver_noextras -- python3 $root/bench.py $drv --no-extras --no-cpu-baseline --no-hbm > $out/bench_driver_noextras_under_rocprof.txt 2>&1
 RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch_20 -- python3 $root/bench.py $drv --repeats 20 --no-extras --no-cpu-baseline --no-hbm > /dev/null 2>&1
 RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write_20 -- python3 $root/bench.py $drv --repeats 20 --no-extras --no-cpu-baseline --no-hbm > /dev/null 2>&1
-RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_2000 -- python3 $root/bench.py --steps 2000 --warmup 2000 --no-extras --no-cpu-baseline --no-hbm > $out/bench_2000_under_rocprof.txt 2>&1
-RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch_2000 -- python3 $root/bench.py --steps 2000 --warmup 2000 --repeats 5 --no-extras --no-cpu-baseline --no-hbm > /dev/null 2>&1
-RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write_2000 -- python3 $root/bench.py --steps 2000 --warmup 2000 --repeats 5 --no-extras --no-cpu-baseline --no-hbm > /dev/null 2>&1
+RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_2000 -- python3 $root/bench.py --steps 2000 --warmup 2000 --full --no-extras --no-cpu-baseline --no-hbm > $out/bench_2000_under_rocprof.txt 2>&1
+RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch_2000 -- python3 $root/bench.py --steps 2000 --warmup 2000 --repeats 5 --full --no-extras --no-cpu-baseline --no-hbm > /dev/null 2>&1
+RPE_BENCH_PREWARM_S=0.1 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write_2000 -- python3 $root/bench.py --steps 2000 --warmup 2000 --repeats 5 --full --no-extras --no-cpu-baseline --no-hbm > /dev/null 2>&1
 for d in prof_driver prof_driver_noextras prof_2000; do f=$(ls $out/$d/*/*_kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $out/${d}_kernel_stats.csv; done
 for d in pmc_fetch_20 pmc_write_20 pmc_fetch_2000 pmc_write_2000; do f=$(ls $out/$d/*/*_counter_collection.csv 2>/dev/null | head -1); [ -n "$f" ] && (head -1 $f; grep normal_eq_resident $f) > $out/${d}_counters.csv; done
 rm -rf $out/prof_driver $out/prof_driver_noextras $out/prof_2000 $out/pmc_fetch_20 $out/pmc_write_20 $out/pmc_fetch_2000 $out/pmc_write_2000

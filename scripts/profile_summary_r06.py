@@ -67,13 +67,13 @@ for steps, st_name, st_dst, tagn in ((20, "prof_driver_noextras", "r06_bench_dri
         e.update(traffic_bytes_per_launch=traffic, traffic_bytes_per_step=traffic / steps, FETCH_SIZE_KiB_median=fe["median_KiB"], WRITE_SIZE_KiB_median=wr["median_KiB"],
                  pmc_dispatches=[fe["dispatches"], wr["dispatches"]], pmc_files=[fe["file"], wr["file"]], grid_size=fe["grid"], correction=CORR)
     e["source"] = "scripts/collect_evidence_r06.sh -> scripts/profile_summary_r06.py"
-    e["command"] = ("rocprofv3 ... -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-hbm" if steps == 20 else
-                    "rocprofv3 ... -- python3 bench.py --steps 2000 --warmup 2000 --no-extras --no-cpu-baseline --no-hbm")
+    e["command"] = ("rocprofv3 ... -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline --no-hbm" if steps == 20 else
+                    "rocprofv3 ... -- python3 bench.py --steps 2000 --warmup 2000 --full --no-extras --no-cpu-baseline --no-hbm")
     entries.append(e)
 index["normal_eq_resident_p2p_f32"] = entries
 full = pick(stats_rows("prof_driver", "r06_bench_driver_cmd_rocprofv3_kernel_stats.csv"), RES)
 index["driver_command_with_extras"] = None if not full else {
-    "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5", "rocprofv3_avg_launch_us": full["avg_ns"] * 1e-3, "calls": full["calls"],
+    "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full", "rocprofv3_avg_launch_us": full["avg_ns"] * 1e-3, "calls": full["calls"],
     "file": full["file"], "note": "all launches of this kernel name in the run: pre-warm, host-thread tuning, timed (20 steps each), the --warmup launch (5) and the convergence leg's"}
 # ---- the bandwidth-bound launches (normal_eq_kernel), told apart by grid size / bytes: 20 M, 10 M point-to-point, 1 M point-to-plane
 hbm = {}

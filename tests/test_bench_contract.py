@@ -123,3 +123,15 @@ def test_sharded_record_check_judges_every_entry_on_its_own_scale():
     assert np.max(np.abs(bad[:29] - rec[:29])) <= 2e-6 * np.max(np.abs(rec[:29])) and not bench.record_close(bad, rec, 2e-6)
     half = rec * 0.5                                   # a missing shard
     assert not bench.record_close(half, rec, 2e-6)
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    import numpy as np
+    pose = np.concatenate([np.eye(3).reshape(9), [0.1, -0.2, 0.3]])
+    bench.dump_outputs(str(tmp_path / "out"), pose, {"step_norm": 1e-12, "cost": 3.5})
+    got = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(got) == {"pose.npy", "step_norm.npy", "cost.npy"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["pose.npy"], pose) and got["step_norm.npy"].tolist() == [1e-12] and got["cost.npy"].tolist() == [3.5]
+    bench.dump_outputs(str(tmp_path / "out2"), pose, {"step_norm": 0.5})   # a path that returns no cost writes no cost.npy
+    assert sorted(p.name for p in (tmp_path / "out2").iterdir()) == ["pose.npy", "step_norm.npy"]

@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(tmp_path, extra_env, gpus=3):
+def _run(tmp_path, extra_env, gpus=3, full=True):
     # a torch / package stub that explodes on import: neither the parent nor a dry-run rank may import them
     stub = tmp_path / "stubs"
     (stub / "torch").mkdir(parents=True, exist_ok=True)
@@ -17,8 +17,8 @@ def _run(tmp_path, extra_env, gpus=3):
     env = dict(os.environ, PYTHONPATH=str(stub), RPE_BENCH_DRY_RUN="1", RPE_LIBRARY="/nonexistent/librgbdpose_hip.so", **extra_env)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "5"], env=env,
-                          capture_output=True, text=True, timeout=120)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "5"] + (["--full"] if full else []),
+                          env=env, capture_output=True, text=True, timeout=120)
 
 
 def test_bare_shell_launch_spawns_ranks_and_forwards_rank0(tmp_path):
@@ -60,3 +60,12 @@ def test_single_gpu_invocation_does_not_spawn(tmp_path):
     j = json.loads(r.stdout.strip().splitlines()[-1])
     assert j["world"] == 1 and j["rank"] == 0
     assert j["collective_plan"]["headline"] == "none" and j["collective_plan"]["rccl_ranks_expected"] == 0
+
+
+def test_plain_run_plans_the_headline_collective_only(tmp_path):
+    """Without --full the ranks set up the headline's collective and time nothing beside it."""
+    for want, headline in (("auto", "rccl"), ("auto_p2p", "rccl"), ("host", "host")):
+        r = _run(tmp_path, {"RPE_BENCH_COLLECTIVE": want}, gpus=2, full=False)
+        assert r.returncode == 0, r.stderr
+        j = json.loads(r.stdout.strip().splitlines()[-1])
+        assert j["steps"] == 20 and j["collective_plan"]["headline"] == headline and j["collective_plan"]["timed_beside"] == [], (want, j)

@@ -24,7 +24,7 @@ def test_bench_two_ranks_one_gpu_from_a_bare_shell():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r, line, j = run_bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--repeats", "10", "--n-total", "614400",
-                        "--no-cpu-baseline"], env, timeout=900)
+                        "--no-cpu-baseline", "--full"], env, timeout=900)
     assert j["n_gpus"] == 2 and j["scaling"] == "strong" and j["steps"] == 20 and j["value"] > 1e9
     assert j["config"]["global_corr"] == 614400 and j["config"]["corr_rank0"] == 307200
     assert 0.8 * 614400 < j["config"]["valid_corr_per_step"] < 614400

@@ -18,7 +18,7 @@ def test_bench_collective_path_on_rccl_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RPE_BENCH_FORCE_DIST="1", RPE_BENCH_PREWARM_STEPS="300", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547",
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r, line, j = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--repeats", "10", "--no-cpu-baseline",
-                        "--no-extras", "--no-hbm"], env, timeout=900)
+                        "--no-extras", "--no-hbm", "--full"], env, timeout=900)
     cfg = j["config"]
     assert j["n_gpus"] == 1 and j["value"] > 1e9
     assert cfg["collective"].startswith("rccl:") and "library-owned communicator" in cfg["collective"]
