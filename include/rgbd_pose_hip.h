@@ -434,6 +434,40 @@ typedef struct { int kind; int max_iter; double tol; double dist_thr; double cos
 int rpe_icp(rpe_context* ctx, const rpe_icp_options* opt, double* pose12, int* iters_out, double* last_step, double* final_cost,
             int64_t* matched);
 
+/* ---- coarse-to-fine pyramids of frame and model (KinectFusion-style ICP).  Conventions, followed bit for bit:
+ * Levels l = 0 .. L-1, L <= RPE_MAX_LEVELS; level l is (width >> l) x (height >> l) pixels and every level must have one
+ * (RPE_ERR_ARG otherwise).  Level camera, computed in double and cast to fp32 like the level-0 camera: level 0 is the camera itself,
+ * level l >= 1 has fx / 2^l, fy / 2^l, cx_l = (cx + 0.5) / 2^l - 0.5, cy_l likewise (level-1 pixel u is centred on level-0
+ * coordinate 2u + 0.5).  Frame depth pyramid (fp32 metres, NaN = invalid): level 0 = depth * depth_scale, NaN outside (dmin, dmax);
+ * level l+1 pixel (u, v) with c = level-l depth at (2u, 2v): NaN if c is, else the mean of the 2 x 2 block's valid depths d with
+ * |d - c| <= max_jump, summed in the order (2v,2u) (2v,2u+1) (2v+1,2u) (2v+1,2u+1) with 0 for an excluded pixel and divided by their
+ * count (fp32, no FMA contraction).  Frame maps of level l = F1's arithmetic on the level's metric depth (scale 1, same dmin / dmax /
+ * max_jump) with the level camera; level 0 is bitwise what rpe_frame_set_depth builds.  Model levels: rpe_model_from_frame moves
+ * every level of the frame (F2 on each); rpe_model_build_pyramid resizes an uploaded level 0 (KinectFusion): block a = (2u,2v),
+ * b = (2u+1,2v), c = (2u,2v+1), d = (2u+1,2v+1) of level l; a vertex is valid iff all four are (no NaN component), value
+ * (((a + b) + c) + d) * 0.25f; a normal is valid iff all four are, the same sum divided by sqrtf(x*x + y*y + z*z), NaN at length 0;
+ * vertices and normals independently. */
+enum { RPE_MAX_LEVELS = 4, RPE_MAP_DEPTH = 5 };
+/* F1p: rpe_frame_set_depth plus the frame's pyramid of `levels` levels (metric depth and maps of every level; two launches).
+ * rpe_frame_set_depth resets the frame to one level (and keeps no metric depth). */
+int rpe_frame_set_depth_pyramid(rpe_context* ctx, const void* depth, int depth_type, const rpe_camera* cam, double depth_scale,
+                                double dmin, double dmax, double max_jump, int levels);
+/* one map of one level: which = RPE_MAP_* (3 x w_l*h_l floats; model maps: the model's level) or RPE_MAP_DEPTH (w_l*h_l floats of
+ * metric depth, frames set by rpe_frame_set_depth_pyramid only).  rpe_frame_download keeps rejecting RPE_MAP_DEPTH. */
+int rpe_frame_download_level(rpe_context* ctx, int which, int level, float* out);
+/* the fp64 camera of a level of the frame (model = 0) or of the model (model = 1): the values the kernels' fp32 camera was cast from */
+int rpe_frame_level_camera(rpe_context* ctx, int level, int model, rpe_camera* out);
+/* F2p: levels 1 .. levels-1 of the model from its level 0 (one launch); rpe_model_upload resets the model to one level */
+int rpe_model_build_pyramid(rpe_context* ctx, int levels);
+/* coarse-to-fine ICP: levels L-1 .. 0, each rpe_icp's loop (every execution form of opt, opt->tol ending the level early) on that
+ * level's frame and model maps, from the pose the coarser level returned.  iters_per_level[l] rounds at level l (0 = finest; coarse
+ * levels may have 0, level 0 needs >= 1; opt->max_iter is not used), dist_thr_per_level[l] its distance gate (NULL: opt->dist_thr
+ * everywhere).  One host wait per level.  iters_out[l] = rounds run at level l; last_step / final_cost / matched and the solver
+ * slots (XW XC BV NW NC, n = width*height) are level 0's, as rpe_icp leaves them.  RPE_ERR_STATE when the frame or the model has
+ * fewer than `levels` levels. */
+int rpe_icp_pyramid(rpe_context* ctx, const rpe_icp_options* opt, int levels, const int* iters_per_level, const double* dist_thr_per_level,
+                    double* pose12, int* iters_out, double* last_step, double* final_cost, int64_t* matched);
+
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.
  * 3 x K inputs are column-major doubles whose values are rounded to dtype before use. */

@@ -197,8 +197,9 @@ class Context:
         return L.RpeCamera(float(fx), float(fy), float(cx), float(cy), int(w), int(h))
 
     def frame_set_depth(self, depth: np.ndarray, cam=(585.0, 585.0, 320.0, 240.0, 640, 480), depth_scale: float | None = None,
-                        dmin: float = 0.0, dmax: float = 1e30, max_jump: float = 0.1):
-        """depth: (height, width) uint16 (default scale 0.001: millimetres) or float32 (default scale 1: metres)."""
+                        dmin: float = 0.0, dmax: float = 1e30, max_jump: float = 0.1, levels: int = 1):
+        """depth: (height, width) uint16 (default scale 0.001: millimetres) or float32 (default scale 1: metres).
+        levels > 1 also builds the coarse-to-fine pyramid (rpe_frame_set_depth_pyramid); levels = 1 is rpe_frame_set_depth."""
         k = self._camera(cam)
         d = np.ascontiguousarray(depth)
         if d.shape != (k.height, k.width):
@@ -209,16 +210,37 @@ class Context:
             kind, scale = L.DEPTH_F32, 1.0 if depth_scale is None else depth_scale
         else:
             raise TypeError("depth must be uint16 or float32")
-        L.check(L.lib().rpe_frame_set_depth(self._h, _p(d), kind, C.byref(k), scale, dmin, dmax, max_jump))
+        if levels == 1:
+            L.check(L.lib().rpe_frame_set_depth(self._h, _p(d), kind, C.byref(k), scale, dmin, dmax, max_jump))
+        else:
+            L.check(L.lib().rpe_frame_set_depth_pyramid(self._h, _p(d), kind, C.byref(k), scale, dmin, dmax, max_jump, int(levels)))
         self._pixels = k.width * k.height
         return self
 
-    def frame_download(self, which: int) -> np.ndarray:
-        """One map as (pixels, 3) float32; pixels of the model's view for the MAP_MODEL_* maps."""
-        n = self._model_pixels if which >= L.MAP_MODEL_VERTEX else self._pixels
-        out = np.empty((n, 3), np.float32)
-        L.check(L.lib().rpe_frame_download(self._h, which, _p(out)))
+    def frame_download(self, which: int, level: int = 0) -> np.ndarray:
+        """One map as (pixels, 3) float32 (MAP_DEPTH: (pixels,) metres) of pyramid level `level`; pixels of the model's view for the
+        MAP_MODEL_* maps."""
+        if level == 0 and which != L.MAP_DEPTH:
+            n = self._model_pixels if which >= L.MAP_MODEL_VERTEX else self._pixels
+            out = np.empty((n, 3), np.float32)
+            L.check(L.lib().rpe_frame_download(self._h, which, _p(out)))
+            return out
+        k = self.frame_camera(level, which in (L.MAP_MODEL_VERTEX, L.MAP_MODEL_NORMAL))
+        n = k[4] * k[5]
+        out = np.empty(n if which == L.MAP_DEPTH else (n, 3), np.float32)
+        L.check(L.lib().rpe_frame_download_level(self._h, which, level, _p(out)))
         return out
+
+    def frame_camera(self, level: int = 0, model: bool = False):
+        """(fx, fy, cx, cy, width, height) of a pyramid level of the frame (or the model), the fp64 values the kernels' camera was cast from."""
+        k = L.RpeCamera()
+        L.check(L.lib().rpe_frame_level_camera(self._h, level, int(model), C.byref(k)))
+        return (k.fx, k.fy, k.cx, k.cy, k.width, k.height)
+
+    def model_build_pyramid(self, levels: int):
+        """Levels 1 .. levels-1 of the model from its level 0 (KinectFusion resize)."""
+        L.check(L.lib().rpe_model_build_pyramid(self._h, int(levels)))
+        return self
 
     def model_from_frame(self, pose12):
         p = np.array(pose12, np.float64).reshape(12)
@@ -255,6 +277,26 @@ class Context:
         self.n, self.dtype = self._pixels, L.F32
         return p, it.value, step.value, cost.value, m.value
 
+
+    def icp_pyramid(self, pose12, iters=(10, 5, 4), dist_thr=None, kind: int = L.RES_P2PLANE, tol: float = 1e-6, cos_thr: float = 0.9,
+                    use_normals: bool = True, device_resident: bool = False, fused: bool = False):
+        """Coarse-to-fine ICP over len(iters) levels; iters[l] rounds at level l (0 = finest).  dist_thr: one gate per level, one gate
+        for every level, or None (0.1 m, icp's default).  Returns (pose12, rounds per level, last |delta|, cost, pairs of the last round),
+        the last three of level 0."""
+        p = np.array(pose12, np.float64).reshape(12).copy()
+        levels = len(iters)
+        it_in = np.ascontiguousarray(iters, np.int32)
+        one = 0.1 if dist_thr is None else dist_thr
+        thr = None if np.ndim(one) == 0 else np.ascontiguousarray(one, np.float64)
+        if thr is not None and len(thr) != levels:
+            raise ValueError("dist_thr needs one gate per level")
+        o = L.RpeIcpOptions(kind, 1, tol, float(one) if thr is None else 0.0, cos_thr, int(use_normals), int(device_resident), int(fused))
+        it_out = np.zeros(levels, np.int32)
+        step, cost, m = C.c_double(0), C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_pyramid(self._h, C.byref(o), levels, _p(it_in), None if thr is None else _p(thr), _p(p), _p(it_out), C.byref(step),
+                                        C.byref(cost), C.byref(m)))
+        self.n, self.dtype = self._pixels, L.F32
+        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
 
     def gn_steps_dist(self, kind: int, pose12_inout: np.ndarray, steps: int, flags: int = 0) -> float:
         """`steps` sharded GN steps in place, the loop inside the library; returns the last |delta|."""

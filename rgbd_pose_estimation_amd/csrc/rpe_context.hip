@@ -196,6 +196,7 @@ void rpe_destroy(rpe_context* c) {
   for (float* m : c->fe.fmap) if (m) (void)hipFree(m);
   for (float* m : c->fe.mmap) if (m) (void)hipFree(m);
   if (c->fe.d_count) (void)hipFree(c->fe.d_count);
+  if (c->fe.fdepth) (void)hipFree(c->fe.fdepth);
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);

@@ -6,6 +6,10 @@
 //                               u - cx = f X / Z), unit bearing vectors (the conversion of Simulator.hpp:215-222) and a
 //                               normal map (central differences of the vertex map, oriented towards the camera)
 //   F2  to_world_kernel         frame maps -> world maps under a pose (Xw = R^T (Xc - t)): the model of the next frame
+//   F1p depth_pyramid_kernel + pyramid_maps_kernel: metric depth of every pyramid level (LDS tiles), then F1's arithmetic on
+//                               every level (workgroups partitioned by level)
+//   F2p model_pyramid_kernel    model maps of levels 1 .. L-1 from level 0 (KinectFusion resize); F2 on all levels at once = one
+//                               to_world_kernel launch over the concatenated levels
 //   F3  associate_kernel        projective data association of the frame against the model under a pose guess, with a
 //                               distance and a normal-angle gate; writes XW XC BV NW NC aligned per pixel
 //
@@ -63,12 +67,13 @@ __device__ __forceinline__ void load4(const float* __restrict__ in, int64_t g, i
 }
 
 // ---------------------------------------------------------------------------------------------- F1
+// the maps of pixel group g (4 consecutive pixels) of one image: shared by F1 (raw depth, the caller's scale) and F1p (metric depth
+// of one pyramid level, scale 1) so that every level is built by the same operations
 template <class D>
-__global__ __launch_bounds__(kFeBlock) void frame_maps_kernel(const D* __restrict__ depth, Camera cam, float scale, float dmin, float dmax,
-                             float max_jump, float* __restrict__ vmap, float* __restrict__ nmap, float* __restrict__ bmap) {
+__device__ __forceinline__ void frame_maps_group(const D* __restrict__ depth, const Camera& cam, float scale, float dmin, float dmax,
+                                                 float max_jump, int64_t g, float* __restrict__ vmap, float* __restrict__ nmap,
+                                                 float* __restrict__ bmap) {
   const int64_t n = (int64_t)cam.width * cam.height;
-  const int64_t g = (int64_t)blockIdx.x * kFeBlock + threadIdx.x;
-  if (g * 4 >= n) return;
   float V[12], N[12], B[12];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -111,6 +116,90 @@ __global__ __launch_bounds__(kFeBlock) void frame_maps_kernel(const D* __restric
   store4(bmap, g, n, B);
 }
 
+template <class D>
+__global__ __launch_bounds__(kFeBlock) void frame_maps_kernel(const D* __restrict__ depth, Camera cam, float scale, float dmin, float dmax,
+                             float max_jump, float* __restrict__ vmap, float* __restrict__ nmap, float* __restrict__ bmap) {
+  const int64_t n = (int64_t)cam.width * cam.height;
+  const int64_t g = (int64_t)blockIdx.x * kFeBlock + threadIdx.x;
+  if (g * 4 >= n) return;
+  frame_maps_group(depth, cam, scale, dmin, dmax, max_jump, g, vmap, nmap, bmap);
+}
+
+// ---------------------------------------------------------------------------------------------- F1p
+// Launch one: raw depth -> metric depth of every pyramid level.  A workgroup owns a 32 x 32 tile of level 0 (4 pixels of a row per
+// lane, 16-byte stores where the row allows), keeps it in LDS and halves it in place level by level: the tile origin is a multiple
+// of 2^(kMaxLevels-1), so the 2 x 2 block of every coarser pixel lies inside the tile.  Level l+1 pixel (u, v), c = level-l depth at
+// (2u, 2v): NaN if c is NaN, else the mean of the block's valid depths within max_jump of c, summed in the order (2v,2u) (2v,2u+1)
+// (2v+1,2u) (2v+1,2u+1).
+constexpr int kPyrTile = 32;
+
+template <class D>
+__global__ __launch_bounds__(kFeBlock) void depth_pyramid_kernel(const D* __restrict__ raw, PyramidGeometry P, float scale, float dmin,
+                                                                 float dmax, float max_jump, float* __restrict__ out) {
+  __shared__ float tile[kPyrTile][kPyrTile + 1];
+  const int w = P.cam[0].width, h = P.cam[0].height;
+  const int tiles_x = (w + kPyrTile - 1) / kPyrTile;
+  const int u0 = (blockIdx.x % tiles_x) * kPyrTile, v0 = (blockIdx.x / tiles_x) * kPyrTile;
+  const float nan = qnan();
+  {  // level 0: thread t owns row t / 8, columns 4 (t % 8) .. +3 of the tile
+    const int r = threadIdx.x / 8, c = 4 * (threadIdx.x % 8);
+    const int v = v0 + r, u = u0 + c;
+    float z[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      z[k] = nan;
+      if (v < h && u + k < w) {
+        const float d = (float)raw[(int64_t)v * w + u + k] * scale;
+        z[k] = d > dmin && d < dmax ? d : nan;
+      }
+      tile[r][c + k] = z[k];
+    }
+    if (v < h) {
+      float* o = out + (int64_t)v * w + u;
+      if ((w & 3) == 0 && u + 3 < w) *reinterpret_cast<float4*>(o) = make_float4(z[0], z[1], z[2], z[3]);
+      else for (int k = 0; k < 4; k++) if (u + k < w) o[k] = z[k];
+    }
+  }
+  for (int l = 1; l < P.levels; l++) {
+    __syncthreads();
+    const int side = kPyrTile >> l;                 // tile side at level l
+    const int wl = P.cam[l].width, hl = P.cam[l].height;
+    const int ul = u0 >> l, vl = v0 >> l;
+    float z = nan;
+    const int r = threadIdx.x / side, c = threadIdx.x % side;
+    const bool mine = r < side;
+    if (mine) {
+      const float a = tile[2 * r][2 * c], b = tile[2 * r][2 * c + 1], e = tile[2 * r + 1][2 * c], f = tile[2 * r + 1][2 * c + 1];
+      if (a == a) {   // (a NaN block centre stays NaN; NaN members fail their gate)
+        const bool ka = fabsf(a - a) <= max_jump, kb = fabsf(b - a) <= max_jump, ke = fabsf(e - a) <= max_jump,
+                   kf = fabsf(f - a) <= max_jump;
+        const float sum = (((ka ? a : 0.0f) + (kb ? b : 0.0f)) + (ke ? e : 0.0f)) + (kf ? f : 0.0f);
+        z = sum / (float)((ka ? 1 : 0) + (kb ? 1 : 0) + (ke ? 1 : 0) + (kf ? 1 : 0));
+      }
+    }
+    __syncthreads();
+    if (mine) {
+      tile[r][c] = z;
+      if (vl + r < hl && ul + c < wl) out[P.off[l] + (int64_t)(vl + r) * wl + ul + c] = z;
+    }
+  }
+}
+
+// Launch two: the maps of every level, workgroups partitioned by level (P.block0), each level exactly F1 on its metric depth
+__global__ __launch_bounds__(kFeBlock) void pyramid_maps_kernel(const float* __restrict__ depth, PyramidGeometry P, float dmin, float dmax,
+                                                                float max_jump, float* __restrict__ vmap, float* __restrict__ nmap,
+                                                                float* __restrict__ bmap) {
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < kMaxLevels; k++) l += (k < P.levels && (int)blockIdx.x >= P.block0[k]) ? 1 : 0;
+  const Camera cam = P.cam[l];
+  const int64_t n = (int64_t)cam.width * cam.height;
+  const int64_t g = (int64_t)((int)blockIdx.x - P.block0[l]) * kFeBlock + threadIdx.x;
+  if (g * 4 >= n) return;
+  const int64_t o = P.off[l];
+  frame_maps_group(depth + o, cam, 1.0f, dmin, dmax, max_jump, g, vmap + 3 * o, nmap + 3 * o, bmap + 3 * o);
+}
+
 // ---------------------------------------------------------------------------------------------- F2
 __global__ __launch_bounds__(kFeBlock) void to_world_kernel(const float* __restrict__ vmap, const float* __restrict__ nmap, int64_t n,
                              PoseF T, float* __restrict__ vw, float* __restrict__ nw) {
@@ -127,6 +216,81 @@ __global__ __launch_bounds__(kFeBlock) void to_world_kernel(const float* __restr
   store4(vw, g, n, OV);
   store4(nw, g, n, ON);
 }
+
+// ---------------------------------------------------------------------------------------------- F2p
+// Model pyramid (the KinectFusion resize): level-(l+1) pixel (u, v) from the level-l block a = (2u, 2v), b = (2u+1, 2v),
+// c = (2u, 2v+1), d = (2u+1, 2v+1).  Vertex: valid iff all four are (no NaN component), value (((a + b) + c) + d) * 0.25f.  Normal:
+// valid iff all four are, the same sum divided by its length sqrtf((x*x + y*y) + z*z), NaN at length 0.  One launch for every
+// level: a thread of level l evaluates its quad tree down to level 0 (Resize<l>), whose inner nodes are bit for bit the level-1 ..
+// l-1 values other threads write.
+template <int LV> struct Resize {
+  // the block's four members are summed in a rolled loop above level 1 (the unrolled quad tree of level 3 would hold 64 pixels live)
+  static constexpr int kUnroll = LV == 1 ? 4 : 1;
+  template <bool NORMAL>
+  static __device__ __forceinline__ bool node(const float* __restrict__ m, int w0, int u, int v, float (&o)[3]) {
+    float s[3] = {0.f, 0.f, 0.f};
+    bool ok = true;
+#pragma unroll kUnroll
+    for (int q = 0; q < 4; q++) {
+      float c[3];
+      ok = Resize<LV - 1>::template node<NORMAL>(m, w0, 2 * u + (q & 1), 2 * v + (q >> 1), c) && ok;
+#pragma unroll
+      for (int k = 0; k < 3; k++) s[k] = q == 0 ? c[k] : s[k] + c[k];
+    }
+    if (!NORMAL) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) o[k] = ok ? s[k] * 0.25f : qnan();
+      return ok;
+    }
+    const float len = sqrtf(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+    const bool good = ok && len > 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) o[k] = good ? s[k] / len : qnan();
+    return good;
+  }
+};
+template <> struct Resize<0> {
+  template <bool NORMAL>
+  static __device__ __forceinline__ bool node(const float* __restrict__ m, int w0, int u, int v, float (&o)[3]) {
+    const int64_t j = 3 * ((int64_t)v * w0 + u);
+    o[0] = m[j]; o[1] = m[j + 1]; o[2] = m[j + 2];
+    return o[0] == o[0] && o[1] == o[1] && o[2] == o[2];
+  }
+};
+
+template <int LV>
+__device__ __forceinline__ void model_group(const PyramidGeometry& P, int64_t g, float* __restrict__ mv, float* __restrict__ mn) {
+  const Camera cam = P.cam[LV];
+  const int64_t n = (int64_t)cam.width * cam.height;
+  float V[12], N[12];
+#pragma unroll 1
+  for (int k = 0; k < 4; k++) {
+    const int64_t i = g * 4 + k;
+    float v3[3] = {qnan(), qnan(), qnan()}, n3[3] = {qnan(), qnan(), qnan()};
+    if (i < n) {
+      const int u = (int)(i % cam.width), v = (int)(i / cam.width);
+      (void)Resize<LV>::template node<false>(mv, P.cam[0].width, u, v, v3);
+      (void)Resize<LV>::template node<true>(mn, P.cam[0].width, u, v, n3);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; q++) { V[3 * k + q] = v3[q]; N[3 * k + q] = n3[q]; }
+  }
+  store4(mv + 3 * P.off[LV], g, n, V);
+  store4(mn + 3 * P.off[LV], g, n, N);
+}
+
+// reads level 0 of mv / mn, writes levels 1 .. P.levels-1; workgroups partitioned by level (P.block0[1] = 0)
+__global__ __launch_bounds__(kFeBlock) void model_pyramid_kernel(PyramidGeometry P, float* __restrict__ mv, float* __restrict__ mn) {
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < kMaxLevels; k++) l += (k < P.levels && (int)blockIdx.x >= P.block0[k]) ? 1 : 0;
+  const int64_t g = (int64_t)((int)blockIdx.x - P.block0[l]) * kFeBlock + threadIdx.x;
+  if (g * 4 >= (int64_t)P.cam[l].width * P.cam[l].height) return;
+  if (l == 1) model_group<1>(P, g, mv, mn);
+  else if (l == 2) model_group<2>(P, g, mv, mn);
+  else if (l == 3) model_group<3>(P, g, mv, mn);
+}
+static_assert(kMaxLevels == 4, "model_pyramid_kernel dispatches levels 1 .. 3");
 
 // ---------------------------------------------------------------------------------------------- F3
 // T: pose guess of the frame (Xc = R Xw + t).  M: pose of the model view (world -> model camera), mcam its intrinsics.
@@ -193,6 +357,36 @@ hipError_t launch_frame_maps(const void* d_depth, int depth_type, const Camera& 
     hipLaunchKernelGGL(frame_maps_kernel<float>, dim3(fe_grid(n)), dim3(kFeBlock), 0, s, (const float*)d_depth, cam, scale, dmin, dmax,
         max_jump,
                        vmap, nmap, bmap);
+  return hipGetLastError();
+}
+
+hipError_t launch_frame_pyramid(const void* d_depth, int depth_type, const PyramidGeometry& geo, float scale, float dmin, float dmax,
+                                float max_jump, float* depth_out, float* vmap, float* nmap, float* bmap, hipStream_t s) {
+  PyramidGeometry P = geo;
+  const int w = P.cam[0].width, h = P.cam[0].height;
+  const int tiles = ((w + kPyrTile - 1) / kPyrTile) * ((h + kPyrTile - 1) / kPyrTile);
+  if (depth_type == 0)
+    hipLaunchKernelGGL(depth_pyramid_kernel<unsigned short>, dim3(tiles), dim3(kFeBlock), 0, s, (const unsigned short*)d_depth, P, scale,
+                       dmin, dmax, max_jump, depth_out);
+  else
+    hipLaunchKernelGGL(depth_pyramid_kernel<float>, dim3(tiles), dim3(kFeBlock), 0, s, (const float*)d_depth, P, scale, dmin, dmax,
+                       max_jump, depth_out);
+  int blocks = 0;
+  for (int l = 0; l < P.levels; l++) { P.block0[l] = blocks; blocks += fe_grid((int64_t)P.cam[l].width * P.cam[l].height); }
+  for (int l = P.levels; l <= kMaxLevels; l++) P.block0[l] = blocks;
+  hipLaunchKernelGGL(pyramid_maps_kernel, dim3(blocks), dim3(kFeBlock), 0, s, (const float*)depth_out, P, dmin, dmax, max_jump, vmap, nmap,
+                     bmap);
+  return hipGetLastError();
+}
+
+hipError_t launch_model_pyramid(const PyramidGeometry& geo, float* mv, float* mn, hipStream_t s) {
+  PyramidGeometry P = geo;
+  if (P.levels < 2) return hipSuccess;
+  int blocks = 0;
+  P.block0[0] = 0;
+  for (int l = 1; l < P.levels; l++) { P.block0[l] = blocks; blocks += fe_grid((int64_t)P.cam[l].width * P.cam[l].height); }
+  for (int l = P.levels; l <= kMaxLevels; l++) P.block0[l] = blocks;
+  hipLaunchKernelGGL(model_pyramid_kernel, dim3(blocks), dim3(kFeBlock), 0, s, P, mv, mn);
   return hipGetLastError();
 }
 

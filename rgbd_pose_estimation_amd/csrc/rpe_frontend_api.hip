@@ -51,13 +51,24 @@ int claim_slots(rpe_context* c, int64_t n) {
   for (int s = 0; s < RPE_NUM_ARRAYS; s++) { c->arr[s] = c->store[s]; arrays_changed(c, s, true); }
   return RPE_OK;
 }
-int associate_launch(rpe_context* c, const double* pose12, double dist_thr, double cos_thr, int use_normals, bool pose_on_device,
-    bool count) {
+// one pyramid level of frame and model: maps, pixels, model camera (level 0 = the single-level front end)
+struct Level { const float* f[3]; const float* m[2]; int64_t n; rpe::Camera mcam; };
+Level level_of(rpe_context* c, int l) {
   auto& F = c->fe;
-  const int64_t n = (int64_t)F.cam.width * F.cam.height;
+  Level L;
+  for (int k = 0; k < 3; k++) L.f[k] = F.fmap[k] + 3 * F.fgeo.off[l];
+  for (int k = 0; k < 2; k++) L.m[k] = F.mmap[k] + 3 * F.mgeo.off[l];
+  L.n = (int64_t)F.fgeo.cam[l].width * F.fgeo.cam[l].height;
+  L.mcam = F.mgeo.cam[l];
+  return L;
+}
+int associate_launch(rpe_context* c, const Level& lv, const double* pose12, double dist_thr, double cos_thr, int use_normals,
+    bool pose_on_device, bool count) {
+  auto& F = c->fe;
+  const int64_t n = lv.n;
   const float d = (float)dist_thr;
   if (count) HIP_TRY(hipMemsetAsync(F.d_count, 0, sizeof(int), c->stream));
-  HIP_TRY(rpe::launch_associate(F.fmap[0], F.fmap[1], F.fmap[2], n, F.mmap[0], F.mmap[1], F.mcam, pose_f(pose12), pose_f(F.mpose),
+  HIP_TRY(rpe::launch_associate(lv.f[0], lv.f[1], lv.f[2], n, lv.m[0], lv.m[1], lv.mcam, pose_f(pose12), pose_f(F.mpose),
       d * d,
                                 (float)cos_thr, use_normals, pose_on_device ? c->d_gn_pose : nullptr,
                                 pose_on_device ? &c->d_gn_state->done : nullptr, (float*)c->arr[RPE_XW], (float*)c->arr[RPE_XC],
@@ -68,6 +79,49 @@ int associate_ready(rpe_context* c) {
   if (!c) return fail(RPE_ERR_ARG, "null context");
   if (!c->fe.have_frame) return fail(RPE_ERR_STATE, "no frame: call rpe_frame_set_depth first");
   if (!c->fe.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_from_frame or rpe_model_upload first");
+  return RPE_OK;
+}
+static_assert(rpe::kMaxLevels == RPE_MAX_LEVELS, "one pyramid depth for kernels and ABI");
+// fp64 level cameras, fp32 casts and level offsets of a `levels`-level pyramid over camera k0 (validated by camera_of).  Levels
+// are concatenated; every level but the last is padded to a multiple of 4 pixels so that the next one starts 16-byte aligned.
+int plan_levels(const rpe_camera& k0, int levels, rpe_camera* kc, rpe::PyramidGeometry* g) {
+  if (levels < 1 || levels > RPE_MAX_LEVELS) return fail(RPE_ERR_ARG, "levels must be 1 .. %d (got %d)", RPE_MAX_LEVELS, levels);
+  *g = rpe::PyramidGeometry{};
+  g->levels = levels;
+  for (int l = 0; l < levels; l++) {
+    rpe_camera k = k0;
+    if (l > 0) {
+      const double s = (double)(1 << l);
+      k.fx = k0.fx / s; k.fy = k0.fy / s; k.cx = (k0.cx + 0.5) / s - 0.5; k.cy = (k0.cy + 0.5) / s - 0.5;
+      k.width = k0.width >> l; k.height = k0.height >> l;
+      if (k.width < 1 || k.height < 1)
+        return fail(RPE_ERR_ARG, "pyramid level %d of a %d x %d camera has no pixel", l, k0.width, k0.height);
+    }
+    int rc = camera_of(&k, &g->cam[l]);
+    if (rc) return rc;
+    kc[l] = k;
+    const int64_t n = (int64_t)k.width * k.height;
+    g->off[l + 1] = g->off[l] + (l + 1 < levels ? (n + 3) / 4 * 4 : n);
+  }
+  for (int l = levels + 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = g->off[levels];
+  return RPE_OK;
+}
+// the one-level pyramid of a single image (rpe_frame_set_depth, rpe_model_upload)
+void one_level(const rpe_camera& k, const rpe::Camera& f, rpe_camera* kc, rpe::PyramidGeometry* g) {
+  *g = rpe::PyramidGeometry{};
+  g->levels = 1; g->cam[0] = f; kc[0] = k;
+  for (int l = 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = (int64_t)f.width * f.height;
+}
+// raw depth of n pixels to the device (and the pair counter)
+int stage_depth(rpe_context* c, const void* depth, int depth_type, int64_t n) {
+  auto& F = c->fe;
+  const size_t bytes = (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4);
+  if (!F.d_depth || F.depth_cap < bytes) {
+    if (F.d_depth) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(F.d_depth)); F.d_depth = nullptr; F.depth_cap = 0; }
+    HIP_TRY(hipMalloc(&F.d_depth, bytes));
+    F.depth_cap = bytes;
+  }
+  if (!F.d_count) HIP_TRY(hipMalloc((void**)&F.d_count, 64));
   return RPE_OK;
 }
 }  // namespace
@@ -83,20 +137,76 @@ int rpe_frame_set_depth(rpe_context* c, const void* depth, int depth_type, const
   HIP_TRY(hipSetDevice(c->device));
   auto& F = c->fe;
   const int64_t n = (int64_t)k.width * k.height;
-  const size_t bytes = (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4);
-  if (!F.d_depth || F.depth_cap < bytes) {
-    if (F.d_depth) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(F.d_depth)); F.d_depth = nullptr; F.depth_cap = 0; }
-    HIP_TRY(hipMalloc(&F.d_depth, bytes));
-    F.depth_cap = bytes;
-  }
-  if (!F.d_count) HIP_TRY(hipMalloc((void**)&F.d_count, 64));
+  if ((rc = stage_depth(c, depth, depth_type, n))) return rc;
   if ((rc = ensure_maps(c, F.fmap, 3, &F.fcap, n))) return rc;
   F.have_frame = false;
-  HIP_TRY(hipMemcpyAsync(F.d_depth, depth, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_maps(F.d_depth, depth_type, k, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fmap[0],
       F.fmap[1],
                                  F.fmap[2], c->stream));
   F.cam = k; F.have_frame = true;
+  one_level(*cam, k, F.kcam, &F.fgeo);
+  F.have_depth = false;
+  return RPE_OK;
+}
+
+int rpe_frame_set_depth_pyramid(rpe_context* c, const void* depth, int depth_type, const rpe_camera* cam, double depth_scale,
+                                double dmin, double dmax, double max_jump, int levels) {
+  session_end(c);
+  if (!c || !depth || !cam || (depth_type != RPE_DEPTH_U16 && depth_type != RPE_DEPTH_F32)) return fail(RPE_ERR_ARG,
+      "rpe_frame_set_depth_pyramid: bad argument");
+  rpe_camera kc[RPE_MAX_LEVELS];
+  rpe::PyramidGeometry g;
+  int rc = plan_levels(*cam, levels, kc, &g);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  auto& F = c->fe;
+  const int64_t n = (int64_t)g.cam[0].width * g.cam[0].height, total = g.off[levels];
+  if ((rc = stage_depth(c, depth, depth_type, n))) return rc;
+  if ((rc = ensure_maps(c, F.fmap, 3, &F.fcap, total))) return rc;
+  if (!F.fdepth || F.fdcap < (size_t)total * sizeof(float)) {
+    if (F.fdepth) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(F.fdepth)); F.fdepth = nullptr; F.fdcap = 0; }
+    HIP_TRY(hipMalloc((void**)&F.fdepth, (size_t)total * sizeof(float)));
+    F.fdcap = (size_t)total * sizeof(float);
+  }
+  F.have_frame = false; F.have_depth = false;
+  HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(rpe::launch_frame_pyramid(F.d_depth, depth_type, g, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fdepth,
+                                    F.fmap[0], F.fmap[1], F.fmap[2], c->stream));
+  F.cam = g.cam[0]; F.fgeo = g;
+  for (int l = 0; l < levels; l++) F.kcam[l] = kc[l];
+  F.have_frame = true; F.have_depth = true;
+  return RPE_OK;
+}
+
+int rpe_frame_download_level(rpe_context* c, int which, int level, float* out) {
+  session_end(c);
+  if (!c || !out || which < 0 || which > RPE_MAP_DEPTH) return fail(RPE_ERR_ARG, "rpe_frame_download_level: bad argument");
+  auto& F = c->fe;
+  const bool model = which == RPE_MAP_MODEL_VERTEX || which == RPE_MAP_MODEL_NORMAL;
+  if (model ? !F.have_model : !F.have_frame) return fail(RPE_ERR_STATE, model ? "no model" : "no frame");
+  const rpe::PyramidGeometry& g = model ? F.mgeo : F.fgeo;
+  if (level < 0 || level >= g.levels)
+    return fail(RPE_ERR_ARG, "rpe_frame_download_level: level %d of a %d-level %s", level, g.levels, model ? "model" : "frame");
+  if (which == RPE_MAP_DEPTH && !F.have_depth)
+    return fail(RPE_ERR_STATE, "no metric depth: the frame was set by rpe_frame_set_depth, not rpe_frame_set_depth_pyramid");
+  const size_t n = (size_t)g.cam[level].width * g.cam[level].height;
+  const float* src = which == RPE_MAP_DEPTH ? F.fdepth + g.off[level]
+                     : (model ? F.mmap[which - RPE_MAP_MODEL_VERTEX] : F.fmap[which]) + 3 * g.off[level];
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, src, n * (which == RPE_MAP_DEPTH ? 1 : 3) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RPE_OK;
+}
+
+int rpe_frame_level_camera(rpe_context* c, int level, int model, rpe_camera* out) {
+  if (!c || !out) return fail(RPE_ERR_ARG, "rpe_frame_level_camera: bad argument");
+  auto& F = c->fe;
+  if (model ? !F.have_model : !F.have_frame) return fail(RPE_ERR_STATE, model ? "no model" : "no frame");
+  const int levels = model ? F.mgeo.levels : F.fgeo.levels;
+  if (level < 0 || level >= levels)
+    return fail(RPE_ERR_ARG, "rpe_frame_level_camera: level %d of a %d-level %s", level, levels, model ? "model" : "frame");
+  *out = model ? F.mkcam[level] : F.kcam[level];
   return RPE_OK;
 }
 
@@ -120,11 +230,13 @@ int rpe_model_from_frame(rpe_context* c, const double* pose12) {
   auto& F = c->fe;
   if (!F.have_frame) return fail(RPE_ERR_STATE, "no frame: call rpe_frame_set_depth first");
   HIP_TRY(hipSetDevice(c->device));
-  const int64_t n = (int64_t)F.cam.width * F.cam.height;
+  const int64_t n = F.fgeo.off[F.fgeo.levels];   // every level (one level: width * height)
   int rc = ensure_maps(c, F.mmap, 2, &F.mcap, n);
   if (rc) return rc;
   HIP_TRY(rpe::launch_to_world(F.fmap[0], F.fmap[1], n, pose_f(pose12), F.mmap[0], F.mmap[1], c->stream));
   F.mcam = F.cam;
+  F.mgeo = F.fgeo;
+  for (int l = 0; l < RPE_MAX_LEVELS; l++) F.mkcam[l] = F.kcam[l];
   std::memcpy(F.mpose, pose12, sizeof(F.mpose));
   F.have_model = true;
   return RPE_OK;
@@ -144,8 +256,37 @@ int rpe_model_upload(rpe_context* c, const float* vertex_w, const float* normal_
   HIP_TRY(hipMemcpyAsync(F.mmap[1], normal_w, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the caller may free its buffers on return
   F.mcam = k;
+  one_level(*cam, k, F.mkcam, &F.mgeo);
   std::memcpy(F.mpose, pose12, sizeof(F.mpose));
   F.have_model = true;
+  return RPE_OK;
+}
+
+int rpe_model_build_pyramid(rpe_context* c, int levels) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  auto& F = c->fe;
+  if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_from_frame or rpe_model_upload first");
+  rpe_camera kc[RPE_MAX_LEVELS];
+  rpe::PyramidGeometry g;
+  int rc = plan_levels(F.mkcam[0], levels, kc, &g);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = (size_t)g.off[levels] * 3 * sizeof(float);
+  if (F.mcap < bytes) {   // grow, keeping level 0
+    float* fresh[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++) {
+      HIP_TRY(hipMalloc((void**)&fresh[k], bytes));
+      HIP_TRY(hipMemcpyAsync(fresh[k], F.mmap[k], (size_t)g.cam[0].width * g.cam[0].height * 3 * sizeof(float), hipMemcpyDeviceToDevice,
+                             c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 2; k++) { HIP_TRY(hipFree(F.mmap[k])); F.mmap[k] = fresh[k]; }
+    F.mcap = bytes;
+  }
+  HIP_TRY(rpe::launch_model_pyramid(g, F.mmap[0], F.mmap[1], c->stream));
+  F.mgeo = g;
+  for (int l = 0; l < levels; l++) F.mkcam[l] = kc[l];
   return RPE_OK;
 }
 
@@ -156,7 +297,7 @@ int rpe_associate(rpe_context* c, const double* pose12, double dist_thr, double 
   if (!pose12 || !(dist_thr >= 0)) return fail(RPE_ERR_ARG, "rpe_associate: bad argument");
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = claim_slots(c, (int64_t)c->fe.cam.width * c->fe.cam.height))) return rc;
-  if ((rc = associate_launch(c, pose12, dist_thr, cos_thr, use_normals, false, matched != nullptr))) return rc;
+  if ((rc = associate_launch(c, level_of(c, 0), pose12, dist_thr, cos_thr, use_normals, false, matched != nullptr))) return rc;
   // read-out without a D2H copy or a stream synchronisation: a tiny kernel stores the counter into pinned host memory and raises a
   // sequence word
   if (matched) {
@@ -168,32 +309,26 @@ int rpe_associate(rpe_context* c, const double* pose12, double dist_thr, double 
   return RPE_OK;
 }
 
-int rpe_icp(rpe_context* c, const rpe_icp_options* o, double* pose12, int* iters_out, double* last_step, double* final_cost,
-    int64_t* matched) {
-  session_end(c);
-  int rc = associate_ready(c);
-  if (rc) return rc;
-  if (!o || !pose12 || o->max_iter < 1 || (o->kind != RPE_RES_P2P && o->kind != RPE_RES_P2PLANE) || !(o->dist_thr >= 0))
-    return fail(RPE_ERR_ARG, "rpe_icp: bad options (kind must be RPE_RES_P2P or RPE_RES_P2PLANE, max_iter >= 1)");
-  if (o->kind == RPE_RES_P2PLANE && !o->use_normals)
-    return fail(RPE_ERR_ARG, "rpe_icp: point-to-plane needs use_normals = 1 (pairs without a frame normal would poison the sums)");
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = claim_slots(c, (int64_t)c->fe.cam.width * c->fe.cam.height))) return rc;
+namespace {
+// the loop of rpe_icp on one pyramid level (o->max_iter rounds, gate o->dist_thr) after claim_slots(c, lv.n); leave_pairs: a fused
+// loop re-pairs under the returned pose at the end, so that the slots hold those pairs
+int icp_level(rpe_context* c, const rpe_icp_options* o, const Level& lv, bool leave_pairs, double* pose12, int* iters_out,
+              double* last_step, double* final_cost, int64_t* matched) {
+  int rc = RPE_OK;
   int it = 0;
   double step = 0, cost = 0, pairs = 0;
   bool host_rounds = false;
-  auto& F = c->fe;
-  const int64_t n = (int64_t)F.cam.width * F.cam.height;
+  const int64_t n = lv.n;
   const float dgate = (float)o->dist_thr;
   // one round's kernels, enqueued on the context's stream
   auto round = [&](const double* pose, const rpe::ReduceTarget& rt, bool pose_on_device) -> int {
     if (o->fused) {
-      HIP_TRY(rpe::launch_icp_fused(F.fmap[0], F.fmap[1], n, F.mmap[0], F.mmap[1], F.mcam, pose_f(F.mpose), dgate * dgate,
+      HIP_TRY(rpe::launch_icp_fused(lv.f[0], lv.f[1], n, lv.m[0], lv.m[1], lv.mcam, pose_f(c->fe.mpose), dgate * dgate,
           (float)o->cos_thr,
                                     o->use_normals, o->kind, pose, rt, c->stream));
       return RPE_OK;
     }
-    int r = associate_launch(c, pose, o->dist_thr, o->cos_thr, o->use_normals, pose_on_device, false);
+    int r = associate_launch(c, lv, pose, o->dist_thr, o->cos_thr, o->use_normals, pose_on_device, false);
     if (r) return r;
     HIP_TRY(rpe::launch_normal_eq(c->arrays(), o->kind, 0, pose, rt, c->stream));
     return RPE_OK;
@@ -219,7 +354,7 @@ int rpe_icp(rpe_context* c, const rpe_icp_options* o, double* pose12, int* iters
       (void)resident_run_shape(grid, nacc, max_rows, rows_auto, &rt);
       c->seq = base + (unsigned long long)o->max_iter + 1;
       rt.seq = c->seq;
-      HIP_TRY(rpe::launch_icp_resident(F.fmap[0], F.fmap[1], n, F.mmap[0], F.mmap[1], F.mcam, pose_f(F.mpose), dgate * dgate,
+      HIP_TRY(rpe::launch_icp_resident(lv.f[0], lv.f[1], n, lv.m[0], lv.m[1], lv.mcam, pose_f(c->fe.mpose), dgate * dgate,
           (float)o->cos_thr, o->use_normals,
                                        o->kind, nullptr, base, o->max_iter, rt, c->stream));
     } else {
@@ -249,7 +384,7 @@ int rpe_icp(rpe_context* c, const rpe_icp_options* o, double* pose12, int* iters
     int grid = 0, nacc = 0, max_rows = 1, rows_auto = 1;
     rpe::icp_resident_geometry(n, o->kind, c->max_blocks, &grid, &nacc, &max_rows, &rows_auto);
     auto launch = [&](const rpe::ReduceTarget& rt, unsigned long long base) -> hipError_t {
-      return rpe::launch_icp_resident(F.fmap[0], F.fmap[1], n, F.mmap[0], F.mmap[1], F.mcam, pose_f(F.mpose), dgate * dgate,
+      return rpe::launch_icp_resident(lv.f[0], lv.f[1], n, lv.m[0], lv.m[1], lv.mcam, pose_f(c->fe.mpose), dgate * dgate,
           (float)o->cos_thr, o->use_normals,
                                       o->kind, (const unsigned long long*)c->ctl, base, o->max_iter, rt, c->stream);
     };
@@ -277,11 +412,67 @@ int rpe_icp(rpe_context* c, const rpe_icp_options* o, double* pose12, int* iters
     }
   }
   // leave the pairs in the slots
-  if (o->fused && (rc = associate_launch(c, pose12, o->dist_thr, o->cos_thr, o->use_normals, false, false))) return rc;
+  if (leave_pairs && o->fused && (rc = associate_launch(c, lv, pose12, o->dist_thr, o->cos_thr, o->use_normals, false, false))) return rc;
   if (iters_out) *iters_out = it;
   if (last_step) *last_step = step;
   if (final_cost) *final_cost = cost;
   if (matched) *matched = (int64_t)pairs;   // pairs of the last round (the record's weight sum)
+  return RPE_OK;
+}
+
+}  // namespace
+
+int rpe_icp(rpe_context* c, const rpe_icp_options* o, double* pose12, int* iters_out, double* last_step, double* final_cost,
+    int64_t* matched) {
+  session_end(c);
+  int rc = associate_ready(c);
+  if (rc) return rc;
+  if (!o || !pose12 || o->max_iter < 1 || (o->kind != RPE_RES_P2P && o->kind != RPE_RES_P2PLANE) || !(o->dist_thr >= 0))
+    return fail(RPE_ERR_ARG, "rpe_icp: bad options (kind must be RPE_RES_P2P or RPE_RES_P2PLANE, max_iter >= 1)");
+  if (o->kind == RPE_RES_P2PLANE && !o->use_normals)
+    return fail(RPE_ERR_ARG, "rpe_icp: point-to-plane needs use_normals = 1 (pairs without a frame normal would poison the sums)");
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = claim_slots(c, (int64_t)c->fe.cam.width * c->fe.cam.height))) return rc;
+  return icp_level(c, o, level_of(c, 0), true, pose12, iters_out, last_step, final_cost, matched);
+}
+
+int rpe_icp_pyramid(rpe_context* c, const rpe_icp_options* o, int levels, const int* iters_per_level, const double* dist_thr_per_level,
+                    double* pose12, int* iters_out, double* last_step, double* final_cost, int64_t* matched) {
+  session_end(c);
+  int rc = associate_ready(c);
+  if (rc) return rc;
+  if (!o || !pose12 || !iters_per_level || (o->kind != RPE_RES_P2P && o->kind != RPE_RES_P2PLANE) || !(o->dist_thr >= 0))
+    return fail(RPE_ERR_ARG, "rpe_icp_pyramid: bad options (kind must be RPE_RES_P2P or RPE_RES_P2PLANE)");
+  if (o->kind == RPE_RES_P2PLANE && !o->use_normals)
+    return fail(RPE_ERR_ARG, "rpe_icp_pyramid: point-to-plane needs use_normals = 1");
+  if (levels < 1 || levels > RPE_MAX_LEVELS) return fail(RPE_ERR_ARG, "rpe_icp_pyramid: levels must be 1 .. %d (got %d)", RPE_MAX_LEVELS,
+      levels);
+  for (int l = 0; l < levels; l++) {
+    if (iters_per_level[l] < (l == 0 ? 1 : 0))
+      return fail(RPE_ERR_ARG, "rpe_icp_pyramid: level %d needs %s rounds (got %d)", l, l == 0 ? ">= 1" : ">= 0", iters_per_level[l]);
+    if (dist_thr_per_level && !(dist_thr_per_level[l] >= 0))
+      return fail(RPE_ERR_ARG, "rpe_icp_pyramid: bad distance gate at level %d", l);
+  }
+  auto& F = c->fe;
+  if (F.fgeo.levels < levels) return fail(RPE_ERR_STATE, "rpe_icp_pyramid: the frame has %d level(s), %d asked (rpe_frame_set_depth_pyramid)",
+      F.fgeo.levels, levels);
+  if (F.mgeo.levels < levels) return fail(RPE_ERR_STATE, "rpe_icp_pyramid: the model has %d level(s), %d asked (rpe_model_from_frame of a "
+      "pyramid frame, or rpe_model_build_pyramid)", F.mgeo.levels, levels);
+  HIP_TRY(hipSetDevice(c->device));
+  for (int l = levels - 1; l >= 0; l--) {
+    int it = 0;
+    if (iters_per_level[l] > 0) {
+      rpe_icp_options lo = *o;
+      lo.max_iter = iters_per_level[l];
+      if (dist_thr_per_level) lo.dist_thr = dist_thr_per_level[l];
+      const Level lv = level_of(c, l);
+      if ((rc = claim_slots(c, lv.n))) return rc;
+      rc = icp_level(c, &lo, lv, l == 0, pose12, &it, l == 0 ? last_step : nullptr, l == 0 ? final_cost : nullptr,
+                     l == 0 ? matched : nullptr);
+    }
+    if (iters_out) iters_out[l] = it;
+    if (rc) return rc;
+  }
   return RPE_OK;
 }
 

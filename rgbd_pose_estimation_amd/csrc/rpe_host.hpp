@@ -148,6 +148,12 @@ struct rpe_context {
     size_t mcap = 0;
     double mpose[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
     int* d_count = nullptr;
+    // coarse-to-fine pyramid: fp32 level cameras, level offsets into the maps above and level counts (cam / mcam = level 0), the fp64
+    // level cameras they were cast from, and the metric depth of every level (rpe_frame_set_depth_pyramid only: have_depth)
+    rpe::PyramidGeometry fgeo{}, mgeo{};
+    rpe_camera kcam[RPE_MAX_LEVELS] = {}, mkcam[RPE_MAX_LEVELS] = {};
+    float* fdepth = nullptr; size_t fdcap = 0;
+    bool have_depth = false;
   } fe;
 
   rpe::DeviceArrays arrays() const {

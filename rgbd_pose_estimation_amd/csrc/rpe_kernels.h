@@ -212,6 +212,15 @@ hipError_t launch_prosac_order(const float* d_w, int n, int top_k, unsigned int*
 // ---- front end (rpe_frontend.hip): depth frame -> maps -> projective association; fp32 throughout
 struct Camera { float fx, fy, cx, cy; int width, height; };
 struct PoseF { float R[9]; float t[3]; };   // Xc = R Xw + t, R row-major
+// coarse-to-fine pyramid: level l is (width >> l) x (height >> l) pixels, stored at pixel offset off[l] of the concatenated maps
+// (off[l] is a multiple of 4: every level starts 16-byte aligned); block0 is set by the launchers
+constexpr int kMaxLevels = 4;
+struct PyramidGeometry { Camera cam[kMaxLevels]; int64_t off[kMaxLevels + 1]; int block0[kMaxLevels + 1]; int levels; };
+// F1p (two launches): depth_out := metric depth of every level, vmap / nmap / bmap := F1's maps of every level
+hipError_t launch_frame_pyramid(const void* d_depth, int depth_type, const PyramidGeometry& P, float scale, float dmin, float dmax,
+                                float max_jump, float* depth_out, float* vmap, float* nmap, float* bmap, hipStream_t s);
+// F2p (one launch): levels 1 .. P.levels-1 of the model maps from their level 0
+hipError_t launch_model_pyramid(const PyramidGeometry& P, float* mv, float* mn, hipStream_t s);
 // depth_type 0 = uint16 (metres = value * scale), 1 = float32 (metres = value * scale); maps are 3 x (width*height) floats
 hipError_t launch_frame_maps(const void* d_depth, int depth_type, const Camera& cam, float scale, float dmin, float dmax,
     float max_jump,

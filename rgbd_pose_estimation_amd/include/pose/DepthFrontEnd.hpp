@@ -39,6 +39,8 @@ struct IcpOptions {
   bool use_normals = true, device_resident = false, fused = true;
 };
 struct IcpResult { int iterations = 0; double last_step = 0, cost = 0; long long pairs = 0; };
+// coarse-to-fine ICP: rounds run per level (0 = finest); the rest as IcpResult, of level 0
+struct PyramidIcpResult : IcpResult { int level_iterations[RPE_MAX_LEVELS] = {0, 0, 0, 0}; };
 
 class DepthFrontEnd {
  public:
@@ -59,6 +61,13 @@ class DepthFrontEnd {
       const DepthRange& r = DepthRange::millimetres()) { set(depth, RPE_DEPTH_U16, cam, r); }
   void setDepth(const float* depth, const PinholeCamera& cam,
       const DepthRange& r = DepthRange::metres()) { set(depth, RPE_DEPTH_F32, cam, r); }
+  // the frame plus its coarse-to-fine pyramid of `levels` levels (rpe_frame_set_depth_pyramid)
+  void setDepthPyramid(const unsigned short* depth, const PinholeCamera& cam, int levels,
+      const DepthRange& r = DepthRange::millimetres()) { set(depth, RPE_DEPTH_U16, cam, r, levels); }
+  void setDepthPyramid(const float* depth, const PinholeCamera& cam, int levels,
+      const DepthRange& r = DepthRange::metres()) { set(depth, RPE_DEPTH_F32, cam, r, levels); }
+  // levels 1 .. levels-1 of the model from its level 0 (for a model given by setModel)
+  void buildModelPyramid(int levels) { check(rpe_model_build_pyramid(_ctx, levels), "rpe_model_build_pyramid"); }
   // the current frame, seen from T_cw, becomes the model the next frames are registered against
   void setModelFromFrame(const Pose& T_cw) {
     double p[12]; pose12(T_cw, p);
@@ -76,6 +85,15 @@ class DepthFrontEnd {
     check(rpe_frame_download(_ctx, which, m.data()), "rpe_frame_download");
     return m;
   }
+  // one map of one pyramid level: RPE_MAP_* (3 x w_l*h_l) or RPE_MAP_DEPTH (1 x w_l*h_l metres)
+  MatrixX<float> map(int which, int level) const {
+    rpe_camera k;
+    const bool model = which == RPE_MAP_MODEL_VERTEX || which == RPE_MAP_MODEL_NORMAL;
+    check(rpe_frame_level_camera(_ctx, level, model ? 1 : 0, &k), "rpe_frame_level_camera");
+    MatrixX<float> m(which == RPE_MAP_DEPTH ? 1 : 3, k.width * k.height);
+    check(rpe_frame_download_level(_ctx, which, level, m.data()), "rpe_frame_download_level");
+    return m;
+  }
   long long associate(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
     double p[12]; pose12(guess, p);
     int64_t m = 0;
@@ -91,6 +109,23 @@ class DepthFrontEnd {
     IcpResult r;
     int64_t m = 0;
     check(rpe_icp(_ctx, &opt, p, &r.iterations, &r.last_step, &r.cost, &m), "rpe_icp");
+    r.pairs = (long long)m;
+    pose = pose_of(p);
+    return r;
+  }
+  // coarse-to-fine ICP from `pose` (in/out): iters[l] rounds and gate dist_thr[l] at level l (0 = finest; dist_thr empty: o.dist_thr)
+  PyramidIcpResult icpPyramid(Pose& pose, const std::vector<int>& iters, const std::vector<double>& dist_thr = std::vector<double>(),
+                              const IcpOptions& o = IcpOptions()) {
+    if (!dist_thr.empty() && dist_thr.size() != iters.size()) throw DeviceError(RPE_ERR_ARG, "icpPyramid: one gate per level");
+    double p[12]; pose12(pose, p);
+    rpe_icp_options opt;
+    opt.kind = o.kind; opt.max_iter = o.max_iter; opt.tol = o.tol; opt.dist_thr = o.dist_thr; opt.cos_thr = o.cos_thr;
+    opt.use_normals = o.use_normals; opt.device_resident = o.device_resident; opt.fused = o.fused;
+    PyramidIcpResult r;
+    int64_t m = 0;
+    check(rpe_icp_pyramid(_ctx, &opt, (int)iters.size(), iters.data(), dist_thr.empty() ? nullptr : dist_thr.data(), p, r.level_iterations,
+                          &r.last_step, &r.cost, &m), "rpe_icp_pyramid");
+    for (size_t l = 0; l < iters.size(); l++) r.iterations += r.level_iterations[l];
     r.pairs = (long long)m;
     pose = pose_of(p);
     return r;
@@ -126,9 +161,11 @@ class DepthFrontEnd {
  private:
   static rpe_camera cam_of(const PinholeCamera& c) { rpe_camera k; k.fx = c.fx; k.fy = c.fy; k.cx = c.cx; k.cy = c.cy;
       k.width = c.width; k.height = c.height; return k; }
-  void set(const void* depth, int type, const PinholeCamera& cam, const DepthRange& r) {
+  void set(const void* depth, int type, const PinholeCamera& cam, const DepthRange& r, int levels = 1) {
     const rpe_camera k = cam_of(cam);
-    check(rpe_frame_set_depth(_ctx, depth, type, &k, r.scale, r.dmin, r.dmax, r.max_jump), "rpe_frame_set_depth");
+    if (levels == 1) check(rpe_frame_set_depth(_ctx, depth, type, &k, r.scale, r.dmin, r.dmax, r.max_jump), "rpe_frame_set_depth");
+    else check(rpe_frame_set_depth_pyramid(_ctx, depth, type, &k, r.scale, r.dmin, r.dmax, r.max_jump, levels),
+               "rpe_frame_set_depth_pyramid");
     _pixels = cam.width * cam.height;
   }
   rpe_context* _ctx;
