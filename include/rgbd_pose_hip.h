@@ -444,7 +444,7 @@ int rpe_icp(rpe_context* ctx, const rpe_icp_options* opt, double* pose12, int* i
  * count (fp32, no FMA contraction).  Frame maps of level l = F1's arithmetic on the level's metric depth (scale 1, same dmin / dmax /
  * max_jump) with the level camera; level 0 is bitwise what rpe_frame_set_depth builds.  Model levels: rpe_model_from_frame moves
  * every level of the frame (F2 on each); rpe_model_build_pyramid resizes an uploaded level 0 (KinectFusion): block a = (2u,2v),
- * b = (2u+1,2v), c = (2u,2v+1), d = (2u+1,2v+1) of level l; a vertex is valid iff all four are (no NaN component), value
+ * b = (2u+1,2v), c = (2u,2v+1), d = (2u+1,2v+1) of level l; a vertex is valid iff all four level-l values have no NaN component, value
  * (((a + b) + c) + d) * 0.25f; a normal is valid iff all four are, the same sum divided by sqrtf(x*x + y*y + z*z), NaN at length 0;
  * vertices and normals independently. */
 enum { RPE_MAX_LEVELS = 4, RPE_MAP_DEPTH = 5 };

@@ -222,7 +222,8 @@ __global__ __launch_bounds__(kFeBlock) void to_world_kernel(const float* __restr
 // c = (2u, 2v+1), d = (2u+1, 2v+1).  Vertex: valid iff all four are (no NaN component), value (((a + b) + c) + d) * 0.25f.  Normal:
 // valid iff all four are, the same sum divided by its length sqrtf((x*x + y*y) + z*z), NaN at length 0.  One launch for every
 // level: a thread of level l evaluates its quad tree down to level 0 (Resize<l>), whose inner nodes are bit for bit the level-1 ..
-// l-1 values other threads write.
+// l-1 values other threads write.  A node is valid for the level above iff its value has no NaN component, as that level reads it
+// from memory: four valid members can still give a NaN component (Inf + -Inf, Inf / Inf).
 template <int LV> struct Resize {
   // the block's four members are summed in a rolled loop above level 1 (the unrolled quad tree of level 3 would hold 64 pixels live)
   static constexpr int kUnroll = LV == 1 ? 4 : 1;
@@ -240,13 +241,13 @@ template <int LV> struct Resize {
     if (!NORMAL) {
 #pragma unroll
       for (int k = 0; k < 3; k++) o[k] = ok ? s[k] * 0.25f : qnan();
-      return ok;
+      return o[0] == o[0] && o[1] == o[1] && o[2] == o[2];
     }
     const float len = sqrtf(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
     const bool good = ok && len > 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; k++) o[k] = good ? s[k] / len : qnan();
-    return good;
+    return o[0] == o[0] && o[1] == o[1] && o[2] == o[2];
   }
 };
 template <> struct Resize<0> {

@@ -1,6 +1,7 @@
 """GPU parity of the coarse-to-fine pyramids (F1p / F2p of csrc/rpe_frontend.hip, rpe_icp_pyramid) against tests/pyramid_oracle.py.
 Maps of every level are BIT-EXACT; the pyramid ICP returns the same bits as the chained single-level calls it stands for, and one
 level of it is rpe_icp."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -10,7 +11,7 @@ import pytest
 
 import pyramid_oracle as PO
 from frontend_util import FO, SMALL_CAM, oracle_icp, pose12, rot, two_views
-from rgbd_pose_estimation_amd import _lib as L, simulator as S
+from rgbd_pose_estimation_amd import _lib as L, api, simulator as S
 from util import rot_err
 
 pytestmark = pytest.mark.gpu
@@ -128,23 +129,160 @@ def test_icp_pyramid_one_level_is_icp(gpu_ctx_factory, form):
     assert ctx.n == FULL_CAM[4] * FULL_CAM[5]
 
 
-@pytest.mark.parametrize("form", ["host", "fused"])
-def test_icp_pyramid_is_the_chained_single_level_run(gpu_ctx_factory, form):
-    """L = 3 against what a caller does today: per level a fresh context, the level's metric depth uploaded as a frame of the level camera."""
-    iters, thr = (4, 3, 3), (0.15, 0.2, 0.3)
-    ctx = gpu_ctx_factory()
-    dA, dB, pA, pB = load_pyramid_pair(ctx, FULL_CAM, 3)
-    got = ctx.icp_pyramid(pA, iters, thr, L.RES_P2PLANE, 1e-7, 0.8, **FORMS[form])
-    zA, zB = PO.depth_pyramid(dA, 1.0, *RANGE, 3), PO.depth_pyramid(dB, 1.0, *RANGE, 3)
-    p, its = pA, {}
-    for l in (2, 1, 0):
-        c = gpu_ctx_factory()
-        cam_l = PO.level_camera(FULL_CAM, l)
-        c.frame_set_depth(zA[l], cam_l, 1.0, *RANGE)
+@contextlib.contextmanager
+def fresh_context():
+    c = api.Context(0)
+    try:
+        yield c
+    finally:
+        c.close()
+
+
+def chained_icp(load_model, zB, cam, pose, iters, thr, form, tol=1e-7):
+    """What a caller does without rpe_icp_pyramid: per level (coarse to fine) a fresh context holding the level's model
+    (load_model(ctx, level)) and the level's metric depth uploaded as a frame of the level camera; rpe_icp with that level's rounds
+    and gate; a level of 0 rounds is skipped.  Returns what icp_pyramid returns."""
+    p, its, rest = np.array(pose, np.float64), [0] * len(iters), None
+    for l in reversed(range(len(iters))):
+        if iters[l] == 0:
+            continue
+        with fresh_context() as c:
+            load_model(c, l)
+            c.frame_set_depth(zB[l], PO.level_camera(cam, l), 1.0, *RANGE)
+            p, its[l], *rest = c.icp(p, L.RES_P2PLANE, iters[l], tol, thr[l], 0.8, **FORMS[form])
+    return (p, tuple(its), *rest)
+
+
+def model_of_frames(zA, cam, pA):
+    def load(c, l):
+        c.frame_set_depth(zA[l], PO.level_camera(cam, l), 1.0, *RANGE)
         c.model_from_frame(pA)
-        c.frame_set_depth(zB[l], cam_l, 1.0, *RANGE)
-        p, its[l], step, cost, pairs = c.icp(p, L.RES_P2PLANE, iters[l], 1e-7, thr[l], 0.8, **FORMS[form])
-    assert np.array_equal(got[0], p) and got[1] == (its[0], its[1], its[2]) and got[2:] == (step, cost, pairs), (got, p, its)
+    return load
+
+
+def assert_same_run(got, want):
+    """bit for bit: pose, rounds per level, and the last level's step, cost and pairs"""
+    assert np.array_equal(got[0], want[0]) and got[1] == want[1] and got[2:] == want[2:], (got, want)
+
+
+CHAINS = {"L3": ((4, 3, 3), (0.15, 0.2, 0.3)),
+          "L4_one_round_level": ((4, 3, 1, 3), (0.15, 0.2, 0.3, 0.4)),
+          "L4_no_round_level": ((4, 0, 3, 2), (0.15, 0.2, 0.3, 0.4))}
+
+
+@pytest.mark.parametrize("chain", list(CHAINS))
+@pytest.mark.parametrize("form", list(FORMS))
+def test_icp_pyramid_is_the_chained_single_level_run(gpu_ctx_factory, form, chain):
+    """Every form, up to RPE_MAX_LEVELS levels, levels of 1 round (the per-round path even in the resident forms) and of none: the
+    pyramid returns the bits of the chained single-level runs."""
+    iters, thr = CHAINS[chain]
+    levels = len(iters)
+    ctx = gpu_ctx_factory()
+    dA, dB, pA, pB = load_pyramid_pair(ctx, FULL_CAM, levels)
+    got = ctx.icp_pyramid(pA, iters, thr, L.RES_P2PLANE, 1e-7, 0.8, **FORMS[form])
+    zA, zB = PO.depth_pyramid(dA, 1.0, *RANGE, levels), PO.depth_pyramid(dB, 1.0, *RANGE, levels)
+    assert_same_run(got, chained_icp(model_of_frames(zA, FULL_CAM, pA), zB, FULL_CAM, pA, iters, thr, form))
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_icp_pyramid_stops_early_at_a_coarse_level(gpu_ctx_factory, form):
+    """tol ends coarse levels before their rounds run out; every level's round count is the chained runs' count."""
+    iters, thr, tol = (10, 12, 12, 12), (0.15, 0.2, 0.3, 0.4), 1e-4
+    ctx = gpu_ctx_factory()
+    dA, dB, pA, pB = load_pyramid_pair(ctx, FULL_CAM, 4)
+    got = ctx.icp_pyramid(pA, iters, thr, L.RES_P2PLANE, tol, 0.8, **FORMS[form])
+    zA, zB = PO.depth_pyramid(dA, 1.0, *RANGE, 4), PO.depth_pyramid(dB, 1.0, *RANGE, 4)
+    want = chained_icp(model_of_frames(zA, FULL_CAM, pA), zB, FULL_CAM, pA, iters, thr, form, tol)
+    assert_same_run(got, want)
+    assert any(0 < got[1][l] < iters[l] for l in (1, 2, 3)), got[1]
+
+
+# the model's principal point differs from the frame's: each level must associate through the model's own level camera
+MODEL_CAMS = {"same": FULL_CAM, "shifted": (FULL_CAM[0], FULL_CAM[1], FULL_CAM[2] + 3.5, FULL_CAM[3] - 2.25, FULL_CAM[4], FULL_CAM[5])}
+
+
+def uploaded_pair(mcam):
+    """frame B of the full camera; the model: the world maps of view A seen by mcam (level 0, as a caller uploads it)."""
+    (RA, tA, _), (RB, tB, dB) = two_views(FULL_CAM, MOTION, noise=0.002, seed=0)
+    dA = S.render_depth(RA, tA, mcam, noise_sigma=0.002, rng=np.random.default_rng(7))
+    V, N, _ = FO.frame_maps(dA, mcam, 1.0, *RANGE)
+    pA = pose12(RA, tA)
+    MV0, MN0 = FO.to_world(V, N, pA)
+    return dB, pA, MV0, MN0
+
+
+@pytest.mark.parametrize("model_cam", list(MODEL_CAMS))
+@pytest.mark.parametrize("form", list(FORMS))
+def test_icp_pyramid_on_an_uploaded_model(gpu_ctx_factory, form, model_cam):
+    """rpe_model_upload + rpe_model_build_pyramid, then the pyramid ICP: the bits of the chained runs whose models are uploaded
+    levels of PO.model_pyramid with their level cameras."""
+    iters, thr, levels = (4, 3, 1, 3), (0.15, 0.2, 0.3, 0.4), 4
+    mcam = MODEL_CAMS[model_cam]
+    dB, pA, MV0, MN0 = uploaded_pair(mcam)
+    ctx = gpu_ctx_factory()
+    ctx.model_upload(MV0, MN0, mcam, pA)
+    ctx.model_build_pyramid(levels)
+    set_pyramid(ctx, dB, FULL_CAM, 1.0, levels)
+    got = ctx.icp_pyramid(pA, iters, thr, L.RES_P2PLANE, 1e-7, 0.8, **FORMS[form])
+    model = PO.model_pyramid(MV0, MN0, mcam, levels)
+
+    def load(c, l):
+        c.model_upload(*model[l], PO.level_camera(mcam, l), pA)
+    assert_same_run(got, chained_icp(load, PO.depth_pyramid(dB, 1.0, *RANGE, levels), FULL_CAM, pA, iters, thr, form))
+
+
+@pytest.mark.parametrize("model_cam", list(MODEL_CAMS))
+def test_icp_pyramid_on_an_uploaded_model_matches_the_oracle_loop(gpu_ctx_factory, oracle, model_cam):
+    iters, thr, levels = (4, 3, 1, 3), (0.15, 0.2, 0.3, 0.4), 4
+    mcam = MODEL_CAMS[model_cam]
+    dB, pA, MV0, MN0 = uploaded_pair(mcam)
+    ctx = gpu_ctx_factory()
+    ctx.model_upload(MV0, MN0, mcam, pA)
+    ctx.model_build_pyramid(levels)
+    set_pyramid(ctx, dB, FULL_CAM, 1.0, levels)
+    got = ctx.icp_pyramid(pA, iters, thr, L.RES_P2PLANE, 0.0, 0.8)
+    B, model = PO.frame_pyramid(dB, FULL_CAM, 1.0, *RANGE, levels), PO.model_pyramid(MV0, MN0, mcam, levels)
+    p = pA
+    for l in reversed(range(levels)):
+        p, _ = oracle_icp(oracle, B[l][1], B[l][2], B[l][3], *model[l], PO.level_camera(mcam, l), p, pA, L.RES_P2PLANE, iters[l], thr[l],
+                          0.8)
+    assert got[1] == iters
+    assert rot_err(got[0][:9].reshape(3, 3), p[:9].reshape(3, 3)) < 1e-6 and np.linalg.norm(got[0][9:] - p[9:]) < 1e-6
+
+
+SMALL_PYR_CAM = (91.4, 91.4, 49.5, 37.5, 100, 76)     # level 2 is 25 x 19: 475 pixels, n % 4 = 3
+
+
+def pyramid_icp_run(ctx, cam, levels, upload, form):
+    """frame and model pyramids of one scene on ctx (the model from frame A, or uploaded and resized), then rpe_icp_pyramid; returns
+    the result and every level's frame and model maps."""
+    (RA, tA, dA), (RB, tB, dB) = two_views(cam, MOTION, noise=0.002, seed=levels)
+    pA = pose12(RA, tA)
+    if upload:
+        V, N, _ = FO.frame_maps(dA, cam, 1.0, *RANGE)
+        ctx.model_upload(*FO.to_world(V, N, pA), cam, pA)
+        ctx.model_build_pyramid(levels)
+    else:
+        set_pyramid(ctx, dA, cam, 1.0, levels)
+        ctx.model_from_frame(pA)
+    set_pyramid(ctx, dB, cam, 1.0, levels)
+    got = ctx.icp_pyramid(pA, (4, 3, 1, 3)[:levels], (0.15, 0.2, 0.3, 0.4)[:levels], L.RES_P2PLANE, 1e-7, 0.8, **FORMS[form])
+    maps = [ctx.frame_download(m, l) for l in range(levels)
+            for m in (L.MAP_DEPTH, L.MAP_VERTEX, L.MAP_NORMAL, L.MAP_BEARING, L.MAP_MODEL_VERTEX, L.MAP_MODEL_NORMAL)]
+    return got, maps
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_icp_pyramid_context_reuse_across_cameras(gpu_ctx_factory, form):
+    """One context: L = 4 at 640 x 480, then L = 3 at 100 x 76 with an uploaded model, then the first run again.  The level buffers
+    only grow, so each run must not see the offsets, padding or contents another camera left: every result is a fresh context's."""
+    ctx = gpu_ctx_factory()
+    for cam, levels, upload in ((FULL_CAM, 4, False), (SMALL_PYR_CAM, 3, True), (FULL_CAM, 4, False)):
+        got, maps = pyramid_icp_run(ctx, cam, levels, upload, form)
+        with fresh_context() as c:
+            want, want_maps = pyramid_icp_run(c, cam, levels, upload, form)
+        assert_same_run(got, want)
+        assert all(same(a, b) for a, b in zip(maps, want_maps)), (cam, levels)
 
 
 def test_icp_pyramid_matches_the_oracle_loop(gpu_ctx_factory, oracle):

@@ -112,3 +112,138 @@ def test_library_exports_the_pyramid_entry_points():
     want = {"rpe_frame_set_depth_pyramid", "rpe_frame_download_level", "rpe_frame_level_camera", "rpe_model_build_pyramid", "rpe_icp_pyramid"}
     assert want <= exported, sorted(want - exported)
     assert want <= set(L.SYMBOLS)
+
+
+# ---- the edges of the jump gate, the smallest levels and the model resize (the cases the GPU edge tests lean on)
+f32 = np.float32
+
+
+def _one_block(a, b, e, f, max_jump):
+    return PO.downsample_depth(np.array([[a, b], [e, f]], f32), max_jump)[0, 0]
+
+
+def _mean(*xs):
+    s = f32(xs[0])
+    for x in xs[1:]:
+        s = f32(s + f32(x))
+    return f32(s / f32(len(xs)))
+
+
+def test_gate_tie_at_max_jump_is_kept():
+    """On the 1/8 grid in [1, 2) every difference is exact: members exactly max_jump = 0.125 above or below the top-left pixel are
+    averaged (the gate is <=), one 2 * max_jump away is not."""
+    got = _one_block(1.25, 1.375, 1.375, 1.5, 0.125)
+    assert got == _mean(1.25, 1.375, 1.375) and got != f32(1.25)
+    assert _one_block(1.25, 1.125, 1.0, 1.125, 0.125) == _mean(1.25, 1.125, 1.125)
+    assert _one_block(1.5, 1.375, 1.625, 1.625, 0.125) == _mean(1.5, 1.375, 1.625, 1.625)
+
+
+def test_gate_one_ulp_past_max_jump_is_dropped():
+    up = np.nextafter(f32(1.375), f32(2))        # 0.125 + 2^-23 above 1.25
+    dn = np.nextafter(f32(1.125), f32(0))        # 0.125 + 2^-23 below 1.25
+    inside = np.nextafter(f32(1.375), f32(0))    # 0.125 - 2^-23 above
+    assert f32(up - f32(1.25)) > f32(0.125) and f32(f32(1.25) - dn) > f32(0.125)
+    assert _one_block(1.25, up, dn, 1.25, 0.125) == _mean(1.25, 1.25)
+    assert _one_block(1.25, inside, dn, up, 0.125) == _mean(1.25, inside)
+
+
+def test_gate_of_zero_keeps_equal_depths_only():
+    eps = np.nextafter(f32(1.5), f32(2))
+    assert _one_block(1.5, 1.5, eps, 1.25, 0.0) == f32(1.5)
+    assert _one_block(1.5, 1.75, eps, 1.25, 0.0) == f32(1.5)      # only the top-left pixel, count 1
+    assert _one_block(1.5, 1.5, 1.5, 1.5, 0.0) == f32(1.5)
+
+
+def test_nan_top_left_at_a_coarse_level():
+    """An all-invalid level-0 block makes a NaN level-1 pixel; as the top-left of its level-1 block it invalidates the level-2 pixel
+    although its three neighbours are valid."""
+    z = np.full((4, 4), 2.0, f32)
+    z[0:2, 0:2] = np.nan
+    pyr = PO.depth_pyramid(z, 1.0, 0.1, 10.0, 0.1, 3)
+    assert np.isnan(pyr[1][0, 0]) and (pyr[1].reshape(-1)[1:] == f32(2.0)).all()
+    assert np.isnan(pyr[2][0, 0])
+
+
+def test_block_where_only_the_top_left_survives():
+    assert _one_block(1.0, 1.5, 0.5, np.nan, 0.125) == f32(1.0)
+    assert _one_block(1.0, np.nan, np.nan, np.nan, 1e30) == f32(1.0)
+
+
+def test_one_pixel_top_level():
+    """An 8 x 8 camera: level 3 is one pixel, with a vertex and a bearing but no normal (no neighbours)."""
+    cam = (8.0, 8.0, 3.5, 3.5, 8, 8)
+    assert PO.level_camera(cam, 3) == (1.0, 1.0, 0.0, 0.0, 1, 1)
+    rng = np.random.default_rng(5)
+    depth = rng.uniform(1.9, 2.1, (8, 8)).astype(f32)
+    pyr = PO.frame_pyramid(depth, cam, 1.0, 0.1, 10.0, 0.5, 4)
+    assert [p[0].shape for p in pyr] == [(8, 8), (4, 4), (2, 2), (1, 1)]
+    z, V, N, B = pyr[3]
+    assert z[0, 0] == PO.downsample_depth(pyr[2][0], 0.5)[0, 0] and not np.isnan(z).any()
+    assert V.shape == (1, 3) and not np.isnan(V).any() and not np.isnan(B).any()
+    assert np.isnan(N).all()
+
+
+def test_model_resize_partial_nan_and_infinities():
+    """One NaN component invalidates the whole coarse vertex (and normal).  Valid members can sum to a NaN component (Inf + -Inf):
+    that coarse pixel keeps its other components at its level, and the level above treats it as invalid."""
+    w, h = 8, 8
+    MV = np.tile(np.array([0.5, -0.25, 2.0], f32), (w * h, 1))
+    MN = np.tile(np.array([0.0, 0.6, -0.8], f32), (w * h, 1))
+    MV[1, 1] = np.nan                             # (1, 0): block (0, 0) of level 1
+    MN[2 * w + 2, 0] = np.nan                     # (2, 2): block (1, 1) of level 1
+    MV[4, 0], MV[5, 0] = np.inf, -np.inf          # (4, 0), (5, 0): block (2, 0) of level 1 sums Inf + -Inf
+    MV[6 * w + 0, 1] = np.inf                     # (0, 6): block (0, 3) of level 1 is Inf in y
+    MV[6 * w + 2, 1] = -np.inf                    # (2, 6): block (1, 3) of level 1 is -Inf in y; they meet at level 2
+    levels = PO.model_pyramid(MV, MN, (8.0, 8.0, 3.5, 3.5, w, h), 4)
+    (V1, N1), (V2, N2), (V3, N3) = levels[1:]
+    V1, N1 = V1.reshape(4, 4, 3), N1.reshape(4, 4, 3)
+    assert np.isnan(V1[0, 0]).all() and not np.isnan(N1[0, 0]).any()
+    assert np.isnan(N1[1, 1]).all() and not np.isnan(V1[1, 1]).any()
+    assert np.isnan(V1[0, 2, 0]) and V1[0, 2, 1] == f32(-0.25) and V1[0, 2, 2] == f32(2.0)
+    assert V1[3, 0, 1] == np.inf and V1[3, 1, 1] == -np.inf
+    V2 = V2.reshape(2, 2, 3)
+    assert np.isnan(V2[0, 0]).all() and np.isnan(V2[0, 1]).all()          # invalid members below
+    assert np.isnan(V2[1, 0, 1]) and V2[1, 0, 0] == f32(0.5) and V2[1, 0, 2] == f32(2.0)   # Inf + -Inf first met here
+    assert not np.isnan(V2[1, 1]).any()
+    assert np.isnan(V3).all()
+
+
+def test_model_resize_normals_cancel_at_level_two():
+    """Four valid, non-zero level-1 normals n, -n, n, -n: the level-2 sum is exactly zero, so the level-2 normal is NaN (the vertex is
+    not)."""
+    w, h = 4, 4
+    n = np.array([0.36, 0.48, -0.8], f32)
+    MN = np.array([n if (x >> 1) % 2 == 0 else -n for y in range(h) for x in range(w)], f32)
+    MV = np.random.default_rng(2).normal(size=(w * h, 3)).astype(f32)
+    levels = PO.model_pyramid(MV, MN, (4.0, 4.0, 1.5, 1.5, w, h), 3)
+    N1 = levels[1][1]
+    assert not np.isnan(N1).any() and np.array_equal(N1[0], -N1[1])
+    assert np.isnan(levels[2][1]).all() and not np.isnan(levels[2][0]).any()
+
+
+def test_model_resize_infinite_normal_component():
+    w, h = 4, 4
+    MN = np.tile(np.array([0.0, 0.6, -0.8], f32), (w * h, 1))
+    MN[0, 0] = np.inf                             # level 1: sum (Inf, 2.4, -3.2), length Inf -> (NaN, 0, -0)
+    MV = np.zeros((w * h, 3), f32)
+    levels = PO.model_pyramid(MV, MN, (4.0, 4.0, 1.5, 1.5, w, h), 3)
+    N1 = levels[1][1]
+    assert np.isnan(N1[0, 0]) and N1[0, 1] == 0 and N1[0, 2] == 0
+    assert np.isnan(levels[2][1]).all()
+
+
+@pytest.mark.parametrize("u16", [False, True])
+def test_gate_stress_depth_holds_exact_ties(u16):
+    """The generator of the GPU edge tests does put members exactly max_jump and one ulp either side of it from the top-left pixel,
+    and gives level-1 pixels averaged over 1, 2, 3 and 4 members at max_jump = 0.125."""
+    import pyramid_cases as PC
+    z, scale = PC.gate_stress_depth(100, 76, 1, u16)
+    m = PO.metric_depth(z, scale, 0.5, 3.0)
+    a = m[0::2, 0::2]
+    with np.errstate(invalid="ignore"):
+        d = np.abs(np.stack([m[0::2, 1::2], m[1::2, 0::2], m[1::2, 1::2]]) - a)
+        cnt = 1 + (d <= f32(0.125)).sum(0)
+    assert (d == f32(0.125)).sum() > 100
+    assert {1, 2, 3, 4} <= set(np.unique(cnt[~np.isnan(a)]).tolist())
+    if not u16:
+        assert (d == f32(0.125) + f32(2.0 ** -23)).sum() > 10 and (d == f32(0.125) - f32(2.0 ** -23)).sum() > 10
