@@ -468,6 +468,40 @@ int rpe_model_build_pyramid(rpe_context* ctx, int levels);
 int rpe_icp_pyramid(rpe_context* ctx, const rpe_icp_options* opt, int levels, const int* iters_per_level, const double* dist_thr_per_level,
                     double* pose12, int* iters_out, double* last_step, double* final_cost, int64_t* matched);
 
+/* ---- TSDF volume (KinectFusion): frames fused into a truncated signed distance volume, raycast into the model.  With it,
+ * rpe_frame_set_depth_pyramid -> rpe_volume_raycast -> rpe_model_build_pyramid -> rpe_icp_pyramid -> rpe_volume_integrate tracks
+ * frame to model with every map on the GPU.  Conventions, followed bit for bit (fp32, the written order, no FMA contraction):
+ * Geometry is cast once: o = (float)origin, s = (float)voxel_size, tr = (float)trunc, W = (float)max_weight; poses as everywhere in
+ * Part 3 (each of the 12 doubles cast to fp32).  One volume per context: dim[0] x dim[1] x dim[2] voxels, each {tsdf, weight} (two
+ * floats) at index (k * dim[1] + j) * dim[0] + i; weight 0 = unobserved (rpe_volume_init clears everything to 0); the centre of
+ * voxel (i, j, k) is o + ((float)i + 0.5f) * s per axis.
+ * Integrate (the frame's level-0 vertex map under pose12, Xc = R Xw + t), per voxel: pc = R p + t, each row summed left to right;
+ * skipped unless pc.z > 0; pixel uf = floorf(fx * (pc.x / pc.z) + cx + 0.5f), vf likewise, skipped unless inside the image;
+ * d = z of the frame's level-0 vertex map there (the metric depth, NaN where invalid: skipped); sdf = d - pc.z, skipped unless
+ * sdf >= -tr; f = fminf(1.0f, sdf / tr); tsdf := (tsdf * w + f) / (w + 1.0f), w := fminf(w + 1.0f, W).  A skipped voxel is never
+ * stored (its 16-byte pair may be loaded): its bits stay.
+ * Field F(p): g = (p - o) / s - 0.5f per axis, i0 = floorf(g), a = g - i0; known iff 0 <= i0 <= dim - 2 on every axis and all 8
+ * corner weights are > 0; with lerp(x, y, t) = x + (y - x) * t it is: lerps along x for the (j, k) corner pairs (0,0) (1,0) (0,1)
+ * (1,1), then along y ((0,0) with (1,0), (0,1) with (1,1)), then along z.
+ * Raycast (pose12, camera cam, range (dmin, dmax)), ray of pixel (u, v): xn = ((float)u - cx) / fx, yn likewise; samples at camera
+ * depths z_k = dmin + (float)k * s while z_k < dmax, each the camera point (xn * z, yn * z, z) moved to the world (Xw = R^T (Xc - t),
+ * as rpe_model_from_frame).  Hit: the first k where F(z_k) and F(z_k+1) are both known with F_k > 0 and F_k+1 <= 0;
+ * z* = z_k + s * (F_k / (F_k - F_k+1)); model vertex = world point of (xn * z*, yn * z*, z*).  Model normal at that world point pw:
+ * the central differences F(pw + s e) - F(pw - s e) per axis (pw.x + s etc. in fp32), divided by sqrtf(x*x + y*y + z*z); NaN if any
+ * of the six samples is unknown or the length is 0 (the vertex stays).  The gradient points towards free space (the camera), as the
+ * frame normals do.  No hit: NaN vertex and normal.  The model after a raycast is exactly what rpe_model_upload of those maps with
+ * (cam, pose12) leaves: one level, model pose pose12, model camera cam (rpe_model_build_pyramid adds levels). */
+typedef struct { int dim[3]; double voxel_size; double origin[3]; double trunc; int max_weight; } rpe_volume_desc;
+/* (re)allocate and clear the context's volume: dims 2 .. 1024, voxel_size and trunc > 0, origin finite, max_weight >= 1 */
+int rpe_volume_init(rpe_context* ctx, const rpe_volume_desc* desc);
+/* fuse the current frame (level 0) seen from pose12 into the volume; RPE_ERR_STATE without a volume or a frame */
+int rpe_volume_integrate(rpe_context* ctx, const double* pose12);
+/* the model := the volume raycast from pose12 with intrinsics cam over camera depths (dmin, dmax): 0 <= dmin < dmax, both finite,
+ * at most 2^22 samples per ray ((dmax - dmin) / voxel_size); RPE_ERR_STATE without a volume */
+int rpe_volume_raycast(rpe_context* ctx, const double* pose12, const rpe_camera* cam, double dmin, double dmax);
+/* copy the volume to the host: 2 x voxels floats {tsdf, weight} in voxel index order */
+int rpe_volume_download(rpe_context* ctx, float* tsdf_weight);
+
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.
  * 3 x K inputs are column-major doubles whose values are rounded to dtype before use. */

@@ -33,6 +33,7 @@ SYMBOLS = [
     "rpe_normal_eq_joint", "rpe_gn_refine_joint", "rpe_gn_refine_device", "rpe_gn_step", "rpe_comm_unique_id", "rpe_comm_init", "rpe_comm_destroy", "rpe_comm_count", "rpe_device_bus_id", "rpe_gn_step_dist", "rpe_gn_steps_dist", "rpe_gn_steps_dist_device", "rpe_p2p_export", "rpe_p2p_init", "rpe_p2p_pause", "rpe_p2p_destroy", "rpe_host_sqrt_cut", "rpe_hostex_init", "rpe_hostex_destroy", "rpe_host_exchange_open", "rpe_host_exchange_allreduce_f64", "rpe_host_exchange_allreduce_i32", "rpe_host_exchange_set_label", "rpe_host_exchange_labels_collide", "rpe_host_exchange_unlink", "rpe_host_exchange_close", "rpe_gn_refine", "rpe_debug_loop_profile", "rpe_debug_resident_state", "rpe_debug_inject_resident_fault", "rpe_debug_device_gn_update", "rpe_tune_host_thread", "rpe_timing_enable", "rpe_timing_collect", "rpe_timing_calibrate", "rpe_score", "rpe_ransac33_batch", "rpe_ransac_p3p_batch", "rpe_inlier_mask", "rpe_score_session_begin", "rpe_score_session_end", "rpe_prosac_order", "rpe_nl_round", "rpe_run", "rpe_host_hypotheses", "rpe_run_replay",
     "rpe_frame_set_depth", "rpe_frame_download", "rpe_model_from_frame", "rpe_model_upload", "rpe_associate", "rpe_icp",
     "rpe_frame_set_depth_pyramid", "rpe_frame_download_level", "rpe_frame_level_camera", "rpe_model_build_pyramid", "rpe_icp_pyramid",
+    "rpe_volume_init", "rpe_volume_integrate", "rpe_volume_raycast", "rpe_volume_download",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -54,6 +55,10 @@ class RpeCamera(C.Structure):
 class RpeIcpOptions(C.Structure):
     _fields_ = [("kind", C.c_int), ("max_iter", C.c_int), ("tol", C.c_double), ("dist_thr", C.c_double), ("cos_thr", C.c_double),
                 ("use_normals", C.c_int), ("device_resident", C.c_int), ("fused", C.c_int)]
+
+
+class RpeVolumeDesc(C.Structure):
+    _fields_ = [("dim", C.c_int * 3), ("voxel_size", C.c_double), ("origin", C.c_double * 3), ("trunc", C.c_double), ("max_weight", C.c_int)]
 
 
 class RpeError(RuntimeError):
@@ -170,6 +175,10 @@ def lib():
         L.rpe_model_build_pyramid.argtypes = [C.c_void_p, C.c_int]
         L.rpe_icp_pyramid.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]
+        L.rpe_volume_init.argtypes = [C.c_void_p, C.POINTER(RpeVolumeDesc)]
+        L.rpe_volume_integrate.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_volume_raycast.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RpeCamera), C.c_double, C.c_double]
+        L.rpe_volume_download.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

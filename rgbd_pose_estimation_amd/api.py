@@ -57,6 +57,7 @@ class Context:
         self.dtype = L.F32
         self._keep = {}
         self._pixels = self._model_pixels = 0   # front end: pixels of the current frame / of the model view
+        self._vol_dims = (0, 0, 0)              # TSDF volume: voxels per axis (volume_init)
 
     def close(self):
         if self._h:
@@ -297,6 +298,39 @@ class Context:
                                         C.byref(cost), C.byref(m)))
         self.n, self.dtype = self._pixels, L.F32
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
+
+    # ---- TSDF volume (Part 3): frames fused into the context's volume, raycast into the model
+    def volume_init(self, dims, voxel_size: float, origin, trunc: float, max_weight: int = 64):
+        """(Re)allocate and clear the volume: dims = (d0, d1, d2) voxels (2 .. 1024 each), origin = world corner of voxel (0, 0, 0)."""
+        d = L.RpeVolumeDesc((C.c_int * 3)(*[int(x) for x in dims]), float(voxel_size), (C.c_double * 3)(*[float(x) for x in origin]),
+                            float(trunc), int(max_weight))
+        L.check(L.lib().rpe_volume_init(self._h, C.byref(d)))
+        self._vol_dims = tuple(int(x) for x in dims)
+        return self
+
+    def volume_integrate(self, pose12):
+        """Fuse the current frame (level 0), seen from pose12 (Xc = R Xw + t), into the volume."""
+        p = np.array(pose12, np.float64).reshape(12)
+        L.check(L.lib().rpe_volume_integrate(self._h, _p(p)))
+        return self
+
+    def volume_raycast(self, pose12, cam, dmin: float, dmax: float, levels: int = 1):
+        """The model := the volume raycast from pose12 with camera cam over camera depths (dmin, dmax); levels > 1 also builds the
+        model pyramid (rpe_model_build_pyramid)."""
+        k = self._camera(cam)
+        p = np.array(pose12, np.float64).reshape(12)
+        L.check(L.lib().rpe_volume_raycast(self._h, _p(p), C.byref(k), float(dmin), float(dmax)))
+        self._model_pixels = k.width * k.height
+        if levels > 1:
+            self.model_build_pyramid(levels)
+        return self
+
+    def volume_download(self) -> np.ndarray:
+        """The volume as (d2, d1, d0, 2) float32: [..., 0] = tsdf, [..., 1] = weight (0 = unobserved)."""
+        d0, d1, d2 = self._vol_dims
+        out = np.empty((d2, d1, d0, 2), np.float32)
+        L.check(L.lib().rpe_volume_download(self._h, _p(out)))
+        return out
 
     def gn_steps_dist(self, kind: int, pose12_inout: np.ndarray, steps: int, flags: int = 0) -> float:
         """`steps` sharded GN steps in place, the loop inside the library; returns the last |delta|."""

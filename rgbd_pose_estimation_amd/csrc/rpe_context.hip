@@ -157,7 +157,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
     std::lock_guard<std::mutex> g(m);
     if (device < 64 && !loaded[device]) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
-      rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac();
+      rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume();
       loaded[device] = true;
     }
   }
@@ -197,6 +197,7 @@ void rpe_destroy(rpe_context* c) {
   for (float* m : c->fe.mmap) if (m) (void)hipFree(m);
   if (c->fe.d_count) (void)hipFree(c->fe.d_count);
   if (c->fe.fdepth) (void)hipFree(c->fe.fdepth);
+  if (c->vol.d) (void)hipFree(c->vol.d);
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);

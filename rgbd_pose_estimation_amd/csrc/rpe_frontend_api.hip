@@ -7,31 +7,6 @@ using namespace rpeh;
 extern "C" {
 // ---------------------------------------------------------------------------------------------- Part 3: front end
 namespace {
-int camera_of(const rpe_camera* cam, rpe::Camera* out) {
-  if (!cam || cam->width < 1 || cam->height < 1 || !(cam->fx > 0) || !(cam->fy > 0)
-      || (int64_t)cam->width * cam->height > (int64_t)1 << 28)
-    return fail(RPE_ERR_ARG, "bad camera (need width, height >= 1 and fx, fy > 0)");
-  out->fx = (float)cam->fx; out->fy = (float)cam->fy; out->cx = (float)cam->cx; out->cy = (float)cam->cy;
-  out->width = cam->width; out->height = cam->height;
-  return RPE_OK;
-}
-rpe::PoseF pose_f(const double* p12) {
-  rpe::PoseF T;
-  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
-  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
-  return T;
-}
-// (re)allocate `count` float maps of n pixels each
-int ensure_maps(rpe_context* c, float** maps, int count, size_t* cap, int64_t n) {
-  const size_t bytes = (size_t)n * 3 * sizeof(float);
-  if (maps[0] && *cap >= bytes) return RPE_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < count; i++) { if (maps[i]) { HIP_TRY(hipFree(maps[i])); maps[i] = nullptr; } }
-  *cap = 0;
-  for (int i = 0; i < count; i++) HIP_TRY(hipMalloc((void**)&maps[i], bytes));
-  *cap = bytes;
-  return RPE_OK;
-}
 // the solver slots the association writes: the context's own storage, n = pixels, fp32
 int claim_slots(rpe_context* c, int64_t n) {
   const size_t bytes = (size_t)n * 3 * sizeof(float);
@@ -105,12 +80,6 @@ int plan_levels(const rpe_camera& k0, int levels, rpe_camera* kc, rpe::PyramidGe
   }
   for (int l = levels + 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = g->off[levels];
   return RPE_OK;
-}
-// the one-level pyramid of a single image (rpe_frame_set_depth, rpe_model_upload)
-void one_level(const rpe_camera& k, const rpe::Camera& f, rpe_camera* kc, rpe::PyramidGeometry* g) {
-  *g = rpe::PyramidGeometry{};
-  g->levels = 1; g->cam[0] = f; kc[0] = k;
-  for (int l = 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = (int64_t)f.width * f.height;
 }
 // raw depth of n pixels to the device (and the pair counter)
 int stage_depth(rpe_context* c, const void* depth, int depth_type, int64_t n) {

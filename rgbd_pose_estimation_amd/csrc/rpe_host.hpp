@@ -6,6 +6,7 @@
 //   rpe_session.hip       resident scoring sessions (K4r)
 //   rpe_dist.hip          sharded contexts: RCCL communicator, in-kernel peer-to-peer, host-side exchange, sharded steps
 //   rpe_frontend_api.hip  Part 3: depth-frame front end and ICP
+//   rpe_volume_api.hip    Part 3: TSDF volume (integrate, raycast into the model)
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -155,6 +156,12 @@ struct rpe_context {
     float* fdepth = nullptr; size_t fdcap = 0;
     bool have_depth = false;
   } fe;
+  // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
+  struct Volume {
+    rpe::VolumeGeometry g{};
+    float* d = nullptr; size_t cap = 0;   // bytes allocated
+    bool have = false;
+  } vol;
 
   rpe::DeviceArrays arrays() const {
     rpe::DeviceArrays A;
@@ -305,6 +312,40 @@ struct SlotHold {
 ResidentSlot& resident_mutex(int device);
 int resident_run_shape(int grid, int nacc, int max_rows, int rows_auto, rpe::ReduceTarget* rt);
 void note_lost_grid(rpe_context* c);
+
+// ---- front-end helpers shared by rpe_frontend_api.hip and rpe_volume_api.hip
+// an rpe_camera validated and cast to the kernels' fp32 camera
+inline int camera_of(const rpe_camera* cam, rpe::Camera* out) {
+  if (!cam || cam->width < 1 || cam->height < 1 || !(cam->fx > 0) || !(cam->fy > 0)
+      || (int64_t)cam->width * cam->height > (int64_t)1 << 28)
+    return fail(RPE_ERR_ARG, "bad camera (need width, height >= 1 and fx, fy > 0)");
+  out->fx = (float)cam->fx; out->fy = (float)cam->fy; out->cx = (float)cam->cx; out->cy = (float)cam->cy;
+  out->width = cam->width; out->height = cam->height;
+  return RPE_OK;
+}
+inline rpe::PoseF pose_f(const double* p12) {
+  rpe::PoseF T;
+  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
+  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
+  return T;
+}
+// (re)allocate `count` float maps of n pixels each
+inline int ensure_maps(rpe_context* c, float** maps, int count, size_t* cap, int64_t n) {
+  const size_t bytes = (size_t)n * 3 * sizeof(float);
+  if (maps[0] && *cap >= bytes) return RPE_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < count; i++) { if (maps[i]) { HIP_TRY(hipFree(maps[i])); maps[i] = nullptr; } }
+  *cap = 0;
+  for (int i = 0; i < count; i++) HIP_TRY(hipMalloc((void**)&maps[i], bytes));
+  *cap = bytes;
+  return RPE_OK;
+}
+// the one-level pyramid of a single image (rpe_frame_set_depth, rpe_model_upload, rpe_volume_raycast)
+inline void one_level(const rpe_camera& k, const rpe::Camera& f, rpe_camera* kc, rpe::PyramidGeometry* g) {
+  *g = rpe::PyramidGeometry{};
+  g->levels = 1; g->cam[0] = f; kc[0] = k;
+  for (int l = 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = (int64_t)f.width * f.height;
+}
 
 // ---- rpe_session.hip
 void session_end(rpe_context* c);      // every entry point that queues work behind the context's stream, reads the masks or reuses the host-side record area calls this first

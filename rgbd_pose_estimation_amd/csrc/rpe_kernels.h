@@ -106,7 +106,7 @@ int resident_cap_device();
 // Each kernel unit is a code object of its own that the runtime loads on the first launch out of it (a few milliseconds, once per
 // process and device).  rpe_create touches one kernel of every unit so that the first frame does not pay for it in the middle of a run.
 void preload_normal_eq(); void preload_icp(); void preload_joint(); void preload_score(); void preload_nl();
-void preload_frontend(); void preload_hypotheses(); void preload_prosac();
+void preload_frontend(); void preload_hypotheses(); void preload_prosac(); void preload_volume();
 void resident_geometry(const DeviceArrays& A, int kind, int max_blocks, int* grid, int* nacc, int* max_rows, int* rows_auto);
 // The solving workgroup of an autonomous resident loop (rpe_residuals.hpp solver_loop): ONE workgroup, launched on a stream of its own
 // BEFORE the workers' kernel (launch_normal_eq_resident / launch_normal_eq_joint_resident with rt.solver = 1, same rt otherwise); nacc =
@@ -232,6 +232,14 @@ hipError_t launch_associate(const float* vmap, const float* nmap, const float* b
                             const Camera& mcam, const PoseF& T, const PoseF& M, float dist_sq, float cos_thr, int use_normals,
                             const double* pose_dev, const int* done, float* xw, float* xc, float* bv, float* nw, float* nc, int* d_count,
                             hipStream_t s);
+// ---- TSDF volume (rpe_volume.hip): voxels are float2 {tsdf, weight} at (k * dim1 + j) * dim0 + i; geometry cast from the descriptor's
+// doubles once (include/rgbd_pose_hip.h Part 3)
+struct VolumeGeometry { int dim[3]; float o[3]; float s, tr, W; };
+// V1: fuse the level-0 vertex map (its z = metric depth, NaN = invalid) of camera `cam` under T (Xc = R Xw + t)
+hipError_t launch_volume_integrate(float* vol, const VolumeGeometry& G, const float* vmap, const Camera& cam, const PoseF& T, hipStream_t s);
+// V2: world vertex / normal maps (3 x width*height floats) of the view T with intrinsics cam, samples in (dmin, dmax)
+hipError_t launch_volume_raycast(const float* vol, const VolumeGeometry& G, const Camera& cam, const PoseF& T, float dmin, float dmax,
+                                 float* mv, float* mn, hipStream_t s);
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

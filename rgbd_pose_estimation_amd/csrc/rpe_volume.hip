@@ -1,0 +1,185 @@
+// gfx950 kernels of the TSDF VOLUME (the KinectFusion half of the front end): depth frames are fused into a truncated signed distance
+// volume, and the volume is raycast from a pose into the model maps the next frame's ICP registers against.
+//
+//   V1  volume_integrate_kernel   one frame (level-0 vertex map) into the volume under a pose: a streaming read-modify-write over the
+//                                 voxels the frame sees.  Voxels are float2 {tsdf, weight}; a lane owns 4 consecutive voxels (two
+//                                 16-byte pairs) and projects all four before it touches the volume, so that a voxel outside the
+//                                 frustum, behind the surface or on invalid depth costs no volume traffic.
+//   V2  volume_raycast_kernel     one ray per pixel, marched at fixed steps of one voxel through trilinear gathers of the volume,
+//                                 up to the first zero crossing; the hit and the volume's gradient there become the model's world
+//                                 vertex and normal.  A workgroup owns a 16 x 16 pixel tile (four 8 x 8 waves), so that neighbouring
+//                                 rays gather the same L2 lines.
+//
+// The conventions (include/rgbd_pose_hip.h Part 3, "TSDF volume") are followed BIT-EXACTLY: fp32, the written order, no FMA contraction;
+// tests/volume_oracle.py is their numpy statement.
+#include "rpe_assoc.h"
+
+namespace rpe {
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kVolBlock = 256;    // integrate: 4 voxels per lane
+constexpr int kRayTile = 16;      // raycast: 16 x 16 pixels per workgroup, 8 x 8 per wave
+
+__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
+
+// ---------------------------------------------------------------------------------------------- V1
+// Voxel (i, j, k), centre p = o + ((float)i + 0.5f) * s per axis; camera point pc = R p + t (rows left to right); pixel = nearest
+// (floorf(f * x / z + c + 0.5f)); d = z of the level-0 vertex map there (NaN = invalid depth); sdf = d - pc.z; updated iff pc.z > 0,
+// the pixel is in the image, d is valid and sdf >= -tr: f = fminf(1, sdf / tr), tsdf = (tsdf * w + f) / (w + 1), w = fminf(w + 1, W).
+__device__ __forceinline__ bool voxel_sdf(const VolumeGeometry& G, const float* __restrict__ vmap, const Camera& cam, const PoseF& T, int i,
+                                          int j, int k, float& f) {
+  const float px = G.o[0] + ((float)i + 0.5f) * G.s, py = G.o[1] + ((float)j + 0.5f) * G.s, pz = G.o[2] + ((float)k + 0.5f) * G.s;
+  const float cx = T.R[0] * px + T.R[1] * py + T.R[2] * pz + T.t[0];
+  const float cy = T.R[3] * px + T.R[4] * py + T.R[5] * pz + T.t[1];
+  const float cz = T.R[6] * px + T.R[7] * py + T.R[8] * pz + T.t[2];
+  if (!(cz > 0.0f)) return false;
+  const float uf = floorf(cam.fx * (cx / cz) + cam.cx + 0.5f), vf = floorf(cam.fy * (cy / cz) + cam.cy + 0.5f);
+  if (!(uf >= 0.0f && uf <= (float)(cam.width - 1) && vf >= 0.0f && vf <= (float)(cam.height - 1))) return false;
+  const float d = vmap[3 * ((int64_t)(int)vf * cam.width + (int)uf) + 2];
+  if (d != d) return false;
+  const float sdf = d - cz;
+  if (!(sdf >= -G.tr)) return false;
+  f = fminf(1.0f, sdf / G.tr);
+  return true;
+}
+
+__device__ __forceinline__ void fuse(float& tsdf, float& w, float f, float W) {
+  tsdf = (tsdf * w + f) / (w + 1.0f);
+  w = fminf(w + 1.0f, W);
+}
+
+// nvox <= 2^30 (dims <= 1024): the flat voxel index fits 32 bits, byte offsets do not
+__global__ __launch_bounds__(kVolBlock) void volume_integrate_kernel(float* __restrict__ vol, VolumeGeometry G, int64_t nvox,
+                                                                     const float* __restrict__ vmap, Camera cam, PoseF T) {
+  const int64_t first = ((int64_t)blockIdx.x * kVolBlock + threadIdx.x) * 4;
+  if (first >= nvox) return;
+  const unsigned flat = (unsigned)first, d0 = (unsigned)G.dim[0], d1 = (unsigned)G.dim[1];
+  int i = (int)(flat % d0), j = (int)((flat / d0) % d1), k = (int)(flat / d0 / d1);
+  float f[4];
+  bool up[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    f[q] = 0.0f;
+    up[q] = first + q < nvox && voxel_sdf(G, vmap, cam, T, i, j, k, f[q]);
+    if (++i == G.dim[0]) { i = 0; if (++j == G.dim[1]) { j = 0; ++k; } }
+  }
+  // the two 16-byte pairs of the lane: loaded if either voxel is updated, each updated voxel stored (a pair as one 16-byte store)
+  float4 v[2];
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const int64_t a = first + 2 * p;
+    v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (up[2 * p] || up[2 * p + 1]) {
+      if (a + 1 < nvox) v[p] = *reinterpret_cast<const float4*>(vol + 2 * a);
+      else { const float2 h = *reinterpret_cast<const float2*>(vol + 2 * a); v[p].x = h.x; v[p].y = h.y; }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const bool lo = up[2 * p], hi = up[2 * p + 1];
+    if (!lo && !hi) continue;
+    float* q = vol + 2 * (first + 2 * p);
+    if (lo) fuse(v[p].x, v[p].y, f[2 * p], G.W);
+    if (hi) fuse(v[p].z, v[p].w, f[2 * p + 1], G.W);
+    if (lo && hi) *reinterpret_cast<float4*>(q) = v[p];
+    else if (lo) *reinterpret_cast<float2*>(q) = make_float2(v[p].x, v[p].y);
+    else *reinterpret_cast<float2*>(q + 2) = make_float2(v[p].z, v[p].w);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- V2
+// F(p): g = (p - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; known iff 0 <= i0 <= dim - 2 on every axis and all eight corner
+// weights are > 0; trilinear with lerp(x, y, t) = x + (y - x) * t along x for (j, k) = (0,0) (1,0) (0,1) (1,1), then y, then z.
+__device__ __forceinline__ float lerp(float x, float y, float t) { return x + (y - x) * t; }
+
+__device__ __forceinline__ bool field(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz, float& F) {
+  const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
+  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+  if (!(fx >= 0.0f && fx <= (float)(G.dim[0] - 2) && fy >= 0.0f && fy <= (float)(G.dim[1] - 2) && fz >= 0.0f &&
+        fz <= (float)(G.dim[2] - 2)))
+    return false;
+  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
+  const int64_t sy = 2 * (int64_t)G.dim[0], sz = sy * G.dim[1];
+  const float* b = vol + (int64_t)(int)fz * sz + (int64_t)(int)fy * sy + 2 * (int64_t)(int)fx;
+  const float2 v000 = *reinterpret_cast<const float2*>(b), v100 = *reinterpret_cast<const float2*>(b + 2);
+  const float2 v010 = *reinterpret_cast<const float2*>(b + sy), v110 = *reinterpret_cast<const float2*>(b + sy + 2);
+  const float2 v001 = *reinterpret_cast<const float2*>(b + sz), v101 = *reinterpret_cast<const float2*>(b + sz + 2);
+  const float2 v011 = *reinterpret_cast<const float2*>(b + sz + sy), v111 = *reinterpret_cast<const float2*>(b + sz + sy + 2);
+  if (!(v000.y > 0.0f && v100.y > 0.0f && v010.y > 0.0f && v110.y > 0.0f && v001.y > 0.0f && v101.y > 0.0f && v011.y > 0.0f &&
+        v111.y > 0.0f))
+    return false;
+  const float c00 = lerp(v000.x, v100.x, ax), c10 = lerp(v010.x, v110.x, ax), c01 = lerp(v001.x, v101.x, ax), c11 = lerp(v011.x, v111.x, ax);
+  const float c0 = lerp(c00, c10, ay), c1 = lerp(c01, c11, ay);
+  F = lerp(c0, c1, az);
+  return true;
+}
+
+// Ray of pixel (u, v): xn = ((float)u - cx) / fx, yn likewise; samples z_k = dmin + (float)k * s while z_k < dmax, each the camera
+// point (xn z, yn z, z) moved to the world (to_world).  Hit: the first k with F(z_k), F(z_k+1) known, F_k > 0 >= F_k+1:
+// z* = z_k + s * (F_k / (F_k - F_k+1)), vertex = to_world(xn z*, yn z*, z*); normal = the central differences F(pw +- s e_axis)
+// divided by sqrtf(x*x + y*y + z*z) (NaN if a sample is unknown or the length is 0).  No hit: NaN vertex and normal.
+__global__ __launch_bounds__(kRayTile * kRayTile) void volume_raycast_kernel(const float* __restrict__ vol, VolumeGeometry G, Camera cam,
+                                                                             PoseF T, float dmin, float dmax, float* __restrict__ mv,
+                                                                             float* __restrict__ mn) {
+  const int tiles_x = (cam.width + kRayTile - 1) / kRayTile;
+  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const int u = (blockIdx.x % tiles_x) * kRayTile + (wave % 2) * 8 + lane % 8;
+  const int v = (blockIdx.x / tiles_x) * kRayTile + (wave / 2) * 8 + lane / 8;
+  if (u >= cam.width || v >= cam.height) return;
+  const float xn = ((float)u - cam.cx) / cam.fx, yn = ((float)v - cam.cy) / cam.fy;
+  const float s = G.s;
+  float zh = qnan();
+  bool prev = false;
+  float Fp = 0.0f, zp = 0.0f;
+  for (int k = 0;; k++) {
+    const float z = dmin + (float)k * s;
+    if (!(z < dmax)) break;
+    float wx, wy, wz, Fk;
+    to_world(T, xn * z, yn * z, z, wx, wy, wz);
+    const bool known = field(vol, G, wx, wy, wz, Fk);
+    if (known && prev && Fp > 0.0f && Fk <= 0.0f) { zh = zp + s * (Fp / (Fp - Fk)); break; }
+    prev = known; Fp = Fk; zp = z;
+  }
+  float ox = qnan(), oy = qnan(), oz = qnan(), nx = qnan(), ny = qnan(), nz = qnan();
+  if (zh == zh) {
+    to_world(T, xn * zh, yn * zh, zh, ox, oy, oz);
+    float a, b, c, d, e, f;
+    const bool ok = field(vol, G, ox + s, oy, oz, a) && field(vol, G, ox - s, oy, oz, b) && field(vol, G, ox, oy + s, oz, c) &&
+                    field(vol, G, ox, oy - s, oz, d) && field(vol, G, ox, oy, oz + s, e) && field(vol, G, ox, oy, oz - s, f);
+    if (ok) {
+      const float gx = a - b, gy = c - d, gz = e - f;
+      const float len = sqrtf(gx * gx + gy * gy + gz * gz);
+      if (len > 0.0f) { nx = gx / len; ny = gy / len; nz = gz / len; }
+    }
+  }
+  const int64_t o = 3 * ((int64_t)v * cam.width + u);
+  mv[o] = ox; mv[o + 1] = oy; mv[o + 2] = oz;
+  mn[o] = nx; mn[o + 1] = ny; mn[o + 2] = nz;
+}
+
+}  // namespace
+
+hipError_t launch_volume_integrate(float* vol, const VolumeGeometry& G, const float* vmap, const Camera& cam, const PoseF& T,
+                                   hipStream_t s) {
+  const int64_t nvox = (int64_t)G.dim[0] * G.dim[1] * G.dim[2];
+  const int64_t blocks = (nvox + 4 * kVolBlock - 1) / (4 * kVolBlock);
+  hipLaunchKernelGGL(volume_integrate_kernel, dim3((unsigned)blocks), dim3(kVolBlock), 0, s, vol, G, nvox, vmap, cam, T);
+  return hipGetLastError();
+}
+
+hipError_t launch_volume_raycast(const float* vol, const VolumeGeometry& G, const Camera& cam, const PoseF& T, float dmin, float dmax,
+                                 float* mv, float* mn, hipStream_t s) {
+  const int tiles = ((cam.width + kRayTile - 1) / kRayTile) * ((cam.height + kRayTile - 1) / kRayTile);
+  hipLaunchKernelGGL(volume_raycast_kernel, dim3(tiles), dim3(kRayTile * kRayTile), 0, s, vol, G, cam, T, dmin, dmax, mv, mn);
+  return hipGetLastError();
+}
+
+void preload_volume() {
+  hipFuncAttributes a;
+  if (hipFuncGetAttributes(&a, (const void*)volume_integrate_kernel) != hipSuccess) (void)hipGetLastError();
+}
+
+}  // namespace rpe

@@ -11,6 +11,10 @@
 //   fe.attach(adapter, pairs);                                          // the solvers find the arrays resident: no upload
 //   nl_shinji_kneip_ransac<float>(adapter, ...);
 //
+// Frame-to-model tracking against a TSDF volume (KinectFusion):
+//   fe.initVolume(desc);  fe.setDepthPyramid(d0, cam, 3);  fe.integrate(T0);
+//   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.raycast(T, cam, range, 3);  fe.icpPyramid(T, {6, 4, 3});  fe.integrate(T);
+//
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
 #define RPE_DEPTH_FRONT_END_HEADER
@@ -37,6 +41,12 @@ struct IcpOptions {
   // true
   // keeps solve and update on the GPU instead (also one launch, the grid iterates by itself: 12 us per round; no busy host thread)
   bool use_normals = true, device_resident = false, fused = true;
+};
+// TSDF volume (rpe_volume_init): dim[0] x dim[1] x dim[2] voxels of voxel_size metres from the world corner origin
+struct VolumeDesc {
+  int dim[3] = {256, 256, 256};
+  double voxel_size = 0.02, origin[3] = {-2.56, -2.56, -0.5}, trunc = 0.06;
+  int max_weight = 64;
 };
 struct IcpResult { int iterations = 0; double last_step = 0, cost = 0; long long pairs = 0; };
 // coarse-to-fine ICP: rounds run per level (0 = finest); the rest as IcpResult, of level 0
@@ -130,6 +140,32 @@ class DepthFrontEnd {
     pose = pose_of(p);
     return r;
   }
+  // (re)allocate and clear the TSDF volume
+  void initVolume(const VolumeDesc& d) {
+    rpe_volume_desc v;
+    for (int a = 0; a < 3; a++) { v.dim[a] = d.dim[a]; v.origin[a] = d.origin[a]; }
+    v.voxel_size = d.voxel_size; v.trunc = d.trunc; v.max_weight = d.max_weight;
+    check(rpe_volume_init(_ctx, &v), "rpe_volume_init");
+    _vol = d;
+  }
+  // fuse the current frame (level 0), seen from T_cw, into the volume
+  void integrate(const Pose& T_cw) {
+    double p[12]; pose12(T_cw, p);
+    check(rpe_volume_integrate(_ctx, p), "rpe_volume_integrate");
+  }
+  // the model := the volume raycast from T_cw with camera cam over camera depths (r.dmin, r.dmax), plus its pyramid of `levels`
+  void raycast(const Pose& T_cw, const PinholeCamera& cam, const DepthRange& r, int levels = 1) {
+    double p[12]; pose12(T_cw, p);
+    const rpe_camera k = cam_of(cam);
+    check(rpe_volume_raycast(_ctx, p, &k, r.dmin, r.dmax), "rpe_volume_raycast");
+    if (levels > 1) buildModelPyramid(levels);
+  }
+  // the volume on the host: 2 x voxels floats {tsdf, weight}, voxel (i, j, k) at column (k * dim1 + j) * dim0 + i
+  MatrixX<float> volume() const {
+    MatrixX<float> m(2, _vol.dim[0] * _vol.dim[1] * _vol.dim[2]);
+    check(rpe_volume_download(_ctx, m.data()), "rpe_volume_download");
+    return m;
+  }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
     Pairs P;
@@ -170,6 +206,7 @@ class DepthFrontEnd {
   }
   rpe_context* _ctx;
   int _device, _pixels;
+  VolumeDesc _vol;
 };
 
 }  // namespace rpe

@@ -1,0 +1,169 @@
+"""CPU: pins the numpy statement of the TSDF volume (tests/volume_oracle.py) with analytic cases, recomputes the oracle figures the GPU
+accuracy and tracking thresholds are set from (tests/volume_cases.py), and checks that the library exports the volume entry points, that
+the volume kernels neither spill nor carry scratch, that the volume's host unit has no device code, and that the C++ driver compiles."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import isa_tools as T
+import volume_cases as VC
+import volume_oracle as VO
+from frontend_util import FO, SMALL_CAM, pose12, rot
+from rgbd_pose_estimation_amd import _lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
+f32 = np.float32
+I12 = pose12(np.eye(3), np.zeros(3))
+SYMS = {"rpe_volume_init", "rpe_volume_integrate", "rpe_volume_raycast", "rpe_volume_download"}
+
+
+def plane_volume(D=2.0, max_weight=8, times=1, cam=SMALL_CAM):
+    """a fronto-parallel plane at depth D, seen by an identity camera, fused `times` times"""
+    fx, fy, cx, cy, w, h = cam
+    G = VO.Geometry((40, 32, 60), 0.05, (-1.0, -0.8, 0.5), 0.15, max_weight)
+    V = FO.frame_maps(np.full((h, w), D, f32), cam, 1.0, 0.1, 10.0, 0.1)[0]
+    vol = G.empty()
+    for _ in range(times):
+        vol = VO.integrate(vol, G, V, cam, I12)
+    return G, vol
+
+
+def test_plane_tsdf_on_the_optical_axis():
+    D = 2.0
+    G, vol = plane_volume(D)
+    col = vol[:, 16, 20]                  # voxel centre x = -0.025, y = 0.025: on the optical axis's pixel
+    zc = G.o[2] + (np.arange(60, dtype=f32) + f32(0.5)) * G.s
+    sdf = f32(D) - zc
+    fused = sdf >= -G.tr
+    assert np.array_equal(col[fused, 0], np.minimum(f32(1), sdf[fused] / G.tr))
+    assert np.all(col[fused, 1] == 1)
+    assert np.all(col[~fused] == 0) and (~fused).sum() > 10        # more than tr behind the plane: untouched
+    assert np.all(vol[zc > f32(D) + G.tr] == 0)                   # no voxel of a slice more than tr behind the plane is touched
+
+
+def test_weight_clamp_and_running_mean():
+    G, vol = plane_volume(max_weight=3, times=5)
+    w = vol[..., 1]
+    assert w.max() == f32(3) and set(np.unique(w)) <= {f32(0), f32(3)}
+    _, once = plane_volume(max_weight=3, times=1)
+    seen = once[..., 1] > 0
+    # the same f every time: (t * w + f) / (w + 1) stays f up to rounding
+    assert np.abs(vol[..., 0][seen] - once[..., 0][seen]).max() < 1e-6
+
+
+def test_invalid_depth_and_out_of_image_voxels_are_skipped():
+    fx, fy, cx, cy, w, h = SMALL_CAM
+    G = VO.Geometry((40, 32, 60), 0.05, (-1.0, -0.8, 0.5), 0.15, 8)
+    depth = np.full((h, w), 2.0, f32)
+    depth[:, : w // 2] = 0                                         # the left half has no depth
+    V = FO.frame_maps(depth, SMALL_CAM, 1.0, 0.1, 10.0, 0.1)[0]
+    vol = VO.integrate(G.empty(), G, V, SMALL_CAM, I12)
+    xc = G.o[0] + (np.arange(40, dtype=f32) + f32(0.5)) * G.s
+    assert np.all(vol[:, :, xc < -0.1, 1] == 0) and np.any(vol[:, :, xc > 0.1, 1] > 0)
+    behind = VO.integrate(G.empty(), G, V, SMALL_CAM, pose12(rot(0, np.pi, 0), np.zeros(3)))   # looking away: nothing in front
+    assert np.all(behind == 0)
+
+
+def test_raycast_of_the_plane():
+    D = 2.0
+    G, vol = plane_volume(D)
+    MV, MN = VO.raycast(vol, G, SMALL_CAM, I12, 0.1, 4.0)
+    hit = ~np.isnan(MV).any(1)
+    assert hit.mean() > 0.8
+    z = MV[hit, 2]
+    assert np.abs(z.astype(np.float64) - D).max() <= 4 * np.spacing(f32(D))      # within a few ulp of D
+    good = ~np.isnan(MN).any(1)
+    assert good.mean() > 0.7 and np.array_equal(MN[good], np.tile(f32([0, 0, -1]), (good.sum(), 1)))
+    # the same plane from a camera moved back by 0.5 m: the camera-frame normal is still (0, 0, -1)
+    p = pose12(np.eye(3), np.array([0.0, 0.0, 0.5]))
+    MV2, MN2 = VO.raycast(vol, G, SMALL_CAM, p, 0.1, 4.0)
+    h2 = ~np.isnan(MV2).any(1)
+    assert np.abs(MV2[h2, 2].astype(np.float64) - D).max() <= 4 * np.spacing(f32(D))
+
+
+def test_raycast_of_a_tilted_plane_gives_its_normal():
+    fx, fy, cx, cy, w, h = SMALL_CAM
+    n = np.array([0.3, -0.2, 1.0]); n /= np.linalg.norm(n)
+    d = 2.0
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    depth = (d / (n[0] * (u - cx) / fx + n[1] * (v - cy) / fy + n[2])).astype(f32)
+    G = VO.Geometry((60, 48, 70), 0.04, (-1.2, -1.0, 0.6), 0.12, 8)
+    V = FO.frame_maps(depth, SMALL_CAM, 1.0, 0.1, 10.0, 0.1)[0]
+    vol = VO.integrate(G.empty(), G, V, SMALL_CAM, I12)
+    MV, MN = VO.raycast(vol, G, SMALL_CAM, I12, 0.1, 4.0)
+    good = ~np.isnan(MN).any(1)
+    assert good.mean() > 0.6
+    # on the plane (the oracle: median 6.7e-4 m, max 3.0e-3 m; nearest-pixel projection quantises the projective distance)
+    e = np.abs(MV[good].astype(np.float64) @ n - d)
+    assert np.median(e) < 1e-3 and e.max() < 4e-3
+    # its normal, towards the camera (per pixel: median 1.1e-2, p95 2.8e-2; their mean to 1e-3)
+    N = MN[good].astype(np.float64)
+    a = np.abs(N - (-n)).max(1)
+    assert np.median(a) < 1.5e-2 and np.percentile(a, 95) < 4e-2
+    m = N.mean(0)
+    assert np.abs(m / np.linalg.norm(m) - (-n)).max() < 3e-3, m / np.linalg.norm(m)
+
+
+def test_empty_volume_raycasts_to_nan():
+    G = VO.Geometry((8, 8, 8), 0.1, (-0.4, -0.4, 0.5), 0.3, 4)
+    MV, MN = VO.raycast(G.empty(), G, SMALL_CAM, I12, 0.1, 2.0)
+    assert np.isnan(MV).all() and np.isnan(MN).all()
+
+
+def test_accuracy_figures():
+    """the oracle figures behind volume_cases.ACC_* (the GPU accuracy test's thresholds)"""
+    med, p95, cover = VC.oracle_accuracy()
+    assert abs(med - 8.5e-4) < 5e-5 and abs(p95 - 6.8e-3) < 5e-4 and abs(cover - 0.948) < 1e-3, (med, p95, cover)
+    assert med < VC.ACC_MEDIAN and p95 < VC.ACC_P95 and cover > VC.ACC_COVERAGE
+
+
+def test_tracking_loop_figures(oracle):
+    """the oracle's run of the tracking loop behind volume_cases.TRACK_* (the GPU tracking test's thresholds)"""
+    est = VC.oracle_tracking(oracle)
+    errs = [VC.pose_error(e, VC.track_pose(f)) for f, e in enumerate(est)]
+    rot_max, pos_max = max(e[0] for e in errs), max(e[1] for e in errs)
+    assert rot_max < 6e-4 and pos_max < 3.5e-3, errs
+    assert rot_max < VC.TRACK_ROT / 2 and pos_max < VC.TRACK_POS / 2
+
+
+def _built():
+    from rgbd_pose_estimation_amd import build as B
+    return B.build()
+
+
+def test_header_and_library_export_the_volume_entry_points():
+    lib = _built()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
+    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    assert SYMS <= exported, sorted(SYMS - exported)
+    assert SYMS <= set(L.SYMBOLS)
+    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
+    for s in SYMS:
+        assert f"int {s}(" in hdr
+    assert "rpe_volume_desc" in hdr
+
+
+def test_volume_kernels_do_not_spill():
+    _built()
+    rows = T.kernel_resources(os.path.join(LIB, "rpe_volume.o"))
+    assert {r["mangled"].split("volume_")[1].split("_kernel")[0] for r in rows} == {"integrate", "raycast"}, rows
+    assert not [(r["name"], r["vgpr_spill"]) for r in rows if r["vgpr_spill"] > 0]
+    assert not [(r["name"], r["scratch"]) for r in rows if r["scratch"] > 16]
+    assert all(r["vgpr"] + r["agpr"] <= 512 for r in rows)
+
+
+def test_volume_host_unit_has_no_device_code_and_stays_small():
+    _built()
+    assert T.kernel_resources(os.path.join(LIB, "rpe_volume_api.o")) == []
+    assert os.path.getsize(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_volume_api.hip")) < 40 * 1024
+
+
+def test_volume_cpp_driver_compiles(tmp_path):
+    lib = _built()
+    inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
+                           os.path.join(ROOT, "tests", "cpp", "volume_track.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",
+                           "-Wl,-rpath," + os.path.dirname(lib), "-o", str(tmp_path / "volume_track")])
