@@ -501,6 +501,37 @@ int rpe_volume_integrate(rpe_context* ctx, const double* pose12);
 int rpe_volume_raycast(rpe_context* ctx, const double* pose12, const rpe_camera* cam, double dmin, double dmax);
 /* copy the volume to the host: 2 x voxels floats {tsdf, weight} in voxel index order */
 int rpe_volume_download(rpe_context* ctx, float* tsdf_weight);
+/* copy 2 x voxels floats {tsdf, weight}, in voxel index order, into the context's volume (the inverse of rpe_volume_download);
+ * RPE_ERR_STATE without a volume.  The bits are taken as given. */
+int rpe_volume_upload(rpe_context* ctx, const float* tsdf_weight);
+
+/* ---- Mesh: marching cubes over the volume, the triangle mesh of its zero level set, built in device buffers the context owns.
+ * Conventions, followed bit for bit (fp32, the written order, no FMA contraction; tests/mesh_oracle.py states them in numpy):
+ * Cubes: cube (i, j, k) exists for 0 <= i <= d0-2, 0 <= j <= d1-2, 0 <= k <= d2-2; its corner n = di + 2*dj + 4*dk is voxel
+ * (i+di, j+dj, k+dk).  wmin = (float)min_weight (min_weight finite and > 0, also in fp32).  A corner is known iff weight >= wmin and
+ * its tsdf is finite; a cube is active iff all 8 corners are known.  Case = the 8-bit mask of the corners with tsdf <= 0 (the
+ * raycast's split: F > 0 is free space).  Edges: 0-3 the x-edges for (dj, dk) = (0,0) (1,0) (0,1) (1,1), 4-7 the y-edges for (di, dk),
+ * 8-11 the z-edges for (di, dj); the edge from corner a to b = a + e_axis is crossed iff (Fa > 0) != (Fb > 0) and belongs to voxel a
+ * with that axis (each voxel owns at most 3 potential vertices).
+ * Vertices: one on every crossed edge that at least one active cube contains, ordered by the owning voxel's index
+ * (k*d1 + j)*d0 + i, then by axis x < y < z.  Position: t = Fa / (Fa - Fb) (never 0 / 0; t in [0, 1]); along the edge's axis
+ * o + (((float)ia + 0.5f) + t) * s, on the other two axes the voxel centre o + ((float)i + 0.5f) * s.  Normal: exactly the raycast's
+ * model normal at the vertex (six F(p +- s e) samples, F with weight > 0, not wmin; NaN if a sample is unknown or the length is 0).
+ * Triangles: emitted by active cubes with case != 0, 255, ordered by cube index (k*d1 + j)*d0 + i, then in table order; three int32
+ * vertex ids each, wound so that (v1 - v0) x (v2 - v0) points to the free side (tsdf > 0), the side of the normal.
+ * Table (csrc/rpe_mc_tables.h, generated by scripts/gen_mc_tables.py): on each cube face the crossed edges are joined into segments;
+ * on an ambiguous face (four crossed edges) the two tsdf <= 0 corners are joined across the diagonal (a rule of the face's four values
+ * alone, so neighbouring cubes agree and the mesh has no cracks).  Segments chain into closed loops; each loop is fan-triangulated
+ * from its vertex with the lowest edge number, in the direction the winding requires; loops in the order of that edge.  At most 5
+ * triangles per case.
+ * The mesh lives until the next rpe_volume_mesh (whether or not it succeeds) or rpe_volume_init.  Workspace: 6 bytes per voxel,
+ * allocated on the first extraction and kept with the volume. */
+/* marching cubes over the volume: builds the mesh in device buffers the context owns and returns its size (one host wait);
+ * RPE_ERR_STATE without a volume, RPE_ERR_ARG for a bad min_weight or a mesh of 2^31 or more vertices (the ids are int32) */
+int rpe_volume_mesh(rpe_context* ctx, double min_weight, int64_t* n_vertices, int64_t* n_triangles);
+/* copy the last extracted mesh out: vertices and normals 3 x n_vertices floats (normals may be NULL), triangles 3 x n_triangles int32;
+ * RPE_ERR_STATE before any extraction or after rpe_volume_init */
+int rpe_volume_mesh_download(rpe_context* ctx, float* vertices, float* normals, int32_t* triangles);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

@@ -34,6 +34,7 @@ SYMBOLS = [
     "rpe_frame_set_depth", "rpe_frame_download", "rpe_model_from_frame", "rpe_model_upload", "rpe_associate", "rpe_icp",
     "rpe_frame_set_depth_pyramid", "rpe_frame_download_level", "rpe_frame_level_camera", "rpe_model_build_pyramid", "rpe_icp_pyramid",
     "rpe_volume_init", "rpe_volume_integrate", "rpe_volume_raycast", "rpe_volume_download",
+    "rpe_volume_upload", "rpe_volume_mesh", "rpe_volume_mesh_download",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -179,6 +180,9 @@ def lib():
         L.rpe_volume_integrate.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_volume_raycast.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RpeCamera), C.c_double, C.c_double]
         L.rpe_volume_download.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_volume_upload.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_volume_mesh.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.rpe_volume_mesh_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

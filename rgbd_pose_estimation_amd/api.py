@@ -332,6 +332,26 @@ class Context:
         L.check(L.lib().rpe_volume_download(self._h, _p(out)))
         return out
 
+    def volume_upload(self, vol):
+        """Replace the volume's voxels with `vol`, (d2, d1, d0, 2) float32 as volume_download returns it; the bits are taken as given."""
+        d0, d1, d2 = self._vol_dims
+        a = np.ascontiguousarray(vol, np.float32)
+        if a.shape != (d2, d1, d0, 2):
+            raise ValueError(f"volume_upload: expected shape {(d2, d1, d0, 2)}, got {a.shape}")
+        L.check(L.lib().rpe_volume_upload(self._h, _p(a)))
+        return self
+
+    def volume_mesh(self, min_weight: float = 1.0):
+        """Marching cubes over the volume (corners with weight >= min_weight): (vertices (V, 3) float32, normals (V, 3) float32, NaN
+        where the field is unknown, triangles (T, 3) int32), wound so that (v1 - v0) x (v2 - v0) points to free space."""
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().rpe_volume_mesh(self._h, float(min_weight), C.byref(nv), C.byref(nt)))
+        V = np.empty((nv.value, 3), np.float32)
+        N = np.empty((nv.value, 3), np.float32)
+        T = np.empty((nt.value, 3), np.int32)
+        L.check(L.lib().rpe_volume_mesh_download(self._h, _p(V), _p(N), _p(T)))
+        return V, N, T
+
     def gn_steps_dist(self, kind: int, pose12_inout: np.ndarray, steps: int, flags: int = 0) -> float:
         """`steps` sharded GN steps in place, the loop inside the library; returns the last |delta|."""
         step = C.c_double(0)

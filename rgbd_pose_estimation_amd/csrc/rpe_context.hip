@@ -157,7 +157,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
     std::lock_guard<std::mutex> g(m);
     if (device < 64 && !loaded[device]) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
-      rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume();
+      rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
       loaded[device] = true;
     }
   }
@@ -198,6 +198,8 @@ void rpe_destroy(rpe_context* c) {
   if (c->fe.d_count) (void)hipFree(c->fe.d_count);
   if (c->fe.fdepth) (void)hipFree(c->fe.fdepth);
   if (c->vol.d) (void)hipFree(c->vol.d);
+  if (c->vol.ws) (void)hipFree(c->vol.ws);
+  for (void* m : {(void*)c->vol.mv, (void*)c->vol.mn, (void*)c->vol.mt}) if (m) (void)hipFree(m);
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);

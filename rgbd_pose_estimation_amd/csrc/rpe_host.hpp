@@ -6,7 +6,8 @@
 //   rpe_session.hip       resident scoring sessions (K4r)
 //   rpe_dist.hip          sharded contexts: RCCL communicator, in-kernel peer-to-peer, host-side exchange, sharded steps
 //   rpe_frontend_api.hip  Part 3: depth-frame front end and ICP
-//   rpe_volume_api.hip    Part 3: TSDF volume (integrate, raycast into the model)
+//   rpe_volume_api.hip    Part 3: TSDF volume (integrate, raycast into the model, upload / download)
+//   rpe_mesh_api.hip      Part 3: mesh extraction from the TSDF volume (marching cubes) and its download
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -161,6 +162,12 @@ struct rpe_context {
     rpe::VolumeGeometry g{};
     float* d = nullptr; size_t cap = 0;   // bytes allocated
     bool have = false;
+    // mesh extraction (rpe_mesh_api.hip): the workspace (allocated on the first extraction, freed when the volume grows) and the
+    // last mesh, 3 x nv vertex / normal floats and 3 x nt int32 ids (valid while have_mesh)
+    void* ws = nullptr; size_t ws_cap = 0;
+    float *mv = nullptr, *mn = nullptr; int32_t* mt = nullptr; size_t mv_cap = 0, mt_cap = 0;
+    int64_t nv = 0, nt = 0;
+    bool have_mesh = false;
   } vol;
 
   rpe::DeviceArrays arrays() const {

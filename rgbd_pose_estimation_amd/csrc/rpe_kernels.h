@@ -106,7 +106,7 @@ int resident_cap_device();
 // Each kernel unit is a code object of its own that the runtime loads on the first launch out of it (a few milliseconds, once per
 // process and device).  rpe_create touches one kernel of every unit so that the first frame does not pay for it in the middle of a run.
 void preload_normal_eq(); void preload_icp(); void preload_joint(); void preload_score(); void preload_nl();
-void preload_frontend(); void preload_hypotheses(); void preload_prosac(); void preload_volume();
+void preload_frontend(); void preload_hypotheses(); void preload_prosac(); void preload_volume(); void preload_mesh();
 void resident_geometry(const DeviceArrays& A, int kind, int max_blocks, int* grid, int* nacc, int* max_rows, int* rows_auto);
 // The solving workgroup of an autonomous resident loop (rpe_residuals.hpp solver_loop): ONE workgroup, launched on a stream of its own
 // BEFORE the workers' kernel (launch_normal_eq_resident / launch_normal_eq_joint_resident with rt.solver = 1, same rt otherwise); nacc =
@@ -240,6 +240,24 @@ hipError_t launch_volume_integrate(float* vol, const VolumeGeometry& G, const fl
 // V2: world vertex / normal maps (3 x width*height floats) of the view T with intrinsics cam, samples in (dmin, dmax)
 hipError_t launch_volume_raycast(const float* vol, const VolumeGeometry& G, const Camera& cam, const PoseF& T, float dmin, float dmax,
                                  float* mv, float* mn, hipStream_t s);
+// ---- mesh extraction (rpe_mesh.hip): marching cubes over the volume, ids placed by scans over chunks of kMeshChunk voxels.  The
+// workspace is one allocation of mesh_workspace_bytes(nvox) (6 bytes per voxel plus 24 per chunk), cut by mesh_workspace.
+constexpr int kMeshChunk = 4096;
+struct MeshWorkspace {
+  int chunks = 0;
+  unsigned char *cases = nullptr, *used = nullptr;   // per voxel: the case of its cube, its used-edge bits
+  int* first = nullptr;                              // per voxel with used edges: its first vertex id
+  unsigned *chunk_v = nullptr, *chunk_t = nullptr;   // per chunk: vertex and triangle counts
+  long long *off_v = nullptr, *off_t = nullptr;      // per chunk: their exclusive offsets
+  long long* totals = nullptr;                       // {vertices, triangles}
+};
+size_t mesh_workspace_bytes(int64_t nvox);
+MeshWorkspace mesh_workspace(void* ws, int64_t nvox);
+// M1-M3: cases, used edges, chunk counts, their scan and the totals (min weight wmin > 0)
+hipError_t launch_mesh_count(const float* vol, const VolumeGeometry& G, float wmin, const MeshWorkspace& W, hipStream_t s);
+// M4-M5 after launch_mesh_count: 3 x V vertex and normal floats, 3 x T int32 triangle ids
+hipError_t launch_mesh_emit(const float* vol, const VolumeGeometry& G, const MeshWorkspace& W, float* vertices, float* normals,
+                            int* triangles, hipStream_t s);
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

@@ -1,0 +1,70 @@
+// Part 3 of include/rgbd_pose_hip.h: the mesh of the TSDF volume (kernels in rpe_mesh.hip).  Marching cubes over the context's volume
+// into device buffers the context owns: three launches, one host wait for the totals, two launches; the download copies them out.
+#include "rpe_host.hpp"
+#include <cmath>
+using namespace rpeh;
+
+extern "C" {
+
+int rpe_volume_mesh(rpe_context* c, double min_weight, int64_t* n_vertices, int64_t* n_triangles) {
+  session_end(c);
+  if (c) c->vol.have_mesh = false;   // the last mesh lives until this call, whatever it returns
+  if (!c || !n_vertices || !n_triangles) return fail(RPE_ERR_ARG, "rpe_volume_mesh: bad argument");
+  auto& V = c->vol;
+  if (!V.have) return fail(RPE_ERR_STATE, "no volume: call rpe_volume_init first");
+  const float wmin = (float)min_weight;
+  if (!(min_weight > 0) || !std::isfinite(min_weight) || !(wmin > 0))
+    return fail(RPE_ERR_ARG, "rpe_volume_mesh: min_weight must be finite and > 0, also in fp32 (got %g)", min_weight);
+  HIP_TRY(hipSetDevice(c->device));
+  const int64_t nvox = (int64_t)V.g.dim[0] * V.g.dim[1] * V.g.dim[2];
+  const size_t ws = rpe::mesh_workspace_bytes(nvox);
+  if (!V.ws || V.ws_cap < ws) {
+    if (V.ws) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.ws)); V.ws = nullptr; V.ws_cap = 0; }
+    HIP_TRY(hipMalloc(&V.ws, ws));
+    V.ws_cap = ws;
+  }
+  const rpe::MeshWorkspace W = rpe::mesh_workspace(V.ws, nvox);
+  HIP_TRY(rpe::launch_mesh_count(V.d, V.g, wmin, W, c->stream));
+  long long tot[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, W.totals, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (tot[0] >= ((long long)1 << 31))
+    return fail(RPE_ERR_ARG, "rpe_volume_mesh: %lld vertices; the int32 triangle ids hold fewer than 2^31", tot[0]);
+  const size_t vb = (size_t)tot[0] * 3 * sizeof(float), tb = (size_t)tot[1] * 3 * sizeof(int32_t);
+  if (V.mv_cap < vb) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (float** m : {&V.mv, &V.mn}) if (*m) { HIP_TRY(hipFree(*m)); *m = nullptr; }
+    V.mv_cap = 0;
+    HIP_TRY(hipMalloc((void**)&V.mv, vb));
+    HIP_TRY(hipMalloc((void**)&V.mn, vb));
+    V.mv_cap = vb;
+  }
+  if (V.mt_cap < tb) {
+    if (V.mt) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.mt)); V.mt = nullptr; V.mt_cap = 0; }
+    HIP_TRY(hipMalloc((void**)&V.mt, tb));
+    V.mt_cap = tb;
+  }
+  if (tot[0] > 0) HIP_TRY(rpe::launch_mesh_emit(V.d, V.g, W, V.mv, V.mn, V.mt, c->stream));
+  V.nv = tot[0]; V.nt = tot[1];
+  V.have_mesh = true;
+  *n_vertices = V.nv; *n_triangles = V.nt;
+  return RPE_OK;
+}
+
+int rpe_volume_mesh_download(rpe_context* c, float* vertices, float* normals, int32_t* triangles) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "rpe_volume_mesh_download: bad argument");
+  const auto& V = c->vol;
+  if (!V.have) return fail(RPE_ERR_STATE, "no volume: call rpe_volume_init first");
+  if (!V.have_mesh) return fail(RPE_ERR_STATE, "no mesh: call rpe_volume_mesh first (rpe_volume_init drops the mesh)");
+  if ((V.nv > 0 && !vertices) || (V.nt > 0 && !triangles)) return fail(RPE_ERR_ARG, "rpe_volume_mesh_download: bad argument");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t vb = (size_t)V.nv * 3 * sizeof(float), tb = (size_t)V.nt * 3 * sizeof(int32_t);
+  if (vb) HIP_TRY(hipMemcpyAsync(vertices, V.mv, vb, hipMemcpyDeviceToHost, c->stream));
+  if (vb && normals) HIP_TRY(hipMemcpyAsync(normals, V.mn, vb, hipMemcpyDeviceToHost, c->stream));
+  if (tb) HIP_TRY(hipMemcpyAsync(triangles, V.mt, tb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RPE_OK;
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 // The conventions (include/rgbd_pose_hip.h Part 3, "TSDF volume") are followed BIT-EXACTLY: fp32, the written order, no FMA contraction;
 // tests/volume_oracle.py is their numpy statement.
 #include "rpe_assoc.h"
+#include "rpe_volume_field.hpp"
 
 namespace rpe {
 
@@ -91,31 +92,7 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_kernel(float* __re
 }
 
 // ---------------------------------------------------------------------------------------------- V2
-// F(p): g = (p - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; known iff 0 <= i0 <= dim - 2 on every axis and all eight corner
-// weights are > 0; trilinear with lerp(x, y, t) = x + (y - x) * t along x for (j, k) = (0,0) (1,0) (0,1) (1,1), then y, then z.
-__device__ __forceinline__ float lerp(float x, float y, float t) { return x + (y - x) * t; }
-
-__device__ __forceinline__ bool field(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz, float& F) {
-  const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
-  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
-  if (!(fx >= 0.0f && fx <= (float)(G.dim[0] - 2) && fy >= 0.0f && fy <= (float)(G.dim[1] - 2) && fz >= 0.0f &&
-        fz <= (float)(G.dim[2] - 2)))
-    return false;
-  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
-  const int64_t sy = 2 * (int64_t)G.dim[0], sz = sy * G.dim[1];
-  const float* b = vol + (int64_t)(int)fz * sz + (int64_t)(int)fy * sy + 2 * (int64_t)(int)fx;
-  const float2 v000 = *reinterpret_cast<const float2*>(b), v100 = *reinterpret_cast<const float2*>(b + 2);
-  const float2 v010 = *reinterpret_cast<const float2*>(b + sy), v110 = *reinterpret_cast<const float2*>(b + sy + 2);
-  const float2 v001 = *reinterpret_cast<const float2*>(b + sz), v101 = *reinterpret_cast<const float2*>(b + sz + 2);
-  const float2 v011 = *reinterpret_cast<const float2*>(b + sz + sy), v111 = *reinterpret_cast<const float2*>(b + sz + sy + 2);
-  if (!(v000.y > 0.0f && v100.y > 0.0f && v010.y > 0.0f && v110.y > 0.0f && v001.y > 0.0f && v101.y > 0.0f && v011.y > 0.0f &&
-        v111.y > 0.0f))
-    return false;
-  const float c00 = lerp(v000.x, v100.x, ax), c10 = lerp(v010.x, v110.x, ax), c01 = lerp(v001.x, v101.x, ax), c11 = lerp(v011.x, v111.x, ax);
-  const float c0 = lerp(c00, c10, ay), c1 = lerp(c01, c11, ay);
-  F = lerp(c0, c1, az);
-  return true;
-}
+// F(p) and the model normal: rpe_volume_field.hpp (shared with the mesh normals of rpe_mesh.hip).
 
 // Ray of pixel (u, v): xn = ((float)u - cx) / fx, yn likewise; samples z_k = dmin + (float)k * s while z_k < dmax, each the camera
 // point (xn z, yn z, z) moved to the world (to_world).  Hit: the first k with F(z_k), F(z_k+1) known, F_k > 0 >= F_k+1:
@@ -146,14 +123,7 @@ __global__ __launch_bounds__(kRayTile * kRayTile) void volume_raycast_kernel(con
   float ox = qnan(), oy = qnan(), oz = qnan(), nx = qnan(), ny = qnan(), nz = qnan();
   if (zh == zh) {
     to_world(T, xn * zh, yn * zh, zh, ox, oy, oz);
-    float a, b, c, d, e, f;
-    const bool ok = field(vol, G, ox + s, oy, oz, a) && field(vol, G, ox - s, oy, oz, b) && field(vol, G, ox, oy + s, oz, c) &&
-                    field(vol, G, ox, oy - s, oz, d) && field(vol, G, ox, oy, oz + s, e) && field(vol, G, ox, oy, oz - s, f);
-    if (ok) {
-      const float gx = a - b, gy = c - d, gz = e - f;
-      const float len = sqrtf(gx * gx + gy * gy + gz * gz);
-      if (len > 0.0f) { nx = gx / len; ny = gy / len; nz = gz / len; }
-    }
+    (void)field_normal(vol, G, ox, oy, oz, nx, ny, nz);   // leaves the NaN normal where a sample is unknown
   }
   const int64_t o = 3 * ((int64_t)v * cam.width + u);
   mv[o] = ox; mv[o + 1] = oy; mv[o + 2] = oz;

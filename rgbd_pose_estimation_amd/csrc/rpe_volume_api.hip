@@ -25,8 +25,10 @@ int rpe_volume_init(rpe_context* c, const rpe_volume_desc* d) {
   auto& V = c->vol;
   const size_t bytes = (size_t)g.dim[0] * g.dim[1] * g.dim[2] * 2 * sizeof(float);
   V.have = false;
+  V.have_mesh = false;
   if (!V.d || V.cap < bytes) {
     if (V.d) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.d)); V.d = nullptr; V.cap = 0; }
+    if (V.ws) { HIP_TRY(hipFree(V.ws)); V.ws = nullptr; V.ws_cap = 0; }   // the mesh workspace follows the volume's size
     HIP_TRY(hipMalloc((void**)&V.d, bytes));
     V.cap = bytes;
   }
@@ -79,6 +81,17 @@ int rpe_volume_download(rpe_context* c, float* out) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(out, c->vol.d, (size_t)g.dim[0] * g.dim[1] * g.dim[2] * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return RPE_OK;
+}
+
+int rpe_volume_upload(rpe_context* c, const float* in) {
+  session_end(c);
+  if (!c || !in) return fail(RPE_ERR_ARG, "rpe_volume_upload: bad argument");
+  if (!c->vol.have) return fail(RPE_ERR_STATE, "no volume: call rpe_volume_init first");
+  const rpe::VolumeGeometry& g = c->vol.g;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(c->vol.d, in, (size_t)g.dim[0] * g.dim[1] * g.dim[2] * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's buffer is free again on return
   return RPE_OK;
 }
 

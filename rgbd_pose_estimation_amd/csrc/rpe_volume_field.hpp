@@ -1,0 +1,54 @@
+// The volume's field F(p), shared by the raycast (rpe_volume.hip V2) and the mesh normals (rpe_mesh.hip M4); device code only.
+// Followed BIT-EXACTLY (include/rgbd_pose_hip.h Part 3, "Field"): FMA contraction is off from here to the end of the including unit.
+#pragma once
+#include "rpe_kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace rpe {
+namespace {
+
+// F(p): g = (p - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; known iff 0 <= i0 <= dim - 2 on every axis and all eight corner
+// weights are > 0; trilinear with lerp(x, y, t) = x + (y - x) * t along x for (j, k) = (0,0) (1,0) (0,1) (1,1), then y, then z.
+__device__ __forceinline__ float lerp(float x, float y, float t) { return x + (y - x) * t; }
+
+__device__ __forceinline__ bool field(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz, float& F) {
+  const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
+  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+  if (!(fx >= 0.0f && fx <= (float)(G.dim[0] - 2) && fy >= 0.0f && fy <= (float)(G.dim[1] - 2) && fz >= 0.0f &&
+        fz <= (float)(G.dim[2] - 2)))
+    return false;
+  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
+  const int64_t sy = 2 * (int64_t)G.dim[0], sz = sy * G.dim[1];
+  const float* b = vol + (int64_t)(int)fz * sz + (int64_t)(int)fy * sy + 2 * (int64_t)(int)fx;
+  const float2 v000 = *reinterpret_cast<const float2*>(b), v100 = *reinterpret_cast<const float2*>(b + 2);
+  const float2 v010 = *reinterpret_cast<const float2*>(b + sy), v110 = *reinterpret_cast<const float2*>(b + sy + 2);
+  const float2 v001 = *reinterpret_cast<const float2*>(b + sz), v101 = *reinterpret_cast<const float2*>(b + sz + 2);
+  const float2 v011 = *reinterpret_cast<const float2*>(b + sz + sy), v111 = *reinterpret_cast<const float2*>(b + sz + sy + 2);
+  if (!(v000.y > 0.0f && v100.y > 0.0f && v010.y > 0.0f && v110.y > 0.0f && v001.y > 0.0f && v101.y > 0.0f && v011.y > 0.0f &&
+        v111.y > 0.0f))
+    return false;
+  const float c00 = lerp(v000.x, v100.x, ax), c10 = lerp(v010.x, v110.x, ax), c01 = lerp(v001.x, v101.x, ax), c11 = lerp(v011.x, v111.x, ax);
+  const float c0 = lerp(c00, c10, ay), c1 = lerp(c01, c11, ay);
+  F = lerp(c0, c1, az);
+  return true;
+}
+
+// the model normal at world point (px, py, pz): the central differences F(p + s e) - F(p - s e) per axis divided by
+// sqrtf(x*x + y*y + z*z); false (the caller leaves NaN) if any of the six samples is unknown or the length is 0
+__device__ __forceinline__ bool field_normal(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz,
+                                             float& nx, float& ny, float& nz) {
+  const float s = G.s;
+  float a, b, c, d, e, f;
+  const bool ok = field(vol, G, px + s, py, pz, a) && field(vol, G, px - s, py, pz, b) && field(vol, G, px, py + s, pz, c) &&
+                  field(vol, G, px, py - s, pz, d) && field(vol, G, px, py, pz + s, e) && field(vol, G, px, py, pz - s, f);
+  if (!ok) return false;
+  const float gx = a - b, gy = c - d, gz = e - f;
+  const float len = sqrtf(gx * gx + gy * gy + gz * gz);
+  if (!(len > 0.0f)) return false;
+  nx = gx / len; ny = gy / len; nz = gz / len;
+  return true;
+}
+
+}  // namespace
+}  // namespace rpe

@@ -14,6 +14,7 @@
 // Frame-to-model tracking against a TSDF volume (KinectFusion):
 //   fe.initVolume(desc);  fe.setDepthPyramid(d0, cam, 3);  fe.integrate(T0);
 //   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.raycast(T, cam, range, 3);  fe.icpPyramid(T, {6, 4, 3});  fe.integrate(T);
+//   rpe::Mesh m = fe.mesh();                                             // the surface: marching cubes on the GPU
 //
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
@@ -47,6 +48,12 @@ struct VolumeDesc {
   int dim[3] = {256, 256, 256};
   double voxel_size = 0.02, origin[3] = {-2.56, -2.56, -0.5}, trunc = 0.06;
   int max_weight = 64;
+};
+// a triangle mesh of the volume's zero level set (DepthFrontEnd::mesh): 3 x V vertices and normals (world frame; NaN normals where
+// the field is unknown), 3 x T vertex ids, wound so that (v1 - v0) x (v2 - v0) points to free space
+struct Mesh {
+  MatrixX<float> vertices, normals;
+  std::vector<int32_t> triangles;
 };
 struct IcpResult { int iterations = 0; double last_step = 0, cost = 0; long long pairs = 0; };
 // coarse-to-fine ICP: rounds run per level (0 = finest); the rest as IcpResult, of level 0
@@ -165,6 +172,23 @@ class DepthFrontEnd {
     MatrixX<float> m(2, _vol.dim[0] * _vol.dim[1] * _vol.dim[2]);
     check(rpe_volume_download(_ctx, m.data()), "rpe_volume_download");
     return m;
+  }
+  // replace the volume's voxels: 2 x voxels floats {tsdf, weight}, the layout volume() returns
+  void uploadVolume(const MatrixX<float>& m) {
+    if (m.rows() != 2 || (long long)m.cols() != (long long)_vol.dim[0] * _vol.dim[1] * _vol.dim[2])
+      throw DeviceError(RPE_ERR_ARG, "uploadVolume: expected 2 x voxels floats");
+    check(rpe_volume_upload(_ctx, m.data()), "rpe_volume_upload");
+  }
+  // marching cubes over the volume, corners with weight >= min_weight (rpe_volume_mesh), brought to the host
+  Mesh mesh(double min_weight = 1) const {
+    int64_t nv = 0, nt = 0;
+    check(rpe_volume_mesh(_ctx, min_weight, &nv, &nt), "rpe_volume_mesh");
+    Mesh M;
+    M.vertices.resize(3, (int)nv);
+    M.normals.resize(3, (int)nv);
+    M.triangles.resize((size_t)nt * 3);
+    check(rpe_volume_mesh_download(_ctx, M.vertices.data(), M.normals.data(), M.triangles.data()), "rpe_volume_mesh_download");
+    return M;
   }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
