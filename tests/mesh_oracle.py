@@ -73,9 +73,12 @@ def used_edges(case):
     return used.astype(np.uint8)
 
 
-def mesh(vol, G, min_weight=1.0):
-    """(vertices (V, 3) f32, normals (V, 3) f32, triangles (T, 3) int32) of rpe_volume_mesh"""
-    d0, d1, d2 = G.dim
+def mesh(vol, G, min_weight=1.0, k0=0, id0=0):
+    """(vertices (V, 3) f32, normals (V, 3) f32, triangles (T, 3) int32) of rpe_volume_mesh.  vol may be the z-slab window
+    [k0, k0 + len(vol)) of a volume whose slabs k0 - 1 and k0 + len(vol) (where they exist) are unobserved: then no active cube
+    reaches outside it, and the window's part of the mesh is this one, with its vertex ids starting at id0 (the vertices of the slabs
+    before k0)."""
+    d0, d1 = G.dim[:2]
     case = cases(vol, min_weight)
     used = used_edges(case)
     flat_used = used.reshape(-1).astype(np.int64)
@@ -83,7 +86,7 @@ def mesh(vol, G, min_weight=1.0):
     vox, axis = np.nonzero(bits)                                        # voxel order, then axis: the vertex order
     ts = vol.reshape(-1, 2)[:, 0]
     strides = np.array([1, d0, d0 * d1], np.int64)
-    i, j, k = vox % d0, (vox // d0) % d1, vox // (d0 * d1)
+    i, j, k = vox % d0, (vox // d0) % d1, vox // (d0 * d1) + k0
     ijk = np.stack([i, j, k], -1)
     Fa, Fb = ts[vox], ts[vox + strides[axis]]
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
@@ -93,9 +96,9 @@ def mesh(vol, G, min_weight=1.0):
             centre = G.o[a] + (ijk[:, a].astype(F) + F(0.5)) * G.s
             along = G.o[a] + ((ijk[:, a].astype(F) + F(0.5)) + t) * G.s
             P[:, a] = np.where(axis == a, along, centre)
-        N = normals(vol, G, P)
+        N = normals(vol, G, P, k0)
     counts = bits.sum(1)
-    first = np.cumsum(counts) - counts                                  # first vertex id per voxel
+    first = id0 + np.cumsum(counts) - counts                            # first vertex id per voxel
     ntri = TRI_COUNT[case.reshape(-1)]
     cube = np.repeat(np.arange(ntri.size), ntri)
     r = np.arange(cube.size) - np.repeat(np.cumsum(ntri) - ntri, ntri)
@@ -105,19 +108,20 @@ def mesh(vol, G, min_weight=1.0):
     ax = EDGE_AXIS[edges]
     lower = flat_used[owner] & ((1 << ax) - 1)
     ids = first[owner] + (lower & 1) + ((lower >> 1) & 1)
+    assert ids.size == 0 or ids.max() < 2 ** 31
     return P, N, ids.astype(np.int32).reshape(-1, 3)
 
 
-def normals(vol, G, P):
+def normals(vol, G, P, k0=0):
     """the raycast's model normal at P: central differences of F over +- s per axis, normalised; NaN if a sample is unknown or the
-    length is 0"""
+    length is 0.  vol may be a z-slab window from k0, unobserved outside (volume_oracle.field)."""
     s = G.s
     samples = []
     for a in range(3):
         for sign in (1, -1):
             Q = P.copy()
             Q[:, a] = P[:, a] + s if sign > 0 else P[:, a] - s
-            samples.append(VO.field(vol, G, Q))
+            samples.append(VO.field(vol, G, Q, k0))
     good = np.ones(len(P), bool)
     for _, kn in samples:
         good &= kn

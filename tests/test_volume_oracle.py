@@ -67,6 +67,33 @@ def test_invalid_depth_and_out_of_image_voxels_are_skipped():
     assert np.all(behind == 0)
 
 
+@pytest.mark.parametrize("weight_bits, name", [(0x7fc00000, "nan"), (0xffc12345, "negative_nan_payload"), (0x7f800001, "snan"),
+                                                (0x7fa00005, "snan_payload"), (0x7f800000, "inf")])
+def test_fminf_weight_of_nan_and_inf_is_max_weight(weight_bits, name):
+    """w := fminf(w + 1.0f, W): a NaN w + 1 (a quiet or signalling NaN weight; the add quiets it) gives W, as does +Inf; once at W,
+    the next frame keeps W.  np.minimum would give NaN."""
+    fx, fy, cx, cy, w, h = SMALL_CAM
+    G = VO.Geometry((40, 32, 60), 0.05, (-1.0, -0.8, 0.5), 0.15, 8)
+    V = FO.frame_maps(np.full((h, w), 2.0, f32), SMALL_CAM, 1.0, 0.1, 10.0, 0.1)[0]
+    vol = G.empty()
+    vol[..., 0] = 0.25
+    vol[..., 1] = np.array([weight_bits], np.uint32).view(f32)[0]
+    out, ok = VO.integrate(vol, G, V, SMALL_CAM, I12, with_mask=True)
+    assert ok.sum() > 1000, name
+    assert np.all(out[..., 1][ok] == G.W), (name, np.unique(out[..., 1][ok]))
+    assert np.array_equal(out[~ok].view(np.uint32), vol[~ok].view(np.uint32))          # skipped voxels keep their bits
+    again = VO.integrate(out, G, V, SMALL_CAM, I12)
+    assert np.all(again[..., 1][ok] == G.W)
+
+
+def test_fminf_of_a_nan_f_is_one():
+    """f = fminf(1.0f, sdf / tr) as numpy states it: fmin, not minimum (a NaN quotient would give 1, not NaN)"""
+    with np.errstate(invalid="ignore"):
+        assert np.fmin(f32(1.0), f32(np.nan)) == f32(1.0)
+    src = open(os.path.join(ROOT, "tests", "volume_oracle.py")).read()
+    assert "np.minimum" not in src and src.count("np.fmin(") == 2
+
+
 def test_raycast_of_the_plane():
     D = 2.0
     G, vol = plane_volume(D)

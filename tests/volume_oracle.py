@@ -22,17 +22,20 @@ class Geometry:
         return np.zeros((d2, d1, d0, 2), F)
 
 
-def voxel_centres(G):
-    """per axis: o + ((float)i + 0.5f) * s, shaped to broadcast over (d2, d1, d0)"""
-    c = [G.o[a] + (np.arange(G.dim[a], dtype=F) + F(0.5)) * G.s for a in range(3)]
+def voxel_centres(G, k0=0, k1=None):
+    """per axis: o + ((float)i + 0.5f) * s, shaped to broadcast over (k1 - k0, d1, d0): the z-slab window [k0, k1) of the volume"""
+    k1 = G.dim[2] if k1 is None else k1
+    c = [G.o[a] + (np.arange(G.dim[a], dtype=F) + F(0.5)) * G.s for a in range(2)]
+    c.append(G.o[2] + (np.arange(k0, k1).astype(F) + F(0.5)) * G.s)
     return c[0][None, None, :], c[1][None, :, None], c[2][:, None, None]
 
 
-def integrate(vol, G, V, cam, pose12):
-    """V1: a new volume with the frame (level-0 vertex map V, (h*w, 3)) of camera cam fused in under pose12 (Xc = R Xw + t)."""
+def integrate(vol, G, V, cam, pose12, k0=0, with_mask=False):
+    """V1: a new volume with the frame (level-0 vertex map V, (h*w, 3)) of camera cam fused in under pose12 (Xc = R Xw + t).
+    vol may be the z-slab window [k0, k0 + len(vol)) of the volume; with_mask also returns the updated voxels (d2, d1, d0) bool."""
     fx, fy, cx, cy, w, h = FO._cam(cam)
     R, t = FO._pose_f(pose12)
-    px, py, pz = voxel_centres(G)
+    px, py, pz = voxel_centres(G, k0, k0 + vol.shape[0])
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         qx = R[0] * px + R[1] * py + R[2] * pz + t[0]
         qy = R[3] * px + R[4] * py + R[5] * pz + t[1]
@@ -46,22 +49,23 @@ def integrate(vol, G, V, cam, pose12):
         ok &= ~np.isnan(d)
         sdf = d - qz
         ok &= sdf >= -G.tr
-        f = np.minimum(F(1.0), sdf / G.tr)
+        f = np.fmin(F(1.0), sdf / G.tr)                          # fminf: a NaN operand gives the other one
         ts, wt = vol[..., 0], vol[..., 1]
         nts = (ts * wt + f) / (wt + F(1.0))
-        nwt = np.minimum(wt + F(1.0), G.W)
+        nwt = np.fmin(wt + F(1.0), G.W)                          # a NaN weight becomes W
     out = vol.copy()
     out[..., 0] = np.where(ok, nts, ts)
     out[..., 1] = np.where(ok, nwt, wt)
-    return out
+    return (out, ok) if with_mask else out
 
 
 def _lerp(x, y, t):
     return x + (y - x) * t
 
 
-def field(vol, G, X):
-    """F at world points X (n, 3): (value (n,), known (n,))."""
+def field(vol, G, X, k0=0):
+    """F at world points X (n, 3): (value (n,), known (n,)).  vol may be the z-slab window [k0, k0 + len(vol)) of the volume, every
+    voxel outside it unobserved (weight 0): a point whose cell reaches outside the window is unknown."""
     d0, d1, d2 = G.dim
     with np.errstate(invalid="ignore", over="ignore"):
         g = [(X[:, a] - G.o[a]) / G.s - F(0.5) for a in range(3)]
@@ -69,8 +73,10 @@ def field(vol, G, X):
         ok = np.ones(len(X), bool)
         for a in range(3):
             ok &= (i0[a] >= F(0)) & (i0[a] <= F(G.dim[a] - 2))
+        ok &= (i0[2] >= F(k0)) & (i0[2] <= F(k0 + vol.shape[0] - 2))
         ax, ay, az = [g[a] - i0[a] for a in range(3)]
     i, j, k = [np.where(ok, i0[a], F(0)).astype(np.int64) for a in range(3)]
+    k = np.where(ok, k - k0, 0)
     flat = vol.reshape(-1, 2)
     base = (k * d1 + j) * d0 + i
     v = {}
@@ -87,8 +93,20 @@ def field(vol, G, X):
     return _lerp(c0, c1, az), ok
 
 
+def windows_field(windows, G, X):
+    """F at X of a volume held as z-slab windows [(k0, vol), ...], unobserved (weight 0) outside them"""
+    val, known = np.zeros(len(X), F), np.zeros(len(X), bool)
+    for k0, vol in windows:
+        v, kn = field(vol, G, X, k0)
+        val = np.where(kn, v, val)
+        known |= kn
+    return val, known
+
+
 def raycast(vol, G, cam, pose12, dmin, dmax):
-    """V2: world vertex and normal maps ((h*w, 3) each) of the view pose12 with camera cam over camera depths (dmin, dmax)."""
+    """V2: world vertex and normal maps ((h*w, 3) each) of the view pose12 with camera cam over camera depths (dmin, dmax).  vol is
+    the volume or a list of its z-slab windows [(k0, slab), ...], unobserved outside them."""
+    fld = (lambda X: windows_field(vol, G, X)) if isinstance(vol, list) else (lambda X: field(vol, G, X))
     fx, fy, cx, cy, w, h = FO._cam(cam)
     R, t = FO._pose_f(pose12)
     xn = np.broadcast_to(((np.arange(w, dtype=F) - cx) / fx)[None, :], (h, w)).reshape(-1)
@@ -106,7 +124,7 @@ def raycast(vol, G, cam, pose12, dmin, dmax):
             if not z < hi:
                 break
             X = FO._to_world(R, t, np.stack([xn[live] * z, yn[live] * z, np.full(live.size, z, F)], -1))
-            Fk, known = field(vol, G, X)
+            Fk, known = fld(X)
             hit = known & prev[live] & (Fp[live] > F(0)) & (Fk <= F(0))
             hl = live[hit]
             zh[hl] = zp[hl] + s * (Fp[hl] / (Fp[hl] - Fk[hit]))
@@ -125,7 +143,7 @@ def raycast(vol, G, cam, pose12, dmin, dmax):
             for sign in (1, -1):
                 Q = P.copy()
                 Q[:, a] = P[:, a] + s if sign > 0 else P[:, a] - s
-                samples.append(field(vol, G, Q))
+                samples.append(fld(Q))
         good = np.ones(len(idx), bool)
         for _, kn in samples:
             good &= kn
