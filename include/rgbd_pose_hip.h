@@ -533,6 +533,46 @@ int rpe_volume_mesh(rpe_context* ctx, double min_weight, int64_t* n_vertices, in
  * RPE_ERR_STATE before any extraction or after rpe_volume_init */
 int rpe_volume_mesh_download(rpe_context* ctx, float* vertices, float* normals, int32_t* triangles);
 
+/* ---- Colour: a registered RGB image fused beside the depth, and the fused colour sampled at the model's and the mesh's vertices.
+ * Conventions, followed bit for bit (fp32, the written order, no FMA contraction; tests/color_oracle.py states them in numpy).
+ * h(x) = fp32 -> IEEE binary16, round to nearest even, subnormals kept, overflow to +-Inf, every NaN to the quiet NaN 0x7e00.
+ * Frame colour: width*height*3 bytes, row-major, at the current frame's level-0 size, REGISTERED to the depth image: pixel (u, v) of
+ * both images sees the same ray (a separate colour camera must be reprojected by the caller).  Stored on the device as RGBA8 with
+ * A = 255.  rpe_frame_set_depth and rpe_frame_set_depth_pyramid drop it.
+ * Colour volume: beside {tsdf, weight}, at the same voxel index; a voxel is four binary16 {r, g, b, wc} (8 bytes, channels on the
+ * 0..255 scale), wc = 0: no colour observed.  It comes into being, all zeros, on the first rpe_volume_integrate_color or
+ * rpe_volume_color_upload after rpe_volume_init; rpe_volume_init drops it; the plain rpe_volume_integrate never touches it.
+ * Integrate with colour (pose12): {tsdf, weight} are updated exactly as rpe_volume_integrate does it (same voxels, same bits).  A voxel
+ * that this rule updates AND whose sdf <= tr (inside the truncation band) also gets a colour update: the observation o = the frame
+ * colour at the same (uf, vf), each channel (float)byte; with w = (float)wc before the update, each channel
+ * c := h(((float)c * w + o) / (w + 1.0f)), then wc := h(fminf(w + 1.0f, W)) (for W > 2048 the weight stops at 2048: 2049 rounds to
+ * 2048; a NaN weight becomes W, as in the tsdf rule).  A voxel without a colour update is never stored (its 16-byte pair may be loaded).
+ * Colour field C(p): F's g, i0, a and in-range rule; known iff in range and all 8 corner COLOUR weights are > 0 (the tsdf weights
+ * play no part); each channel with F's lerp order on (float) of the binary16 values.  q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f),
+ * 255.0f) + 0.5f) (a NaN channel gives 0, +Inf 255).  Output RGBA8: (q(r), q(g), q(b), 255) when known, (0, 0, 0, 0) when unknown or
+ * at a NaN point.
+ * Model colour = C at the level-0 model vertex of each pixel; mesh colour = C at each vertex of the last mesh.  So a mesh colour is bit
+ * for bit the model colour at the same point.  Any call that replaces the model (rpe_volume_raycast, rpe_model_upload,
+ * rpe_model_from_frame) drops the model colour.  Colour calls without the colour state they need return RPE_ERR_STATE. */
+enum { RPE_COLOR_RGB8 = 0, RPE_COLOR_BGR8 = 1 };
+enum { RPE_COLOR_FRAME = 0, RPE_COLOR_MODEL = 1 };
+/* the current frame's colour: width*height*3 bytes in `format` order (RPE_COLOR_*8); RPE_ERR_STATE without a frame */
+int rpe_frame_set_color(rpe_context* ctx, const uint8_t* pixels, int format);
+/* rpe_volume_integrate plus the colour update of the band voxels; RPE_ERR_STATE without a volume, a frame or a frame colour */
+int rpe_volume_integrate_color(rpe_context* ctx, const double* pose12);
+/* the model colour map := C at the model's level-0 vertices (after rpe_volume_raycast, rpe_model_upload or rpe_model_from_frame);
+ * RPE_ERR_STATE without a model or a colour volume */
+int rpe_model_sample_color(rpe_context* ctx);
+/* copy the frame colour (which = RPE_COLOR_FRAME) or the model colour (RPE_COLOR_MODEL) out: 4 x width*height bytes RGBA8 */
+int rpe_color_download(rpe_context* ctx, int which, uint8_t* rgba);
+/* RGBA8 colours of the last mesh's vertices, 4 x n_vertices bytes (nothing for an empty mesh); RPE_ERR_STATE without a mesh or a
+ * colour volume */
+int rpe_volume_mesh_colors(rpe_context* ctx, uint8_t* rgba);
+/* copy the colour volume out: 4 x voxels binary16 bit patterns {r, g, b, wc} in voxel index order; RPE_ERR_STATE without one */
+int rpe_volume_color_download(rpe_context* ctx, uint16_t* rgbw);
+/* the inverse of rpe_volume_color_download (the bits are taken as given); RPE_ERR_STATE without a volume */
+int rpe_volume_color_upload(rpe_context* ctx, const uint16_t* rgbw);
+
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.
  * 3 x K inputs are column-major doubles whose values are rounded to dtype before use. */

@@ -23,6 +23,8 @@ DEPTH_U16, DEPTH_F32 = 0, 1
 MAP_VERTEX, MAP_NORMAL, MAP_BEARING, MAP_MODEL_VERTEX, MAP_MODEL_NORMAL = 0, 1, 2, 3, 4
 MAP_DEPTH = 5
 MAX_LEVELS = 4
+COLOR_RGB8, COLOR_BGR8 = 0, 1
+COLOR_FRAME, COLOR_MODEL = 0, 1
 
 # every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -35,6 +37,8 @@ SYMBOLS = [
     "rpe_frame_set_depth_pyramid", "rpe_frame_download_level", "rpe_frame_level_camera", "rpe_model_build_pyramid", "rpe_icp_pyramid",
     "rpe_volume_init", "rpe_volume_integrate", "rpe_volume_raycast", "rpe_volume_download",
     "rpe_volume_upload", "rpe_volume_mesh", "rpe_volume_mesh_download",
+    "rpe_frame_set_color", "rpe_volume_integrate_color", "rpe_model_sample_color", "rpe_color_download", "rpe_volume_mesh_colors",
+    "rpe_volume_color_download", "rpe_volume_color_upload",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -183,6 +187,13 @@ def lib():
         L.rpe_volume_upload.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_volume_mesh.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.rpe_volume_mesh_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_frame_set_color.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rpe_volume_integrate_color.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_model_sample_color.argtypes = [C.c_void_p]
+        L.rpe_color_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rpe_volume_mesh_colors.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_volume_color_download.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_volume_color_upload.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

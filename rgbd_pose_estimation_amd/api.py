@@ -58,6 +58,8 @@ class Context:
         self._keep = {}
         self._pixels = self._model_pixels = 0   # front end: pixels of the current frame / of the model view
         self._vol_dims = (0, 0, 0)              # TSDF volume: voxels per axis (volume_init)
+        self._frame_hw = None                   # (height, width) of the current frame (frame_set_color's shape)
+        self._mesh_nv = None                    # vertices of the last mesh (volume_mesh_colors)
 
     def close(self):
         if self._h:
@@ -216,6 +218,7 @@ class Context:
         else:
             L.check(L.lib().rpe_frame_set_depth_pyramid(self._h, _p(d), kind, C.byref(k), scale, dmin, dmax, max_jump, int(levels)))
         self._pixels = k.width * k.height
+        self._frame_hw = (k.height, k.width)
         return self
 
     def frame_download(self, which: int, level: int = 0) -> np.ndarray:
@@ -306,6 +309,7 @@ class Context:
                             float(trunc), int(max_weight))
         L.check(L.lib().rpe_volume_init(self._h, C.byref(d)))
         self._vol_dims = tuple(int(x) for x in dims)
+        self._mesh_nv = None
         return self
 
     def volume_integrate(self, pose12):
@@ -345,12 +349,75 @@ class Context:
         """Marching cubes over the volume (corners with weight >= min_weight): (vertices (V, 3) float32, normals (V, 3) float32, NaN
         where the field is unknown, triangles (T, 3) int32), wound so that (v1 - v0) x (v2 - v0) points to free space."""
         nv, nt = C.c_int64(0), C.c_int64(0)
+        self._mesh_nv = None
         L.check(L.lib().rpe_volume_mesh(self._h, float(min_weight), C.byref(nv), C.byref(nt)))
+        self._mesh_nv = nv.value
         V = np.empty((nv.value, 3), np.float32)
         N = np.empty((nv.value, 3), np.float32)
         T = np.empty((nt.value, 3), np.int32)
         L.check(L.lib().rpe_volume_mesh_download(self._h, _p(V), _p(N), _p(T)))
         return V, N, T
+
+    # ---- colour (Part 3): a registered RGB frame fused beside the depth, sampled back at the model's and the mesh's vertices
+    def frame_set_color(self, rgb, order: str = "rgb"):
+        """The current frame's colour: (height, width, 3) uint8 registered to its depth (pixel (u, v) of both sees the same ray), channels
+        in `order` "rgb" or "bgr".  A new depth drops it."""
+        fmt = {"rgb": L.COLOR_RGB8, "bgr": L.COLOR_BGR8}.get(str(order).lower())
+        if fmt is None:
+            raise ValueError(f"frame_set_color: order must be 'rgb' or 'bgr', got {order!r}")
+        a = np.ascontiguousarray(rgb)
+        if a.dtype != np.uint8:
+            raise TypeError("frame_set_color: the image must be uint8")
+        if self._frame_hw is not None and a.shape != self._frame_hw + (3,):
+            raise ValueError(f"frame_set_color: expected shape {self._frame_hw + (3,)}, got {a.shape}")
+        L.check(L.lib().rpe_frame_set_color(self._h, _p(a), fmt))
+        return self
+
+    def volume_integrate_color(self, pose12):
+        """volume_integrate plus the colour of the frame fused into the voxels inside the truncation band."""
+        p = np.array(pose12, np.float64).reshape(12)
+        L.check(L.lib().rpe_volume_integrate_color(self._h, _p(p)))
+        return self
+
+    def volume_color_download(self) -> np.ndarray:
+        """The colour volume as (d2, d1, d0, 4) float16: [..., :3] = r, g, b on the 0..255 scale, [..., 3] = colour weight (0 = none)."""
+        d0, d1, d2 = self._vol_dims
+        out = np.empty((d2, d1, d0, 4), np.float16)
+        L.check(L.lib().rpe_volume_color_download(self._h, _p(out)))
+        return out
+
+    def volume_color_upload(self, cvol):
+        """Replace the colour volume with `cvol`, (d2, d1, d0, 4) float16 as volume_color_download returns it; the bits are taken as
+        given."""
+        d0, d1, d2 = self._vol_dims
+        a = np.ascontiguousarray(cvol)
+        if a.dtype != np.float16 or a.shape != (d2, d1, d0, 4):
+            raise ValueError(f"volume_color_upload: expected float16 of shape {(d2, d1, d0, 4)}, got {a.dtype} {a.shape}")
+        L.check(L.lib().rpe_volume_color_upload(self._h, _p(a)))
+        return self
+
+    def frame_color(self) -> np.ndarray:
+        """The frame colour as the device holds it: (height, width, 4) uint8 RGBA with A = 255."""
+        h, w = self._frame_hw if self._frame_hw is not None else (0, 0)
+        out = np.empty((h, w, 4) if h else (1, 1, 4), np.uint8)
+        L.check(L.lib().rpe_color_download(self._h, L.COLOR_FRAME, _p(out)))
+        return out
+
+    def model_color(self) -> np.ndarray:
+        """Samples the colour field at the model's level-0 vertices (rpe_model_sample_color) and returns the map: (height, width, 4)
+        uint8 RGBA of the model's view, A = 255 where the colour is known and (0, 0, 0, 0) where it is not."""
+        L.check(L.lib().rpe_model_sample_color(self._h))
+        k = self.frame_camera(0, model=True)
+        out = np.empty((k[5], k[4], 4), np.uint8)
+        L.check(L.lib().rpe_color_download(self._h, L.COLOR_MODEL, _p(out)))
+        return out
+
+    def volume_mesh_colors(self) -> np.ndarray:
+        """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh): the colour field there, as model_color samples it."""
+        n = self._mesh_nv or 0
+        out = np.empty((n, 4), np.uint8)
+        L.check(L.lib().rpe_volume_mesh_colors(self._h, _p(out) if n else None))
+        return out
 
     def gn_steps_dist(self, kind: int, pose12_inout: np.ndarray, steps: int, flags: int = 0) -> float:
         """`steps` sharded GN steps in place, the loop inside the library; returns the last |delta|."""

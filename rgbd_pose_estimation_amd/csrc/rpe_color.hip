@@ -1,0 +1,192 @@
+// gfx950 kernels of the COLOUR half of the TSDF volume: a registered RGB image is fused beside the depth, and the fused colour is
+// sampled back at world points (the model's vertices, the mesh's vertices).
+//
+//   C1  frame_color_kernel              the 3-byte staging upload of one frame into its RGBA8 map (A = 255), RGB or BGR order.
+//   C2  volume_integrate_color_kernel   V1 (rpe_volume.hip) plus the colour: the tsdf half is V1's code (voxel_project / fuse of
+//                                       rpe_volume_field.hpp) and touches the same voxels with the same bits; a voxel that V1 updates
+//                                       and that lies inside the truncation band (sdf <= tr) also blends the frame colour of its pixel
+//                                       into its four binary16 {r, g, b, wc}.  A lane owns 4 voxels: two 16-byte {tsdf, w} pairs and two
+//                                       16-byte colour pairs, each loaded and stored only where one of its voxels is updated, plus one
+//                                       4-byte frame-colour gather per band voxel.
+//   C3  color_sample_kernel             RGBA8 of the colour field C at N world points (stride 3 floats), one lane per point, eight 8-byte
+//                                       corner gathers.  Serves the model colour map and the mesh colours.
+//
+// The conventions (include/rgbd_pose_hip.h Part 3, "Colour") are followed BIT-EXACTLY: fp32, the written order, no FMA contraction;
+// tests/color_oracle.py is their numpy statement.
+#include "rpe_assoc.h"
+#include "rpe_volume_field.hpp"
+
+namespace rpe {
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kVolBlock = 256;    // C2: 4 voxels per lane, as V1
+constexpr int kColorBlock = 256;  // C1, C3: one pixel / point per lane
+
+// binary16 <-> fp32.  h(x): round to nearest even, subnormals kept, every NaN to the quiet NaN 0x7e00.
+__device__ __forceinline__ float h2f(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
+__device__ __forceinline__ unsigned f2h(float x) { return x == x ? (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x) : 0x7e00u; }
+
+// ---------------------------------------------------------------------------------------------- C1
+__global__ __launch_bounds__(kColorBlock) void frame_color_kernel(const unsigned char* __restrict__ rgb, int64_t n, int bgr,
+                                                                  unsigned int* __restrict__ rgba) {
+  const int64_t i = (int64_t)blockIdx.x * kColorBlock + threadIdx.x;
+  if (i >= n) return;
+  const unsigned a = rgb[3 * i], g = rgb[3 * i + 1], c = rgb[3 * i + 2];
+  const unsigned r = bgr ? c : a, b = bgr ? a : c;
+  rgba[i] = r | g << 8 | b << 16 | 0xff000000u;
+}
+
+// ---------------------------------------------------------------------------------------------- C2
+// One voxel's colour {r, g, b, wc} as two words (rg = r | g << 16, bw = b | wc << 16) and the observation o (RGBA8): with w = (float)wc
+// before the update, each channel c := h(((float)c * w + o) / (w + 1.0f)), then wc := h(fminf(w + 1.0f, W)).
+__device__ __forceinline__ void blend(unsigned& rg, unsigned& bw, unsigned o, float W) {
+  const float w = h2f(bw >> 16);
+  const float r = (h2f(rg & 0xffffu) * w + (float)(o & 0xffu)) / (w + 1.0f);
+  const float g = (h2f(rg >> 16) * w + (float)((o >> 8) & 0xffu)) / (w + 1.0f);
+  const float b = (h2f(bw & 0xffffu) * w + (float)((o >> 16) & 0xffu)) / (w + 1.0f);
+  rg = f2h(r) | f2h(g) << 16;
+  bw = f2h(b) | f2h(fminf(w + 1.0f, W)) << 16;
+}
+
+// nvox <= 2^30 (dims <= 1024): the flat voxel index fits 32 bits, byte offsets do not
+__global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float* __restrict__ vol, unsigned short* __restrict__ cvol,
+                                                                           VolumeGeometry G, int64_t nvox, const float* __restrict__ vmap,
+                                                                           const unsigned int* __restrict__ rgba, Camera cam, PoseF T) {
+  const int64_t first = ((int64_t)blockIdx.x * kVolBlock + threadIdx.x) * 4;
+  if (first >= nvox) return;
+  const unsigned flat = (unsigned)first, d0 = (unsigned)G.dim[0], d1 = (unsigned)G.dim[1];
+  int i = (int)(flat % d0), j = (int)((flat / d0) % d1), k = (int)(flat / d0 / d1);
+  float f[4], sdf[4];
+  int64_t pix[4];
+  bool up[4], band[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    f[q] = 0.0f; sdf[q] = 0.0f; pix[q] = 0;
+    up[q] = first + q < nvox && voxel_project(G, vmap, cam, T, i, j, k, f[q], sdf[q], pix[q]);
+    band[q] = up[q] && sdf[q] <= G.tr;
+    if (++i == G.dim[0]) { i = 0; if (++j == G.dim[1]) { j = 0; ++k; } }
+  }
+  // the lane's two {tsdf, w} pairs and two colour pairs: a pair is loaded if either of its voxels is updated (colour: in the band)
+  float4 v[2];
+  uint4 c[2];
+  unsigned o[4];
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const int64_t a = first + 2 * p;
+    v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (up[2 * p] || up[2 * p + 1]) {
+      if (a + 1 < nvox) v[p] = *reinterpret_cast<const float4*>(vol + 2 * a);
+      else { const float2 h = *reinterpret_cast<const float2*>(vol + 2 * a); v[p].x = h.x; v[p].y = h.y; }
+    }
+    c[p] = make_uint4(0u, 0u, 0u, 0u);
+    if (band[2 * p] || band[2 * p + 1]) {
+      if (a + 1 < nvox) c[p] = *reinterpret_cast<const uint4*>(cvol + 4 * a);
+      else { const uint2 h = *reinterpret_cast<const uint2*>(cvol + 4 * a); c[p].x = h.x; c[p].y = h.y; }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; q++) o[q] = band[q] ? rgba[pix[q]] : 0u;
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const bool lo = up[2 * p], hi = up[2 * p + 1];
+    if (!lo && !hi) continue;
+    float* q = vol + 2 * (first + 2 * p);
+    if (lo) fuse(v[p].x, v[p].y, f[2 * p], G.W);
+    if (hi) fuse(v[p].z, v[p].w, f[2 * p + 1], G.W);
+    if (lo && hi) *reinterpret_cast<float4*>(q) = v[p];
+    else if (lo) *reinterpret_cast<float2*>(q) = make_float2(v[p].x, v[p].y);
+    else *reinterpret_cast<float2*>(q + 2) = make_float2(v[p].z, v[p].w);
+  }
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const bool lo = band[2 * p], hi = band[2 * p + 1];
+    if (!lo && !hi) continue;
+    unsigned short* q = cvol + 4 * (first + 2 * p);
+    if (lo) blend(c[p].x, c[p].y, o[2 * p], G.W);
+    if (hi) blend(c[p].z, c[p].w, o[2 * p + 1], G.W);
+    if (lo && hi) *reinterpret_cast<uint4*>(q) = c[p];
+    else if (lo) *reinterpret_cast<uint2*>(q) = make_uint2(c[p].x, c[p].y);
+    else *reinterpret_cast<uint2*>(q + 4) = make_uint2(c[p].z, c[p].w);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- C3
+// C(p): F's g, i0, a and in-range rule; known iff in range and all eight corner colour weights are > 0; each channel with F's lerp
+// order on (float) of the binary16 values.  q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f).
+__device__ __forceinline__ unsigned quantise(float x) { return (unsigned)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f); }
+
+__device__ __forceinline__ float trilerp(float v000, float v100, float v010, float v110, float v001, float v101, float v011, float v111,
+                                         float ax, float ay, float az) {
+  const float c00 = lerp(v000, v100, ax), c10 = lerp(v010, v110, ax), c01 = lerp(v001, v101, ax), c11 = lerp(v011, v111, ax);
+  const float c0 = lerp(c00, c10, ay), c1 = lerp(c01, c11, ay);
+  return lerp(c0, c1, az);
+}
+
+__global__ __launch_bounds__(kColorBlock) void color_sample_kernel(const unsigned short* __restrict__ cvol, VolumeGeometry G,
+                                                                   const float* __restrict__ pts, int64_t n,
+                                                                   unsigned int* __restrict__ rgba) {
+  const int64_t e = (int64_t)blockIdx.x * kColorBlock + threadIdx.x;
+  if (e >= n) return;
+  const float px = pts[3 * e], py = pts[3 * e + 1], pz = pts[3 * e + 2];
+  unsigned out = 0u;
+  const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
+  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
+  if (fx >= 0.0f && fx <= (float)(G.dim[0] - 2) && fy >= 0.0f && fy <= (float)(G.dim[1] - 2) && fz >= 0.0f &&
+      fz <= (float)(G.dim[2] - 2)) {
+    const float ax = gx - fx, ay = gy - fy, az = gz - fz;
+    const int64_t sy = 4 * (int64_t)G.dim[0], sz = sy * G.dim[1];
+    const unsigned short* b = cvol + (int64_t)(int)fz * sz + (int64_t)(int)fy * sy + 4 * (int64_t)(int)fx;
+    uint2 v[8];   // corner n = di + 2 dj + 4 dk
+#pragma unroll
+    for (int m = 0; m < 8; m++) v[m] = *reinterpret_cast<const uint2*>(b + ((m & 4) ? sz : 0) + ((m & 2) ? sy : 0) + ((m & 1) ? 4 : 0));
+    bool known = true;
+#pragma unroll
+    for (int m = 0; m < 8; m++) known = known && h2f(v[m].y >> 16) > 0.0f;
+    if (known) {
+      float ch[3];
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+        float x[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) x[m] = h2f(a == 0 ? v[m].x & 0xffffu : a == 1 ? v[m].x >> 16 : v[m].y & 0xffffu);
+        ch[a] = trilerp(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], ax, ay, az);
+      }
+      out = quantise(ch[0]) | quantise(ch[1]) << 8 | quantise(ch[2]) << 16 | 0xff000000u;
+    }
+  }
+  rgba[e] = out;
+}
+
+}  // namespace
+
+hipError_t launch_frame_color(const unsigned char* rgb, int64_t n, int bgr, unsigned int* rgba, hipStream_t s) {
+  const int64_t blocks = (n + kColorBlock - 1) / kColorBlock;
+  hipLaunchKernelGGL(frame_color_kernel, dim3((unsigned)blocks), dim3(kColorBlock), 0, s, rgb, n, bgr, rgba);
+  return hipGetLastError();
+}
+
+hipError_t launch_volume_integrate_color(float* vol, unsigned short* cvol, const VolumeGeometry& G, const float* vmap,
+                                         const unsigned int* rgba, const Camera& cam, const PoseF& T, hipStream_t s) {
+  const int64_t nvox = (int64_t)G.dim[0] * G.dim[1] * G.dim[2];
+  const int64_t blocks = (nvox + 4 * kVolBlock - 1) / (4 * kVolBlock);
+  hipLaunchKernelGGL(volume_integrate_color_kernel, dim3((unsigned)blocks), dim3(kVolBlock), 0, s, vol, cvol, G, nvox, vmap, rgba, cam, T);
+  return hipGetLastError();
+}
+
+hipError_t launch_color_sample(const unsigned short* cvol, const VolumeGeometry& G, const float* pts, int64_t n, unsigned int* rgba,
+                               hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int64_t blocks = (n + kColorBlock - 1) / kColorBlock;
+  hipLaunchKernelGGL(color_sample_kernel, dim3((unsigned)blocks), dim3(kColorBlock), 0, s, cvol, G, pts, n, rgba);
+  return hipGetLastError();
+}
+
+void preload_color() {
+  hipFuncAttributes a;
+  if (hipFuncGetAttributes(&a, (const void*)volume_integrate_color_kernel) != hipSuccess) (void)hipGetLastError();
+}
+
+}  // namespace rpe

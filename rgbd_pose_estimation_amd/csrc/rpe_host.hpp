@@ -8,6 +8,7 @@
 //   rpe_frontend_api.hip  Part 3: depth-frame front end and ICP
 //   rpe_volume_api.hip    Part 3: TSDF volume (integrate, raycast into the model, upload / download)
 //   rpe_mesh_api.hip      Part 3: mesh extraction from the TSDF volume (marching cubes) and its download
+//   rpe_color_api.hip     Part 3: frame colour, the colour volume beside the TSDF, model and mesh colours
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -156,6 +157,12 @@ struct rpe_context {
     rpe_camera kcam[RPE_MAX_LEVELS] = {}, mkcam[RPE_MAX_LEVELS] = {};
     float* fdepth = nullptr; size_t fdcap = 0;
     bool have_depth = false;
+    // colour (rpe_color_api.hip): the frame's 3-byte staging upload and its RGBA8 map (level-0 pixels, dropped by a new depth), and
+    // the model's RGBA8 colour map (level-0 pixels, sampled from the colour volume, dropped by any call that replaces the model)
+    unsigned char* d_rgb = nullptr; size_t rgb_cap = 0;
+    unsigned int* fcolor = nullptr; size_t fccap = 0;
+    unsigned int* mcolor = nullptr; size_t mccap = 0;
+    bool have_fcolor = false, have_mcolor = false;
   } fe;
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
   struct Volume {
@@ -168,6 +175,11 @@ struct rpe_context {
     float *mv = nullptr, *mn = nullptr; int32_t* mt = nullptr; size_t mv_cap = 0, mt_cap = 0;
     int64_t nv = 0, nt = 0;
     bool have_mesh = false;
+    // colour volume (rpe_color_api.hip): 4 binary16 {r, g, b, wc} per voxel at the tsdf's index, allocated and cleared on the first
+    // colour integrate or upload after rpe_volume_init (have_color); mc = the RGBA8 colours of the last mesh's vertices
+    unsigned short* cd = nullptr; size_t ccap = 0;
+    bool have_color = false;
+    unsigned int* mc = nullptr; size_t mc_cap = 0;
   } vol;
 
   rpe::DeviceArrays arrays() const {

@@ -106,7 +106,7 @@ int resident_cap_device();
 // Each kernel unit is a code object of its own that the runtime loads on the first launch out of it (a few milliseconds, once per
 // process and device).  rpe_create touches one kernel of every unit so that the first frame does not pay for it in the middle of a run.
 void preload_normal_eq(); void preload_icp(); void preload_joint(); void preload_score(); void preload_nl();
-void preload_frontend(); void preload_hypotheses(); void preload_prosac(); void preload_volume(); void preload_mesh();
+void preload_frontend(); void preload_hypotheses(); void preload_prosac(); void preload_volume(); void preload_mesh(); void preload_color();
 void resident_geometry(const DeviceArrays& A, int kind, int max_blocks, int* grid, int* nacc, int* max_rows, int* rows_auto);
 // The solving workgroup of an autonomous resident loop (rpe_residuals.hpp solver_loop): ONE workgroup, launched on a stream of its own
 // BEFORE the workers' kernel (launch_normal_eq_resident / launch_normal_eq_joint_resident with rt.solver = 1, same rt otherwise); nacc =
@@ -258,6 +258,15 @@ hipError_t launch_mesh_count(const float* vol, const VolumeGeometry& G, float wm
 // M4-M5 after launch_mesh_count: 3 x V vertex and normal floats, 3 x T int32 triangle ids
 hipError_t launch_mesh_emit(const float* vol, const VolumeGeometry& G, const MeshWorkspace& W, float* vertices, float* normals,
                             int* triangles, hipStream_t s);
+// ---- colour (rpe_color.hip): frame colour RGBA8 per pixel; colour volume 4 binary16 {r, g, b, wc} per voxel, the tsdf's voxel index
+// C1: n pixels of 3 bytes (bgr = 1: B, G, R order) -> RGBA8 with A = 255
+hipError_t launch_frame_color(const unsigned char* rgb, int64_t n, int bgr, unsigned int* rgba, hipStream_t s);
+// C2: V1 on vol plus the colour update of the band voxels (updated and sdf <= tr) from the frame colour rgba (level-0 pixels)
+hipError_t launch_volume_integrate_color(float* vol, unsigned short* cvol, const VolumeGeometry& G, const float* vmap,
+                                         const unsigned int* rgba, const Camera& cam, const PoseF& T, hipStream_t s);
+// C3: RGBA8 of the colour field C at n world points (stride 3 floats)
+hipError_t launch_color_sample(const unsigned short* cvol, const VolumeGeometry& G, const float* pts, int64_t n, unsigned int* rgba,
+                               hipStream_t s);
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

@@ -27,30 +27,7 @@ constexpr int kRayTile = 16;      // raycast: 16 x 16 pixels per workgroup, 8 x 
 __device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
 
 // ---------------------------------------------------------------------------------------------- V1
-// Voxel (i, j, k), centre p = o + ((float)i + 0.5f) * s per axis; camera point pc = R p + t (rows left to right); pixel = nearest
-// (floorf(f * x / z + c + 0.5f)); d = z of the level-0 vertex map there (NaN = invalid depth); sdf = d - pc.z; updated iff pc.z > 0,
-// the pixel is in the image, d is valid and sdf >= -tr: f = fminf(1, sdf / tr), tsdf = (tsdf * w + f) / (w + 1), w = fminf(w + 1, W).
-__device__ __forceinline__ bool voxel_sdf(const VolumeGeometry& G, const float* __restrict__ vmap, const Camera& cam, const PoseF& T, int i,
-                                          int j, int k, float& f) {
-  const float px = G.o[0] + ((float)i + 0.5f) * G.s, py = G.o[1] + ((float)j + 0.5f) * G.s, pz = G.o[2] + ((float)k + 0.5f) * G.s;
-  const float cx = T.R[0] * px + T.R[1] * py + T.R[2] * pz + T.t[0];
-  const float cy = T.R[3] * px + T.R[4] * py + T.R[5] * pz + T.t[1];
-  const float cz = T.R[6] * px + T.R[7] * py + T.R[8] * pz + T.t[2];
-  if (!(cz > 0.0f)) return false;
-  const float uf = floorf(cam.fx * (cx / cz) + cam.cx + 0.5f), vf = floorf(cam.fy * (cy / cz) + cam.cy + 0.5f);
-  if (!(uf >= 0.0f && uf <= (float)(cam.width - 1) && vf >= 0.0f && vf <= (float)(cam.height - 1))) return false;
-  const float d = vmap[3 * ((int64_t)(int)vf * cam.width + (int)uf) + 2];
-  if (d != d) return false;
-  const float sdf = d - cz;
-  if (!(sdf >= -G.tr)) return false;
-  f = fminf(1.0f, sdf / G.tr);
-  return true;
-}
-
-__device__ __forceinline__ void fuse(float& tsdf, float& w, float f, float W) {
-  tsdf = (tsdf * w + f) / (w + 1.0f);
-  w = fminf(w + 1.0f, W);
-}
+// The voxel's projection (voxel_sdf) and update (fuse): rpe_volume_field.hpp (shared with the colour integrate of rpe_color.hip).
 
 // nvox <= 2^30 (dims <= 1024): the flat voxel index fits 32 bits, byte offsets do not
 __global__ __launch_bounds__(kVolBlock) void volume_integrate_kernel(float* __restrict__ vol, VolumeGeometry G, int64_t nvox,

@@ -26,9 +26,11 @@ int rpe_volume_init(rpe_context* c, const rpe_volume_desc* d) {
   const size_t bytes = (size_t)g.dim[0] * g.dim[1] * g.dim[2] * 2 * sizeof(float);
   V.have = false;
   V.have_mesh = false;
+  V.have_color = false;
   if (!V.d || V.cap < bytes) {
     if (V.d) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.d)); V.d = nullptr; V.cap = 0; }
     if (V.ws) { HIP_TRY(hipFree(V.ws)); V.ws = nullptr; V.ws_cap = 0; }   // the mesh workspace follows the volume's size
+    if (V.cd) { HIP_TRY(hipFree(V.cd)); V.cd = nullptr; V.ccap = 0; }     // ... and so does the colour volume
     HIP_TRY(hipMalloc((void**)&V.d, bytes));
     V.cap = bytes;
   }
@@ -65,6 +67,7 @@ int rpe_volume_raycast(rpe_context* c, const double* pose12, const rpe_camera* c
   const int64_t n = (int64_t)k.width * k.height;
   if ((rc = ensure_maps(c, F.mmap, 2, &F.mcap, n))) return rc;
   F.have_model = false;
+  F.have_mcolor = false;
   HIP_TRY(rpe::launch_volume_raycast(c->vol.d, c->vol.g, k, pose_f(pose12), (float)dmin, (float)dmax, F.mmap[0], F.mmap[1], c->stream));
   F.mcam = k;
   one_level(*cam, k, F.mkcam, &F.mgeo);

@@ -1,5 +1,6 @@
-// The volume's field F(p), shared by the raycast (rpe_volume.hip V2) and the mesh normals (rpe_mesh.hip M4); device code only.
-// Followed BIT-EXACTLY (include/rgbd_pose_hip.h Part 3, "Field"): FMA contraction is off from here to the end of the including unit.
+// Device code shared by the volume's kernels: the voxel projection and update of the integrate (rpe_volume.hip V1, and the tsdf half of
+// rpe_color.hip C2) and the volume's field F(p) (the raycast V2 and the mesh normals of rpe_mesh.hip M4).
+// Followed BIT-EXACTLY (include/rgbd_pose_hip.h Part 3, "TSDF volume"): FMA contraction is off from here to the end of the including unit.
 #pragma once
 #include "rpe_kernels.h"
 
@@ -7,6 +8,40 @@
 
 namespace rpe {
 namespace {
+
+// Voxel (i, j, k), centre p = o + ((float)i + 0.5f) * s per axis; camera point pc = R p + t (rows left to right); pixel = nearest
+// (floorf(f * x / z + c + 0.5f)); d = z of the level-0 vertex map there (NaN = invalid depth); sdf = d - pc.z; updated iff pc.z > 0,
+// the pixel is in the image, d is valid and sdf >= -tr: f = fminf(1, sdf / tr), tsdf = (tsdf * w + f) / (w + 1), w = fminf(w + 1, W).
+// voxel_project also hands out sdf and the pixel's index (v * width + u) of an updated voxel.
+__device__ __forceinline__ bool voxel_project(const VolumeGeometry& G, const float* __restrict__ vmap, const Camera& cam, const PoseF& T,
+                                              int i, int j, int k, float& f, float& sdf, int64_t& pix) {
+  const float px = G.o[0] + ((float)i + 0.5f) * G.s, py = G.o[1] + ((float)j + 0.5f) * G.s, pz = G.o[2] + ((float)k + 0.5f) * G.s;
+  const float cx = T.R[0] * px + T.R[1] * py + T.R[2] * pz + T.t[0];
+  const float cy = T.R[3] * px + T.R[4] * py + T.R[5] * pz + T.t[1];
+  const float cz = T.R[6] * px + T.R[7] * py + T.R[8] * pz + T.t[2];
+  if (!(cz > 0.0f)) return false;
+  const float uf = floorf(cam.fx * (cx / cz) + cam.cx + 0.5f), vf = floorf(cam.fy * (cy / cz) + cam.cy + 0.5f);
+  if (!(uf >= 0.0f && uf <= (float)(cam.width - 1) && vf >= 0.0f && vf <= (float)(cam.height - 1))) return false;
+  pix = (int64_t)(int)vf * cam.width + (int)uf;
+  const float d = vmap[3 * pix + 2];
+  if (d != d) return false;
+  sdf = d - cz;
+  if (!(sdf >= -G.tr)) return false;
+  f = fminf(1.0f, sdf / G.tr);
+  return true;
+}
+
+__device__ __forceinline__ bool voxel_sdf(const VolumeGeometry& G, const float* __restrict__ vmap, const Camera& cam, const PoseF& T, int i,
+                                          int j, int k, float& f) {
+  float sdf;
+  int64_t pix;
+  return voxel_project(G, vmap, cam, T, i, j, k, f, sdf, pix);
+}
+
+__device__ __forceinline__ void fuse(float& tsdf, float& w, float f, float W) {
+  tsdf = (tsdf * w + f) / (w + 1.0f);
+  w = fminf(w + 1.0f, W);
+}
 
 // F(p): g = (p - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; known iff 0 <= i0 <= dim - 2 on every axis and all eight corner
 // weights are > 0; trilinear with lerp(x, y, t) = x + (y - x) * t along x for (j, k) = (0,0) (1,0) (0,1) (1,1), then y, then z.

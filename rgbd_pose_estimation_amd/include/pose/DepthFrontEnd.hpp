@@ -15,6 +15,8 @@
 //   fe.initVolume(desc);  fe.setDepthPyramid(d0, cam, 3);  fe.integrate(T0);
 //   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.raycast(T, cam, range, 3);  fe.icpPyramid(T, {6, 4, 3});  fe.integrate(T);
 //   rpe::Mesh m = fe.mesh();                                             // the surface: marching cubes on the GPU
+// With a registered RGB image per frame (pixel (u, v) of colour and depth see the same ray), the volume also fuses colour:
+//   fe.setDepth(d, cam);  fe.setColor(rgb);  fe.integrateColor(T);  ...  fe.modelColor();  fe.meshColors();   // RGBA8, 4 bytes each
 //
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
@@ -154,6 +156,7 @@ class DepthFrontEnd {
     v.voxel_size = d.voxel_size; v.trunc = d.trunc; v.max_weight = d.max_weight;
     check(rpe_volume_init(_ctx, &v), "rpe_volume_init");
     _vol = d;
+    _mesh_vertices = -1;
   }
   // fuse the current frame (level 0), seen from T_cw, into the volume
   void integrate(const Pose& T_cw) {
@@ -182,13 +185,39 @@ class DepthFrontEnd {
   // marching cubes over the volume, corners with weight >= min_weight (rpe_volume_mesh), brought to the host
   Mesh mesh(double min_weight = 1) const {
     int64_t nv = 0, nt = 0;
+    _mesh_vertices = -1;
     check(rpe_volume_mesh(_ctx, min_weight, &nv, &nt), "rpe_volume_mesh");
+    _mesh_vertices = nv;
     Mesh M;
     M.vertices.resize(3, (int)nv);
     M.normals.resize(3, (int)nv);
     M.triangles.resize((size_t)nt * 3);
     check(rpe_volume_mesh_download(_ctx, M.vertices.data(), M.normals.data(), M.triangles.data()), "rpe_volume_mesh_download");
     return M;
+  }
+  // the current frame's colour: width*height*3 bytes (RPE_COLOR_RGB8 or RPE_COLOR_BGR8 order) registered to its depth; a new depth
+  // drops it
+  void setColor(const uint8_t* rgb, int format = RPE_COLOR_RGB8) { check(rpe_frame_set_color(_ctx, rgb, format), "rpe_frame_set_color"); }
+  // integrate(T_cw) plus the frame's colour fused into the voxels inside the truncation band
+  void integrateColor(const Pose& T_cw) {
+    double p[12]; pose12(T_cw, p);
+    check(rpe_volume_integrate_color(_ctx, p), "rpe_volume_integrate_color");
+  }
+  // the colour field at the model's level-0 vertices (after raycast / setModel / setModelFromFrame): 4 x width*height bytes RGBA8,
+  // A = 255 where the colour is known, 0 0 0 0 where it is not
+  std::vector<uint8_t> modelColor() const {
+    rpe_camera k;
+    check(rpe_model_sample_color(_ctx), "rpe_model_sample_color");
+    check(rpe_frame_level_camera(_ctx, 0, 1, &k), "rpe_frame_level_camera");
+    std::vector<uint8_t> out((size_t)k.width * k.height * 4);
+    check(rpe_color_download(_ctx, RPE_COLOR_MODEL, out.data()), "rpe_color_download");
+    return out;
+  }
+  // the colour field at the vertices of the last mesh(): 4 x n_vertices bytes RGBA8, bit for bit the model colour at the same points
+  std::vector<uint8_t> meshColors() const {
+    std::vector<uint8_t> out((size_t)(_mesh_vertices > 0 ? _mesh_vertices : 0) * 4);
+    check(rpe_volume_mesh_colors(_ctx, out.empty() ? nullptr : out.data()), "rpe_volume_mesh_colors");
+    return out;
   }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
@@ -231,6 +260,7 @@ class DepthFrontEnd {
   rpe_context* _ctx;
   int _device, _pixels;
   VolumeDesc _vol;
+  mutable int64_t _mesh_vertices = -1;   // vertices of the last mesh() (meshColors' size), -1 before one
 };
 
 }  // namespace rpe

@@ -241,9 +241,9 @@ def default_room():
     return np.array([-2.5, -1.6, -1.0]), np.array([2.7, 1.5, 5.0]), spheres
 
 
-def render_depth(R, t, cam=DEFAULT_CAMERA, room=None, noise_sigma: float = 0.0, rng=None, as_u16: bool = False):
-    """Depth image (height, width) of the room seen by the camera Xc = R Xw + t: float32 metres, or uint16 millimetres.
-    noise_sigma: Gaussian depth noise in metres (rng required)."""
+def _cast(R, t, cam, room):
+    """(camera centre C0 in the world, world ray direction of every pixel (h*w, 3), ray parameter of the first hit (inf = none)):
+    the ray of pixel (u, v) is C0 + lambda * d with camera z = lambda."""
     fx, fy, cx, cy, w, h = cam
     lo, hi, spheres = room if room is not None else default_room()
     R = np.asarray(R, np.float64)
@@ -272,6 +272,14 @@ def render_depth(R, t, cam=DEFAULT_CAMERA, room=None, noise_sigma: float = 0.0, 
             l = (-b - np.sqrt(np.where(disc > 0, disc, np.nan))) / (2 * a)
             ok = (disc > 0) & (l > 1e-9)
             lam = np.where(ok & (l < lam), l, lam)
+    return C0, d, lam
+
+
+def render_depth(R, t, cam=DEFAULT_CAMERA, room=None, noise_sigma: float = 0.0, rng=None, as_u16: bool = False):
+    """Depth image (height, width) of the room seen by the camera Xc = R Xw + t: float32 metres, or uint16 millimetres.
+    noise_sigma: Gaussian depth noise in metres (rng required)."""
+    w, h = cam[4], cam[5]
+    _, _, lam = _cast(R, t, cam, room)
     z = np.where(np.isfinite(lam), lam, 0.0)
     if noise_sigma > 0:
         z = np.where(z > 0, z + noise_sigma * rng.standard_normal(z.shape), 0.0)
@@ -279,3 +287,30 @@ def render_depth(R, t, cam=DEFAULT_CAMERA, room=None, noise_sigma: float = 0.0, 
     if as_u16:
         return np.clip(np.rint(z * 1000.0), 0, 65535).astype(np.uint16)
     return z.astype(np.float32)
+
+
+# Colour of the room for the colour front end (rpe_frame_set_color): per channel a sinusoid of the world point with wavelengths of
+# 1.2 .. 1.6 m, so that a volume of 4-cm voxels holds it (30 or more voxels per period).  Wave vectors (rad / m) and phases of r, g, b.
+TEXTURE_K = ((1.0, 5.0, 0.6), (1.5, 0.0, 3.7), (0.0, 2.0, 4.5))
+TEXTURE_PHASE = (0.3, 1.2, 2.0)
+
+
+def room_texture(P):
+    """RGB in 0 .. 255 (float64, (n, 3)) of world points P (n, 3): channel c = 127.5 + 120 * sin(k_c . P + phi_c)"""
+    P = np.asarray(P, np.float64).reshape(-1, 3)
+    K, phi = np.array(TEXTURE_K), np.array(TEXTURE_PHASE)
+    return 127.5 + 120.0 * np.sin(P @ K.T + phi)
+
+
+def render_rgb(R, t, cam=DEFAULT_CAMERA, room=None, texture=None):
+    """Colour image (height, width, 3) uint8 of the room seen by the camera Xc = R Xw + t, registered to render_depth's image: each
+    pixel is texture (default room_texture) at the pixel's noise-free hit point, rounded to the nearest integer and clipped to
+    0 .. 255; black where the ray hits nothing."""
+    w, h = cam[4], cam[5]
+    C0, d, lam = _cast(R, t, cam, room)
+    hit = np.isfinite(lam)
+    out = np.zeros((len(d), 3), np.uint8)
+    P = C0 + lam[hit, None] * d[hit]
+    tex = (texture or room_texture)(P)
+    out[hit] = np.clip(np.rint(tex), 0, 255).astype(np.uint8)
+    return out.reshape(h, w, 3)

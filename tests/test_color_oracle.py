@@ -1,0 +1,375 @@
+"""CPU: pins the numpy statement of the colour volume (tests/color_oracle.py) with cases derived by hand, recomputes the oracle figures
+the GPU colour accuracy threshold is set from (tests/color_cases.py), checks simulator.render_rgb against its texture, the PLY colours,
+the library's colour exports, that the colour kernels neither spill nor carry scratch, and that the C++ colour driver compiles."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import color_cases as CC
+import color_oracle as CO
+import isa_tools as T
+import volume_oracle as VO
+from frontend_util import FO, SMALL_CAM, pose12, rot
+from rgbd_pose_estimation_amd import _lib as L
+from rgbd_pose_estimation_amd import mesh as M
+from rgbd_pose_estimation_amd import simulator as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
+f32, f16 = np.float32, np.float16
+I12 = pose12(np.eye(3), np.zeros(3))
+SYMS = {"rpe_frame_set_color", "rpe_volume_integrate_color", "rpe_model_sample_color", "rpe_color_download", "rpe_volume_mesh_colors",
+        "rpe_volume_color_download", "rpe_volume_color_upload"}
+
+
+def plane(D=2.0, max_weight=64, trunc=0.15):
+    """a fronto-parallel plane at depth D seen by an identity camera: (geometry, level-0 vertex map), tr = 3 voxels"""
+    fx, fy, cx, cy, w, h = SMALL_CAM
+    G = VO.Geometry((40, 32, 60), 0.05, (-1.0, -0.8, 0.5), trunc, max_weight)
+    V = FO.frame_maps(np.full((h, w), D, f32), SMALL_CAM, 1.0, 0.1, 10.0, 0.1)[0]
+    return G, V
+
+
+def solid(rgb):
+    fx, fy, cx, cy, w, h = SMALL_CAM
+    return CO.frame_rgba(np.broadcast_to(np.array(rgb, np.uint8), (h, w, 3)))
+
+
+def fuse(G, V, frames, cvol=None, vol=None):
+    vol = G.empty() if vol is None else vol
+    cvol = CO.empty(G) if cvol is None else cvol
+    band = None
+    for rgba in frames:
+        vol, cvol, band = CO.integrate(vol, cvol, G, V, rgba, SMALL_CAM, I12, with_band=True)
+    return vol, cvol, band
+
+
+def h16(x):
+    """one fp32 value -> binary16 bits, scalar by scalar (independent of the oracle's vectorised h)"""
+    x = f32(x)
+    return 0x7E00 if x != x else int(np.array([x], f32).astype(f16).view(np.uint16)[0])
+
+
+def test_h_rounds_to_nearest_even_keeps_subnormals_and_canonicalises_nan():
+    cases = {2049.0: 0x6800, 2050.0: 0x6801, 2051.0: 0x6802, 65504.0: 0x7BFF, 65519.0: 0x7BFF, 65520.0: 0x7C00, -65520.0: 0xFC00,
+             2.0 ** -24: 0x0001, 2.0 ** -25: 0x0000, 1.5 * 2.0 ** -24: 0x0002, 2.0 ** -14: 0x0400, -0.0: 0x8000, 127.5: 0x57F8,
+             float("inf"): 0x7C00, float("-inf"): 0xFC00}
+    for x, bits in cases.items():
+        assert int(CO.h(np.array([x], f32))[0]) == bits, (x, hex(bits))
+    nans = np.array([0x7FC00000, 0xFFC12345, 0x7F800001, 0x7FA00005], np.uint32).view(f32)
+    assert np.all(CO.h(nans) == 0x7E00)
+    allbits = np.arange(0, 1 << 16, dtype=np.uint32).astype(np.uint16)
+    finite = ~np.isnan(allbits.view(f16))
+    assert np.array_equal(CO.h(CO.f32(allbits[finite])), allbits[finite])     # binary16 -> fp32 -> binary16 is the identity
+
+
+def test_constant_colour_frames_give_exactly_that_colour_on_band_voxels():
+    G, V = plane()
+    vol, cvol, band = fuse(G, V, [solid((10, 200, 77))] * 3)
+    assert band.sum() > 1000
+    c = cvol[band]
+    assert np.all(CO.f32(c[:, :3]) == np.array([10, 200, 77], f32)) and np.all(CO.f32(c[:, 3]) == 3)
+    assert np.all(cvol[~band] == 0)
+
+
+def test_voxels_beyond_the_band_keep_colour_zero():
+    """updated voxels with sdf > tr (free space in front of the band): tsdf weight 1, f = 1, colour untouched"""
+    D = 2.0
+    G, V = plane(D)
+    vol, cvol, band = fuse(G, V, [solid((1, 2, 3))])
+    zc = G.o[2] + (np.arange(60, dtype=f32) + f32(0.5)) * G.s
+    sdf = f32(D) - zc                                          # the optical axis's column: identity camera, pixel depth D
+    col_w, col_c = vol[:, 16, 20, 1], cvol[:, 16, 20]
+    free = (col_w > 0) & (sdf > G.tr)
+    inband = (col_w > 0) & (sdf <= G.tr)
+    assert free.sum() > 10 and inband.sum() >= 5
+    assert np.all(col_c[free] == 0) and np.all(vol[:, 16, 20, 0][free] == 1)
+    assert np.all(CO.f32(col_c[inband, 3]) == 1) and np.all(CO.f32(col_c[inband, :3]) == np.array([1, 2, 3], f32))
+    assert (vol[..., 1] > 0).sum() > 2 * band.sum()           # most updated voxels are free space: no colour traffic there
+
+
+def test_alternating_frames_give_the_binary16_running_means():
+    """0 / 255 alternately: c1 = 255, then (255 * 1 + 0) / 2 = 127.5, (127.5 * 2 + 255) / 3 = 170, (170 * 3 + 0) / 4 = 127.5,
+    (127.5 * 4 + 255) / 5 = 153, ... each step rounded to binary16; the weight stops at W = 64"""
+    G, V = plane(max_weight=64)
+    frames = [solid((255, 0, 255) if n % 2 == 0 else (0, 255, 0)) for n in range(70)]
+    vol, cvol = G.empty(), CO.empty(G)
+    want_c, want_w = 0.0, 0.0
+    for n, rgba in enumerate(frames):
+        vol, cvol, band = CO.integrate(vol, cvol, G, V, rgba, SMALL_CAM, I12, with_band=True)
+        o = f32(255 if n % 2 == 0 else 0)
+        bits = h16((f32(want_c) * f32(want_w) + o) / (f32(want_w) + f32(1)))
+        want_c = float(np.array([bits], np.uint16).view(f16)[0])
+        want_w = float(np.array([h16(min(f32(want_w) + f32(1), f32(64)))], np.uint16).view(f16)[0])
+        got = cvol[band]
+        assert np.all(got[:, 0] == bits) and np.all(got[:, 2] == bits), n
+        assert np.all(CO.f32(got[:, 3]) == want_w), n
+        if n < 5:
+            assert want_c == [255.0, 127.5, 170.0, 127.5, 153.0][n]
+    assert want_w == 64
+
+
+def test_max_weight_one_blends_each_frame_half_and_half():
+    """W = 1: the first frame sets the colour, every later one is averaged in with weight 1 against 1 (the stored colour counts as one
+    observation), so the colour after frames a, b is (a + b) / 2 -- not the last observation"""
+    G, V = plane(max_weight=1)
+    _, cvol, band = fuse(G, V, [solid((200, 0, 100)), solid((100, 50, 0))])
+    c = cvol[band]
+    assert np.all(CO.f32(c[:, :3]) == np.array([150, 25, 50], f32)) and np.all(CO.f32(c[:, 3]) == 1)
+    _, cvol, band = fuse(G, V, [solid((200, 0, 100)), solid((100, 50, 0)), solid((0, 0, 0))])
+    assert np.all(CO.f32(cvol[band][:, :3]) == np.array([75, 12.5, 25], f32))
+
+
+def test_max_weight_5000_stops_at_2048():
+    """W = 5000: 2047 -> 2048 -> 2048 (2049 rounds to 2048 in binary16)"""
+    G, V = plane(max_weight=5000)
+    start = CO.empty(G)
+    start[..., 3] = CO.h(np.array([2047.0], f32))[0]
+    start[..., 0] = CO.h(np.array([100.0], f32))[0]
+    _, c1, band = fuse(G, V, [solid((200, 0, 0))], cvol=start)
+    assert np.all(CO.f32(c1[band][:, 3]) == 2048)
+    assert np.all(CO.f32(c1[band][:, 0]) == f32(np.float16((100.0 * 2047 + 200) / 2048)))
+    _, c2, band = fuse(G, V, [solid((200, 0, 0))], cvol=c1)
+    assert np.all(CO.f32(c2[band][:, 3]) == 2048)
+
+
+def _special_voxel_cases():
+    """(channel bits, weight bits, observation, expected channel bits, expected weight bits) derived by hand, W = 64"""
+    H = lambda x: h16(x)  # noqa: E731
+    nan, inf, ninf = 0x7E00, 0x7C00, 0xFC00
+    return [
+        (H(10), H(0), 40, H(40), H(1)),                           # first observation
+        (0x8000, H(0), 40, H(40), H(1)),                          # -0 channel: -0 * 0 + 40 = 40
+        (0x8000, H(1), 0, 0x0000, H(2)),                          # (-0 * 1 + 0) / 2 = +0 (the add gives +0)
+        (0x7E01, H(3), 40, nan, H(4)),                            # NaN channel stays NaN, canonical
+        (0xFFFF, H(3), 40, nan, H(4)),                            # negative NaN with a payload
+        (H(10), 0x7E00, 40, nan, H(64)),                          # NaN weight: NaN channel, weight W
+        (H(10), 0x7C00, 40, nan, H(64)),                          # +Inf weight: 10 * Inf / Inf = NaN, weight W
+        (inf, H(2), 40, inf, H(3)),                               # +Inf channel
+        (ninf, H(2), 40, ninf, H(3)),                             # -Inf channel
+        (0x0001, H(1), 0, 0x0000, H(2)),                          # subnormal 2^-24 * 1 / 2 = 2^-25: a tie, to even (0)
+        (0x0003, H(1), 0, 0x0002, H(2)),                          # 3 * 2^-24 / 2 = 1.5 * 2^-24: a tie, to even (2)
+        (H(-10), H(1), 20, H(5), H(2)),                           # negative channel: (-10 + 20) / 2
+        (H(10), H(-1), 40, inf, H(0)),                            # weight -1: (-10 + 40) / 0 = +Inf, weight 0
+        (H(50), H(-1), 40, ninf, H(0)),                           # (-50 + 40) / 0 = -Inf
+        (H(40), H(-1), 40, nan, H(0)),                            # (-40 + 40) / 0 = 0 / 0
+        (H(10), H(-3), 40, H(-5), H(-2)),                         # weight -3: (-30 + 40) / -2 = -5, weight -2
+        (H(100), H(2.5), 0, H(100 * 2.5 / 3.5), H(3.5)),          # odd weight
+        (H(100), 0x0001, 0, H(f32(100) * f32(2.0 ** -24) / f32(1 + 2.0 ** -24)), H(1)),   # subnormal weight: 1 + 2^-24 is 1 in fp32
+        (H(65504), H(63), 255, H(f32((f32(65504) * f32(63) + f32(255)) / f32(64))), H(64)),
+    ]
+
+
+def test_special_channels_and_weights_go_through_integrate():
+    G, V = plane(max_weight=64)
+    cases = _special_voxel_cases()
+    _, _, band = fuse(G, V, [solid((0, 0, 0))])
+    idx = [tuple(x) for x in np.argwhere(band)]
+    assert len(idx) >= len(cases)
+    for o in sorted({c[2] for c in cases}):                  # one solid frame per observation value
+        sel = [(idx[n], c) for n, c in enumerate(cases) if c[2] == o]
+        start = CO.empty(G)
+        for (k, j, i), (cb, wb, _, _, _) in sel:
+            start[k, j, i] = (cb, cb, cb, wb)
+        _, out, band2 = CO.integrate(G.empty(), start, G, V, solid((o, o, o)), SMALL_CAM, I12, with_band=True)
+        assert np.array_equal(band2, band)
+        for (k, j, i), (cb, wb, _, want_c, want_w) in sel:
+            assert list(out[k, j, i]) == [want_c] * 3 + [want_w], (hex(cb), hex(wb), o, [hex(x) for x in out[k, j, i]])
+
+
+def test_quantise():
+    x = np.array([np.nan, np.inf, -np.inf, -0.0, 0.0, 2.0 ** -149, 0.49999997, 0.5, 1.5, 2.5, 254.49998, 254.5, 255.0, 255.4, 300.0, -3.0],
+                 f32)
+    # 0.49999997 + 0.5 is 1 - 2^-25, a tie in fp32 that rounds to 1.0: q gives 1 (the rule rounds in fp32, not in the reals)
+    want = [0, 255, 0, 0, 0, 0, 1, 1, 2, 3, 254, 255, 255, 255, 255, 0]
+    assert list(CO.quantise(x)) == want
+
+
+def _ramp_volume(G, coef, w=1.0):
+    d0, d1, d2 = G.dim
+    k, j, i = np.meshgrid(np.arange(d2), np.arange(d1), np.arange(d0), indexing="ij")
+    cvol = CO.empty(G)
+    for a in range(3):
+        cvol[..., a] = CO.h((coef[a][0] + coef[a][1] * i + coef[a][2] * j + coef[a][3] * k).astype(f32))
+    cvol[..., 3] = CO.h(np.full(i.shape, w, f32))
+    return cvol
+
+
+def test_linear_ramp_is_reproduced_within_quantisation():
+    G = VO.Geometry((12, 10, 9), 0.1, (-0.5, -0.4, 1.0), 0.3, 64)
+    coef = [(10.0, 8.0, 2.0, 1.0), (200.0, -4.0, 3.0, -2.0), (30.0, 1.0, 1.0, 12.0)]   # integers: exact in binary16
+    cvol = _ramp_volume(G, coef, w=3.0)
+    rng = np.random.default_rng(1)
+    lo, hi = G.o + f32(0.5) * G.s, G.o + (np.array(G.dim) - f32(0.5)) * G.s
+    X = (lo + rng.random((5000, 3)) * (hi - lo) * 0.999).astype(f32)
+    out = CO.sample(cvol, G, X)
+    assert np.all(out[:, 3] == 255)
+    g = (X.astype(np.float64) - G.o.astype(np.float64)) / float(G.s) - 0.5
+    for a in range(3):
+        lin = coef[a][0] + coef[a][1] * g[:, 0] + coef[a][2] * g[:, 1] + coef[a][3] * g[:, 2]
+        assert np.all(np.abs(out[:, a] - np.clip(lin, 0, 255)) <= 0.5 + 1e-3), a
+    # outside the range of cells: unknown
+    assert np.all(CO.sample(cvol, G, np.array([G.o - f32(0.01), hi + f32(0.01), [np.nan, 0, 0]], f32)) == 0)
+
+
+def test_colour_is_unknown_where_one_corner_has_no_colour_whatever_the_tsdf_weight():
+    G = VO.Geometry((6, 6, 6), 0.1, (0.0, 0.0, 0.0), 0.3, 64)
+    cvol = _ramp_volume(G, [(50.0, 0, 0, 0)] * 3, w=1.0)
+    cvol[2, 3, 4, 3] = 0                                  # voxel (i, j, k) = (4, 3, 2) without colour (its tsdf weight plays no part)
+    centres = [G.o[a] + (np.arange(G.dim[a], dtype=f32) + f32(0.5)) * G.s for a in range(3)]
+    # points in every cell: cell (i0, j0, k0) has voxel (4, 3, 2) as a corner iff i0 in {3, 4}, j0 in {2, 3}, k0 in {1, 2}
+    P, touches = [], []
+    for k0 in range(5):
+        for j0 in range(5):
+            for i0 in range(5):
+                P.append([centres[0][i0] + f32(0.03), centres[1][j0] + f32(0.05), centres[2][k0] + f32(0.07)])
+                touches.append(i0 in (3, 4) and j0 in (2, 3) and k0 in (1, 2))
+    out = CO.sample(cvol, G, np.array(P, f32))
+    touches = np.array(touches)
+    assert touches.sum() == 8
+    assert np.all(out[touches] == 0) and np.all(out[~touches] == [50, 50, 50, 255])
+
+
+def test_z_slab_windows_join_to_the_full_volume():
+    fx, fy, cx, cy, w, h = SMALL_CAM
+    G = VO.Geometry((40, 32, 60), 0.05, (-1.0, -0.8, 0.5), 0.15, 8)
+    p = pose12(rot(0.05, -0.1, 0.02), np.array([0.05, -0.02, -0.3]))
+    d = S.render_depth(p[:9].reshape(3, 3), p[9:], SMALL_CAM)
+    V = FO.frame_maps(d, SMALL_CAM, 1.0, 0.1, 10.0, 0.1)[0]
+    rgba = CO.frame_rgba(S.render_rgb(p[:9].reshape(3, 3), p[9:], SMALL_CAM))
+    vol, cvol = CO.integrate(G.empty(), CO.empty(G), G, V, rgba, SMALL_CAM, p)
+    assert (cvol[..., 3] > 0).sum() > 1000
+    parts = [CO.integrate(G.empty()[k0:k1], CO.empty(G)[k0:k1], G, V, rgba, SMALL_CAM, p, k0) for k0, k1 in ((0, 17), (17, 40), (40, 60))]
+    assert np.array_equal(np.concatenate([q[1] for q in parts]), cvol)
+    assert np.array_equal(np.concatenate([q[0] for q in parts]).view(np.uint32), vol.view(np.uint32))
+    X = (G.o + np.random.default_rng(2).random((4000, 3)).astype(f32) * np.array(G.dim, f32) * G.s).astype(f32)
+    windows = [(0, cvol[:31]), (30, cvol[30:])]                              # overlapping by one slice: every cell lies in one
+    assert np.array_equal(CO.windows_sample(windows, G, X), CO.sample(cvol, G, X))
+
+
+def test_tsdf_half_is_the_volume_oracle():
+    G, V = plane()
+    vol, cvol = CO.integrate(G.empty(), CO.empty(G), G, V, solid((1, 2, 3)), SMALL_CAM, I12)
+    assert np.array_equal(vol.view(np.uint32), VO.integrate(G.empty(), G, V, SMALL_CAM, I12).view(np.uint32))
+
+
+def test_render_rgb_is_the_texture_at_the_hit_points():
+    cam = SMALL_CAM
+    R, t = rot(0.05, -0.1, 0.02), np.array([0.1, -0.05, 0.2])
+    img = S.render_rgb(R, t, cam)
+    z = S.render_depth(R, t, cam).astype(np.float64).reshape(-1)
+    fx, fy, cx, cy, w, h = cam
+    u, v = np.meshgrid(np.arange(w), np.arange(h))
+    Xc = np.stack([(u.reshape(-1) - cx) / fx * z, (v.reshape(-1) - cy) / fy * z, z], 1)
+    P = (Xc - t) @ R                                          # R^T (Xc - t)
+    want = np.clip(np.rint(S.room_texture(P)), 0, 255)
+    diff = np.abs(img.reshape(-1, 3).astype(np.float64) - want)
+    assert np.all(z > 0) and diff.max() <= 1 and (diff == 0).mean() > 0.999
+    # a room seen from outside: the rays that miss it are black, the rest are textured
+    room = (np.array([-0.5, -0.5, 3.0]), np.array([0.5, 0.5, 4.0]), np.zeros((0, 4)))
+    img2 = S.render_rgb(np.eye(3), np.zeros(3), cam, room)
+    d2 = S.render_depth(np.eye(3), np.zeros(3), cam, room)
+    miss = d2 == 0
+    assert 0.2 < miss.mean() < 0.95 and np.all(img2[miss] == 0) and np.any(img2[~miss] > 0)
+    # a texture given by the caller
+    flat = S.render_rgb(R, t, cam, texture=lambda X: np.tile([1.4, 200.6, 300.0], (len(X), 1)))
+    assert np.all(flat.reshape(-1, 3) == [1, 201, 255])
+
+
+def test_render_depth_is_unchanged_by_the_shared_ray_cast():
+    """render_depth and render_rgb share the ray cast; a depth frame rendered here equals the one computed the old way inline"""
+    cam = SMALL_CAM
+    R, t = rot(0.05, -0.1, 0.02), np.array([0.1, -0.05, 0.2])
+    C0, d, lam = S._cast(R, t, cam, None)
+    z = np.where(np.isfinite(lam), lam, 0.0).reshape(cam[5], cam[4]).astype(f32)
+    assert np.array_equal(S.render_depth(R, t, cam).view(np.uint32), z.view(np.uint32))
+
+
+def test_texture_wavelengths_fit_a_4cm_volume():
+    for k in S.TEXTURE_K:
+        assert 2 * np.pi / np.linalg.norm(k) >= 0.5
+
+
+def test_accuracy_figures():
+    """the oracle figures behind color_cases.ACC_* (the GPU colour accuracy test's thresholds)"""
+    med, p95, cover = CC.oracle_color_accuracy()
+    print(f"oracle colour accuracy: median {med}, p95 {p95}, coverage {cover:.4f}")
+    assert np.allclose(med, CC.ORACLE_MEDIAN, atol=2e-3) and np.allclose(p95, CC.ORACLE_P95, atol=2e-2)
+    assert abs(cover - CC.ORACLE_COVERAGE) < 2e-3
+
+
+def test_ply_round_trip_keeps_colours_and_read_ply_is_unchanged(tmp_path):
+    rng = np.random.default_rng(4)
+    V = rng.standard_normal((50, 3)).astype(f32)
+    N = rng.standard_normal((50, 3)).astype(f32)
+    Tri = rng.integers(0, 50, (70, 3)).astype(np.int32)
+    Cl = rng.integers(0, 256, (50, 4)).astype(np.uint8)
+    for normals in (None, N):
+        plain, col = str(tmp_path / "plain.ply"), str(tmp_path / "col.ply")
+        M.write_ply(plain, V, Tri, normals)
+        M.write_ply(col, V, Tri, normals, colors=Cl)
+        a, b = M.read_ply(plain), M.read_ply(col)
+        assert len(a) == len(b) == 3
+        for x, y in zip(a, b):
+            assert (x is None and y is None) or (x.dtype == y.dtype and np.array_equal(x, y))
+        assert np.array_equal(M.read_ply_colors(col), Cl) and M.read_ply_colors(plain) is None
+        head = open(col, "rb").read().split(b"end_header\n")[0].decode()
+        assert "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face" in head
+    with pytest.raises(ValueError):
+        M.write_ply(str(tmp_path / "bad.ply"), V, Tri, colors=Cl[:10])
+    M.write_ply(str(tmp_path / "empty.ply"), np.zeros((0, 3), f32), np.zeros((0, 3), np.int32), colors=np.zeros((0, 4), np.uint8))
+    v0, t0, n0 = M.read_ply(str(tmp_path / "empty.ply"))
+    assert v0.shape == (0, 3) and t0.shape == (0, 3) and n0 is None and M.read_ply_colors(str(tmp_path / "empty.ply")).shape == (0, 4)
+
+
+def _built():
+    from rgbd_pose_estimation_amd import build as B
+    return B.build()
+
+
+def test_header_and_library_export_the_colour_entry_points():
+    lib = _built()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
+    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    assert SYMS <= exported, sorted(SYMS - exported)
+    assert SYMS <= set(L.SYMBOLS)
+    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
+    for s in SYMS:
+        assert f"int {s}(" in hdr
+    for e in ("RPE_COLOR_RGB8 = 0", "RPE_COLOR_BGR8 = 1", "RPE_COLOR_FRAME = 0", "RPE_COLOR_MODEL = 1"):
+        assert e in hdr
+    assert (L.COLOR_RGB8, L.COLOR_BGR8, L.COLOR_FRAME, L.COLOR_MODEL) == (0, 1, 0, 1)
+
+
+def test_colour_kernels_do_not_spill():
+    _built()
+    rows = T.kernel_resources(os.path.join(LIB, "rpe_color.o"))
+    names = {r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows}
+    assert names == {"frame_color", "volume_integrate_color", "color_sample"}, rows
+    assert not [(r["name"], r["vgpr_spill"]) for r in rows if r["vgpr_spill"] > 0]
+    assert not [(r["name"], r["scratch"]) for r in rows if r["scratch"] > 16]
+    assert all(r["vgpr"] + r["agpr"] <= 512 for r in rows)
+
+
+def test_colour_host_unit_has_no_device_code():
+    _built()
+    assert T.kernel_resources(os.path.join(LIB, "rpe_color_api.o")) == []
+
+
+def test_volume_kernels_keep_their_instructions_beside_the_colour_integrate():
+    """V1 and C2 share voxel_project / fuse (rpe_volume_field.hpp): the tsdf half of C2 is V1's code, and V1 still carries no colour"""
+    _built()
+    rows = T.kernel_resources(os.path.join(LIB, "rpe_volume.o"))
+    assert {r["mangled"].split("volume_")[1].split("_kernel")[0] for r in rows} == {"integrate", "raycast"}
+    src = open(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_color.hip")).read()
+    assert "voxel_project(" in src and "fuse(" in src
+
+
+def test_colour_cpp_driver_compiles(tmp_path):
+    lib = _built()
+    inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
+                           os.path.join(ROOT, "tests", "cpp", "volume_color.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",
+                           "-Wl,-rpath," + os.path.dirname(lib), "-o", str(tmp_path / "volume_color")])
