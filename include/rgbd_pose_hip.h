@@ -573,6 +573,68 @@ int rpe_volume_color_download(rpe_context* ctx, uint16_t* rgbw);
 /* the inverse of rpe_volume_color_download (the bits are taken as given); RPE_ERR_STATE without a volume */
 int rpe_volume_color_upload(rpe_context* ctx, const uint16_t* rgbw);
 
+/* ---- Photometric term: tracking against the model's colour beside its geometry.  Point-to-plane ICP has nothing to hold three of
+ * the six degrees of freedom with wherever the view is one plane (a wall, a floor, a corridor); the intensity of a textured plane
+ * does.  Conventions, followed bit for bit for everything per pixel (fp32, the written order, no FMA contraction;
+ * tests/photo_oracle.py states them in numpy); the sums are held to a rounding bound.
+ * Model colour without a volume: rpe_model_color_upload (the companion of rpe_model_upload) and rpe_model_color_from_frame (for
+ * rpe_model_from_frame users: frame-to-frame RGB-D odometry).  As before, any call that replaces the model drops the model colour.
+ * Intensity of an RGBA8 pixel: I = ((0.299f * r + 0.587f * g) + 0.114f * b) on the 0..255 scale, NaN when A = 0.
+ * Frame intensity pyramid (one float per pixel per level; level sizes and cameras are the depth pyramid's): level 0 from the frame
+ * colour; level l+1 = (((a + b) + c) + d) * 0.25f over the 2 x 2 block a = (2u,2v), b = (2u+1,2v), c = (2u,2v+1), d = (2u+1,2v+1) of
+ * level l (the order of rpe_model_build_pyramid), NaN if any of the four is.
+ * Model photometric map, one float4 {I, gx, gy, zm} per model pixel per level: I as above (level 0 from the model colour, coarser
+ * levels by the same block mean); gx = 0.5f * (I(u+1,v) - I(u-1,v)), gy = 0.5f * (I(u,v+1) - I(u,v-1)) (NaN on the border or beside
+ * a NaN); zm = z of the level's model vertex in the MODEL camera's frame, ((R_m[6] * X + R_m[7] * Y) + R_m[8] * Z) + t_m[2], and NaN
+ * wherever the level's model normal has a NaN component.  The model normals are NaN across depth jumps, so this one poison keeps
+ * every bilinear and gradient stencil off the occlusion edges.
+ * The term, per frame pixel of level l under the pose (R, t) (Xc = R Xw + t), with Xc the frame vertex, If the frame intensity,
+ * (R_m, t_m) and (fx, fy, cx, cy, w, h) the model view's pose and camera at that level:
+ *  1. Xw = R^T (Xc - t) and Xm = R_m Xw + t_m exactly as rpe_associate forms them; needs Xc and If finite and Xm.z > 0.
+ *  2. x = fx * (Xm.x / Xm.z) + cx, y likewise; x0 = floorf(x), y0 = floorf(y); needs 0 <= x0 <= w - 2 and 0 <= y0 <= h - 2;
+ *     a = x - x0, b = y - y0.
+ *  3. The four map entries at (x0, y0) (x0+1, y0) (x0, y0+1) (x0+1, y0+1): all sixteen floats finite, and |zm - Xm.z| <= dist_thr
+ *     for each of the four (the occlusion gate; dist_thr in fp32).
+ *  4. Is, Gx, Gy = bilinear of I, gx, gy with lerp(p, q, s) = p + (q - p) * s: along x for both rows, then along y.
+ *  5. r = Is - If.  With z = Xm.z, u = Gx * fx, v = Gy * fy:  q = (u / z, v / z, -((u * Xm.x + v * Xm.y) / (z * z)));
+ *     A = -(R_m R^T), A[i][j] = -((R_m[3i] * R[3j] + R_m[3i+1] * R[3j+1]) + R_m[3i+2] * R[3j+2]) on the fp32 poses;
+ *     a3[j] = (q[0] * A[0][j] + q[1] * A[1][j]) + q[2] * A[2][j];  J = [a3 | Xc x a3] with (Xc x a3)[0] = Xc.y * a3[2] - Xc.z * a3[1]
+ *     and cyclic, in the tangent order (upsilon, omega) of rpe_normal_eq, update T <- exp(delta) T.
+ *  6. r' = lam * r, J' = lam * J, lam = (float)weight in metres per intensity level, accumulated the way every Gauss-Newton kernel
+ *     here accumulates a row: fp32 fused multiply-adds into partial sums of one group of 4 consecutive pixels, widened to fp64 per
+ *     group.  Steps 1-5 are bit for bit the oracle's; every sum is within 8 * 2^-24 of the sum of the magnitudes of its products.
+ * Whatever replaces the frame's depth or colour, the model or the model colour drops the prepared maps. */
+enum { RPE_PHOTO_FRAME = 0, RPE_PHOTO_MODEL = 1 };
+/* the model colour map given by the caller: 4 x width*height bytes RGBA8 at the model's level-0 size, A = 0: unknown;
+ * RPE_ERR_STATE without a model */
+int rpe_model_color_upload(rpe_context* ctx, const uint8_t* rgba);
+/* model colour := the current frame colour (device to device); RPE_ERR_STATE unless the model's level 0 has the frame's size and
+ * the frame has a colour */
+int rpe_model_color_from_frame(rpe_context* ctx);
+/* the frame intensity pyramid and the model photometric map of `levels` levels (two launches); RPE_ERR_STATE without a frame colour,
+ * a model colour, or `levels` levels of both the frame (rpe_frame_set_depth_pyramid) and the model */
+int rpe_photo_prepare(rpe_context* ctx, int levels);
+/* one prepared map of one level: RPE_PHOTO_FRAME (w_l*h_l floats) or RPE_PHOTO_MODEL (4 x w_l*h_l floats {I, gx, gy, zm} per pixel) */
+int rpe_photo_download(rpe_context* ctx, int which, int level, float* out);
+/* the photometric normal equations of one level alone, for callers who combine terms themselves: the 32 doubles of rpe_normal_eq --
+ * H upper triangle (21) | g (6) | [27] cost = sum r'^2 | [28] photometric pairs | [29] pivot floor.  weight finite and > 0 */
+int rpe_photo_normal_eq(rpe_context* ctx, int level, const double* pose12, double dist_thr, double weight, double* out32);
+/* {r, J[0..5]} (unscaled) of every frame pixel of the level, as 7 planes of w_l*h_l floats (rows[k * w_l*h_l + pixel]), NaN where the
+ * pixel has no pair.  Plane 0 is the residual image. */
+int rpe_photo_rows(rpe_context* ctx, int level, const double* pose12, double dist_thr, float* rows);
+/* rpe_icp / rpe_icp_pyramid with the photometric term beside the geometric one: per round ONE launch that forms the point-to-plane
+ * row exactly as the fused ICP round does and the photometric row above, one record (H and g the sums of both terms, the two costs
+ * and the two pair counts apart), one host wait, the host solve and left update of rpe_icp; opt->tol ends a level early.  Host-driven
+ * only: opt->device_resident = 1 is RPE_ERR_ARG, opt->fused is not consulted, opt->kind must be RPE_RES_P2PLANE with use_normals = 1
+ * (RPE_ERR_ARG otherwise); photo_weight finite and > 0; RPE_ERR_STATE when the maps are not prepared for the levels asked.
+ * final_cost / matched are the geometric cost and pairs of the last round as rpe_icp reports them, photo_cost / photo_matched (may be
+ * NULL) the photometric ones; the pyramid form reports level 0's.  On return the solver slots hold the pairs under the returned pose. */
+int rpe_icp_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double photo_weight, double* pose12, int* iters_out, double* last_step,
+                 double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched);
+int rpe_icp_pyramid_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double photo_weight, int levels, const int* iters_per_level,
+                         const double* dist_thr_per_level, double* pose12, int* iters_out, double* last_step, double* final_cost,
+                         int64_t* matched, double* photo_cost, int64_t* photo_matched);
+
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.
  * 3 x K inputs are column-major doubles whose values are rounded to dtype before use. */

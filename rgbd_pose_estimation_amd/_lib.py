@@ -25,6 +25,7 @@ MAP_DEPTH = 5
 MAX_LEVELS = 4
 COLOR_RGB8, COLOR_BGR8 = 0, 1
 COLOR_FRAME, COLOR_MODEL = 0, 1
+PHOTO_FRAME, PHOTO_MODEL = 0, 1
 
 # every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -39,6 +40,8 @@ SYMBOLS = [
     "rpe_volume_upload", "rpe_volume_mesh", "rpe_volume_mesh_download",
     "rpe_frame_set_color", "rpe_volume_integrate_color", "rpe_model_sample_color", "rpe_color_download", "rpe_volume_mesh_colors",
     "rpe_volume_color_download", "rpe_volume_color_upload",
+    "rpe_model_color_upload", "rpe_model_color_from_frame", "rpe_photo_prepare", "rpe_photo_download", "rpe_photo_normal_eq", "rpe_photo_rows",
+    "rpe_icp_rgbd", "rpe_icp_pyramid_rgbd",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -194,6 +197,16 @@ def lib():
         L.rpe_volume_mesh_colors.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_volume_color_download.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_volume_color_upload.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_model_color_upload.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_model_color_from_frame.argtypes = [C.c_void_p]
+        L.rpe_photo_prepare.argtypes = [C.c_void_p, C.c_int]
+        L.rpe_photo_download.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rpe_photo_normal_eq.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+        L.rpe_photo_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p]
+        L.rpe_icp_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+        L.rpe_icp_pyramid_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

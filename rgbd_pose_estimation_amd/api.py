@@ -412,6 +412,79 @@ class Context:
         L.check(L.lib().rpe_color_download(self._h, L.COLOR_MODEL, _p(out)))
         return out
 
+    # ---- photometric term (Part 3): tracking against the model's colour beside its geometry
+    def model_color_upload(self, rgba):
+        """The model colour map given by the caller: (height, width, 4) uint8 RGBA at the model's level-0 size, A = 0: unknown."""
+        k = self.frame_camera(0, model=True)
+        a = np.ascontiguousarray(rgba)
+        if a.dtype != np.uint8 or a.size != k[4] * k[5] * 4:
+            raise ValueError(f"model_color_upload: expected uint8 of shape {(k[5], k[4], 4)}, got {a.dtype} {a.shape}")
+        L.check(L.lib().rpe_model_color_upload(self._h, _p(a)))
+        return self
+
+    def model_color_from_frame(self):
+        """Model colour := the current frame colour (for model_from_frame users: frame-to-frame RGB-D odometry)."""
+        L.check(L.lib().rpe_model_color_from_frame(self._h))
+        return self
+
+    def photo_prepare(self, levels: int = 1):
+        """The frame intensity pyramid and the model photometric map of `levels` levels, from the frame colour and the model colour."""
+        L.check(L.lib().rpe_photo_prepare(self._h, int(levels)))
+        return self
+
+    def photo_download(self, which: int, level: int = 0) -> np.ndarray:
+        """PHOTO_FRAME: the frame intensity of a level, (pixels,) float32; PHOTO_MODEL: the model map, (pixels, 4) = I, gx, gy, zm."""
+        k = self.frame_camera(level, which == L.PHOTO_MODEL)
+        n = k[4] * k[5]
+        out = np.empty((n, 4) if which == L.PHOTO_MODEL else n, np.float32)
+        L.check(L.lib().rpe_photo_download(self._h, int(which), int(level), _p(out)))
+        return out
+
+    def photo_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, weight: float = 0.01) -> np.ndarray:
+        """The photometric normal equations alone: H upper triangle (21) | g (6) | cost | pairs | pivot floor | pad, 32 float64."""
+        p = np.array(pose12, np.float64).reshape(12)
+        out = np.zeros(32, np.float64)
+        L.check(L.lib().rpe_photo_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(weight), _p(out)))
+        return out
+
+    def photo_rows(self, pose12, level: int = 0, dist_thr: float = 0.1) -> np.ndarray:
+        """(7, pixels) float32: the unscaled residual (row 0: the residual image) and Jacobian row of every frame pixel of the level,
+        NaN where the pixel has no pair."""
+        p = np.array(pose12, np.float64).reshape(12)
+        k = self.frame_camera(level)
+        out = np.empty((7, k[4] * k[5]), np.float32)
+        L.check(L.lib().rpe_photo_rows(self._h, int(level), _p(p), float(dist_thr), _p(out)))
+        return out
+
+    def icp_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9):
+        """icp with the photometric term (weight in metres per intensity level) beside point-to-plane, one launch per round; returns
+        (pose12, iterations, last |delta|, geometric cost, geometric pairs, photometric cost, photometric pairs) of the last round."""
+        p = np.array(pose12, np.float64).reshape(12).copy()
+        o = L.RpeIcpOptions(L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, 1, 0, 1)
+        it, step, cost, m, pc, pm = C.c_int(0), C.c_double(0), C.c_double(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_rgbd(self._h, C.byref(o), float(weight), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m),
+                                     C.byref(pc), C.byref(pm)))
+        self.n, self.dtype = self._pixels, L.F32
+        return p, it.value, step.value, cost.value, m.value, pc.value, pm.value
+
+    def icp_pyramid_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9):
+        """icp_pyramid with the photometric term; returns (pose12, rounds per level, last |delta|, geometric cost, geometric pairs,
+        photometric cost, photometric pairs), the last five of level 0."""
+        p = np.array(pose12, np.float64).reshape(12).copy()
+        levels = len(iters)
+        it_in = np.ascontiguousarray(iters, np.int32)
+        one = 0.1 if dist_thr is None else dist_thr
+        thr = None if np.ndim(one) == 0 else np.ascontiguousarray(one, np.float64)
+        if thr is not None and len(thr) != levels:
+            raise ValueError("dist_thr needs one gate per level")
+        o = L.RpeIcpOptions(L.RES_P2PLANE, 1, tol, float(one) if thr is None else 0.0, cos_thr, 1, 0, 1)
+        it_out = np.zeros(levels, np.int32)
+        step, cost, m, pc, pm = C.c_double(0), C.c_double(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_pyramid_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), None if thr is None else _p(thr), _p(p),
+                                             _p(it_out), C.byref(step), C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
+        self.n, self.dtype = self._pixels, L.F32
+        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
+
     def volume_mesh_colors(self) -> np.ndarray:
         """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh): the colour field there, as model_color samples it."""
         n = self._mesh_nv or 0

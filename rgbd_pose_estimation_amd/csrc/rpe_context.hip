@@ -158,7 +158,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
     if (device < 64 && !loaded[device]) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
       rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
-      rpe::preload_color();
+      rpe::preload_color(); rpe::preload_photo();
       loaded[device] = true;
     }
   }
@@ -201,7 +201,7 @@ void rpe_destroy(rpe_context* c) {
   if (c->vol.d) (void)hipFree(c->vol.d);
   if (c->vol.ws) (void)hipFree(c->vol.ws);
   for (void* m : {(void*)c->vol.mv, (void*)c->vol.mn, (void*)c->vol.mt}) if (m) (void)hipFree(m);
-  for (void* m : {(void*)c->fe.d_rgb, (void*)c->fe.fcolor, (void*)c->fe.mcolor, (void*)c->vol.cd, (void*)c->vol.mc}) if (m) (void)hipFree(m);
+  for (void* m : {(void*)c->fe.d_rgb, (void*)c->fe.fcolor, (void*)c->fe.mcolor, (void*)c->vol.cd, (void*)c->vol.mc, (void*)c->fe.pint, (void*)c->fe.pmap}) if (m) (void)hipFree(m);
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);

@@ -108,7 +108,7 @@ int rpe_frame_set_depth(rpe_context* c, const void* depth, int depth_type, const
   const int64_t n = (int64_t)k.width * k.height;
   if ((rc = stage_depth(c, depth, depth_type, n))) return rc;
   if ((rc = ensure_maps(c, F.fmap, 3, &F.fcap, n))) return rc;
-  F.have_frame = false; F.have_fcolor = false;
+  F.have_frame = false; F.have_fcolor = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_maps(F.d_depth, depth_type, k, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fmap[0],
       F.fmap[1],
@@ -138,7 +138,7 @@ int rpe_frame_set_depth_pyramid(rpe_context* c, const void* depth, int depth_typ
     HIP_TRY(hipMalloc((void**)&F.fdepth, (size_t)total * sizeof(float)));
     F.fdcap = (size_t)total * sizeof(float);
   }
-  F.have_frame = false; F.have_depth = false; F.have_fcolor = false;
+  F.have_frame = false; F.have_depth = false; F.have_fcolor = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_pyramid(F.d_depth, depth_type, g, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fdepth,
                                     F.fmap[0], F.fmap[1], F.fmap[2], c->stream));
@@ -202,7 +202,7 @@ int rpe_model_from_frame(rpe_context* c, const double* pose12) {
   const int64_t n = F.fgeo.off[F.fgeo.levels];   // every level (one level: width * height)
   int rc = ensure_maps(c, F.mmap, 2, &F.mcap, n);
   if (rc) return rc;
-  F.have_mcolor = false;
+  F.have_mcolor = false; F.photo_levels = 0;
   HIP_TRY(rpe::launch_to_world(F.fmap[0], F.fmap[1], n, pose_f(pose12), F.mmap[0], F.mmap[1], c->stream));
   F.mcam = F.cam;
   F.mgeo = F.fgeo;
@@ -222,7 +222,7 @@ int rpe_model_upload(rpe_context* c, const float* vertex_w, const float* normal_
   auto& F = c->fe;
   const int64_t n = (int64_t)k.width * k.height;
   if ((rc = ensure_maps(c, F.mmap, 2, &F.mcap, n))) return rc;
-  F.have_mcolor = false;
+  F.have_mcolor = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.mmap[0], vertex_w, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(F.mmap[1], normal_w, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the caller may free its buffers on return
@@ -255,6 +255,7 @@ int rpe_model_build_pyramid(rpe_context* c, int levels) {
     for (int k = 0; k < 2; k++) { HIP_TRY(hipFree(F.mmap[k])); F.mmap[k] = fresh[k]; }
     F.mcap = bytes;
   }
+  F.photo_levels = 0;   // the model's levels move: the photometric map is laid out by them
   HIP_TRY(rpe::launch_model_pyramid(g, F.mmap[0], F.mmap[1], c->stream));
   F.mgeo = g;
   for (int l = 0; l < levels; l++) F.mkcam[l] = kc[l];

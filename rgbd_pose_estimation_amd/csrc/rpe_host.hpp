@@ -9,6 +9,7 @@
 //   rpe_volume_api.hip    Part 3: TSDF volume (integrate, raycast into the model, upload / download)
 //   rpe_mesh_api.hip      Part 3: mesh extraction from the TSDF volume (marching cubes) and its download
 //   rpe_color_api.hip     Part 3: frame colour, the colour volume beside the TSDF, model and mesh colours
+//   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -163,6 +164,12 @@ struct rpe_context {
     unsigned int* fcolor = nullptr; size_t fccap = 0;
     unsigned int* mcolor = nullptr; size_t mccap = 0;
     bool have_fcolor = false, have_mcolor = false;
+    // photometric term (rpe_photo_api.hip): the frame's intensity pyramid (one float per pixel, the frame's level offsets) and the
+    // model's photometric map (float4 {I, gx, gy, zm} per pixel, the model's level offsets), prepared for photo_levels levels
+    // (0 = not prepared: whatever replaces the frame's depth or colour, the model or the model colour resets it)
+    float* pint = nullptr; size_t pint_cap = 0;
+    float* pmap = nullptr; size_t pmap_cap = 0;
+    int photo_levels = 0;
   } fe;
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
   struct Volume {

@@ -267,6 +267,22 @@ hipError_t launch_volume_integrate_color(float* vol, unsigned short* cvol, const
 // C3: RGBA8 of the colour field C at n world points (stride 3 floats)
 hipError_t launch_color_sample(const unsigned short* cvol, const VolumeGeometry& G, const float* pts, int64_t n, unsigned int* rgba,
                                hipStream_t s);
+// ---- photometric term (rpe_photo.hip).  P1: the frame's intensity pyramid (one float per pixel, levels concatenated as G says) from
+// its level-0 RGBA8 colour.  P2: the model's photometric map (float4 {I, gx, gy, zm} per pixel, levels concatenated) from its level-0
+// RGBA8 colour and its world vertex / normal maps; M = world -> model camera
+hipError_t launch_frame_intensity(const unsigned int* rgba, const PyramidGeometry& G, float* out, hipStream_t s);
+hipError_t launch_model_photo(const unsigned int* rgba, const PyramidGeometry& G, const float* mv, const float* mn, const PoseF& M,
+                              float* out4, hipStream_t s);
+// P3: one round of one level in one kernel -- the photometric rows (weight lam, gate dist_thr) and, geometric != 0, the point-to-plane
+// rows of launch_icp_fused (use_normals = 1).  Record of kNlLd doubles: H (21) | g (6) of both terms | geometric cost | geometric
+// pairs | photometric cost | photometric pairs
+hipError_t launch_icp_photo(const float* vmap, const float* nmap, const float* fint, int64_t n, const float* mv, const float* mn,
+                            const float* pmap4, const Camera& mcam, const PoseF& M, float dist_thr, float cos_thr, float lam, int geometric,
+                            const double* pose12, const ReduceTarget& rt, hipStream_t s);
+// P4: rows[k * n + i], k = 0 .. 6: {r, J[0..5]} (unscaled) of frame pixel i, NaN where it has no pair
+hipError_t launch_photo_rows(const float* vmap, const float* fint, int64_t n, const float* pmap4, const Camera& mcam, const PoseF& M,
+                             float dist_thr, const double* pose12, float* rows, hipStream_t s);
+void preload_photo();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

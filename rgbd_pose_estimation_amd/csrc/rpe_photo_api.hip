@@ -1,0 +1,242 @@
+// Part 3 of include/rgbd_pose_hip.h: the photometric term beside ICP (kernels in rpe_photo.hip).  A model colour without a volume, the
+// photometric maps of frame and model, the photometric normal equations and per-pixel rows, and the RGB-D ICP loops: per round ONE
+// launch whose record carries the geometric and the photometric rows, one host wait, the host solve and left update of rpe_icp.
+#include "rpe_host.hpp"
+using namespace rpeh;
+
+namespace {
+template <class T> int ensure_buffer(rpe_context* c, T** p, size_t* cap, size_t bytes) {
+  if (*p && *cap >= bytes) return RPE_OK;
+  if (*p) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(*p)); *p = nullptr; *cap = 0; }
+  HIP_TRY(hipMalloc((void**)p, bytes));
+  *cap = bytes;
+  return RPE_OK;
+}
+// one level of what a round reads: frame vertex / normal / intensity, model vertex / normal / photometric map, pixels, model camera
+struct PhotoLevel { const float *fv, *fn, *fi, *mv, *mn, *pm; int64_t n; rpe::Camera mcam; };
+PhotoLevel photo_level(rpe_context* c, int l) {
+  auto& F = c->fe;
+  PhotoLevel L;
+  L.fv = F.fmap[0] + 3 * F.fgeo.off[l]; L.fn = F.fmap[1] + 3 * F.fgeo.off[l]; L.fi = F.pint + F.fgeo.off[l];
+  L.mv = F.mmap[0] + 3 * F.mgeo.off[l]; L.mn = F.mmap[1] + 3 * F.mgeo.off[l]; L.pm = F.pmap + 4 * F.mgeo.off[l];
+  L.n = (int64_t)F.fgeo.cam[l].width * F.fgeo.cam[l].height;
+  L.mcam = F.mgeo.cam[l];
+  return L;
+}
+int photo_ready(rpe_context* c, int levels, const char* who) {
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  auto& F = c->fe;
+  if (!F.have_frame) return fail(RPE_ERR_STATE, "no frame: call rpe_frame_set_depth first");
+  if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_from_frame, rpe_model_upload or rpe_volume_raycast first");
+  if (F.photo_levels < levels)
+    return fail(RPE_ERR_STATE, "%s: the photometric maps are prepared for %d level(s), %d asked (rpe_photo_prepare; a new depth, colour, "
+                "model or model colour drops them)", who, F.photo_levels, levels);
+  return RPE_OK;
+}
+// one round: launch, wait, the 32-double record of both terms in ne (cost and pairs the geometric ones), the photometric cost / pairs
+int rgbd_round(rpe_context* c, const PhotoLevel& lv, const rpe_icp_options* o, double dist_thr, float lam, int geometric,
+               const double* pose12, double* ne, double* pcost, double* ppairs) {
+  HIP_TRY(rpe::launch_icp_photo(lv.fv, lv.fn, lv.fi, lv.n, lv.mv, lv.mn, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr,
+                                o ? (float)o->cos_thr : 0.f, lam, geometric, pose12, collect_target(c), c->stream));
+  int rc = wait_host(c, rpe::kNlLd);
+  if (rc) return rc;
+  for (int i = 0; i < 32; i++) ne[i] = i < 29 ? c->h_out[i] : 0.0;
+  *pcost = c->h_out[29]; *ppairs = c->h_out[30];
+  return RPE_OK;
+}
+// rpe_icp's host rounds on one level with the combined record
+int rgbd_level(rpe_context* c, const rpe_icp_options* o, int l, int max_iter, double dist_thr, float lam, double* pose12, int* iters_out,
+               double* last_step, double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched) {
+  const PhotoLevel lv = photo_level(c, l);
+  int it = 0, rc;
+  double step = 0, cost = 0, pairs = 0, pcost = 0, ppairs = 0;
+  for (; it < max_iter; it++) {
+    double ne[32], d[6];
+    if ((rc = rgbd_round(c, lv, o, dist_thr, lam, 1, pose12, ne, &pcost, &ppairs))) return rc;
+    cost = ne[27]; pairs = ne[28];
+    if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(false))) {
+      if (iters_out) *iters_out = it;
+      return fail(RPE_ERR_DEGENERATE, "RGB-D ICP: normal equations are not positive definite at iteration %d (%g + %g pairs)", it, pairs,
+                  ppairs);
+    }
+    rpe::se3_left_update(d, pose12);
+    step = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
+    if (step < o->tol) { it++; break; }
+  }
+  if (iters_out) *iters_out = it;
+  if (last_step) *last_step = step;
+  if (final_cost) *final_cost = cost;
+  if (matched) *matched = (int64_t)pairs;
+  if (photo_cost) *photo_cost = pcost;
+  if (photo_matched) *photo_matched = (int64_t)ppairs;
+  return RPE_OK;
+}
+int rgbd_options(const rpe_icp_options* o, double photo_weight, const double* pose12, const char* who) {
+  if (!o || !pose12 || !(o->dist_thr >= 0)) return fail(RPE_ERR_ARG, "%s: bad argument", who);
+  if (o->kind != RPE_RES_P2PLANE || !o->use_normals)
+    return fail(RPE_ERR_ARG, "%s: the geometric term is point-to-plane with use_normals = 1 (kind %d given)", who, o->kind);
+  if (o->device_resident) return fail(RPE_ERR_ARG, "%s: host-driven only (device_resident must be 0)", who);
+  if (!std::isfinite(photo_weight) || !(photo_weight > 0)) return fail(RPE_ERR_ARG, "%s: photo_weight must be finite and > 0", who);
+  return RPE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rpe_model_color_upload(rpe_context* c, const uint8_t* rgba) {
+  session_end(c);
+  if (!c || !rgba) return fail(RPE_ERR_ARG, "rpe_model_color_upload: bad argument");
+  auto& F = c->fe;
+  if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_upload, rpe_model_from_frame or rpe_volume_raycast first");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = (size_t)F.mcam.width * F.mcam.height * 4;
+  int rc = ensure_buffer(c, &F.mcolor, &F.mccap, bytes);
+  if (rc) return rc;
+  F.have_mcolor = false; F.photo_levels = 0;
+  HIP_TRY(hipMemcpyAsync(F.mcolor, rgba, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's buffer is free again on return
+  F.have_mcolor = true;
+  return RPE_OK;
+}
+
+int rpe_model_color_from_frame(rpe_context* c) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  auto& F = c->fe;
+  if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_from_frame first");
+  if (!F.have_frame || !F.have_fcolor) return fail(RPE_ERR_STATE, "no frame colour: call rpe_frame_set_color after the frame's depth");
+  if (F.mcam.width != F.cam.width || F.mcam.height != F.cam.height)
+    return fail(RPE_ERR_STATE, "rpe_model_color_from_frame: the model is %d x %d, the frame %d x %d", F.mcam.width, F.mcam.height,
+                F.cam.width, F.cam.height);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t bytes = (size_t)F.mcam.width * F.mcam.height * 4;
+  int rc = ensure_buffer(c, &F.mcolor, &F.mccap, bytes);
+  if (rc) return rc;
+  F.have_mcolor = false; F.photo_levels = 0;
+  HIP_TRY(hipMemcpyAsync(F.mcolor, F.fcolor, bytes, hipMemcpyDeviceToDevice, c->stream));
+  F.have_mcolor = true;
+  return RPE_OK;
+}
+
+int rpe_photo_prepare(rpe_context* c, int levels) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  if (levels < 1 || levels > RPE_MAX_LEVELS) return fail(RPE_ERR_ARG, "rpe_photo_prepare: levels must be 1 .. %d (got %d)", RPE_MAX_LEVELS, levels);
+  auto& F = c->fe;
+  if (!F.have_frame) return fail(RPE_ERR_STATE, "no frame: call rpe_frame_set_depth first");
+  if (!F.have_fcolor) return fail(RPE_ERR_STATE, "no frame colour: call rpe_frame_set_color after the frame's depth");
+  if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_from_frame, rpe_model_upload or rpe_volume_raycast first");
+  if (!F.have_mcolor)
+    return fail(RPE_ERR_STATE, "no model colour: call rpe_model_sample_color, rpe_model_color_upload or rpe_model_color_from_frame");
+  if (F.fgeo.levels < levels) return fail(RPE_ERR_STATE, "rpe_photo_prepare: the frame has %d level(s), %d asked (rpe_frame_set_depth_pyramid)",
+      F.fgeo.levels, levels);
+  if (F.mgeo.levels < levels) return fail(RPE_ERR_STATE, "rpe_photo_prepare: the model has %d level(s), %d asked (rpe_model_build_pyramid)",
+      F.mgeo.levels, levels);
+  HIP_TRY(hipSetDevice(c->device));
+  rpe::PyramidGeometry fg = F.fgeo, mg = F.mgeo;
+  fg.levels = levels; mg.levels = levels;
+  int rc;
+  if ((rc = ensure_buffer(c, &F.pint, &F.pint_cap, (size_t)fg.off[levels] * sizeof(float)))) return rc;
+  if ((rc = ensure_buffer(c, &F.pmap, &F.pmap_cap, (size_t)mg.off[levels] * 4 * sizeof(float)))) return rc;
+  F.photo_levels = 0;
+  HIP_TRY(rpe::launch_frame_intensity(F.fcolor, fg, F.pint, c->stream));
+  HIP_TRY(rpe::launch_model_photo(F.mcolor, mg, F.mmap[0], F.mmap[1], pose_f(F.mpose), F.pmap, c->stream));
+  F.photo_levels = levels;
+  return RPE_OK;
+}
+
+int rpe_photo_download(rpe_context* c, int which, int level, float* out) {
+  session_end(c);
+  if (!c || !out || (which != RPE_PHOTO_FRAME && which != RPE_PHOTO_MODEL) || level < 0)
+    return fail(RPE_ERR_ARG, "rpe_photo_download: bad argument");
+  int rc = photo_ready(c, level + 1, "rpe_photo_download");
+  if (rc) return rc;
+  auto& F = c->fe;
+  const bool model = which == RPE_PHOTO_MODEL;
+  const rpe::PyramidGeometry& g = model ? F.mgeo : F.fgeo;
+  const size_t n = (size_t)g.cam[level].width * g.cam[level].height;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(out, model ? F.pmap + 4 * g.off[level] : F.pint + g.off[level], n * (model ? 4 : 1) * sizeof(float),
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RPE_OK;
+}
+
+int rpe_photo_normal_eq(rpe_context* c, int level, const double* pose12, double dist_thr, double weight, double* out32) {
+  session_end(c);
+  if (!c || !pose12 || !out32 || level < 0 || !(dist_thr >= 0) || !std::isfinite(weight) || !(weight > 0))
+    return fail(RPE_ERR_ARG, "rpe_photo_normal_eq: bad argument (level >= 0, dist_thr >= 0, weight finite and > 0)");
+  int rc = photo_ready(c, level + 1, "rpe_photo_normal_eq");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  double ne[32], pcost = 0, ppairs = 0;
+  if ((rc = rgbd_round(c, photo_level(c, level), nullptr, dist_thr, (float)weight, 0, pose12, ne, &pcost, &ppairs))) return rc;
+  for (int i = 0; i < 32; i++) out32[i] = i < 27 ? ne[i] : 0.0;
+  out32[27] = pcost; out32[28] = ppairs;
+  out32[29] = rpe::pivot_floor(false);   // for rpe_gn_solve: the rows' products are fp32
+  return RPE_OK;
+}
+
+int rpe_photo_rows(rpe_context* c, int level, const double* pose12, double dist_thr, float* rows) {
+  session_end(c);
+  if (!c || !pose12 || !rows || level < 0 || !(dist_thr >= 0)) return fail(RPE_ERR_ARG, "rpe_photo_rows: bad argument");
+  int rc = photo_ready(c, level + 1, "rpe_photo_rows");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const PhotoLevel lv = photo_level(c, level);
+  float* d_rows = nullptr;
+  HIP_TRY(hipMalloc((void**)&d_rows, (size_t)lv.n * 7 * sizeof(float)));
+  hipError_t e = rpe::launch_photo_rows(lv.fv, lv.fi, lv.n, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr, pose12, d_rows, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, (size_t)lv.n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d_rows);
+  if (e != hipSuccess) return fail(RPE_ERR_HIP, "rpe_photo_rows: %s", hipGetErrorString(e));
+  return RPE_OK;
+}
+
+int rpe_icp_rgbd(rpe_context* c, const rpe_icp_options* o, double photo_weight, double* pose12, int* iters_out, double* last_step,
+                 double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  int rc = rgbd_options(o, photo_weight, pose12, "rpe_icp_rgbd");
+  if (rc) return rc;
+  if (o->max_iter < 1) return fail(RPE_ERR_ARG, "rpe_icp_rgbd: max_iter >= 1");
+  if ((rc = photo_ready(c, 1, "rpe_icp_rgbd"))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = rgbd_level(c, o, 0, o->max_iter, o->dist_thr, (float)photo_weight, pose12, iters_out, last_step, final_cost, matched, photo_cost,
+                       photo_matched))) return rc;
+  // leave the pairs in the solver slots, under the returned pose (as a fused rpe_icp does)
+  return rpe_associate(c, pose12, o->dist_thr, o->cos_thr, o->use_normals, nullptr);
+}
+
+int rpe_icp_pyramid_rgbd(rpe_context* c, const rpe_icp_options* o, double photo_weight, int levels, const int* iters_per_level,
+                         const double* dist_thr_per_level, double* pose12, int* iters_out, double* last_step, double* final_cost,
+                         int64_t* matched, double* photo_cost, int64_t* photo_matched) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  int rc = rgbd_options(o, photo_weight, pose12, "rpe_icp_pyramid_rgbd");
+  if (rc) return rc;
+  if (!iters_per_level || levels < 1 || levels > RPE_MAX_LEVELS)
+    return fail(RPE_ERR_ARG, "rpe_icp_pyramid_rgbd: levels must be 1 .. %d (got %d)", RPE_MAX_LEVELS, levels);
+  for (int l = 0; l < levels; l++) {
+    if (iters_per_level[l] < (l == 0 ? 1 : 0))
+      return fail(RPE_ERR_ARG, "rpe_icp_pyramid_rgbd: level %d needs %s rounds (got %d)", l, l == 0 ? ">= 1" : ">= 0", iters_per_level[l]);
+    if (dist_thr_per_level && !(dist_thr_per_level[l] >= 0))
+      return fail(RPE_ERR_ARG, "rpe_icp_pyramid_rgbd: bad distance gate at level %d", l);
+  }
+  if ((rc = photo_ready(c, levels, "rpe_icp_pyramid_rgbd"))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  for (int l = levels - 1; l >= 0; l--) {
+    int it = 0;
+    const bool fine = l == 0;
+    if (iters_per_level[l] > 0)
+      rc = rgbd_level(c, o, l, iters_per_level[l], dist_thr_per_level ? dist_thr_per_level[l] : o->dist_thr, (float)photo_weight, pose12, &it,
+                      fine ? last_step : nullptr, fine ? final_cost : nullptr, fine ? matched : nullptr, fine ? photo_cost : nullptr,
+                      fine ? photo_matched : nullptr);
+    if (iters_out) iters_out[l] = it;
+    if (rc) return rc;
+  }
+  return rpe_associate(c, pose12, dist_thr_per_level ? dist_thr_per_level[0] : o->dist_thr, o->cos_thr, o->use_normals, nullptr);
+}
+
+}  // extern "C"

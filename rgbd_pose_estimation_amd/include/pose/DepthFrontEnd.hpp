@@ -17,6 +17,9 @@
 //   rpe::Mesh m = fe.mesh();                                             // the surface: marching cubes on the GPU
 // With a registered RGB image per frame (pixel (u, v) of colour and depth see the same ray), the volume also fuses colour:
 //   fe.setDepth(d, cam);  fe.setColor(rgb);  fe.integrateColor(T);  ...  fe.modelColor();  fe.meshColors();   // RGBA8, 4 bytes each
+// ... and tracking can use it: a photometric term beside ICP holds the pose where the view is one plane (a wall, a floor, a corridor)
+//   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.setColor(rgb);  fe.raycast(T, cam, range, 3);  fe.modelColor();
+//                   fe.preparePhoto(3);  fe.icpPyramidRgbd(T, 0.01, {6, 4, 3});  fe.integrateColor(T);
 //
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
@@ -60,6 +63,8 @@ struct Mesh {
 struct IcpResult { int iterations = 0; double last_step = 0, cost = 0; long long pairs = 0; };
 // coarse-to-fine ICP: rounds run per level (0 = finest); the rest as IcpResult, of level 0
 struct PyramidIcpResult : IcpResult { int level_iterations[RPE_MAX_LEVELS] = {0, 0, 0, 0}; };
+// ICP with the photometric term: cost / pairs are the geometric ones, as icp reports them; the photometric ones beside them
+struct RgbdIcpResult : PyramidIcpResult { double photo_cost = 0; long long photo_pairs = 0; };
 
 class DepthFrontEnd {
  public:
@@ -219,6 +224,54 @@ class DepthFrontEnd {
     check(rpe_volume_mesh_colors(_ctx, out.empty() ? nullptr : out.data()), "rpe_volume_mesh_colors");
     return out;
   }
+  // the model colour given by the caller (4 x width*height bytes RGBA8 at the model's level-0 size, A = 0: unknown), for a model
+  // given by setModel
+  void setModelColor(const uint8_t* rgba) { check(rpe_model_color_upload(_ctx, rgba), "rpe_model_color_upload"); }
+  // model colour := the current frame colour, after setModelFromFrame (frame-to-frame RGB-D odometry)
+  void modelColorFromFrame() { check(rpe_model_color_from_frame(_ctx), "rpe_model_color_from_frame"); }
+  // the photometric maps of `levels` levels from the frame colour and the model colour; a new depth, colour, model or model colour
+  // drops them
+  void preparePhoto(int levels = 1) { check(rpe_photo_prepare(_ctx, levels), "rpe_photo_prepare"); }
+  // icp with the photometric term beside point-to-plane (weight in metres per intensity level), one launch per round, host-driven:
+  // o.kind must be RPE_RES_P2PLANE, o.device_resident false; o.fused is not consulted
+  RgbdIcpResult icpRgbd(Pose& pose, double weight = 0.01, const IcpOptions& o = IcpOptions()) {
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    RgbdIcpResult r;
+    int64_t m = 0, pm = 0;
+    check(rpe_icp_rgbd(_ctx, &opt, weight, p, &r.iterations, &r.last_step, &r.cost, &m, &r.photo_cost, &pm), "rpe_icp_rgbd");
+    r.level_iterations[0] = r.iterations;
+    r.pairs = (long long)m; r.photo_pairs = (long long)pm;
+    pose = pose_of(p);
+    return r;
+  }
+  // icpPyramid with the photometric term
+  RgbdIcpResult icpPyramidRgbd(Pose& pose, double weight, const std::vector<int>& iters,
+                               const std::vector<double>& dist_thr = std::vector<double>(), const IcpOptions& o = IcpOptions()) {
+    if (!dist_thr.empty() && dist_thr.size() != iters.size()) throw DeviceError(RPE_ERR_ARG, "icpPyramidRgbd: one gate per level");
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    RgbdIcpResult r;
+    int64_t m = 0, pm = 0;
+    check(rpe_icp_pyramid_rgbd(_ctx, &opt, weight, (int)iters.size(), iters.data(), dist_thr.empty() ? nullptr : dist_thr.data(), p,
+                               r.level_iterations, &r.last_step, &r.cost, &m, &r.photo_cost, &pm), "rpe_icp_pyramid_rgbd");
+    for (size_t l = 0; l < iters.size(); l++) r.iterations += r.level_iterations[l];
+    r.pairs = (long long)m; r.photo_pairs = (long long)pm;
+    pose = pose_of(p);
+    return r;
+  }
+  // the residual image of a level under `pose`: model intensity at the pixel's projection minus the frame's (intensity levels), NaN
+  // where the pixel has no photometric pair (row 0 of rpe_photo_rows)
+  std::vector<float> photoResiduals(const Pose& pose, int level = 0, double dist_thr = 0.1) const {
+    double p[12]; pose12(pose, p);
+    rpe_camera k;
+    check(rpe_frame_level_camera(_ctx, level, 0, &k), "rpe_frame_level_camera");
+    const size_t n = (size_t)k.width * k.height;
+    std::vector<float> rows(7 * n);
+    check(rpe_photo_rows(_ctx, level, p, dist_thr, rows.data()), "rpe_photo_rows");
+    rows.resize(n);
+    return rows;
+  }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
     Pairs P;
@@ -248,6 +301,12 @@ class DepthFrontEnd {
   }
 
  private:
+  static rpe_icp_options options_of(const IcpOptions& o) {
+    rpe_icp_options opt;
+    opt.kind = o.kind; opt.max_iter = o.max_iter; opt.tol = o.tol; opt.dist_thr = o.dist_thr; opt.cos_thr = o.cos_thr;
+    opt.use_normals = o.use_normals; opt.device_resident = o.device_resident; opt.fused = o.fused;
+    return opt;
+  }
   static rpe_camera cam_of(const PinholeCamera& c) { rpe_camera k; k.fx = c.fx; k.fy = c.fy; k.cx = c.cx; k.cy = c.cy;
       k.width = c.width; k.height = c.height; return k; }
   void set(const void* depth, int type, const PinholeCamera& cam, const DepthRange& r, int levels = 1) {
