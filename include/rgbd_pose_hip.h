@@ -635,6 +635,62 @@ int rpe_icp_pyramid_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double ph
                          const double* dist_thr_per_level, double* pose12, int* iters_out, double* last_step, double* final_cost,
                          int64_t* matched, double* photo_cost, int64_t* photo_matched);
 
+/* ---- Features and relocalisation: correspondences WITHOUT a pose guess.  rpe_associate pairs under a guess, so every entry above
+ * that produces a pose from images needs a start inside ICP's basin; a lost tracker has none.  Here keypoints of the frame's colour
+ * and of the model view's colour are described and matched by appearance, the matched pixels' vertices, normals and bearings go into
+ * the five solver slots, and the RANSAC / PROSAC solvers of rpe_run produce the pose that ICP then refines.  Conventions, followed
+ * bit for bit -- everything is integer arithmetic or a comparison (tests/feature_oracle.py states them in numpy):
+ * Sides: RPE_FEAT_FRAME = the frame colour (RGBA8) with the frame's level-0 vertex / normal / bearing maps; RPE_FEAT_MODEL = the model
+ * colour (rpe_model_sample_color, rpe_model_color_upload, rpe_model_color_from_frame) with the model's level-0 world vertex / normal
+ * maps.  rpe_photo_prepare is not needed.  Whatever replaces the frame's depth or colour drops the frame's features, whatever
+ * replaces the model or its colour the model's; a new detection on either side drops the match list.
+ * Luma: Y = (77 r + 150 g + 29 b + 128) >> 8, and 0 where A = 0.  Pixels outside the image count as Y = 0, A = 0.
+ * Detector: segment test on the 16-pixel ring of radius 3, offsets (dx, dy), y down, clockwise from the top: (0,-3) (1,-3) (2,-2)
+ * (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).  A pixel is a corner iff nine
+ * contiguous ring pixels (cyclically) are all > Y + t or all < Y - t (t = threshold, 1 .. 255, default 12), it lies at least 16 pixels
+ * from every image edge, A != 0 at the centre and on all 16 ring pixels, and the view's vertex and normal at the centre are finite
+ * (normals are NaN across depth jumps: silhouette corners stay out).  Score = sum over the ring of max(|Y_ring - Y| - t, 0).
+ * Suppression, 3 x 3: a corner survives iff its score beats all 8 neighbours' (a non-corner scores 0), a tie going to the lower pixel
+ * index v * width + u.  At most max_keypoints (1 .. RPE_MAX_KEYPOINTS, the top_k limit of rpe_prosac_order) are kept: the strongest
+ * by (score descending, pixel index ascending).  The kept ones are LISTED IN PIXEL-INDEX ORDER; a keypoint's id is its list position.
+ * Descriptor: upright, fixed scale, 256 bits over S = the 5 x 5 box sum of Y around a pixel (<= 6375).  Bit i is
+ * S(p + a_i) < S(p + b_i); the 256 offset pairs lie within +-13 (patch plus box stay inside the 16-pixel border) and are
+ * csrc/rpe_brief_table.h, generated by scripts/gen_brief_table.py from the project's PCG32 stream by the rule stated there.  Bit i is
+ * bit i % 32 of word i / 32; eight uint32 per keypoint.
+ * Matching: for frame keypoint q, d1 / d2 = the smallest / second smallest Hamming distance over the model keypoints (the second
+ * over all others, so a duplicate gives d2 = d1), the index that of the first smallest; d2 = 257 with one model keypoint; no match
+ * without any.  Accepted iff d1 <= max_dist and d1 * ratio_den < d2 * ratio_num (ints; defaults 64 and 8 / 10; max_dist 0 .. 256,
+ * ratio terms 1 .. 65536) and, with cross_check = 1, q is in turn the best of its model keypoint under the same tie rule.  Matches
+ * are listed in frame-keypoint order.
+ * Slots: rpe_features_match declares the problem (n = matches, RPE_F32) and fills, per match, XW / NW = the model vertex / normal at
+ * the model keypoint, XC / NC / BV = the frame's vertex / normal / bearing at the frame keypoint.  The match quality 256 - d1 is the
+ * float weight of the match (rpe_matches_download): what a PROSAC solver sorts.
+ * Scope: no orientation, no scale normalisation and no keyframe store yet -- a caller who keeps keyframes re-uploads one with
+ * rpe_model_upload + rpe_model_color_upload and relocalises against it. */
+typedef struct { int threshold; int max_keypoints; } rpe_feature_options;                       /* NULL: {12, RPE_MAX_KEYPOINTS} */
+typedef struct { int max_dist; int ratio_num, ratio_den; int cross_check; } rpe_match_options;  /* NULL: {64, 8, 10, 0} */
+enum { RPE_FEAT_FRAME = 0, RPE_FEAT_MODEL = 1, RPE_MAX_KEYPOINTS = 4096 };
+/* detect and describe the keypoints of one side (six launches, one host wait for the count); RPE_ERR_STATE without the side's depth
+ * or model and colour, RPE_ERR_ARG for options out of range */
+int rpe_features_detect(rpe_context* ctx, int which, const rpe_feature_options* opt, int* count);
+/* the side's keypoints: xy 2 x count int32 (u, v per keypoint), score count int32, desc 8 x count uint32 (any may be NULL);
+ * RPE_ERR_STATE before a detection or after its features were dropped */
+int rpe_features_download(rpe_context* ctx, int which, int32_t* xy, int32_t* score, uint32_t* desc);
+/* match the frame's keypoints against the model's and fill XW XC BV NW NC (n = matches; 0 matches leave an empty problem);
+ * RPE_ERR_STATE unless both sides have features */
+int rpe_features_match(rpe_context* ctx, const rpe_match_options* opt, int* matches);
+/* the last match list: frame / model keypoint ids, d1, d2 and the weight 256 - d1, `matches` values each (any may be NULL) */
+int rpe_matches_download(rpe_context* ctx, int32_t* frame_idx, int32_t* model_idx, int32_t* d1, int32_t* d2, float* weight);
+/* relocalise the frame against the model: detects on each side whose features are missing (or were made with other options), matches,
+ * and runs rpe_run's solver `method` (0 .. 9) with stage `ls` on the matches -- rpe_run itself, on the downloaded arrays, weights =
+ * the match quality for every modality, focal lengths of the frame's camera, RPE_SCORE_EXACT, the stream of `seed`.  iter_io,
+ * confidence, the thresholds, max_votes and mask_out (3 x matches shorts; give room for 3 x RPE_MAX_KEYPOINTS) are rpe_run's.
+ * pose12 = the solver's pose (Xc = R Xw + t), the start for rpe_icp_pyramid(_rgbd).  RPE_ERR_DEGENERATE with fewer than min_matches
+ * (>= 4) matches: *matches is set, pose12 is left untouched.  The slots keep the matches. */
+int rpe_relocalize(rpe_context* ctx, const rpe_feature_options* fopt, const rpe_match_options* mopt, int method, double thre_3d,
+                   double thre_2d, double thre_nl, int* iter_io, double confidence, uint64_t seed, int ls, int min_matches,
+                   double* pose12, int* matches, int* max_votes, short* mask_out);
+
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.
  * 3 x K inputs are column-major doubles whose values are rounded to dtype before use. */

@@ -26,6 +26,8 @@ MAX_LEVELS = 4
 COLOR_RGB8, COLOR_BGR8 = 0, 1
 COLOR_FRAME, COLOR_MODEL = 0, 1
 PHOTO_FRAME, PHOTO_MODEL = 0, 1
+FEAT_FRAME, FEAT_MODEL = 0, 1
+MAX_KEYPOINTS = 4096
 
 # every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -42,6 +44,7 @@ SYMBOLS = [
     "rpe_volume_color_download", "rpe_volume_color_upload",
     "rpe_model_color_upload", "rpe_model_color_from_frame", "rpe_photo_prepare", "rpe_photo_download", "rpe_photo_normal_eq", "rpe_photo_rows",
     "rpe_icp_rgbd", "rpe_icp_pyramid_rgbd",
+    "rpe_features_detect", "rpe_features_download", "rpe_features_match", "rpe_matches_download", "rpe_relocalize",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -63,6 +66,14 @@ class RpeCamera(C.Structure):
 class RpeIcpOptions(C.Structure):
     _fields_ = [("kind", C.c_int), ("max_iter", C.c_int), ("tol", C.c_double), ("dist_thr", C.c_double), ("cos_thr", C.c_double),
                 ("use_normals", C.c_int), ("device_resident", C.c_int), ("fused", C.c_int)]
+
+
+class RpeFeatureOptions(C.Structure):
+    _fields_ = [("threshold", C.c_int), ("max_keypoints", C.c_int)]
+
+
+class RpeMatchOptions(C.Structure):
+    _fields_ = [("max_dist", C.c_int), ("ratio_num", C.c_int), ("ratio_den", C.c_int), ("cross_check", C.c_int)]
 
 
 class RpeVolumeDesc(C.Structure):
@@ -207,6 +218,13 @@ def lib():
                                    C.c_void_p, C.c_void_p]
         L.rpe_icp_pyramid_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_features_detect.argtypes = [C.c_void_p, C.c_int, C.POINTER(RpeFeatureOptions), C.c_void_p]
+        L.rpe_features_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_features_match.argtypes = [C.c_void_p, C.POINTER(RpeMatchOptions), C.c_void_p]
+        L.rpe_matches_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_relocalize.argtypes = [C.c_void_p, C.POINTER(RpeFeatureOptions), C.POINTER(RpeMatchOptions), C.c_int, C.c_double, C.c_double,
+                                     C.c_double, C.c_void_p, C.c_double, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -60,6 +60,7 @@ class Context:
         self._vol_dims = (0, 0, 0)              # TSDF volume: voxels per axis (volume_init)
         self._frame_hw = None                   # (height, width) of the current frame (frame_set_color's shape)
         self._mesh_nv = None                    # vertices of the last mesh (volume_mesh_colors)
+        self._matches = 0                       # matches of the last features_match / relocalize
 
     def close(self):
         if self._h:
@@ -484,6 +485,57 @@ class Context:
                                              _p(it_out), C.byref(step), C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
         self.n, self.dtype = self._pixels, L.F32
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
+
+    # ---- features and relocalisation (Part 3): correspondences without a pose guess
+    def features_detect(self, which: int = L.FEAT_FRAME, threshold: int = 12, max_keypoints: int = L.MAX_KEYPOINTS) -> int:
+        """Detect and describe the keypoints of the frame's colour (FEAT_FRAME) or the model colour (FEAT_MODEL); returns their number."""
+        o = L.RpeFeatureOptions(int(threshold), int(max_keypoints))
+        n = C.c_int(0)
+        L.check(L.lib().rpe_features_detect(self._h, int(which), C.byref(o), C.byref(n)))
+        return n.value
+
+    def features(self, which: int = L.FEAT_FRAME):
+        """(xy (k, 2) int32, score (k,) int32, desc (k, 8) uint32) of the side's last detection, in pixel order."""
+        cap = L.MAX_KEYPOINTS
+        xy, sc, de = np.zeros((cap, 2), np.int32), np.zeros(cap, np.int32), np.zeros((cap, 8), np.uint32)
+        L.check(L.lib().rpe_features_download(self._h, int(which), _p(xy), _p(sc), _p(de)))
+        k = int(np.count_nonzero(sc))     # every keypoint's score is > 0 (relocalize may have detected: the count is read off here)
+        xy, sc, de = xy[:k].copy(), sc[:k].copy(), de[:k].copy()
+        return xy, sc, de
+
+    def features_match(self, max_dist: int = 64, ratio=(8, 10), cross_check: bool = False) -> int:
+        """Match the frame's keypoints against the model's; XW XC BV NW NC of this context become the matches.  Returns their number."""
+        o = L.RpeMatchOptions(int(max_dist), int(ratio[0]), int(ratio[1]), int(cross_check))
+        m = C.c_int(0)
+        L.check(L.lib().rpe_features_match(self._h, C.byref(o), C.byref(m)))
+        self.n, self.dtype, self._matches = m.value, L.F32, m.value
+        return m.value
+
+    def matches(self):
+        """(frame keypoint, model keypoint, d1, d2 int32, weight = 256 - d1 float32) of the last match list, in frame-keypoint order."""
+        m = self._matches
+        fi, mi, d1, d2 = (np.zeros(m, np.int32) for _ in range(4))
+        w = np.zeros(m, np.float32)
+        L.check(L.lib().rpe_matches_download(self._h, _p(fi), _p(mi), _p(d1), _p(d2), _p(w)))
+        return fi, mi, d1, d2, w
+
+    def relocalize(self, method: int, thre_3d: float = 0.0, thre_2d: float = 0.0, thre_nl: float = 0.0, iters: int = 0, confidence: float = 0.99,
+                   seed: int = 1, ls: int = 0, min_matches: int = 12, threshold: int = 12, max_keypoints: int = L.MAX_KEYPOINTS,
+                   max_dist: int = 64, ratio=(8, 10), cross_check: bool = False):
+        """The frame's pose against the model without a pose guess: features on both sides (where missing), matches, rpe_run's solver
+        `method` / `ls` on them.  Returns dict(pose12, matches, iters, max_votes, masks[3, matches]); RpeError with code
+        RPE_ERR_DEGENERATE when fewer than min_matches matches were found.  Refine with icp_pyramid(_rgbd) from pose12."""
+        fo = L.RpeFeatureOptions(int(threshold), int(max_keypoints))
+        mo = L.RpeMatchOptions(int(max_dist), int(ratio[0]), int(ratio[1]), int(cross_check))
+        p = np.zeros(12, np.float64)
+        it, m, mv = C.c_int(int(iters)), C.c_int(0), C.c_int(0)
+        mask = np.zeros(3 * L.MAX_KEYPOINTS, np.int16)
+        try:
+            L.check(L.lib().rpe_relocalize(self._h, C.byref(fo), C.byref(mo), int(method), thre_3d, thre_2d, thre_nl, C.byref(it), confidence,
+                                           int(seed), int(ls), int(min_matches), _p(p), C.byref(m), C.byref(mv), _p(mask)))
+        finally:
+            self.n, self.dtype, self._matches = m.value, L.F32, m.value
+        return dict(pose12=p, matches=m.value, iters=it.value, max_votes=mv.value, masks=mask[:3 * m.value].reshape(3, m.value).copy())
 
     def volume_mesh_colors(self) -> np.ndarray:
         """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh): the colour field there, as model_color samples it."""

@@ -41,7 +41,7 @@ int rpe_frame_set_color(rpe_context* c, const uint8_t* pixels, int format) {
   int rc;
   if ((rc = ensure_buffer(c, &F.d_rgb, &F.rgb_cap, (size_t)n * 3))) return rc;
   if ((rc = ensure_buffer(c, &F.fcolor, &F.fccap, (size_t)n * 4))) return rc;
-  F.have_fcolor = false; F.photo_levels = 0;
+  F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_rgb, pixels, (size_t)n * 3, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_color(F.d_rgb, n, format == RPE_COLOR_BGR8 ? 1 : 0, F.fcolor, c->stream));
   F.have_fcolor = true;
@@ -73,7 +73,7 @@ int rpe_model_sample_color(rpe_context* c) {
   const int64_t n = (int64_t)F.mcam.width * F.mcam.height;
   int rc = ensure_buffer(c, &F.mcolor, &F.mccap, (size_t)n * 4);
   if (rc) return rc;
-  F.have_mcolor = false; F.photo_levels = 0;
+  F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(rpe::launch_color_sample(c->vol.cd, c->vol.g, F.mmap[0], n, F.mcolor, c->stream));
   F.have_mcolor = true;
   return RPE_OK;

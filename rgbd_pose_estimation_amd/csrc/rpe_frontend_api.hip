@@ -4,9 +4,7 @@
 #include <memory>
 using namespace rpeh;
 
-extern "C" {
-// ---------------------------------------------------------------------------------------------- Part 3: front end
-namespace {
+namespace rpeh {
 // the solver slots the association writes: the context's own storage, n = pixels, fp32
 int claim_slots(rpe_context* c, int64_t n) {
   const size_t bytes = (size_t)n * 3 * sizeof(float);
@@ -26,6 +24,11 @@ int claim_slots(rpe_context* c, int64_t n) {
   for (int s = 0; s < RPE_NUM_ARRAYS; s++) { c->arr[s] = c->store[s]; arrays_changed(c, s, true); }
   return RPE_OK;
 }
+}  // namespace rpeh
+
+extern "C" {
+// ---------------------------------------------------------------------------------------------- Part 3: front end
+namespace {
 // one pyramid level of frame and model: maps, pixels, model camera (level 0 = the single-level front end)
 struct Level { const float* f[3]; const float* m[2]; int64_t n; rpe::Camera mcam; };
 Level level_of(rpe_context* c, int l) {
@@ -108,7 +111,7 @@ int rpe_frame_set_depth(rpe_context* c, const void* depth, int depth_type, const
   const int64_t n = (int64_t)k.width * k.height;
   if ((rc = stage_depth(c, depth, depth_type, n))) return rc;
   if ((rc = ensure_maps(c, F.fmap, 3, &F.fcap, n))) return rc;
-  F.have_frame = false; F.have_fcolor = false; F.photo_levels = 0;
+  F.have_frame = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_maps(F.d_depth, depth_type, k, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fmap[0],
       F.fmap[1],
@@ -138,7 +141,7 @@ int rpe_frame_set_depth_pyramid(rpe_context* c, const void* depth, int depth_typ
     HIP_TRY(hipMalloc((void**)&F.fdepth, (size_t)total * sizeof(float)));
     F.fdcap = (size_t)total * sizeof(float);
   }
-  F.have_frame = false; F.have_depth = false; F.have_fcolor = false; F.photo_levels = 0;
+  F.have_frame = false; F.have_depth = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_pyramid(F.d_depth, depth_type, g, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fdepth,
                                     F.fmap[0], F.fmap[1], F.fmap[2], c->stream));
@@ -202,7 +205,7 @@ int rpe_model_from_frame(rpe_context* c, const double* pose12) {
   const int64_t n = F.fgeo.off[F.fgeo.levels];   // every level (one level: width * height)
   int rc = ensure_maps(c, F.mmap, 2, &F.mcap, n);
   if (rc) return rc;
-  F.have_mcolor = false; F.photo_levels = 0;
+  F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(rpe::launch_to_world(F.fmap[0], F.fmap[1], n, pose_f(pose12), F.mmap[0], F.mmap[1], c->stream));
   F.mcam = F.cam;
   F.mgeo = F.fgeo;
@@ -222,7 +225,7 @@ int rpe_model_upload(rpe_context* c, const float* vertex_w, const float* normal_
   auto& F = c->fe;
   const int64_t n = (int64_t)k.width * k.height;
   if ((rc = ensure_maps(c, F.mmap, 2, &F.mcap, n))) return rc;
-  F.have_mcolor = false; F.photo_levels = 0;
+  F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.mmap[0], vertex_w, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(F.mmap[1], normal_w, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the caller may free its buffers on return

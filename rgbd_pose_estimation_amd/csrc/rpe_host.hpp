@@ -10,6 +10,7 @@
 //   rpe_mesh_api.hip      Part 3: mesh extraction from the TSDF volume (marching cubes) and its download
 //   rpe_color_api.hip     Part 3: frame colour, the colour volume beside the TSDF, model and mesh colours
 //   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
+//   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -170,6 +171,16 @@ struct rpe_context {
     float* pint = nullptr; size_t pint_cap = 0;
     float* pmap = nullptr; size_t pmap_cap = 0;
     int photo_levels = 0;
+    // features (rpe_feature_api.hip): per side (RPE_FEAT_FRAME / RPE_FEAT_MODEL) the keypoints of the last detection -- pixel index,
+    // score, xy and 8 descriptor words each, RPE_MAX_KEYPOINTS slots, allocated on first use -- valid while `have` (whatever replaces
+    // the side's depth, model or colour resets it); gen counts the side's detections so that a match list knows what it was made of
+    struct Features { int *pix = nullptr, *score = nullptr, *xy = nullptr; unsigned int* desc = nullptr; int count = 0; bool have = false;
+                      unsigned long long gen = 0; int threshold = 0, max_keypoints = 0; } feat[2];
+    rpe::FeatureWork fwork{};            // the detector's workspace, sized for fwork_pixels pixels (shared by both sides)
+    int64_t fwork_pixels = 0;
+    rpe::MatchLists mlist{};             // best / second best per keypoint and the accepted matches (RPE_MAX_KEYPOINTS slots)
+    int matches = -1;                    // accepted matches of the last rpe_features_match (-1: none) ...
+    unsigned long long match_gen[2] = {0, 0};   // ... made of these detections
   } fe;
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
   struct Volume {
@@ -366,6 +377,9 @@ inline int ensure_maps(rpe_context* c, float** maps, int count, size_t* cap, int
   *cap = bytes;
   return RPE_OK;
 }
+// the solver slots a device-side producer writes (association, feature matches): the context's own storage, n columns, fp32
+// (rpe_frontend_api.hip)
+int claim_slots(rpe_context* c, int64_t n);
 // the one-level pyramid of a single image (rpe_frame_set_depth, rpe_model_upload, rpe_volume_raycast)
 inline void one_level(const rpe_camera& k, const rpe::Camera& f, rpe_camera* kc, rpe::PyramidGeometry* g) {
   *g = rpe::PyramidGeometry{};

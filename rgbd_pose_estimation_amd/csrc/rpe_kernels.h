@@ -283,6 +283,28 @@ hipError_t launch_icp_photo(const float* vmap, const float* nmap, const float* f
 hipError_t launch_photo_rows(const float* vmap, const float* fint, int64_t n, const float* pmap4, const Camera& mcam, const PoseF& M,
                              float dist_thr, const double* pose12, float* rows, hipStream_t s);
 void preload_photo();
+// ---- features (rpe_feature.hip): keypoints, descriptors, matches.  All integer arithmetic; ids come from scans, never from atomics.
+constexpr int kMaxKeypoints = 4096;     // RPE_MAX_KEYPOINTS
+constexpr int kFeatScoreBins = 4096;    // a score is at most 16 * 255
+enum { kFeatCtlSurvivors = 0, kFeatCtlCut = 1, kFeatCtlTies = 2, kFeatCtlCount = 3, kFeatCtlMatches = 4, kFeatCtlWords = 8 };
+// the detector's workspace for an image of n pixels: score (n ints), box sums (n u16), per-chunk survivor counts -> offsets
+// (n / 256 + 2 ints), the score histogram, the control words above and the survivors' pixel indices ((n + w + h + 1) / 4 + 1 ints)
+struct FeatureWork { int* score; unsigned short* box; int* chunk; unsigned int* hist; int* ctl; int* spix; };
+// F1: detect + describe one view.  rgba / vmap / nmap: the view's RGBA8 colour, vertex and normal maps (w x h).  Leaves the number of
+// keypoints in W.ctl[kFeatCtlCount] and pixel index, score, xy and descriptor of keypoint k at slot k, in pixel order.  Six kernels, no
+// host wait.
+hipError_t launch_feature_detect(const unsigned int* rgba, const float* vmap, const float* nmap, int w, int h, int threshold, int max_keypoints,
+                                 const FeatureWork& W, int* kp_pix, int* kp_score, int* kp_xy, unsigned int* kp_desc, hipStream_t s);
+// per keypoint of the list A: d1, index and d2 over the list B (ties to the lower index; d1 = d2 = 257, index -1 without any)
+struct MatchLists { int *d1, *idx, *d2, *back; int *mf, *mm, *md1, *md2; float* mw; };
+hipError_t launch_feature_best(const unsigned int* desc_a, int na, const unsigned int* desc_b, int nb, int* d1, int* idx, int* d2, hipStream_t s);
+// the accepted matches of the nf frame keypoints, in frame-keypoint order (L.mf mm md1 md2 mw), their number in ctl[kFeatCtlMatches]
+hipError_t launch_feature_accept(const MatchLists& L, int nf, int max_dist, int ratio_num, int ratio_den, int cross_check, int* ctl, hipStream_t s);
+// the five solver slots of `matches` matches (3 floats per match each)
+hipError_t launch_feature_gather(const MatchLists& L, int matches, const int* fpix, const int* mpix, const float* fv, const float* fn,
+                                 const float* fb, const float* mv, const float* mn, float* xw, float* xc, float* bv, float* nw, float* nc,
+                                 hipStream_t s);
+void preload_feature();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

@@ -92,7 +92,7 @@ int rpe_model_color_upload(rpe_context* c, const uint8_t* rgba) {
   const size_t bytes = (size_t)F.mcam.width * F.mcam.height * 4;
   int rc = ensure_buffer(c, &F.mcolor, &F.mccap, bytes);
   if (rc) return rc;
-  F.have_mcolor = false; F.photo_levels = 0;
+  F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.mcolor, rgba, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's buffer is free again on return
   F.have_mcolor = true;
@@ -112,7 +112,7 @@ int rpe_model_color_from_frame(rpe_context* c) {
   const size_t bytes = (size_t)F.mcam.width * F.mcam.height * 4;
   int rc = ensure_buffer(c, &F.mcolor, &F.mccap, bytes);
   if (rc) return rc;
-  F.have_mcolor = false; F.photo_levels = 0;
+  F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.mcolor, F.fcolor, bytes, hipMemcpyDeviceToDevice, c->stream));
   F.have_mcolor = true;
   return RPE_OK;

@@ -67,7 +67,7 @@ int rpe_volume_raycast(rpe_context* c, const double* pose12, const rpe_camera* c
   const int64_t n = (int64_t)k.width * k.height;
   if ((rc = ensure_maps(c, F.mmap, 2, &F.mcap, n))) return rc;
   F.have_model = false;
-  F.have_mcolor = false; F.photo_levels = 0;
+  F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(rpe::launch_volume_raycast(c->vol.d, c->vol.g, k, pose_f(pose12), (float)dmin, (float)dmax, F.mmap[0], F.mmap[1], c->stream));
   F.mcam = k;
   one_level(*cam, k, F.mkcam, &F.mgeo);

@@ -20,6 +20,10 @@
 // ... and tracking can use it: a photometric term beside ICP holds the pose where the view is one plane (a wall, a floor, a corridor)
 //   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.setColor(rgb);  fe.raycast(T, cam, range, 3);  fe.modelColor();
 //                   fe.preparePhoto(3);  fe.icpPyramidRgbd(T, 0.01, {6, 4, 3});  fe.integrateColor(T);
+// ... and a LOST tracker recovers without a pose guess: keypoints of the frame's and the model view's colour are matched by appearance
+// and the RANSAC / PROSAC solvers make the pose that ICP then refines
+//   rpe::RelocResult r = fe.relocalize(6 /* shinji_kneip_prosac */, 0.05, 3.0, 0.1);
+//   if (r.ok) { T = r.pose;  fe.preparePhoto(3);  fe.icpPyramidRgbd(T, 0.01, {6, 4, 3}); }
 //
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
@@ -65,6 +69,18 @@ struct IcpResult { int iterations = 0; double last_step = 0, cost = 0; long long
 struct PyramidIcpResult : IcpResult { int level_iterations[RPE_MAX_LEVELS] = {0, 0, 0, 0}; };
 // ICP with the photometric term: cost / pairs are the geometric ones, as icp reports them; the photometric ones beside them
 struct RgbdIcpResult : PyramidIcpResult { double photo_cost = 0; long long photo_pairs = 0; };
+
+// keypoint detection (rpe_features_detect) and matching (rpe_features_match) options; the defaults are the C ABI's
+struct FeatureOptions { int threshold = 12, max_keypoints = RPE_MAX_KEYPOINTS; };
+struct MatchOptions { int max_dist = 64, ratio_num = 8, ratio_den = 10; bool cross_check = false; };
+// relocalize(): ok = false when fewer than min_matches matches were found (pose is then the identity); iterations = the solver's
+// adapted Iter, votes its consensus; masks = 3 x matches shorts (2D-3D | 3D-3D | normal rows), as rpe_run returns them
+struct RelocResult {
+  bool ok = false;
+  SE3<double> pose;
+  int matches = 0, iterations = 0, votes = 0;
+  std::vector<short> masks;
+};
 
 class DepthFrontEnd {
  public:
@@ -271,6 +287,40 @@ class DepthFrontEnd {
     check(rpe_photo_rows(_ctx, level, p, dist_thr, rows.data()), "rpe_photo_rows");
     rows.resize(n);
     return rows;
+  }
+  // keypoints and descriptors of the frame's colour (which = RPE_FEAT_FRAME) or of the model colour (RPE_FEAT_MODEL); returns their
+  // number.  A new depth, colour, model or model colour drops the side's features
+  int detectFeatures(int which, const FeatureOptions& o = FeatureOptions()) {
+    const rpe_feature_options fo = {o.threshold, o.max_keypoints};
+    int n = 0;
+    check(rpe_features_detect(_ctx, which, &fo, &n), "rpe_features_detect");
+    return n;
+  }
+  // match the frame's keypoints against the model's; the solver slots become the matches (n = their number, returned)
+  int matchFeatures(const MatchOptions& o = MatchOptions()) {
+    const rpe_match_options mo = {o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? 1 : 0};
+    int m = 0;
+    check(rpe_features_match(_ctx, &mo, &m), "rpe_features_match");
+    return m;
+  }
+  // the frame's pose against the model WITHOUT a pose guess: features where missing, matches, then rpe_run's solver `method`
+  // (0 .. 9) with stage `ls` on them, seeded with `seed`.  Too few matches is a result (ok = false), every other failure throws
+  RelocResult relocalize(int method, double thre_3d, double thre_2d, double thre_nl, int max_iter = 200, double confidence = 0.99,
+                         uint64_t seed = 1, int ls = 0, int min_matches = 12, const FeatureOptions& f = FeatureOptions(),
+                         const MatchOptions& m = MatchOptions()) {
+    const rpe_feature_options fo = {f.threshold, f.max_keypoints};
+    const rpe_match_options mo = {m.max_dist, m.ratio_num, m.ratio_den, m.cross_check ? 1 : 0};
+    RelocResult r;
+    r.iterations = max_iter;
+    r.masks.assign((size_t)3 * RPE_MAX_KEYPOINTS, 0);
+    double p[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    const int rc = rpe_relocalize(_ctx, &fo, &mo, method, thre_3d, thre_2d, thre_nl, &r.iterations, confidence, seed, ls, min_matches, p,
+                                  &r.matches, &r.votes, r.masks.data());
+    if (rc != RPE_ERR_DEGENERATE) check(rc, "rpe_relocalize");
+    r.ok = rc == RPE_OK;
+    r.masks.resize(r.ok ? (size_t)3 * r.matches : 0);
+    if (r.ok) r.pose = pose_of(p);
+    return r;
   }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {

@@ -302,6 +302,21 @@ def room_texture(P):
     return 127.5 + 120.0 * np.sin(P @ K.T + phi)
 
 
+def cell_texture(P, cell=0.15):
+    """RGB in 0 .. 255 (float64, (n, 3)) of world points P (n, 3): a blocky random texture, per channel a hash of the lattice cell
+    floor(P / cell + 0.5) the point lies in -- corners on every surface, for keypoint detectors (room_texture has none).  The half
+    cell keeps the room's walls (multiples of the default cell) off the cell boundaries, where rounding would pick sides at random."""
+    P = np.asarray(P, np.float64).reshape(-1, 3)
+    c = np.floor(P / cell + 0.5).astype(np.int64).astype(np.uint32)
+    out = np.empty((len(P), 3), np.float64)
+    with np.errstate(over="ignore"):
+        for ch in range(3):
+            h = (c[:, 0] * np.uint32(73856093)) ^ (c[:, 1] * np.uint32(19349663)) ^ (c[:, 2] * np.uint32(83492791)) ^ np.uint32(0x9E3779B1 * (ch + 1) & 0xFFFFFFFF)
+            h ^= h >> np.uint32(16); h *= np.uint32(0x85EBCA6B); h ^= h >> np.uint32(13); h *= np.uint32(0xC2B2AE35); h ^= h >> np.uint32(16)
+            out[:, ch] = (h & np.uint32(255)).astype(np.float64)
+    return out
+
+
 def render_rgb(R, t, cam=DEFAULT_CAMERA, room=None, texture=None):
     """Colour image (height, width, 3) uint8 of the room seen by the camera Xc = R Xw + t, registered to render_depth's image: each
     pixel is texture (default room_texture) at the pixel's noise-free hit point, rounded to the nearest integer and clipped to
