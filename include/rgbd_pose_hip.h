@@ -665,8 +665,8 @@ int rpe_icp_pyramid_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double ph
  * Slots: rpe_features_match declares the problem (n = matches, RPE_F32) and fills, per match, XW / NW = the model vertex / normal at
  * the model keypoint, XC / NC / BV = the frame's vertex / normal / bearing at the frame keypoint.  The match quality 256 - d1 is the
  * float weight of the match (rpe_matches_download): what a PROSAC solver sorts.
- * Scope: no orientation, no scale normalisation and no keyframe store yet -- a caller who keeps keyframes re-uploads one with
- * rpe_model_upload + rpe_model_color_upload and relocalises against it. */
+ * Scope: no orientation and no scale normalisation.  The model is ONE view; a caller who keeps many adds each to the keyframe store
+ * below ("Keyframes") and relocalises against all of them at once -- nothing is re-uploaded or re-detected. */
 typedef struct { int threshold; int max_keypoints; } rpe_feature_options;                       /* NULL: {12, RPE_MAX_KEYPOINTS} */
 typedef struct { int max_dist; int ratio_num, ratio_den; int cross_check; } rpe_match_options;  /* NULL: {64, 8, 10, 0} */
 enum { RPE_FEAT_FRAME = 0, RPE_FEAT_MODEL = 1, RPE_MAX_KEYPOINTS = 4096 };
@@ -690,6 +690,56 @@ int rpe_matches_download(rpe_context* ctx, int32_t* frame_idx, int32_t* model_id
 int rpe_relocalize(rpe_context* ctx, const rpe_feature_options* fopt, const rpe_match_options* mopt, int method, double thre_3d,
                    double thre_2d, double thre_nl, int* iter_io, double confidence, uint64_t seed, int ls, int min_matches,
                    double* pose12, int* matches, int* max_votes, short* mask_out);
+
+/* ---- Keyframes: the model side's features kept on the device, and a frame relocalised against all of them at once.  A lost tracker
+ * does not know which of its keyframes the camera sees; what the solvers need from a keyframe is small -- per keypoint the descriptor
+ * and the world vertex and normal (at most 64 B x RPE_MAX_KEYPOINTS) -- so the context keeps it, and the frame's keypoints are matched
+ * against every keyframe in one pass.  Conventions, bit for bit (tests/keyframe_oracle.py states them in numpy):
+ * Store: a keyframe = the model side's current detection: xy and desc of rpe_features_download(RPE_FEAT_MODEL) and, per keypoint, the
+ * model's level-0 world vertex xw and normal nw at its pixel (count x 3 floats each), with the model's pose (rpe_model_upload's /
+ * rpe_model_from_frame's pose12, informative) and level-0 width and height.  A keyframe made from a tracked frame goes through
+ * rpe_model_from_frame + rpe_model_color_from_frame + rpe_features_detect(RPE_FEAT_MODEL) first.  Ids are 0, 1, ... in insertion order;
+ * at most RPE_MAX_KEYFRAMES.  The store belongs to the context: it survives new frames, new models, rpe_volume_init and new detections
+ * and is freed with the context; its memory grows in steps as keyframes are added.  Removing ONE keyframe is out of scope:
+ * rpe_keyframes_clear empties the store (a saved map comes back through rpe_keyframe_add_host).  Keyframes of different cameras may
+ * share a store.
+ * Query: per keyframe k, count[k] = the number of matches rpe_features_match would accept with keyframe k's keypoints as the model's
+ * (the rules of "Matching" above, over the keypoints of k ALONE: d2 = 257 with one keypoint, no match against an empty keyframe; the
+ * cross-check is per keyframe too).  order = the ids sorted by (count descending, id ascending).  One host wait.
+ * Match: rpe_keyframe_match(id) is rpe_features_match with keyframe id in the model's place: the problem is declared, XW / NW come
+ * from the store, XC / NC / BV from the frame's maps, and rpe_matches_download gives the list (model_idx = the keypoint's position
+ * inside the keyframe).  A new detection on the frame, rpe_keyframes_clear or any later match call drops that list.  Cost: the store's
+ * matcher gives one keyframe a few workgroups only, so ONE such call takes about twice rpe_features_match's time against the same
+ * keypoints as the model; the store pays from the query on, where the keyframes share one launch.
+ * Relocalise: rpe_relocalize_keyframes detects on the frame (if its features are missing or were made with other options), queries,
+ * and walks the ranking over the first `candidates` (>= 1) keyframes, stopping at the first with fewer than min_matches (>= 4)
+ * matches.  Each candidate gets exactly rpe_relocalize's run: the downloaded slots through rpe_run, weights = the match quality for
+ * every modality, the frame's focal lengths, RPE_SCORE_EXACT, the same seed and the same incoming *iter_io; a candidate rpe_run
+ * refuses with RPE_ERR_DEGENERATE is skipped.  The candidate with the most max_votes wins, a tie going to the better rank.  On return
+ * pose12, *keyframe, *matches, *iter_io, *max_votes, mask_out (3 x matches shorts; give room for 3 x RPE_MAX_KEYPOINTS), the slots and
+ * the match list are the winner's.  RPE_ERR_DEGENERATE when the best-ranked keyframe has fewer than min_matches matches (or every
+ * candidate was refused): *keyframe = the best-ranked id, *matches = its count, pose12 is left untouched. */
+enum { RPE_MAX_KEYFRAMES = 256 };
+/* the model side's current features become keyframe *id (may be NULL); RPE_ERR_STATE without a model detection or with a full store */
+int rpe_keyframe_add(rpe_context* ctx, int* id);
+/* the same from host arrays (count 0 .. RPE_MAX_KEYPOINTS; xy 2 x count int32 inside width x height, desc 8 x count uint32, xw / nw
+ * 3 x count floats, NULL allowed for count = 0); RPE_ERR_ARG for bad arguments, RPE_ERR_STATE with a full store */
+int rpe_keyframe_add_host(rpe_context* ctx, int count, const int32_t* xy, const uint32_t* desc, const float* xw, const float* nw,
+                          const double* pose12, int width, int height, int* id);
+/* what the store knows of keyframe id (any output may be NULL); RPE_ERR_ARG for an id that is not in the store */
+int rpe_keyframe_info(rpe_context* ctx, int id, int* count, double* pose12, int* width, int* height);
+/* keyframe id's arrays, shaped as rpe_keyframe_add_host takes them (any may be NULL) */
+int rpe_keyframe_download(rpe_context* ctx, int id, int32_t* xy, uint32_t* desc, float* xw, float* nw);
+int rpe_keyframes_count(rpe_context* ctx, int* count);
+/* empties the store (its memory is kept for the next keyframes) */
+int rpe_keyframes_clear(rpe_context* ctx);
+/* counts[k] and order[r] for the K keyframes of the store (K ints each); RPE_ERR_STATE without frame features or with an empty store */
+int rpe_keyframes_query(rpe_context* ctx, const rpe_match_options* mopt, int* counts, int* order);
+/* rpe_features_match against keyframe id; RPE_ERR_STATE as rpe_keyframes_query, RPE_ERR_ARG for an id that is not in the store */
+int rpe_keyframe_match(rpe_context* ctx, int id, const rpe_match_options* mopt, int* matches);
+int rpe_relocalize_keyframes(rpe_context* ctx, const rpe_feature_options* fopt, const rpe_match_options* mopt, int candidates, int method,
+                             double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence, uint64_t seed, int ls,
+                             int min_matches, double* pose12, int* keyframe, int* matches, int* max_votes, short* mask_out);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

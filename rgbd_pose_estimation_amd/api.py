@@ -537,6 +537,85 @@ class Context:
             self.n, self.dtype, self._matches = m.value, L.F32, m.value
         return dict(pose12=p, matches=m.value, iters=it.value, max_votes=mv.value, masks=mask[:3 * m.value].reshape(3, m.value).copy())
 
+    # ---- keyframes (Part 3): the model side's features kept on the device, a frame relocalised against all of them at once
+    def keyframe_add(self) -> int:
+        """The model side's current features (features_detect(FEAT_MODEL)) become a keyframe of this context's store; returns its id."""
+        i = C.c_int(-1)
+        L.check(L.lib().rpe_keyframe_add(self._h, C.byref(i)))
+        return i.value
+
+    def keyframe_add_host(self, xy, desc, xw, nw, pose12, width: int, height: int) -> int:
+        """A keyframe from host arrays, shaped as keyframe() returns them (a saved map restored); returns its id."""
+        xy, desc = np.ascontiguousarray(xy, np.int32).reshape(-1, 2), np.ascontiguousarray(desc, np.uint32).reshape(-1, 8)
+        xw, nw = np.ascontiguousarray(xw, np.float32).reshape(-1, 3), np.ascontiguousarray(nw, np.float32).reshape(-1, 3)
+        if not len(xy) == len(desc) == len(xw) == len(nw):
+            raise ValueError("xy, desc, xw and nw need one row per keypoint")
+        p = np.ascontiguousarray(pose12, np.float64).reshape(12)
+        i = C.c_int(-1)
+        L.check(L.lib().rpe_keyframe_add_host(self._h, len(xy), _p(xy), _p(desc), _p(xw), _p(nw), _p(p), int(width), int(height), C.byref(i)))
+        return i.value
+
+    def keyframe(self, kf: int):
+        """dict(xy (k, 2) int32, desc (k, 8) uint32, xw (k, 3), nw (k, 3) float32, pose12, width, height) of keyframe kf."""
+        n, w, h = C.c_int(0), C.c_int(0), C.c_int(0)
+        pose = np.zeros(12, np.float64)
+        L.check(L.lib().rpe_keyframe_info(self._h, int(kf), C.byref(n), _p(pose), C.byref(w), C.byref(h)))
+        k = n.value
+        xy, de = np.zeros((k, 2), np.int32), np.zeros((k, 8), np.uint32)
+        xw, nw = np.zeros((k, 3), np.float32), np.zeros((k, 3), np.float32)
+        L.check(L.lib().rpe_keyframe_download(self._h, int(kf), _p(xy), _p(de), _p(xw), _p(nw)))
+        return dict(xy=xy, desc=de, xw=xw, nw=nw, pose12=pose, width=w.value, height=h.value)
+
+    def keyframes_len(self) -> int:
+        """The number of keyframes in the store."""
+        n = C.c_int(0)
+        L.check(L.lib().rpe_keyframes_count(self._h, C.byref(n)))
+        return n.value
+
+    def keyframes_clear(self):
+        L.check(L.lib().rpe_keyframes_clear(self._h))
+
+    def keyframes_query(self, max_dist: int = 64, ratio=(8, 10), cross_check: bool = False):
+        """(counts, order): per keyframe the matches features_match would accept against it, and the ids by (count descending, id)."""
+        k = self.keyframes_len()
+        o = L.RpeMatchOptions(int(max_dist), int(ratio[0]), int(ratio[1]), int(cross_check))
+        counts, order = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32)
+        L.check(L.lib().rpe_keyframes_query(self._h, C.byref(o), _p(counts), _p(order)))
+        return counts[:k], order[:k]
+
+    def keyframe_match(self, kf: int, max_dist: int = 64, ratio=(8, 10), cross_check: bool = False) -> int:
+        """features_match with keyframe kf in the model's place: the slots and matches() are this keyframe's.  Returns the matches."""
+        o = L.RpeMatchOptions(int(max_dist), int(ratio[0]), int(ratio[1]), int(cross_check))
+        m = C.c_int(0)
+        L.check(L.lib().rpe_keyframe_match(self._h, int(kf), C.byref(o), C.byref(m)))
+        self.n, self.dtype, self._matches = m.value, L.F32, m.value
+        return m.value
+
+    def relocalize_keyframes(self, method: int, candidates: int = 3, thre_3d: float = 0.0, thre_2d: float = 0.0, thre_nl: float = 0.0,
+                             iters: int = 0, confidence: float = 0.99, seed: int = 1, ls: int = 0, min_matches: int = 12, threshold: int = 12,
+                             max_keypoints: int = L.MAX_KEYPOINTS, max_dist: int = 64, ratio=(8, 10), cross_check: bool = False):
+        """The frame's pose without a pose guess and without knowing which keyframe it sees: the query, then relocalize's solver run on
+        each of the `candidates` best-ranked keyframes with at least min_matches matches; the one with the most votes wins.  Returns
+        dict(pose12, keyframe, matches, iters, max_votes, masks[3, matches]); RpeError with code RPE_ERR_DEGENERATE (and the attributes
+        keyframe / matches of the best-ranked one) when no keyframe has min_matches matches."""
+        fo = L.RpeFeatureOptions(int(threshold), int(max_keypoints))
+        mo = L.RpeMatchOptions(int(max_dist), int(ratio[0]), int(ratio[1]), int(cross_check))
+        p = np.zeros(12, np.float64)
+        it, kf, m, mv = C.c_int(int(iters)), C.c_int(-1), C.c_int(0), C.c_int(0)
+        mask = np.zeros(3 * L.MAX_KEYPOINTS, np.int16)
+        try:
+            L.check(L.lib().rpe_relocalize_keyframes(self._h, C.byref(fo), C.byref(mo), int(candidates), int(method), thre_3d, thre_2d, thre_nl,
+                                                     C.byref(it), confidence, int(seed), int(ls), int(min_matches), _p(p), C.byref(kf),
+                                                     C.byref(m), C.byref(mv), _p(mask)))
+        except L.RpeError as e:
+            if e.code == L.RPE_ERR_DEGENERATE:      # the query ran: the match list is gone.  An argument or state error changed nothing
+                e.keyframe, e.matches = kf.value, m.value
+                self.n, self.dtype, self._matches = 0, L.F32, 0
+            raise
+        self.n, self.dtype, self._matches = m.value, L.F32, m.value
+        return dict(pose12=p, keyframe=kf.value, matches=m.value, iters=it.value, max_votes=mv.value,
+                    masks=mask[:3 * m.value].reshape(3, m.value).copy())
+
     def volume_mesh_colors(self) -> np.ndarray:
         """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh): the colour field there, as model_color samples it."""
         n = self._mesh_nv or 0

@@ -158,7 +158,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
     if (device < 64 && !loaded[device]) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
       rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
-      rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature();
+      rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_keyframe();
       loaded[device] = true;
     }
   }
@@ -207,6 +207,11 @@ void rpe_destroy(rpe_context* c) {
     const auto& W = c->fe.fwork; const auto& M = c->fe.mlist;
     for (void* m : {(void*)W.score, (void*)W.box, (void*)W.chunk, (void*)W.hist, (void*)W.ctl, (void*)W.spix, (void*)M.d1, (void*)M.idx, (void*)M.d2,
                     (void*)M.back, (void*)M.mf, (void*)M.mm, (void*)M.md1, (void*)M.md2, (void*)M.mw}) if (m) (void)hipFree(m);
+  }
+  {
+    const auto& K = c->kf;
+    for (void* m : {(void*)K.st.off, (void*)K.st.desc, (void*)K.st.xw, (void*)K.st.nw, (void*)K.st.xy, (void*)K.back, (void*)K.d1, (void*)K.idx,
+                    (void*)K.d2, (void*)K.rank}) if (m) (void)hipFree(m);
   }
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);

@@ -82,6 +82,7 @@ int match_options(const rpe_match_options* o) {
 }
 bool matches_current(const rpe_context* c) {
   auto& F = c->fe;
+  if (F.match_kf >= 0) return F.matches >= 0 && F.feat[0].have && F.match_gen[0] == F.feat[0].gen;   // rpe_keyframe_match's list
   return F.matches >= 0 && F.feat[0].have && F.feat[1].have && F.match_gen[0] == F.feat[0].gen && F.match_gen[1] == F.feat[1].gen;
 }
 }  // namespace
@@ -138,7 +139,7 @@ int rpe_features_match(rpe_context* c, const rpe_match_options* opt, int* matche
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ensure_lists(c))) return rc;
   const auto& L = F.mlist;
-  F.matches = -1;
+  F.matches = -1; F.match_kf = -1;
   HIP_TRY(rpe::launch_feature_best(A.desc, A.count, B.desc, B.count, L.d1, L.idx, L.d2, c->stream));
   // the cross-check: the same pass with the roles swapped (its distances land in the match lists' slots, rewritten below)
   if (o.cross_check) HIP_TRY(rpe::launch_feature_best(B.desc, B.count, A.desc, A.count, L.md1, L.back, L.md2, c->stream));

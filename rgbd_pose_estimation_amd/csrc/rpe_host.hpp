@@ -11,6 +11,7 @@
 //   rpe_color_api.hip     Part 3: frame colour, the colour volume beside the TSDF, model and mesh colours
 //   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
 //   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
+//   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -181,7 +182,20 @@ struct rpe_context {
     rpe::MatchLists mlist{};             // best / second best per keypoint and the accepted matches (RPE_MAX_KEYPOINTS slots)
     int matches = -1;                    // accepted matches of the last rpe_features_match (-1: none) ...
     unsigned long long match_gen[2] = {0, 0};   // ... made of these detections
+    int match_kf = -1;                   // ... against this keyframe of the store in the model's place (-1: against the model side)
   } fe;
+  // keyframes (rpe_keyframe_api.hip): the packed store (rpe::KeyframeStore, room for `cap` keypoints, grown in steps), per keyframe
+  // what the host keeps, and the query's workspace: back = per store keypoint its best frame keypoint (cap ints), d1 / idx / d2 =
+  // one row of RPE_MAX_KEYPOINTS ints per keyframe (rows_cap rows), rank = counts | order (2 x RPE_MAX_KEYFRAMES ints).  The store
+  // belongs to the context: nothing but rpe_keyframes_clear and rpe_destroy touches it.
+  struct Keyframes {
+    struct Meta { int off = 0, count = 0, width = 0, height = 0; double pose[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}; };
+    std::vector<Meta> meta;
+    rpe::KeyframeStore st{};
+    int64_t cap = 0, used = 0;
+    int *back = nullptr, *d1 = nullptr, *idx = nullptr, *d2 = nullptr, *rank = nullptr;
+    int rows_cap = 0;
+  } kf;
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
   struct Volume {
     rpe::VolumeGeometry g{};

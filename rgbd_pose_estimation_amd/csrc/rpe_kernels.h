@@ -305,6 +305,29 @@ hipError_t launch_feature_gather(const MatchLists& L, int matches, const int* fp
                                  const float* fb, const float* mv, const float* mn, float* xw, float* xc, float* bv, float* nw, float* nc,
                                  hipStream_t s);
 void preload_feature();
+// ---- keyframes (rpe_keyframe.hip): the features of many model views in one packed store, CSR-style -- keyframe k owns the keypoints
+// off[k] .. off[k + 1] - 1 of desc (8 u32 each), xw / nw (3 floats each: the world vertex / normal at the keypoint) and xy (2 ints)
+constexpr int kMaxKeyframes = 256;      // RPE_MAX_KEYFRAMES
+struct KeyframeStore { int* off; unsigned int* desc; float* xw; float* nw; int* xy; };
+// the acceptance test of rpe_features_match as the counting pass applies it; back = per store keypoint the frame keypoint that is its
+// best (the cross-check), or nullptr
+struct KeyframeAccept { int max_dist, ratio_num, ratio_den; const int* back; };
+// K1: the model side's `count` keypoints (pix, xy, desc) and the model's vertex / normal maps at them, to the store from keypoint `base`
+hipError_t launch_keyframe_snapshot(int count, const int* pix, const int* xy, const unsigned int* desc, const float* mv, const float* mn,
+                                    const KeyframeStore& S, int base, hipStream_t s);
+// K2: per keypoint q of list A (na of them) and segment g = 0 .. segments - 1 of list B: d1, index inside the segment and d2 at
+// [g * na + q] (rules of launch_feature_best; d1 / d2 may be nullptr).  Segment g = keyframe seg0 + g of the store whose offsets are
+// `off`, or, off == nullptr, the one list of one_n descriptors from one_lo.  counts != nullptr: counts[seg0 + g] += the pairs that
+// pass `acc` (clear it first).
+hipError_t launch_keyframe_best(const unsigned int* desc_a, int na, const unsigned int* desc_b, const int* off, int seg0, int segments,
+                                int one_lo, int one_n, const KeyframeAccept& acc, int* d1, int* idx, int* d2, int* counts, hipStream_t s);
+// K3: order[r] = the keyframe of rank r by (count descending, id ascending), K <= kMaxKeyframes
+hipError_t launch_keyframe_rank(const int* counts, int K, int* order, hipStream_t s);
+// K4: the five solver slots of `matches` matches (frame keypoint mf, keypoint mm of the keyframe that starts at `base`)
+hipError_t launch_keyframe_gather(const int* mf, const int* mm, int matches, const int* fpix, const float* fv, const float* fn,
+                                  const float* fb, const KeyframeStore& S, int base, float* xw, float* xc, float* bv, float* nw, float* nc,
+                                  hipStream_t s);
+void preload_keyframe();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

@@ -1,0 +1,351 @@
+// Part 3 of include/rgbd_pose_hip.h: keyframes (kernels in rpe_keyframe.hip).  The model side's features -- descriptors, and the world
+// vertex and normal at every keypoint -- kept in a packed store that belongs to the context; one frame matched against all of them in
+// one pass (rpe_keyframes_query: the host waits once, for the counts and the ranking); one keyframe's matches in the solver slots
+// (rpe_keyframe_match); and rpe_relocalize_keyframes: the best-ranked candidates through rpe_run, the one with the most votes kept.
+#include "rpe_host.hpp"
+using namespace rpeh;
+
+namespace {
+constexpr int64_t kStoreStep = 8 * (int64_t)rpe::kMaxKeypoints;                        // the store's first allocation, keypoints
+constexpr int64_t kStoreMax = (int64_t)rpe::kMaxKeyframes * rpe::kMaxKeypoints;
+const rpe_match_options kMatchDefaults = {64, 8, 10, 0};
+
+int match_options(const rpe_match_options* o) {
+  if (o->max_dist < 0 || o->max_dist > 256 || o->ratio_num < 1 || o->ratio_den < 1 || o->ratio_num > 65536 || o->ratio_den > 65536 ||
+      (o->cross_check != 0 && o->cross_check != 1))
+    return fail(RPE_ERR_ARG, "match options: max_dist 0 .. 256 (got %d), ratio_num / ratio_den 1 .. 65536 (got %d / %d), cross_check 0 or 1 (got %d)",
+                o->max_dist, o->ratio_num, o->ratio_den, o->cross_check);
+  return RPE_OK;
+}
+// larger arrays with the first `keep` elements of each kept: every new array first, the copies behind one another, ONE wait, then
+// the old arrays go.  A failure on the way frees what was new and leaves every array, and the capacity beside them, as it was
+struct Grow { void** p; size_t keep, bytes; };    // keep and bytes in bytes
+template <size_t N> int regrow(rpe_context* c, const Grow (&g)[N]) {
+  void* q[N] = {};
+  hipError_t e = hipSuccess;
+  for (size_t i = 0; i < N && e == hipSuccess; i++) e = hipMalloc(&q[i], g[i].bytes);
+  for (size_t i = 0; i < N && e == hipSuccess; i++)
+    if (*g[i].p && g[i].keep) e = hipMemcpyAsync(q[i], *g[i].p, g[i].keep, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    for (void* m : q) if (m) (void)hipFree(m);
+    return fail(RPE_ERR_HIP, "keyframe storage: %s", hipGetErrorString(e));
+  }
+  for (size_t i = 0; i < N; i++) { if (*g[i].p) (void)hipFree(*g[i].p); *g[i].p = q[i]; }
+  return RPE_OK;
+}
+// room for `more` keypoints behind the store's last: the store doubles (from kStoreStep keypoints, up to its bound)
+int ensure_store(rpe_context* c, int more) {
+  auto& K = c->kf;
+  if (!K.st.off) HIP_TRY(hipMalloc((void**)&K.st.off, (rpe::kMaxKeyframes + 1) * sizeof(int)));
+  if (!K.rank) HIP_TRY(hipMalloc((void**)&K.rank, 2 * rpe::kMaxKeyframes * sizeof(int)));
+  const int64_t need = K.used + more;
+  if (need <= K.cap) return RPE_OK;
+  int64_t cap = std::max(K.cap, kStoreStep);
+  while (cap < need) cap *= 2;
+  cap = std::min(cap, kStoreMax);
+  const size_t u = (size_t)K.used, n = (size_t)cap;
+  const Grow g[] = {{(void**)&K.st.desc, 8 * u * sizeof(unsigned int), 8 * n * sizeof(unsigned int)},
+                    {(void**)&K.st.xw, 3 * u * sizeof(float), 3 * n * sizeof(float)},
+                    {(void**)&K.st.nw, 3 * u * sizeof(float), 3 * n * sizeof(float)},
+                    {(void**)&K.st.xy, 2 * u * sizeof(int), 2 * n * sizeof(int)},
+                    {(void**)&K.back, 0, n * sizeof(int)}};
+  int rc = regrow(c, g);
+  if (rc) return rc;
+  K.cap = cap;
+  return RPE_OK;
+}
+// `rows` rows of RPE_MAX_KEYPOINTS ints in each of d1 / idx / d2 (nothing in them outlives a call that asks for more)
+int ensure_rows(rpe_context* c, int rows) {
+  auto& K = c->kf;
+  if (rows <= K.rows_cap) return RPE_OK;
+  int cap = std::max(K.rows_cap, 8);
+  while (cap < rows) cap *= 2;
+  cap = std::min(cap, rpe::kMaxKeyframes);
+  const size_t bytes = (size_t)cap * rpe::kMaxKeypoints * sizeof(int);
+  const Grow g[] = {{(void**)&K.d1, 0, bytes}, {(void**)&K.idx, 0, bytes}, {(void**)&K.d2, 0, bytes}};
+  int rc = regrow(c, g);
+  if (rc) return rc;
+  K.rows_cap = cap;
+  return RPE_OK;
+}
+int new_keyframe(rpe_context* c, int count, const double* pose12, int width, int height, int* id) {
+  auto& K = c->kf;
+  rpe_context::Keyframes::Meta m;
+  m.off = (int)K.used; m.count = count; m.width = width; m.height = height;
+  std::memcpy(m.pose, pose12, sizeof(m.pose));
+  K.meta.push_back(m);
+  K.used += count;
+  const int k = (int)K.meta.size(), end = (int)K.used;
+  if (k == 1) { const int zero = 0; HIP_TRY(hipMemcpyAsync(K.st.off, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream)); }
+  HIP_TRY(hipMemcpyAsync(K.st.off + k, &end, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));      // `end` and the caller's arrays are the host's again
+  if (id) *id = k - 1;
+  return RPE_OK;
+}
+int store_ready(rpe_context* c, const char* who) {
+  if (c->kf.meta.empty()) return fail(RPE_ERR_STATE, "%s: the keyframe store is empty (rpe_keyframe_add)", who);
+  if (!c->fe.feat[RPE_FEAT_FRAME].have) return fail(RPE_ERR_STATE, "%s: no features of the frame (rpe_features_detect)", who);
+  return RPE_OK;
+}
+int ensure_lists(rpe_context* c) {
+  auto& L = c->fe.mlist;
+  for (int** p : {&L.d1, &L.idx, &L.d2, &L.back, &L.mf, &L.mm, &L.md1, &L.md2}) if (!*p) HIP_TRY(hipMalloc((void**)p, rpe::kMaxKeypoints * sizeof(int)));
+  if (!L.mw) HIP_TRY(hipMalloc((void**)&L.mw, rpe::kMaxKeypoints * sizeof(float)));
+  return RPE_OK;
+}
+// several ints a kernel left in device memory, through the pinned words every count of the front end takes: one host wait
+int read_ints(rpe_context* c, const int* d_words, int n, int* out) {
+  const unsigned long long seq = ++c->vote_seq;
+  HIP_TRY(rpe::launch_publish_i32(d_words, n, c->h_votes, c->h_flag2, seq, c->stream));
+  int rc = wait_flag(c, c->h_flag2, seq);
+  if (rc) return rc;
+  std::memcpy(out, c->h_votes, (size_t)n * sizeof(int));
+  return RPE_OK;
+}
+// the frame's keypoints against every keyframe: row k of d1 / idx / d2 = keyframe k's, counts | order in K.rank and on the host
+int query(rpe_context* c, const rpe_match_options& o, int* counts, int* order) {
+  auto& K = c->kf;
+  const auto& A = c->fe.feat[RPE_FEAT_FRAME];
+  const int n = (int)K.meta.size();
+  int rc;
+  if ((rc = ensure_rows(c, n))) return rc;
+  HIP_TRY(hipMemsetAsync(K.rank, 0, (size_t)n * sizeof(int), c->stream));
+  // the cross-check first: every keypoint of the store against the frame's list, one launch
+  if (o.cross_check)
+    HIP_TRY(rpe::launch_keyframe_best(K.st.desc, (int)K.used, A.desc, nullptr, 0, 1, 0, A.count, rpe::KeyframeAccept{0, 1, 1, nullptr}, nullptr,
+                                      K.back, nullptr, nullptr, c->stream));
+  const rpe::KeyframeAccept acc{o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? K.back : nullptr};
+  HIP_TRY(rpe::launch_keyframe_best(A.desc, A.count, K.st.desc, K.st.off, 0, n, 0, 0, acc, K.d1, K.idx, K.d2, K.rank, c->stream));
+  HIP_TRY(rpe::launch_keyframe_rank(K.rank, n, K.rank + n, c->stream));            // the order directly behind the n counts
+  int host[2 * rpe::kMaxKeyframes];
+  if ((rc = read_ints(c, K.rank, 2 * n, host))) return rc;
+  std::memcpy(counts, host, (size_t)n * sizeof(int));
+  std::memcpy(order, host + n, (size_t)n * sizeof(int));
+  return RPE_OK;
+}
+// keyframe `id` in the model's place, from row `row` of d1 / idx / d2 (and K.back behind a cross-check): the accepted list in
+// frame-keypoint order, the problem declared, the five slots filled
+int match_from_row(rpe_context* c, int id, int row, const rpe_match_options& o, int* matches) {
+  auto& F = c->fe;
+  auto& K = c->kf;
+  const auto& A = F.feat[RPE_FEAT_FRAME];
+  const auto& M = K.meta[id];
+  int rc;
+  if ((rc = ensure_lists(c))) return rc;
+  rpe::MatchLists L = F.mlist;
+  const size_t r = (size_t)row * A.count;
+  L.d1 = K.d1 + r; L.idx = K.idx + r; L.d2 = K.d2 + r; L.back = K.back + M.off;
+  F.matches = -1;
+  HIP_TRY(rpe::launch_feature_accept(L, A.count, o.max_dist, o.ratio_num, o.ratio_den, o.cross_check, F.fwork.ctl, c->stream));
+  int m = 0;
+  if ((rc = read_ints(c, F.fwork.ctl + rpe::kFeatCtlMatches, 1, &m))) return rc;
+  if (m > 0) {
+    if ((rc = claim_slots(c, m))) return rc;
+    HIP_TRY(rpe::launch_keyframe_gather(L.mf, L.mm, m, A.pix, F.fmap[0], F.fmap[1], F.fmap[2], K.st, M.off, (float*)c->arr[RPE_XW],
+                                        (float*)c->arr[RPE_XC], (float*)c->arr[RPE_BV], (float*)c->arr[RPE_NW], (float*)c->arr[RPE_NC], c->stream));
+  } else if ((rc = rpe_set_problem(c, 0, RPE_F32))) return rc;
+  F.matches = m; F.match_gen[0] = A.gen; F.match_kf = id;
+  if (matches) *matches = m;
+  return RPE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rpe_keyframe_add(rpe_context* c, int* id) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  auto& F = c->fe;
+  const auto& S = F.feat[RPE_FEAT_MODEL];
+  if (!F.have_model || !S.have) return fail(RPE_ERR_STATE, "rpe_keyframe_add: no features of the model (rpe_features_detect with RPE_FEAT_MODEL)");
+  if ((int)c->kf.meta.size() >= RPE_MAX_KEYFRAMES) return fail(RPE_ERR_STATE, "rpe_keyframe_add: the store is full (%d keyframes)", RPE_MAX_KEYFRAMES);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_store(c, S.count))) return rc;
+  HIP_TRY(rpe::launch_keyframe_snapshot(S.count, S.pix, S.xy, S.desc, F.mmap[0], F.mmap[1], c->kf.st, (int)c->kf.used, c->stream));
+  return new_keyframe(c, S.count, F.mpose, F.mcam.width, F.mcam.height, id);
+}
+
+int rpe_keyframe_add_host(rpe_context* c, int count, const int32_t* xy, const uint32_t* desc, const float* xw, const float* nw,
+                          const double* pose12, int width, int height, int* id) {
+  session_end(c);
+  if (!c || !pose12 || count < 0 || count > RPE_MAX_KEYPOINTS || width < 1 || height < 1 || (count > 0 && (!xy || !desc || !xw || !nw)))
+    return fail(RPE_ERR_ARG, "rpe_keyframe_add_host: bad argument (count 0 .. %d, width, height >= 1, pose12 and the four arrays not NULL)",
+                RPE_MAX_KEYPOINTS);
+  for (int k = 0; k < count; k++)
+    if (xy[2 * k] < 0 || xy[2 * k] >= width || xy[2 * k + 1] < 0 || xy[2 * k + 1] >= height)
+      return fail(RPE_ERR_ARG, "rpe_keyframe_add_host: keypoint %d at (%d, %d) is outside the %d x %d image", k, xy[2 * k], xy[2 * k + 1], width, height);
+  if ((int)c->kf.meta.size() >= RPE_MAX_KEYFRAMES) return fail(RPE_ERR_STATE, "rpe_keyframe_add_host: the store is full (%d keyframes)", RPE_MAX_KEYFRAMES);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_store(c, count))) return rc;
+  auto& K = c->kf;
+  const size_t o = (size_t)K.used, n = (size_t)count;
+  if (n) {
+    HIP_TRY(hipMemcpyAsync(K.st.desc + 8 * o, desc, 8 * n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(K.st.xw + 3 * o, xw, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(K.st.nw + 3 * o, nw, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(K.st.xy + 2 * o, xy, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  return new_keyframe(c, count, pose12, width, height, id);
+}
+
+int rpe_keyframe_info(rpe_context* c, int id, int* count, double* pose12, int* width, int* height) {
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  if (id < 0 || id >= (int)c->kf.meta.size()) return fail(RPE_ERR_ARG, "rpe_keyframe_info: no keyframe %d (%d in the store)", id, (int)c->kf.meta.size());
+  const auto& M = c->kf.meta[id];
+  if (count) *count = M.count;
+  if (pose12) std::memcpy(pose12, M.pose, sizeof(M.pose));
+  if (width) *width = M.width;
+  if (height) *height = M.height;
+  return RPE_OK;
+}
+
+int rpe_keyframe_download(rpe_context* c, int id, int32_t* xy, uint32_t* desc, float* xw, float* nw) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  if (id < 0 || id >= (int)c->kf.meta.size()) return fail(RPE_ERR_ARG, "rpe_keyframe_download: no keyframe %d (%d in the store)", id, (int)c->kf.meta.size());
+  HIP_TRY(hipSetDevice(c->device));
+  const auto& K = c->kf;
+  const size_t o = (size_t)K.meta[id].off, n = (size_t)K.meta[id].count;
+  int rc;
+  if (n && xy && (rc = copy_to_host(c, xy, K.st.xy + 2 * o, 2 * n * sizeof(int)))) return rc;
+  if (n && desc && (rc = copy_to_host(c, desc, K.st.desc + 8 * o, 8 * n * sizeof(unsigned int)))) return rc;
+  if (n && xw && (rc = copy_to_host(c, xw, K.st.xw + 3 * o, 3 * n * sizeof(float)))) return rc;
+  if (n && nw && (rc = copy_to_host(c, nw, K.st.nw + 3 * o, 3 * n * sizeof(float)))) return rc;
+  return RPE_OK;
+}
+
+int rpe_keyframes_count(rpe_context* c, int* count) {
+  if (!c || !count) return fail(RPE_ERR_ARG, "rpe_keyframes_count: bad argument");
+  *count = (int)c->kf.meta.size();
+  return RPE_OK;
+}
+
+int rpe_keyframes_clear(rpe_context* c) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->kf.meta.clear();
+  c->kf.used = 0;                                  // the storage stays, for the next map
+  if (c->fe.match_kf >= 0) { c->fe.matches = -1; c->fe.match_kf = -1; }
+  return RPE_OK;
+}
+
+int rpe_keyframes_query(rpe_context* c, const rpe_match_options* mopt, int* counts, int* order) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  const rpe_match_options o = mopt ? *mopt : kMatchDefaults;
+  int rc = match_options(&o);
+  if (rc || (rc = store_ready(c, "rpe_keyframes_query"))) return rc;   // an empty store has no K ints to ask room for: the state first
+  if (!counts || !order) return fail(RPE_ERR_ARG, "rpe_keyframes_query: counts and order must not be NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  return query(c, o, counts, order);
+}
+
+int rpe_keyframe_match(rpe_context* c, int id, const rpe_match_options* mopt, int* matches) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  const rpe_match_options o = mopt ? *mopt : kMatchDefaults;
+  int rc = match_options(&o);
+  if (rc || (rc = store_ready(c, "rpe_keyframe_match"))) return rc;
+  auto& K = c->kf;
+  if (id < 0 || id >= (int)K.meta.size()) return fail(RPE_ERR_ARG, "rpe_keyframe_match: no keyframe %d (%d in the store)", id, (int)K.meta.size());
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = ensure_rows(c, 1))) return rc;
+  const auto& A = c->fe.feat[RPE_FEAT_FRAME];
+  const auto& M = K.meta[id];
+  c->fe.matches = -1;
+  HIP_TRY(rpe::launch_keyframe_best(A.desc, A.count, K.st.desc, K.st.off, id, 1, 0, 0, rpe::KeyframeAccept{0, 1, 1, nullptr}, K.d1, K.idx, K.d2,
+                                    nullptr, c->stream));
+  if (o.cross_check)
+    HIP_TRY(rpe::launch_keyframe_best(K.st.desc + 8 * (size_t)M.off, M.count, A.desc, nullptr, 0, 1, 0, A.count, rpe::KeyframeAccept{0, 1, 1, nullptr},
+                                      nullptr, K.back + M.off, nullptr, nullptr, c->stream));
+  return match_from_row(c, id, 0, o, matches);
+}
+
+int rpe_relocalize_keyframes(rpe_context* c, const rpe_feature_options* fopt, const rpe_match_options* mopt, int candidates, int method,
+                             double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence, uint64_t seed, int ls,
+                             int min_matches, double* pose12, int* keyframe, int* matches, int* max_votes, short* mask_out) {
+  session_end(c);
+  if (!c || !pose12 || !iter_io || method < 0 || method > 9 || candidates < 1)
+    return fail(RPE_ERR_ARG, "rpe_relocalize_keyframes: bad argument (method 0 .. 9, candidates >= 1, pose12 and iter_io not NULL)");
+  if (min_matches < 4 || min_matches > RPE_MAX_KEYPOINTS) return fail(RPE_ERR_ARG, "rpe_relocalize_keyframes: min_matches 4 .. %d (got %d)",
+                                                                     RPE_MAX_KEYPOINTS, min_matches);
+  const rpe_feature_options fo = fopt ? *fopt : rpe_feature_options{12, RPE_MAX_KEYPOINTS};
+  const rpe_match_options mo = mopt ? *mopt : kMatchDefaults;
+  int rc = match_options(&mo);
+  if (rc) return rc;
+  if (fo.threshold < 1 || fo.threshold > 255 || fo.max_keypoints < 1 || fo.max_keypoints > RPE_MAX_KEYPOINTS)
+    return fail(RPE_ERR_ARG, "feature options: threshold 1 .. 255 (got %d), max_keypoints 1 .. %d (got %d)", fo.threshold, RPE_MAX_KEYPOINTS,
+                fo.max_keypoints);
+  auto& K = c->kf;
+  if (K.meta.empty()) return fail(RPE_ERR_STATE, "rpe_relocalize_keyframes: the keyframe store is empty (rpe_keyframe_add)");
+  {
+    const auto& S = c->fe.feat[RPE_FEAT_FRAME];
+    if (!(S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints) &&
+        (rc = rpe_features_detect(c, RPE_FEAT_FRAME, &fo, nullptr))) return rc;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const int n = (int)K.meta.size();
+  std::vector<int> counts(n), order(n);
+  c->fe.matches = -1;
+  if ((rc = query(c, mo, counts.data(), order.data()))) return rc;
+  if (keyframe) *keyframe = order[0];
+  if (matches) *matches = counts[order[0]];
+  if (counts[order[0]] < min_matches)
+    return fail(RPE_ERR_DEGENERATE, "rpe_relocalize_keyframes: the best keyframe (%d) has %d matches, %d needed (%d keyframes)", order[0],
+                counts[order[0]], min_matches, n);
+  const int iter_in = *iter_io;
+  int win = -1, win_votes = -1, win_iter = iter_in, win_m = 0, last = -1;
+  double win_pose[12];
+  std::vector<short> win_mask, mask;
+  std::vector<float> host;
+  for (int r = 0; r < n && r < candidates && counts[order[r]] >= min_matches; r++) {
+    const int id = order[r];
+    int m = 0;
+    if ((rc = match_from_row(c, id, id, mo, &m))) return rc;
+    last = id;
+    // rpe_relocalize's own run: the downloaded arrays through rpe_run, the match quality as weight of every modality
+    const size_t n3 = (size_t)m * 3;
+    host.resize(5 * n3 + n3);
+    float* a[RPE_NUM_ARRAYS];
+    for (int s = 0; s < RPE_NUM_ARRAYS; s++) {
+      a[s] = host.data() + s * n3;
+      if ((rc = copy_to_host(c, a[s], c->arr[s], n3 * sizeof(float)))) return rc;
+    }
+    float* wq = host.data() + 5 * n3;
+    if ((rc = copy_to_host(c, wq, c->fe.mlist.mw, (size_t)m * sizeof(float)))) return rc;
+    for (int k = 1; k < 3; k++) std::memcpy(wq + (size_t)k * m, wq, (size_t)m * sizeof(float));
+    rpe_problem p{};
+    p.n = m; p.dtype = RPE_F32;
+    p.xw = a[RPE_XW]; p.xc = a[RPE_XC]; p.bv = a[RPE_BV]; p.nw = a[RPE_NW]; p.nc = a[RPE_NC];
+    p.weights = wq; p.wcols = 3;
+    p.fx = c->fe.kcam[0].fx; p.fy = c->fe.kcam[0].fy;
+    double R9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t3[3] = {0, 0, 0};
+    int it = iter_in, votes = 0;
+    mask.assign(n3, 0);
+    rc = rpe_run(method, &p, thre_3d, thre_2d, thre_nl, &it, confidence, seed, ls, RPE_SCORE_EXACT, nullptr, R9, t3, &votes, mask.data());
+    if (rc == RPE_ERR_DEGENERATE) continue;        // refused as rank-deficient: the next candidate
+    if (rc) return rc;
+    if (votes > win_votes) {                       // a tie stays with the better rank
+      win = id; win_votes = votes; win_iter = it; win_m = m;
+      for (int i = 0; i < 9; i++) win_pose[i] = R9[i];
+      for (int i = 0; i < 3; i++) win_pose[9 + i] = t3[i];
+      win_mask.swap(mask);
+    }
+  }
+  if (win < 0) return fail(RPE_ERR_DEGENERATE, "rpe_relocalize_keyframes: every candidate's matches were refused as rank-deficient");
+  if (last != win && (rc = match_from_row(c, win, win, mo, nullptr))) return rc;   // slots and match list are the winner's
+  std::memcpy(pose12, win_pose, sizeof(win_pose));
+  *iter_io = win_iter;
+  if (keyframe) *keyframe = win;
+  if (matches) *matches = win_m;
+  if (max_votes) *max_votes = win_votes;
+  if (mask_out) std::memcpy(mask_out, win_mask.data(), win_mask.size() * sizeof(short));
+  return RPE_OK;
+}
+
+}  // extern "C"

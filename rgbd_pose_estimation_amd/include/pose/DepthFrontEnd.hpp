@@ -24,6 +24,9 @@
 // and the RANSAC / PROSAC solvers make the pose that ICP then refines
 //   rpe::RelocResult r = fe.relocalize(6 /* shinji_kneip_prosac */, 0.05, 3.0, 0.1);
 //   if (r.ok) { T = r.pose;  fe.preparePhoto(3);  fe.icpPyramidRgbd(T, 0.01, {6, 4, 3}); }
+// ... against ALL the keyframes it has kept, without knowing which one the camera sees (the store lives in the context)
+//   at every keyframe: fe.setModelFromFrame(T);  fe.modelColorFromFrame();  fe.detectFeatures(RPE_FEAT_MODEL);  fe.addKeyframe();
+//   when lost:         rpe::KeyframeRelocResult r = fe.relocalizeKeyframes(6, 0.05, 3.0, 0.1);   // r.keyframe = the one it chose
 //
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
@@ -81,6 +84,10 @@ struct RelocResult {
   int matches = 0, iterations = 0, votes = 0;
   std::vector<short> masks;
 };
+// relocalizeKeyframes(): RelocResult against the winning keyframe of the store; ok = false: keyframe / matches are the best-ranked one's
+struct KeyframeRelocResult : RelocResult { int keyframe = -1; };
+// queryKeyframes(): per keyframe the matches the frame would have against it, and the ids by (count descending, id ascending)
+struct KeyframeRanking { std::vector<int> counts, order; };
 
 class DepthFrontEnd {
  public:
@@ -317,6 +324,54 @@ class DepthFrontEnd {
     const int rc = rpe_relocalize(_ctx, &fo, &mo, method, thre_3d, thre_2d, thre_nl, &r.iterations, confidence, seed, ls, min_matches, p,
                                   &r.matches, &r.votes, r.masks.data());
     if (rc != RPE_ERR_DEGENERATE) check(rc, "rpe_relocalize");
+    r.ok = rc == RPE_OK;
+    r.masks.resize(r.ok ? (size_t)3 * r.matches : 0);
+    if (r.ok) r.pose = pose_of(p);
+    return r;
+  }
+  // the model side's current features (detectFeatures(RPE_FEAT_MODEL)) become a keyframe of the context's store; returns its id.  The
+  // store survives new frames and models; clearKeyframes empties it (one keyframe cannot be removed)
+  int addKeyframe() {
+    int id = -1;
+    check(rpe_keyframe_add(_ctx, &id), "rpe_keyframe_add");
+    return id;
+  }
+  int keyframes() const {
+    int n = 0;
+    check(rpe_keyframes_count(_ctx, &n), "rpe_keyframes_count");
+    return n;
+  }
+  void clearKeyframes() { check(rpe_keyframes_clear(_ctx), "rpe_keyframes_clear"); }
+  // the frame's keypoints against every keyframe at once (needs detectFeatures(RPE_FEAT_FRAME) and a non-empty store)
+  KeyframeRanking queryKeyframes(const MatchOptions& o = MatchOptions()) {
+    const rpe_match_options mo = {o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? 1 : 0};
+    KeyframeRanking r;
+    r.counts.assign((size_t)keyframes(), 0);
+    r.order.assign(r.counts.size(), 0);
+    check(rpe_keyframes_query(_ctx, &mo, r.counts.data(), r.order.data()), "rpe_keyframes_query");
+    return r;
+  }
+  // matchFeatures with keyframe `id` in the model's place
+  int matchKeyframe(int id, const MatchOptions& o = MatchOptions()) {
+    const rpe_match_options mo = {o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? 1 : 0};
+    int m = 0;
+    check(rpe_keyframe_match(_ctx, id, &mo, &m), "rpe_keyframe_match");
+    return m;
+  }
+  // relocalize against the store: the query, then relocalize's solver run on each of the `candidates` best-ranked keyframes with at
+  // least min_matches matches; the one with the most votes wins.  No keyframe with enough matches is a result (ok = false)
+  KeyframeRelocResult relocalizeKeyframes(int method, double thre_3d, double thre_2d, double thre_nl, int candidates = 3, int max_iter = 200,
+                                          double confidence = 0.99, uint64_t seed = 1, int ls = 0, int min_matches = 12,
+                                          const FeatureOptions& f = FeatureOptions(), const MatchOptions& m = MatchOptions()) {
+    const rpe_feature_options fo = {f.threshold, f.max_keypoints};
+    const rpe_match_options mo = {m.max_dist, m.ratio_num, m.ratio_den, m.cross_check ? 1 : 0};
+    KeyframeRelocResult r;
+    r.iterations = max_iter;
+    r.masks.assign((size_t)3 * RPE_MAX_KEYPOINTS, 0);
+    double p[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    const int rc = rpe_relocalize_keyframes(_ctx, &fo, &mo, candidates, method, thre_3d, thre_2d, thre_nl, &r.iterations, confidence, seed, ls,
+                                            min_matches, p, &r.keyframe, &r.matches, &r.votes, r.masks.data());
+    if (rc != RPE_ERR_DEGENERATE) check(rc, "rpe_relocalize_keyframes");
     r.ok = rc == RPE_OK;
     r.masks.resize(r.ok ? (size_t)3 * r.matches : 0);
     if (r.ok) r.pose = pose_of(p);

@@ -1,0 +1,215 @@
+"""CPU: the numpy statement of the keyframe store (tests/keyframe_oracle.py) against tests/feature_oracle.py and against itself -- the
+figures of tests/keyframe_cases.py recomputed, the rules of the ranking, relocalisation against eight keyframes end to end in the
+oracles -- and the cross-compiled library: exports, header, ISA resources of the new kernels, the C++ driver compiles."""
+import os
+import subprocess
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+import feature_cases as FC
+import feature_oracle as FE
+import isa_tools as T
+import keyframe_cases as KC
+import keyframe_oracle as KO
+import photo_cases as PC
+import volume_cases as VC
+from rgbd_pose_estimation_amd import _lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
+SYMS = {"rpe_keyframe_add", "rpe_keyframe_add_host", "rpe_keyframe_info", "rpe_keyframe_download", "rpe_keyframes_count",
+        "rpe_keyframes_clear", "rpe_keyframes_query", "rpe_keyframe_match", "rpe_relocalize_keyframes"}
+QUERIES = range(len(KC.KF_MOTIONS))
+
+
+# ---------------------------------------------------------------------------------------------- properties of the statement
+def test_a_keyframe_is_the_model_detection_with_its_world_points():
+    r = KC.room("small")
+    for s, k in zip(r.shots, r.keyframes):
+        xy, _, desc = FE.detect(s.rgba, s.MV, s.MN)
+        pix = xy[:, 1].astype(np.int64) * s.w + xy[:, 0]
+        assert np.array_equal(k["xy"], xy) and np.array_equal(k["desc"], desc)
+        assert np.array_equal(k["xw"], s.MV[pix]) and np.array_equal(k["nw"], s.MN[pix]) and np.isfinite(k["xw"]).all()
+        assert k["xw"].dtype == k["nw"].dtype == np.float32
+
+
+def test_a_store_of_one_keyframe_is_feature_match():
+    r = KC.room("small")
+    q = r.queries[0]
+    xy, desc = q.features()
+    for mopt in (KO.MOPT, (64, 8, 10, True), (256, 2, 1, False)):
+        for s, k in list(zip(r.shots, r.keyframes))[:3]:
+            fi, mi, d1, d2 = FE.match(desc, k["desc"], *mopt)
+            counts, order = KO.query(desc, [k], mopt)
+            assert counts.tolist() == [len(fi)] and order.tolist() == [0]
+            m = KO.match(xy, desc, q.V, q.N, q.B, q.w, k, mopt)
+            assert np.array_equal(m["fi"], fi) and np.array_equal(m["mi"], mi) and np.array_equal(m["d1"], d1) and np.array_equal(m["d2"], d2)
+            # the slots are feature_oracle.slots' with the keyframe's view as the model
+            XW, XC, BV, NW, NC, w = FE.slots(xy, k["xy"], fi, mi, d1, q.V, q.N, q.B, s.MV, s.MN, q.w, s.w)
+            for a, b in ((m["XW"], XW), (m["XC"], XC), (m["BV"], BV), (m["NW"], NW), (m["NC"], NC), (m["w"], w)):
+                assert np.array_equal(a, b, equal_nan=True)
+
+
+def test_permuting_the_store_permutes_the_counts_and_ties_follow_ids():
+    r = KC.room("small")
+    _, desc = r.queries[3].features()
+    counts, order = KO.query(desc, r.keyframes)
+    perm = [5, 2, 7, 0, 3, 6, 1, 4]
+    pc, po = KO.query(desc, [r.keyframes[i] for i in perm])
+    assert pc.tolist() == [counts[i] for i in perm]
+    assert [perm[i] for i in po] == order.tolist()                 # no two counts are equal here: the same keyframes in the same order
+    assert len(set(counts.tolist())) == len(counts)
+    # equal counts: the same keyframe twice -- the lower id first, wherever the pair stands
+    twice = [r.keyframes[1], r.keyframes[3], r.keyframes[1], r.keyframes[0], r.keyframes[3]]
+    tc, to = KO.query(desc, twice)
+    assert tc[0] == tc[2] and tc[1] == tc[4]
+    assert to.tolist().index(0) + 1 == to.tolist().index(2) and to.tolist().index(1) + 1 == to.tolist().index(4)
+    assert sorted(to.tolist()) == list(range(5)) and (np.diff(tc[to]) <= 0).all()
+
+
+def test_empty_and_single_keypoint_keyframes():
+    r = KC.room("small")
+    _, desc = r.queries[0].features()
+    k = r.keyframes[0]
+    empty = dict(xy=k["xy"][:0], desc=k["desc"][:0], xw=k["xw"][:0], nw=k["nw"][:0])
+    one = dict(xy=k["xy"][:1], desc=k["desc"][:1], xw=k["xw"][:1], nw=k["nw"][:1])
+    counts, order = KO.query(desc, [empty, one, k], (256, 8, 10, False))
+    assert counts[0] == 0 and counts[1] == len(desc) and order.tolist() == [1, 2, 0]      # d2 = 257: every keypoint passes the ratio
+    assert KO.query(desc[:0], [empty, one, k])[0].tolist() == [0, 0, 0] and KO.query(desc[:0], [empty, one, k])[1].tolist() == [0, 1, 2]
+
+
+def test_the_walk():
+    runs = []
+
+    def run(i):
+        runs.append(i)
+        return {0: (5, "a"), 1: (9, "b"), 2: (9, "c"), 3: None}.get(i)
+
+    counts, order = np.array([30, 40, 20, 50]), np.array([3, 1, 0, 2])
+    assert KO.walk(counts, order, 3, 12, run) == (1, "b") and runs == [3, 1, 0]            # 3 is refused and skipped
+    del runs[:]
+    assert KO.walk(counts, order, 4, 12, run) == (1, "b") and runs == [3, 1, 0, 2]         # votes tie: the better rank stays
+    del runs[:]
+    assert KO.walk(counts, order, 4, 35, run) == (1, "b") and runs == [3, 1]               # 30 < 35 ends the walk
+    assert KO.walk(counts, order, 1, 12, run) == (3, None) and KO.walk(counts, order, 3, 51, run) == (3, None)
+
+
+# ---------------------------------------------------------------------------------------------- the figures of keyframe_cases.py
+@pytest.mark.parametrize("cam", ["small", "half"])
+def test_room_figures_and_the_end_to_end_claim(oracle, cam):
+    """every one of the eight queries, at both cameras: the counts rank an overlapping keyframe first, the walk over three candidates
+    relocalises within RELOC_BOUND (5 mrad / 15 mm: the issue's bound, stated for SMALL_CAM and held at both sizes), and oracle RGB-D
+    ICP from there ends (a) within KC.TRACK_MARGIN x where the same ICP ends on the same pair from the TRUE pose -- the tracker's own
+    figure for that pair: the relocalised start costs it nothing it would not lose anyway -- and (b) within KC.TRACK_ORDER[cam] x
+    photo_cases.PAIR_ROOM_RGBD, "the order of a tracked pair" (keyframe_cases.py says where the two factors come from)"""
+    r = KC.room(cam)
+    fig = KC.FIGURES[cam]
+    assert tuple(len(k["xy"]) for k in r.keyframes) == fig["keypoints"]
+    for i in QUERIES:
+        q = r.queries[i]
+        o = KC.oracle_relocalise(oracle, q, r.keyframes)
+        f = fig["queries"][i]
+        e = VC.pose_error(o["pose12"], q.pose)
+        k = r.shots[o["keyframe"]]
+        pair = SimpleNamespace(cam=q.cam, pa=k.pose, pb=q.pose, da=k.depth, db=q.depth, ca=k.rgb, cb=q.rgb)
+        after = VC.pose_error(FC.oracle_track(oracle, pair, o["pose12"]), q.pose)
+        floor = VC.pose_error(FC.oracle_track(oracle, pair, q.pose), q.pose)
+        ok = KC.correct(q, q.match(r.keyframes[int(o["order"][0])]))
+        print(cam, i, o["counts"].tolist(), "keyframe", o["keyframe"], "votes", o["votes"], "iters", o["iters"], "reloc", e, "icp", after,
+              "icp from the truth", floor, "correct", ok.mean())
+        assert o["counts"].tolist() == f["counts"] and o["order"].tolist() == sorted(QUERIES, key=lambda j: (-f["counts"][j], j))
+        assert (o["keyframe"], o["votes"], o["iters"]) == (f["keyframe"], f["votes"], f["iters"])
+        assert all(abs(g - w) <= 0.05 * w for g, w in zip(e + after, f["reloc"] + f["icp"]))
+        assert e[0] < KC.RELOC_BOUND[0] and e[1] < KC.RELOC_BOUND[1]
+        assert o["keyframe"] in o["order"][:KC.CANDIDATES].tolist() and ok.mean() > 0.8
+        assert after[0] <= KC.TRACK_MARGIN * floor[0] and after[1] <= KC.TRACK_MARGIN * floor[1]
+        assert after[0] < KC.TRACK_ORDER[cam] * PC.PAIR_ROOM_RGBD[0] and after[1] < KC.TRACK_ORDER[cam] * PC.PAIR_ROOM_RGBD[1]
+
+
+def test_second_candidate_can_be_the_closer_one(oracle):
+    """query 6 at SMALL_CAM: the second-ranked keyframe alone lands closer than the first -- why the entry takes candidates"""
+    r = KC.room("small")
+    q = r.queries[6]
+    one = KC.oracle_relocalise(oracle, q, r.keyframes, candidates=1)
+    order = one["order"].tolist()
+    second = KC.oracle_relocalise(oracle, q, [r.keyframes[order[1]]], candidates=1)
+    e1, e2 = VC.pose_error(one["pose12"], q.pose), VC.pose_error(second["pose12"], q.pose)
+    print("first", order[0], e1, "second", order[1], e2)
+    assert order[:2] == [4, 6] and e2[0] < e1[0] and e2[1] < e1[1]
+
+
+def test_other_case_figures(oracle):
+    kfs = [k for _, k in KC.two_camera_store()]
+    assert [len(k["xy"]) for k in kfs] == [KC.FIGURES["small" if i % 2 == 0 else "half"]["keypoints"][i] for i in QUERIES]
+    for (cam, i), f in KC.TWO_CAMERA.items():
+        q = KC.room(cam).queries[i]
+        o = KC.oracle_relocalise(oracle, q, kfs)
+        assert o["counts"].tolist() == f["counts"] and (o["keyframe"], o["votes"], o["iters"]) == (f["keyframe"], f["votes"], f["iters"])
+        e = VC.pose_error(o["pose12"], q.pose)
+        assert e[0] < KC.RELOC_BOUND[0] and e[1] < KC.RELOC_BOUND[1]
+    shots, tk, q = KC.tiled_store()
+    xy, desc = q.features()
+    assert (len(xy), tuple(len(k["xy"]) for k in tk)) == KC.TILED["keypoints"]
+    counts, order = KO.query(desc, tk, (256, 2, 1, False))
+    assert counts.tolist() == KC.TILED["counts"] and order.tolist() == KC.TILED["order"]
+    m = q.match(tk[0], (256, 2, 1, False))
+    assert int((m["d1"] == m["d2"]).sum()) == KC.TILED["ties"]
+    counts, order = KO.query(desc, tk, (256, 2, 1, True))
+    assert counts.tolist() == KC.TILED["cross_counts"] and order.tolist() == KC.TILED["cross_order"]
+    r = KC.room("small")
+    assert KO.query(r.queries[0].features()[1], r.keyframes, (64, 8, 10, True))[0].tolist() == KC.CROSS_SMALL_0
+
+
+def test_flat_frame_is_degenerate(oracle):
+    f = KC.flat_query()
+    assert len(f.features()[0]) == 0
+    o = KC.oracle_relocalise(oracle, f, KC.room("small").keyframes)
+    assert o["counts"].tolist() == [0] * 8 and o["order"].tolist() == list(QUERIES) and o["pose12"] is None and o["keyframe"] == 0
+
+
+# ---------------------------------------------------------------------------------------------- the cross-compiled library
+def _built():
+    from rgbd_pose_estimation_amd import build as B
+    return B.build()
+
+
+def test_header_and_library_export_the_keyframe_entry_points():
+    lib = _built()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
+    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    assert SYMS <= exported, sorted(SYMS - exported)
+    assert SYMS <= set(L.SYMBOLS)
+    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
+    for s in SYMS:
+        assert f"int {s}(" in hdr
+    assert "RPE_MAX_KEYFRAMES = 256" in hdr and L.MAX_KEYFRAMES == KO.MAX_KEYFRAMES == 256
+    assert "no keyframe store yet" not in hdr and "Removing ONE keyframe is out of scope" in hdr
+    assert L.lib().rpe_abi_version() == 1
+
+
+def test_keyframe_kernels_do_not_spill():
+    _built()
+    rows = T.kernel_resources(os.path.join(LIB, "rpe_keyframe.o"))
+    names = sorted(r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows)
+    assert names == ["kf_best", "kf_gather", "kf_rank", "kf_snapshot"], rows
+    assert not [(r["mangled"], r["vgpr_spill"], r["sgpr_spill"]) for r in rows if r["vgpr_spill"] > 0 or r["sgpr_spill"] > 0]
+    assert not [(r["mangled"], r["scratch"]) for r in rows if r["scratch"] > 0]
+    assert all(r["vgpr"] + r["agpr"] <= 128 for r in rows)
+    assert max(r["lds"] for r in rows) <= 16 * 1024
+
+
+def test_keyframe_host_unit_has_no_device_code():
+    _built()
+    assert T.kernel_resources(os.path.join(LIB, "rpe_keyframe_api.o")) == []
+    assert os.path.getsize(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_keyframe_api.hip")) < 40 * 1024
+    assert os.path.getsize(os.path.join(LIB, "librgbdpose_hip.so")) < 10 * 1024 * 1024
+
+
+def test_keyframe_cpp_driver_compiles(tmp_path):
+    lib = _built()
+    inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
+                           os.path.join(ROOT, "tests", "cpp", "keyframe_reloc.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",
+                           "-Wl,-rpath," + os.path.dirname(lib), "-o", str(tmp_path / "keyframe_reloc")])
