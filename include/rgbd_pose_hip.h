@@ -657,6 +657,21 @@ int rpe_icp_pyramid_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double ph
  * S(p + a_i) < S(p + b_i); the 256 offset pairs lie within +-13 (patch plus box stay inside the 16-pixel border) and are
  * csrc/rpe_brief_table.h, generated by scripts/gen_brief_table.py from the project's PCG32 stream by the rule stated there.  Bit i is
  * bit i % 32 of word i / 32; eight uint32 per keypoint.
+ * Oriented descriptor (RPE_DESC_ORIENTED; RPE_DESC_UPRIGHT, the one above, is the default): the same tests on offsets turned into the
+ * patch's own orientation, so that a camera rolled about its axis sees the same bits (tests/oriented_oracle.py states it in numpy).
+ * The detector -- luma, segment test, score, suppression, cap, keypoint order -- is the same for both kinds.  Moments over the disc
+ * D = {(dx, dy): dx^2 + dy^2 <= 169} (529 offsets; a keypoint lies 16 pixels inside, so D is in the image): m10 = sum_D dx Y(p + d),
+ * m01 = sum_D dy Y(p + d), Y the luma above (0 where A = 0); |m| <= 2914 * 255 fits int32.  Angle bin, 32 bins: with
+ * C[k] = round(1024 cos(2 pi k / 32)) = 1024 1004 946 851 724 569 392 200 0 -200 -392 -569 -724 -851 -946 -1004 -1024 -1004 -946
+ * -851 -724 -569 -392 -200 0 200 392 569 724 851 946 1004 and S[k] = C[(k + 24) % 32] (tabulated, never computed on the device),
+ * bin = the k that maximises m10 C[k] + m01 S[k] in int64, a tie going to the lowest k (m10 = m01 = 0 gives bin 0).  Steering: an
+ * offset (x, y) of the table becomes x' = (x C[bin] - y S[bin] + 512) >> 10, y' = (x S[bin] + y C[bin] + 512) >> 10, the shift
+ * arithmetic (floor); bin 0 is the identity, bins 8, 16 and 24 are exact quarter turns; over the table the steered offsets reach
+ * +-17, which with the box's 2 passes the 16-pixel border.  Bit i is S(p + a'_i) < S(p + b'_i) over the same box sums, a sample
+ * position outside the image reading S = 0 (box sums inside the image count outside pixels as 0 already); the packing is unchanged.
+ * An oriented descriptor whose bin is 0 equals the upright descriptor of the same keypoint.  The kind belongs to the context
+ * (rpe_features_set_descriptor) and applies to every later detection on either side, rpe_relocalize*'s own included; descriptors of
+ * the two kinds are never matched against each other.
  * Matching: for frame keypoint q, d1 / d2 = the smallest / second smallest Hamming distance over the model keypoints (the second
  * over all others, so a duplicate gives d2 = d1), the index that of the first smallest; d2 = 257 with one model keypoint; no match
  * without any.  Accepted iff d1 <= max_dist and d1 * ratio_den < d2 * ratio_num (ints; defaults 64 and 8 / 10; max_dist 0 .. 256,
@@ -665,23 +680,31 @@ int rpe_icp_pyramid_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double ph
  * Slots: rpe_features_match declares the problem (n = matches, RPE_F32) and fills, per match, XW / NW = the model vertex / normal at
  * the model keypoint, XC / NC / BV = the frame's vertex / normal / bearing at the frame keypoint.  The match quality 256 - d1 is the
  * float weight of the match (rpe_matches_download): what a PROSAC solver sorts.
- * Scope: no orientation and no scale normalisation.  The model is ONE view; a caller who keeps many adds each to the keyframe store
+ * Scope: no scale normalisation (the detector works at one scale).  The model is ONE view; a caller who keeps many adds each to the keyframe store
  * below ("Keyframes") and relocalises against all of them at once -- nothing is re-uploaded or re-detected. */
 typedef struct { int threshold; int max_keypoints; } rpe_feature_options;                       /* NULL: {12, RPE_MAX_KEYPOINTS} */
 typedef struct { int max_dist; int ratio_num, ratio_den; int cross_check; } rpe_match_options;  /* NULL: {64, 8, 10, 0} */
 enum { RPE_FEAT_FRAME = 0, RPE_FEAT_MODEL = 1, RPE_MAX_KEYPOINTS = 4096 };
+enum { RPE_DESC_UPRIGHT = 0, RPE_DESC_ORIENTED = 1 };
+/* the descriptor kind of every later detection of this context.  A change of kind drops both sides' features and the match list;
+ * setting the current kind again drops nothing.  RPE_ERR_ARG for any other kind */
+int rpe_features_set_descriptor(rpe_context* ctx, int kind);
+int rpe_features_get_descriptor(rpe_context* ctx, int* kind);
 /* detect and describe the keypoints of one side (six launches, one host wait for the count); RPE_ERR_STATE without the side's depth
  * or model and colour, RPE_ERR_ARG for options out of range */
 int rpe_features_detect(rpe_context* ctx, int which, const rpe_feature_options* opt, int* count);
 /* the side's keypoints: xy 2 x count int32 (u, v per keypoint), score count int32, desc 8 x count uint32 (any may be NULL);
  * RPE_ERR_STATE before a detection or after its features were dropped */
 int rpe_features_download(rpe_context* ctx, int which, int32_t* xy, int32_t* score, uint32_t* desc);
+/* the angle bins (0 .. 31) of the side's keypoints, count int32: all 0 for an upright detection; RPE_ERR_STATE as rpe_features_download */
+int rpe_features_angles(rpe_context* ctx, int which, int32_t* bins);
 /* match the frame's keypoints against the model's and fill XW XC BV NW NC (n = matches; 0 matches leave an empty problem);
  * RPE_ERR_STATE unless both sides have features */
 int rpe_features_match(rpe_context* ctx, const rpe_match_options* opt, int* matches);
 /* the last match list: frame / model keypoint ids, d1, d2 and the weight 256 - d1, `matches` values each (any may be NULL) */
 int rpe_matches_download(rpe_context* ctx, int32_t* frame_idx, int32_t* model_idx, int32_t* d1, int32_t* d2, float* weight);
-/* relocalise the frame against the model: detects on each side whose features are missing (or were made with other options), matches,
+/* relocalise the frame against the model: detects on each side whose features are missing (or were made with other options or another
+ * descriptor kind), matches,
  * and runs rpe_run's solver `method` (0 .. 9) with stage `ls` on the matches -- rpe_run itself, on the downloaded arrays, weights =
  * the match quality for every modality, focal lengths of the frame's camera, RPE_SCORE_EXACT, the stream of `seed`.  iter_io,
  * confidence, the thresholds, max_votes and mask_out (3 x matches shorts; give room for 3 x RPE_MAX_KEYPOINTS) are rpe_run's.
@@ -702,7 +725,11 @@ int rpe_relocalize(rpe_context* ctx, const rpe_feature_options* fopt, const rpe_
  * at most RPE_MAX_KEYFRAMES.  The store belongs to the context: it survives new frames, new models, rpe_volume_init and new detections
  * and is freed with the context; its memory grows in steps as keyframes are added.  Removing ONE keyframe is out of scope:
  * rpe_keyframes_clear empties the store (a saved map comes back through rpe_keyframe_add_host).  Keyframes of different cameras may
- * share a store.
+ * share a store.  A store has ONE descriptor kind, that of its first keyframe (rpe_keyframe_add: the kind of the model's detection;
+ * rpe_keyframe_add_host: the context's current kind); rpe_keyframes_clear forgets it.  RPE_ERR_STATE for a keyframe of the other kind
+ * added to a non-empty store, for rpe_keyframes_query / rpe_keyframe_match with frame features of the other kind, and for
+ * rpe_relocalize_keyframes while the context's kind differs from the store's.  Matching, ranking and the solver runs do not depend on
+ * the kind.
  * Query: per keyframe k, count[k] = the number of matches rpe_features_match would accept with keyframe k's keypoints as the model's
  * (the rules of "Matching" above, over the keypoints of k ALONE: d2 = 257 with one keypoint, no match against an empty keyframe; the
  * cross-check is per keyframe too).  order = the ids sorted by (count descending, id ascending).  One host wait.
@@ -731,6 +758,8 @@ int rpe_keyframe_info(rpe_context* ctx, int id, int* count, double* pose12, int*
 /* keyframe id's arrays, shaped as rpe_keyframe_add_host takes them (any may be NULL) */
 int rpe_keyframe_download(rpe_context* ctx, int id, int32_t* xy, uint32_t* desc, float* xw, float* nw);
 int rpe_keyframes_count(rpe_context* ctx, int* count);
+/* the store's descriptor kind (RPE_DESC_*), -1 while it is empty */
+int rpe_keyframes_descriptor(rpe_context* ctx, int* kind);
 /* empties the store (its memory is kept for the next keyframes) */
 int rpe_keyframes_clear(rpe_context* ctx);
 /* counts[k] and order[r] for the K keyframes of the store (K ints each); RPE_ERR_STATE without frame features or with an empty store */

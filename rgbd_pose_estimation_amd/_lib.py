@@ -28,6 +28,7 @@ COLOR_FRAME, COLOR_MODEL = 0, 1
 PHOTO_FRAME, PHOTO_MODEL = 0, 1
 FEAT_FRAME, FEAT_MODEL = 0, 1
 MAX_KEYPOINTS = 4096
+DESC_UPRIGHT, DESC_ORIENTED = 0, 1
 MAX_KEYFRAMES = 256
 
 # every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
@@ -48,6 +49,7 @@ SYMBOLS = [
     "rpe_features_detect", "rpe_features_download", "rpe_features_match", "rpe_matches_download", "rpe_relocalize",
     "rpe_keyframe_add", "rpe_keyframe_add_host", "rpe_keyframe_info", "rpe_keyframe_download", "rpe_keyframes_count", "rpe_keyframes_clear",
     "rpe_keyframes_query", "rpe_keyframe_match", "rpe_relocalize_keyframes",
+    "rpe_features_set_descriptor", "rpe_features_get_descriptor", "rpe_features_angles", "rpe_keyframes_descriptor",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -224,6 +226,10 @@ def lib():
         L.rpe_features_detect.argtypes = [C.c_void_p, C.c_int, C.POINTER(RpeFeatureOptions), C.c_void_p]
         L.rpe_features_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_features_match.argtypes = [C.c_void_p, C.POINTER(RpeMatchOptions), C.c_void_p]
+        L.rpe_features_set_descriptor.argtypes = [C.c_void_p, C.c_int]
+        L.rpe_features_get_descriptor.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_features_angles.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rpe_keyframes_descriptor.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_matches_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_relocalize.argtypes = [C.c_void_p, C.POINTER(RpeFeatureOptions), C.POINTER(RpeMatchOptions), C.c_int, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p, C.c_double, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

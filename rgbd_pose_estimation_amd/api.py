@@ -503,6 +503,22 @@ class Context:
         xy, sc, de = xy[:k].copy(), sc[:k].copy(), de[:k].copy()
         return xy, sc, de
 
+    def features_set_descriptor(self, kind: int):
+        """The descriptor of every later detection: L.DESC_UPRIGHT (the default) or L.DESC_ORIENTED, which survives a roll of the camera.
+        A change of kind drops both sides' features and the match list."""
+        L.check(L.lib().rpe_features_set_descriptor(self._h, int(kind)))
+
+    def features_descriptor(self) -> int:
+        k = C.c_int(-1)
+        L.check(L.lib().rpe_features_get_descriptor(self._h, C.byref(k)))
+        return k.value
+
+    def features_angles(self, which: int = L.FEAT_FRAME) -> np.ndarray:
+        """(k,) int32: the angle bins (0 .. 31) of the side's keypoints, all 0 for an upright detection."""
+        bins = np.full(L.MAX_KEYPOINTS, -1, np.int32)
+        L.check(L.lib().rpe_features_angles(self._h, int(which), _p(bins)))
+        return bins[:int(np.count_nonzero(bins >= 0))].copy()
+
     def features_match(self, max_dist: int = 64, ratio=(8, 10), cross_check: bool = False) -> int:
         """Match the frame's keypoints against the model's; XW XC BV NW NC of this context become the matches.  Returns their number."""
         o = L.RpeMatchOptions(int(max_dist), int(ratio[0]), int(ratio[1]), int(cross_check))
@@ -571,6 +587,12 @@ class Context:
         n = C.c_int(0)
         L.check(L.lib().rpe_keyframes_count(self._h, C.byref(n)))
         return n.value
+
+    def keyframes_descriptor(self) -> int:
+        """The descriptor kind of the store's keyframes (L.DESC_*), -1 while the store is empty."""
+        k = C.c_int(0)
+        L.check(L.lib().rpe_keyframes_descriptor(self._h, C.byref(k)))
+        return k.value
 
     def keyframes_clear(self):
         L.check(L.lib().rpe_keyframes_clear(self._h))

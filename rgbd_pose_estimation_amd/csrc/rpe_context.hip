@@ -158,7 +158,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
     if (device < 64 && !loaded[device]) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
       rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
-      rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_keyframe();
+      rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_feature_oriented(); rpe::preload_keyframe();
       loaded[device] = true;
     }
   }
@@ -202,7 +202,7 @@ void rpe_destroy(rpe_context* c) {
   if (c->vol.ws) (void)hipFree(c->vol.ws);
   for (void* m : {(void*)c->vol.mv, (void*)c->vol.mn, (void*)c->vol.mt}) if (m) (void)hipFree(m);
   for (void* m : {(void*)c->fe.d_rgb, (void*)c->fe.fcolor, (void*)c->fe.mcolor, (void*)c->vol.cd, (void*)c->vol.mc, (void*)c->fe.pint, (void*)c->fe.pmap}) if (m) (void)hipFree(m);
-  for (auto& f : c->fe.feat) for (void* m : {(void*)f.pix, (void*)f.score, (void*)f.xy, (void*)f.desc}) if (m) (void)hipFree(m);
+  for (auto& f : c->fe.feat) for (void* m : {(void*)f.pix, (void*)f.score, (void*)f.xy, (void*)f.desc, (void*)f.bin}) if (m) (void)hipFree(m);
   {
     const auto& W = c->fe.fwork; const auto& M = c->fe.mlist;
     for (void* m : {(void*)W.score, (void*)W.box, (void*)W.chunk, (void*)W.hist, (void*)W.ctl, (void*)W.spix, (void*)M.d1, (void*)M.idx, (void*)M.d2,

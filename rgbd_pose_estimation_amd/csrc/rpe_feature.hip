@@ -12,7 +12,8 @@
 //   D5  feat_select_kernel     one workgroup walks the survivors: kept iff score > T, or score == T and among the first `ties` of
 //                              those in pixel order; the kept ones' slot = their rank (two scans per 1024 survivors).
 //   D6  feat_describe_kernel   one wave per keypoint: lane l makes tests l, l + 64, l + 128, l + 192 on the box-sum image, four ballots
-//                              are the eight words, lanes 0-7 store them (one 32-byte row).
+//                              are the eight words, lanes 0-7 store them (one 32-byte row).  (RPE_DESC_ORIENTED: its sibling D6o in
+//                              rpe_feature_oriented.hip takes this kernel's place in the detection.)
 //   M1  feat_best_kernel       16 lanes per keypoint of list A, its descriptor in 8 registers; list B streams through LDS in tiles of
 //                              256 descriptors laid out word-major (lanes of a group read consecutive banks, the wave's four groups the
 //                              same addresses); (d1, index, d2) per lane, merged across the 16 lanes under the tie rule.
@@ -301,7 +302,8 @@ __global__ __launch_bounds__(256) void feat_gather_kernel(MatchLists L, int matc
 }  // namespace
 
 hipError_t launch_feature_detect(const unsigned int* rgba, const float* vmap, const float* nmap, int w, int h, int threshold, int max_keypoints,
-                                 const FeatureWork& W, int* kp_pix, int* kp_score, int* kp_xy, unsigned int* kp_desc, hipStream_t s) {
+                                 const FeatureWork& W, int kind, int* kp_pix, int* kp_score, int* kp_xy, unsigned int* kp_desc, int* kp_bin,
+                                 hipStream_t s) {
   const int n = w * h, nchunks = (n + kChunk - 1) / kChunk;
   hipError_t e = hipMemsetAsync(W.hist, 0, kFeatScoreBins * sizeof(unsigned int), s);
   if (e != hipSuccess) return e;
@@ -311,6 +313,7 @@ hipError_t launch_feature_detect(const unsigned int* rgba, const float* vmap, co
   hipLaunchKernelGGL(feat_scan_kernel, dim3(1), dim3(kWide), 0, s, W.chunk, nchunks, W.hist, max_keypoints, W.ctl);
   hipLaunchKernelGGL(feat_compact_kernel, dim3(nchunks), dim3(kChunk), 0, s, W.score, n, w, W.chunk, W.spix);
   hipLaunchKernelGGL(feat_select_kernel, dim3(1), dim3(kWide), 0, s, W.score, W.spix, max_keypoints, W.ctl, kp_pix, kp_score);
+  if (kind == kDescOriented) return launch_feature_describe_oriented(rgba, W.box, w, h, max_keypoints, W.ctl, kp_pix, kp_xy, kp_desc, kp_bin, s);
   hipLaunchKernelGGL(feat_describe_kernel, dim3((max_keypoints + 3) / 4), dim3(256), 0, s, W.box, w, W.ctl, kp_pix, kp_xy, kp_desc);
   return hipGetLastError();
 }

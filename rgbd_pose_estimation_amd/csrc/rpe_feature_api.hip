@@ -45,7 +45,8 @@ int ensure_side(rpe_context* c, int which) {
   if ((rc = ensure(c, &S.pix, rpe::kMaxKeypoints))) return rc;
   if ((rc = ensure(c, &S.score, rpe::kMaxKeypoints))) return rc;
   if ((rc = ensure(c, &S.xy, 2 * rpe::kMaxKeypoints))) return rc;
-  return ensure(c, &S.desc, 8 * rpe::kMaxKeypoints);
+  if ((rc = ensure(c, &S.desc, 8 * rpe::kMaxKeypoints))) return rc;
+  return ensure(c, &S.bin, rpe::kMaxKeypoints);
 }
 int ensure_lists(rpe_context* c) {
   auto& L = c->fe.mlist;
@@ -104,9 +105,10 @@ int rpe_features_detect(rpe_context* c, int which, const rpe_feature_options* op
   if ((rc = ensure_work(c, k.width, k.height)) || (rc = ensure_side(c, which))) return rc;
   S.have = false;
   HIP_TRY(rpe::launch_feature_detect(model ? F.mcolor : F.fcolor, model ? F.mmap[0] : F.fmap[0], model ? F.mmap[1] : F.fmap[1], k.width,
-                                     k.height, o.threshold, o.max_keypoints, F.fwork, S.pix, S.score, S.xy, S.desc, c->stream));
+                                     k.height, o.threshold, o.max_keypoints, F.fwork, F.desc_kind, S.pix, S.score, S.xy, S.desc, S.bin,
+                                     c->stream));
   if ((rc = read_count(c, F.fwork.ctl + rpe::kFeatCtlCount, &S.count))) return rc;
-  S.have = true; S.gen++; S.threshold = o.threshold; S.max_keypoints = o.max_keypoints;
+  S.have = true; S.gen++; S.threshold = o.threshold; S.max_keypoints = o.max_keypoints; S.kind = F.desc_kind;
   if (count) *count = S.count;
   return RPE_OK;
 }
@@ -124,6 +126,36 @@ int rpe_features_download(rpe_context* c, int which, int32_t* xy, int32_t* score
   if (n && score && (rc = copy_to_host(c, score, S.score, n * sizeof(int)))) return rc;
   if (n && desc && (rc = copy_to_host(c, desc, S.desc, n * 8 * sizeof(unsigned int)))) return rc;
   return RPE_OK;
+}
+
+int rpe_features_set_descriptor(rpe_context* c, int kind) {
+  session_end(c);
+  if (!c || (kind != RPE_DESC_UPRIGHT && kind != RPE_DESC_ORIENTED))
+    return fail(RPE_ERR_ARG, "rpe_features_set_descriptor: kind RPE_DESC_UPRIGHT or RPE_DESC_ORIENTED (got %d)", kind);
+  auto& F = c->fe;
+  if (kind == F.desc_kind) return RPE_OK;
+  F.desc_kind = kind;                    // descriptors of two kinds never meet: both sides and the match list go
+  F.feat[0].have = false; F.feat[1].have = false; F.matches = -1; F.match_kf = -1;
+  return RPE_OK;
+}
+
+int rpe_features_get_descriptor(rpe_context* c, int* kind) {
+  if (!c || !kind) return fail(RPE_ERR_ARG, "rpe_features_get_descriptor: bad argument");
+  *kind = c->fe.desc_kind;
+  return RPE_OK;
+}
+
+int rpe_features_angles(rpe_context* c, int which, int32_t* bins) {
+  session_end(c);
+  if (!c || (which != RPE_FEAT_FRAME && which != RPE_FEAT_MODEL)) return fail(RPE_ERR_ARG, "rpe_features_angles: bad argument");
+  auto& S = c->fe.feat[which];
+  if (!S.have) return fail(RPE_ERR_STATE, "no features of the %s: call rpe_features_detect (a new depth, colour or model drops them)",
+                           which == RPE_FEAT_MODEL ? "model" : "frame");
+  const size_t n = (size_t)S.count;
+  if (!n || !bins) return RPE_OK;
+  if (S.kind != RPE_DESC_ORIENTED) { std::memset(bins, 0, n * sizeof(int32_t)); return RPE_OK; }   // an upright patch is not turned
+  HIP_TRY(hipSetDevice(c->device));
+  return copy_to_host(c, bins, S.bin, n * sizeof(int));
 }
 
 int rpe_features_match(rpe_context* c, const rpe_match_options* opt, int* matches) {
@@ -186,7 +218,7 @@ int rpe_relocalize(rpe_context* c, const rpe_feature_options* fopt, const rpe_ma
   for (int which : {RPE_FEAT_FRAME, RPE_FEAT_MODEL}) {
     if ((rc = side_ready(c, which))) return rc;
     const auto& S = c->fe.feat[which];
-    if (S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints) continue;   // detected already, with these options
+    if (S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints && S.kind == c->fe.desc_kind) continue;   // detected already, with these options and this descriptor
     if ((rc = rpe_features_detect(c, which, &fo, nullptr))) return rc;
   }
   int m = 0;

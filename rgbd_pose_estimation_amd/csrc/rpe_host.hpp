@@ -175,8 +175,11 @@ struct rpe_context {
     // features (rpe_feature_api.hip): per side (RPE_FEAT_FRAME / RPE_FEAT_MODEL) the keypoints of the last detection -- pixel index,
     // score, xy and 8 descriptor words each, RPE_MAX_KEYPOINTS slots, allocated on first use -- valid while `have` (whatever replaces
     // the side's depth, model or colour resets it); gen counts the side's detections so that a match list knows what it was made of
+    // kind / bin: the descriptor kind the detection was made with and, for RPE_DESC_ORIENTED, the keypoints' angle bins.  desc_kind is
+    // the context's kind (rpe_features_set_descriptor): what the next detection on either side uses
     struct Features { int *pix = nullptr, *score = nullptr, *xy = nullptr; unsigned int* desc = nullptr; int count = 0; bool have = false;
-                      unsigned long long gen = 0; int threshold = 0, max_keypoints = 0; } feat[2];
+                      unsigned long long gen = 0; int threshold = 0, max_keypoints = 0; int kind = 0; int* bin = nullptr; } feat[2];
+    int desc_kind = 0;
     rpe::FeatureWork fwork{};            // the detector's workspace, sized for fwork_pixels pixels (shared by both sides)
     int64_t fwork_pixels = 0;
     rpe::MatchLists mlist{};             // best / second best per keypoint and the accepted matches (RPE_MAX_KEYPOINTS slots)
@@ -195,6 +198,7 @@ struct rpe_context {
     int64_t cap = 0, used = 0;
     int *back = nullptr, *d1 = nullptr, *idx = nullptr, *d2 = nullptr, *rank = nullptr;
     int rows_cap = 0;
+    int kind = -1;                       // the descriptor kind of every keyframe in the store: its first one's (-1: the store is empty)
   } kf;
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
   struct Volume {

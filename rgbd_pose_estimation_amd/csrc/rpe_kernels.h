@@ -292,9 +292,17 @@ enum { kFeatCtlSurvivors = 0, kFeatCtlCut = 1, kFeatCtlTies = 2, kFeatCtlCount =
 struct FeatureWork { int* score; unsigned short* box; int* chunk; unsigned int* hist; int* ctl; int* spix; };
 // F1: detect + describe one view.  rgba / vmap / nmap: the view's RGBA8 colour, vertex and normal maps (w x h).  Leaves the number of
 // keypoints in W.ctl[kFeatCtlCount] and pixel index, score, xy and descriptor of keypoint k at slot k, in pixel order.  Six kernels, no
-// host wait.
+// host wait.  kind = kDescUpright: D6, kp_bin untouched; kDescOriented: the sixth kernel is launch_feature_describe_oriented, which
+// leaves the angle bin of keypoint k in kp_bin[k] too.
+enum { kDescUpright = 0, kDescOriented = 1 };   // RPE_DESC_*
 hipError_t launch_feature_detect(const unsigned int* rgba, const float* vmap, const float* nmap, int w, int h, int threshold, int max_keypoints,
-                                 const FeatureWork& W, int* kp_pix, int* kp_score, int* kp_xy, unsigned int* kp_desc, hipStream_t s);
+                                 const FeatureWork& W, int kind, int* kp_pix, int* kp_score, int* kp_xy, unsigned int* kp_desc, int* kp_bin,
+                                 hipStream_t s);
+// D6o (rpe_feature_oriented.hip): xy, the oriented descriptor and the angle bin of the keypoints D5 left in kp_pix / ctl[kFeatCtlCount]
+hipError_t launch_feature_describe_oriented(const unsigned int* rgba, const unsigned short* box, int w, int h, int max_keypoints,
+                                            const int* ctl, const int* kp_pix, int* kp_xy, unsigned int* kp_desc, int* kp_bin,
+                                            hipStream_t s);
+void preload_feature_oriented();
 // per keypoint of the list A: d1, index and d2 over the list B (ties to the lower index; d1 = d2 = 257, index -1 without any)
 struct MatchLists { int *d1, *idx, *d2, *back; int *mf, *mm, *md1, *md2; float* mw; };
 hipError_t launch_feature_best(const unsigned int* desc_a, int na, const unsigned int* desc_b, int nb, int* d1, int* idx, int* d2, hipStream_t s);

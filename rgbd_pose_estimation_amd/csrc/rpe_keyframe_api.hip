@@ -69,8 +69,9 @@ int ensure_rows(rpe_context* c, int rows) {
   K.rows_cap = cap;
   return RPE_OK;
 }
-int new_keyframe(rpe_context* c, int count, const double* pose12, int width, int height, int* id) {
+int new_keyframe(rpe_context* c, int kind, int count, const double* pose12, int width, int height, int* id) {
   auto& K = c->kf;
+  if (K.meta.empty()) K.kind = kind;
   rpe_context::Keyframes::Meta m;
   m.off = (int)K.used; m.count = count; m.width = width; m.height = height;
   std::memcpy(m.pose, pose12, sizeof(m.pose));
@@ -86,6 +87,16 @@ int new_keyframe(rpe_context* c, int count, const double* pose12, int width, int
 int store_ready(rpe_context* c, const char* who) {
   if (c->kf.meta.empty()) return fail(RPE_ERR_STATE, "%s: the keyframe store is empty (rpe_keyframe_add)", who);
   if (!c->fe.feat[RPE_FEAT_FRAME].have) return fail(RPE_ERR_STATE, "%s: no features of the frame (rpe_features_detect)", who);
+  if (c->fe.feat[RPE_FEAT_FRAME].kind != c->kf.kind)
+    return fail(RPE_ERR_STATE, "%s: the frame's descriptors are of kind %d, the store's of kind %d (rpe_features_set_descriptor)", who,
+                c->fe.feat[RPE_FEAT_FRAME].kind, c->kf.kind);
+  return RPE_OK;
+}
+// a store has one kind of descriptor, its first keyframe's
+int kind_fits(rpe_context* c, int kind, const char* who) {
+  if (!c->kf.meta.empty() && c->kf.kind != kind)
+    return fail(RPE_ERR_STATE, "%s: descriptors of kind %d, the store's are of kind %d (rpe_keyframes_clear starts another store)", who, kind,
+                c->kf.kind);
   return RPE_OK;
 }
 int ensure_lists(rpe_context* c) {
@@ -160,11 +171,12 @@ int rpe_keyframe_add(rpe_context* c, int* id) {
   const auto& S = F.feat[RPE_FEAT_MODEL];
   if (!F.have_model || !S.have) return fail(RPE_ERR_STATE, "rpe_keyframe_add: no features of the model (rpe_features_detect with RPE_FEAT_MODEL)");
   if ((int)c->kf.meta.size() >= RPE_MAX_KEYFRAMES) return fail(RPE_ERR_STATE, "rpe_keyframe_add: the store is full (%d keyframes)", RPE_MAX_KEYFRAMES);
-  HIP_TRY(hipSetDevice(c->device));
   int rc;
+  if ((rc = kind_fits(c, S.kind, "rpe_keyframe_add"))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
   if ((rc = ensure_store(c, S.count))) return rc;
   HIP_TRY(rpe::launch_keyframe_snapshot(S.count, S.pix, S.xy, S.desc, F.mmap[0], F.mmap[1], c->kf.st, (int)c->kf.used, c->stream));
-  return new_keyframe(c, S.count, F.mpose, F.mcam.width, F.mcam.height, id);
+  return new_keyframe(c, S.kind, S.count, F.mpose, F.mcam.width, F.mcam.height, id);
 }
 
 int rpe_keyframe_add_host(rpe_context* c, int count, const int32_t* xy, const uint32_t* desc, const float* xw, const float* nw,
@@ -177,8 +189,9 @@ int rpe_keyframe_add_host(rpe_context* c, int count, const int32_t* xy, const ui
     if (xy[2 * k] < 0 || xy[2 * k] >= width || xy[2 * k + 1] < 0 || xy[2 * k + 1] >= height)
       return fail(RPE_ERR_ARG, "rpe_keyframe_add_host: keypoint %d at (%d, %d) is outside the %d x %d image", k, xy[2 * k], xy[2 * k + 1], width, height);
   if ((int)c->kf.meta.size() >= RPE_MAX_KEYFRAMES) return fail(RPE_ERR_STATE, "rpe_keyframe_add_host: the store is full (%d keyframes)", RPE_MAX_KEYFRAMES);
-  HIP_TRY(hipSetDevice(c->device));
   int rc;
+  if ((rc = kind_fits(c, c->fe.desc_kind, "rpe_keyframe_add_host"))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
   if ((rc = ensure_store(c, count))) return rc;
   auto& K = c->kf;
   const size_t o = (size_t)K.used, n = (size_t)count;
@@ -188,7 +201,7 @@ int rpe_keyframe_add_host(rpe_context* c, int count, const int32_t* xy, const ui
     HIP_TRY(hipMemcpyAsync(K.st.nw + 3 * o, nw, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(K.st.xy + 2 * o, xy, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   }
-  return new_keyframe(c, count, pose12, width, height, id);
+  return new_keyframe(c, c->fe.desc_kind, count, pose12, width, height, id);
 }
 
 int rpe_keyframe_info(rpe_context* c, int id, int* count, double* pose12, int* width, int* height) {
@@ -223,6 +236,12 @@ int rpe_keyframes_count(rpe_context* c, int* count) {
   return RPE_OK;
 }
 
+int rpe_keyframes_descriptor(rpe_context* c, int* kind) {
+  if (!c || !kind) return fail(RPE_ERR_ARG, "rpe_keyframes_descriptor: bad argument");
+  *kind = c->kf.meta.empty() ? -1 : c->kf.kind;
+  return RPE_OK;
+}
+
 int rpe_keyframes_clear(rpe_context* c) {
   session_end(c);
   if (!c) return fail(RPE_ERR_ARG, "null context");
@@ -230,6 +249,7 @@ int rpe_keyframes_clear(rpe_context* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->kf.meta.clear();
   c->kf.used = 0;                                  // the storage stays, for the next map
+  c->kf.kind = -1;
   if (c->fe.match_kf >= 0) { c->fe.matches = -1; c->fe.match_kf = -1; }
   return RPE_OK;
 }
@@ -283,9 +303,12 @@ int rpe_relocalize_keyframes(rpe_context* c, const rpe_feature_options* fopt, co
                 fo.max_keypoints);
   auto& K = c->kf;
   if (K.meta.empty()) return fail(RPE_ERR_STATE, "rpe_relocalize_keyframes: the keyframe store is empty (rpe_keyframe_add)");
+  if (c->fe.desc_kind != K.kind)
+    return fail(RPE_ERR_STATE, "rpe_relocalize_keyframes: the context describes with kind %d, the store's descriptors are of kind %d "
+                "(rpe_features_set_descriptor)", c->fe.desc_kind, K.kind);
   {
     const auto& S = c->fe.feat[RPE_FEAT_FRAME];
-    if (!(S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints) &&
+    if (!(S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints && S.kind == c->fe.desc_kind) &&
         (rc = rpe_features_detect(c, RPE_FEAT_FRAME, &fo, nullptr))) return rc;
   }
   HIP_TRY(hipSetDevice(c->device));

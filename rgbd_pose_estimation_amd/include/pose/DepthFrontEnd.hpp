@@ -24,6 +24,7 @@
 // and the RANSAC / PROSAC solvers make the pose that ICP then refines
 //   rpe::RelocResult r = fe.relocalize(6 /* shinji_kneip_prosac */, 0.05, 3.0, 0.1);
 //   if (r.ok) { T = r.pose;  fe.preparePhoto(3);  fe.icpPyramidRgbd(T, 0.01, {6, 4, 3}); }
+// ... also when the camera has ROLLED since (tipped, shaken, picked up): fe.setDescriptor(RPE_DESC_ORIENTED) once, before any detection
 // ... against ALL the keyframes it has kept, without knowing which one the camera sees (the store lives in the context)
 //   at every keyframe: fe.setModelFromFrame(T);  fe.modelColorFromFrame();  fe.detectFeatures(RPE_FEAT_MODEL);  fe.addKeyframe();
 //   when lost:         rpe::KeyframeRelocResult r = fe.relocalizeKeyframes(6, 0.05, 3.0, 0.1);   // r.keyframe = the one it chose
@@ -302,6 +303,24 @@ class DepthFrontEnd {
     int n = 0;
     check(rpe_features_detect(_ctx, which, &fo, &n), "rpe_features_detect");
     return n;
+  }
+  // the descriptor of every later detection on either side, relocalize's own included: RPE_DESC_UPRIGHT (the default) or
+  // RPE_DESC_ORIENTED, which survives a roll of the camera at the price of about a third of the matches without one.  A change of
+  // kind drops both sides' features and the match list; a keyframe store holds one kind
+  void setDescriptor(int kind) { check(rpe_features_set_descriptor(_ctx, kind), "rpe_features_set_descriptor"); }
+  int descriptor() const {
+    int kind = 0;
+    check(rpe_features_get_descriptor(_ctx, &kind), "rpe_features_get_descriptor");
+    return kind;
+  }
+  // the angle bins (0 .. 31, steps of 2 pi / 32) of the side's keypoints; all 0 for an upright detection
+  std::vector<int32_t> featureAngles(int which) {
+    std::vector<int32_t> bins((size_t)RPE_MAX_KEYPOINTS, -1);
+    check(rpe_features_angles(_ctx, which, bins.data()), "rpe_features_angles");
+    size_t n = 0;
+    while (n < bins.size() && bins[n] >= 0) n++;
+    bins.resize(n);
+    return bins;
   }
   // match the frame's keypoints against the model's; the solver slots become the matches (n = their number, returned)
   int matchFeatures(const MatchOptions& o = MatchOptions()) {

@@ -1,0 +1,180 @@
+"""CPU: the numpy statement of the oriented descriptor (tests/oriented_oracle.py) against itself -- the table, the tie rule, the
+quarter turns, the steered reach, bin 0 = the upright descriptor -- the figures of tests/oriented_cases.py recomputed (what a roll does
+to the upright descriptor and what the oriented one makes of it, matches and relocalisation end to end in the oracles), the case
+conditions the GPU tests rely on, and the cross-compiled library: exports, header, ISA resources of the new kernel, the C++ driver."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import feature_cases as FC
+import feature_oracle as FE
+import isa_tools as T
+import oriented_cases as OC
+import oriented_oracle as OO
+import volume_cases as VC
+from rgbd_pose_estimation_amd import _lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
+SYMS = {"rpe_features_set_descriptor", "rpe_features_get_descriptor", "rpe_features_angles", "rpe_keyframes_descriptor"}
+
+
+# ---------------------------------------------------------------------------------------------- properties of the statement
+def test_the_table_is_the_rounded_circle():
+    k = np.arange(OO.BINS)
+    assert np.array_equal(OO.COS, np.rint(1024 * np.cos(2 * np.pi * k / OO.BINS)).astype(np.int64))
+    assert np.array_equal(OO.SIN, np.rint(1024 * np.sin(2 * np.pi * k / OO.BINS)).astype(np.int64))
+    assert OO.COS[:9].tolist() == [1024, 1004, 946, 851, 724, 569, 392, 200, 0]
+    assert len(OO.DISC) == 529 and np.abs(OO.DISC[:, 0]).sum() == 2914 and np.abs(OO.DISC[:, 1]).sum() == 2914
+    assert 2914 * 255 * 1024 * 2 < 2 ** 63
+
+
+def test_a_tie_goes_to_the_lowest_bin():
+    assert OO.angle_bin(0, 0) == 0                                               # the 32-way tie
+    assert OO.angle_bin(1, 0) == 0 and OO.angle_bin(0, 1) == 8 and OO.angle_bin(-1, 0) == 16 and OO.angle_bin(0, -1) == 24
+    # C[1] = C[31] and S[31] = -S[1]: a moment on the x axis scores bins k and 32 - k alike, never better than bin 0
+    assert OO.angle_bin(5, 0) == 0 and OO.angle_bin(-5, 0) == 16
+    # 1024 x = 1004 x + 200 y at x = 10 y: the moment (10, 1) scores bins 0 and 1 alike, (-10, -1) bins 16 and 17: the lower one
+    for m10, m01, lo in ((10, 1, 0), (-10, -1, 16), (-1, 10, 8), (1, -10, 24)):
+        sc = m10 * OO.COS + m01 * OO.SIN
+        assert sc[lo] == sc[lo + 1] == sc.max() and (sc == sc.max()).sum() == 2 and OO.angle_bin(m10, m01) == lo
+    assert OO.angle_bin(np.array([3, -3]), np.array([3, 3])).tolist() == [4, 12]
+
+
+def test_quarter_turns_are_exact_and_bin_0_is_the_identity():
+    P = OO.steer(np.array([0, 8, 16, 24]))
+    x, y = FE.PAIRS[:, (0, 2)], FE.PAIRS[:, (1, 3)]
+    for k, (sx, sy) in enumerate([(x, y), (-y, x), (-x, -y), (y, -x)]):
+        assert np.array_equal(P[k][:, (0, 2)], sx) and np.array_equal(P[k][:, (1, 3)], sy), k
+
+
+def test_steered_reach_is_17_at_most():
+    P = OO.steer(np.arange(OO.BINS))
+    assert P.shape == (OO.BINS, 256, 4) and np.abs(P).max() == 17                # with the box's 2: past the 16 px border
+    R = OC.reach_bins()
+    assert all(len(b) >= 1 for b in R.values()), R
+
+
+def test_bin_0_is_the_upright_descriptor():
+    p = OC.pair("small", "roll0.6")
+    xy, sc, de, bins = OO.detect(p.frame.rgba, p.frame.V, p.frame.N)
+    uxy, usc, ude = p.frame.detect()
+    assert np.array_equal(xy, uxy) and np.array_equal(sc, usc)                   # the detector is the same
+    pix = xy[:, 1].astype(np.int64) * p.frame.w + xy[:, 0]
+    S = FE.box_sums(FE.luma(p.frame.rgba))
+    assert np.array_equal(OO.describe(S, pix, p.frame.w, np.zeros(len(pix), np.int64)), ude)
+    zero = bins == 0
+    assert zero.sum() >= 3 and np.array_equal(de[zero], ude[zero]) and not np.array_equal(de[~zero], ude[~zero])
+    assert len(np.unique(bins)) == OO.BINS and bins.min() == 0 and bins.max() == OO.BINS - 1
+
+
+def test_a_sample_outside_the_image_reads_zero():
+    S = np.arange(1, 13).reshape(3, 4)
+    x, y = np.array([-1, 0, 3, 4, 2, 2]), np.array([0, 0, 2, 2, -1, 3])
+    assert OO.sample(S, x, y).tolist() == [0, 1, 12, 0, 0, 0]
+
+
+def test_the_edge_view_has_samples_outside_every_edge():
+    """the condition the GPU edge test relies on, and the lone dots' tie"""
+    p, placed, lone = OC.edge_pair()
+    h, w = p.cam[5], p.cam[4]
+    for view in (p.frame, p.model):
+        xy, _, _, bins = OO.detect(view.rgba, view.V, view.N)
+        at = {(int(u), int(v)): int(b) for (u, v), b in zip(xy, bins)}
+        for edge, spots in placed.items():
+            assert len(spots) >= 1
+            for u, v, b in spots:
+                assert at.get((u, v)) == b, (edge, u, v, b, at.get((u, v)))
+                P = OO.steer(np.array([b]))[0]
+                X, Y = u + P[:, (0, 2)], v + P[:, (1, 3)]
+                out = {"left": X < 0, "right": X >= w, "top": Y < 0, "bottom": Y >= h}[edge]
+                assert out.any(), (edge, u, v, b)
+        found = [at[d] for d in lone if d in at]
+        assert len(found) >= 3 and not any(found)                                  # zero moments: bin 0
+
+
+def test_holes_lie_inside_the_discs():
+    p = OC.holes_pair()
+    xy = p.model.detect()[0]
+    known = p.model_rgba[..., 3] != 0
+    inside = sum(int((~known[v + OO.DISC[:, 1], u + OO.DISC[:, 0]]).any()) for u, v in xy)
+    assert len(xy) > 100 and inside == len(xy)
+
+
+# ---------------------------------------------------------------------------------------------- the figures of oriented_cases.py
+@pytest.mark.parametrize("cam,motion", sorted(OC.FIGURES))
+def test_pair_figures(oracle, cam, motion):
+    p = OC.pair(cam, motion)
+    up, orr = p.oracle(), OC.oracle(p)
+    cu, co = p.correct(up), p.correct(orr)
+    fig = OC.FIGURES[(cam, motion)]
+    print(cam, motion, len(up["fxy"]), len(up["mxy"]), len(up["fi"]), cu.mean(), len(orr["fi"]), co.mean())
+    assert (len(up["fxy"]), len(up["mxy"])) == (len(orr["fxy"]), len(orr["mxy"])) == fig["keypoints"]
+    assert len(up["fi"]) == fig["upright"][0] and abs(cu.mean() - fig["upright"][1]) < 6e-4      # recorded to three places
+    assert len(orr["fi"]) == fig["oriented"][0] and abs(co.mean() - fig["oriented"][1]) < 6e-4
+    assert np.array_equal(orr["w"], (256 - orr["d1"]).astype(np.float32)) and (np.diff(orr["fi"]) > 0).all()
+    # end to end: the oracle-side solver on the oriented matches
+    pose, r = FC.oracle_relocalise(oracle, p, orr)
+    start, reloc = VC.pose_error(p.pa, p.pb), VC.pose_error(pose, p.pb)
+    print("   start", start, "reloc", reloc, "votes", r["max_votes"], "iters", r["iters"])
+    near = lambda got, want: all(abs(g - w) <= 0.05 * w for g, w in zip(got, want))
+    assert (r["max_votes"], r["iters"]) == (fig["votes"], fig["iters"]) and near(start, fig["start"]) and near(reloc, fig["reloc"])
+    if cam == "half":
+        assert reloc[0] < OC.RELOC_BOUND[0] and reloc[1] < OC.RELOC_BOUND[1]
+
+
+@pytest.mark.parametrize("motion", ["roll0.6", "roll1.2", "roll3.0"])
+def test_a_roll_kills_the_upright_descriptor_and_not_the_oriented(motion):
+    p = OC.pair("half", motion)
+    up, orr = p.oracle(), OC.oracle(p)
+    assert p.correct(up).mean() < 0.10 and p.correct(orr).mean() > 0.80
+    assert len(orr["fi"]) > 5 * len(up["fi"])
+
+
+@pytest.mark.parametrize("motion", ["roll0.6", "roll3.0", "wide2_rz-0.7"])
+def test_upright_relocalisation_is_lost_under_a_roll(oracle, motion):
+    p = OC.pair("half", motion)
+    pose, _ = FC.oracle_relocalise(oracle, p, p.oracle())
+    e = VC.pose_error(pose, p.pb)
+    assert not (e[0] < 0.3)                                                       # lost, or no pose at all (NaN)
+
+
+# ---------------------------------------------------------------------------------------------- the cross-compiled library
+def _built():
+    from rgbd_pose_estimation_amd import build as B
+    return B.build()
+
+
+def test_header_and_library_export_the_descriptor_entry_points():
+    lib = _built()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
+    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    assert SYMS <= exported, sorted(SYMS - exported)
+    assert SYMS <= set(L.SYMBOLS)
+    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
+    for s in SYMS:
+        assert f"int {s}(" in hdr
+    assert "RPE_DESC_UPRIGHT = 0, RPE_DESC_ORIENTED = 1" in hdr and (L.DESC_UPRIGHT, L.DESC_ORIENTED) == (0, 1)
+    assert " ".join(str(c) for c in OO.COS) in " ".join(hdr.replace(" *", " ").split())        # the table as the header states it
+    assert "typedef struct { int threshold; int max_keypoints; } rpe_feature_options;" in hdr       # the layout stays
+    assert L.lib().rpe_abi_version() == 1
+
+
+def test_oriented_kernel_does_not_spill():
+    _built()
+    rows = T.kernel_resources(os.path.join(LIB, "rpe_feature_oriented.o"))
+    names = [r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows]
+    assert names == ["feat_describe_oriented"], rows
+    r = rows[0]
+    assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0 and r["lds"] == 0
+    assert r["vgpr"] + r["agpr"] <= 64                                           # one wave per keypoint: full occupancy
+
+
+def test_oriented_cpp_driver_compiles(tmp_path):
+    lib = _built()
+    inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
+                           os.path.join(ROOT, "tests", "cpp", "oriented_reloc.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",
+                           "-Wl,-rpath," + os.path.dirname(lib), "-o", str(tmp_path / "oriented_reloc")])
