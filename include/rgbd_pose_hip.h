@@ -468,6 +468,35 @@ int rpe_model_build_pyramid(rpe_context* ctx, int levels);
 int rpe_icp_pyramid(rpe_context* ctx, const rpe_icp_options* opt, int levels, const int* iters_per_level, const double* dist_thr_per_level,
                     double* pose12, int* iters_out, double* last_step, double* final_cost, int64_t* matched);
 
+/* ---- Depth filter (optional, off by default): a bilateral filter on the frame's metric depth in front of F1 / F1p, the first kernel
+ * of a KinectFusion pipeline.  A depth camera's noise grows with the square of the range and is centimetres at room distances, more
+ * than the spacing of neighbouring pixels' rays: the central-difference normals of raw depth are then mostly noise, and with them the
+ * point-to-plane residual, the cos_thr gate and the stored normals.  Conventions, followed bit for bit (fp32, the written order, no FMA
+ * contraction; tests/filter_oracle.py states them in numpy):
+ * Cast once: r = radius (1 .. RPE_FILTER_MAX_RADIUS), a = (float)depth_cut, b = (float)depth_cut_z2.  m(u, v) = the metric depth of
+ * level 0 as above: d = (float)raw * scale, NaN unless d > dmin && d < dmax.  Spatial weights, made on the host:
+ * ws[dy][dx] = (float)exp(-(double)(dx*dx + dy*dy) / (2 * sigma_space * sigma_space)), double, libm's exp.  Pixel (u, v): c = m(u, v);
+ * c NaN gives NaN (holes are not filled).  cut = a + b * (c * c), inv = 1.0f / cut.  For dy = -r .. r (outer), dx = -r .. r (inner),
+ * neighbours inside the image only: d = m(u + dx, v + dy), t = (d - c) * inv, x = t * t; the neighbour counts iff x < 1.0f (a NaN one
+ * does not), with wr = (1.0f - x) * (1.0f - x), wgt = ws[dy][dx] * wr, num += wgt * d, den += wgt.  out = num / den (den >= 1: the
+ * centre).  The range kernel is the biweight, a polynomial with support `cut`: the depth difference at which a neighbour stops
+ * counting is depth_cut + depth_cut_z2 z^2 metres, the z^2 term following the sensor's noise law (a constant cut cannot be right at
+ * 1 m and at 5 m at once).  Nothing bleeds across a depth step larger than cut.
+ * The filtered image is handed, as RPE_DEPTH_F32 with scale 1, to the kernels of rpe_frame_set_depth / rpe_frame_set_depth_pyramid,
+ * which re-apply (dmin, dmax): level 0 of the frame is F1 on the filtered depth, coarser levels follow from it by the block rule
+ * above, RPE_MAP_DEPTH level 0 downloads the filtered depth, and rpe_volume_integrate fuses the filtered vertex map.  Fusing the raw
+ * depth beside filtered tracking is out of scope: a caller who wants that builds the frame twice.
+ * The setting belongs to the context and applies to the NEXT rpe_frame_set_depth*; the current frame is not touched.  A frame build
+ * with the filter on is one launch more (2 for rpe_frame_set_depth, 3 for the pyramid) and no extra host wait; the filtered buffer
+ * is allocated on first use and reused.  With the filter off every function returns the bits it returned without it. */
+enum { RPE_FILTER_MAX_RADIUS = 4 };
+typedef struct { int radius; double sigma_space, depth_cut, depth_cut_z2; } rpe_depth_filter;
+/* radius 0 or filter = NULL: off (the other fields are then not looked at).  RPE_ERR_ARG for a radius outside 0 .. RPE_FILTER_MAX_RADIUS,
+ * sigma_space or depth_cut not finite and > 0, depth_cut_z2 not finite or < 0; the setting is then unchanged. */
+int rpe_frame_set_filter(rpe_context* ctx, const rpe_depth_filter* filter);
+/* the current setting: {0, 0, 0, 0} while off */
+int rpe_frame_get_filter(rpe_context* ctx, rpe_depth_filter* out);
+
 /* ---- TSDF volume (KinectFusion): frames fused into a truncated signed distance volume, raycast into the model.  With it,
  * rpe_frame_set_depth_pyramid -> rpe_volume_raycast -> rpe_model_build_pyramid -> rpe_icp_pyramid -> rpe_volume_integrate tracks
  * frame to model with every map on the GPU.  Conventions, followed bit for bit (fp32, the written order, no FMA contraction):

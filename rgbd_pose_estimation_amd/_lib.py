@@ -30,6 +30,7 @@ FEAT_FRAME, FEAT_MODEL = 0, 1
 MAX_KEYPOINTS = 4096
 DESC_UPRIGHT, DESC_ORIENTED = 0, 1
 MAX_KEYFRAMES = 256
+FILTER_MAX_RADIUS = 4
 
 # every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -50,6 +51,7 @@ SYMBOLS = [
     "rpe_keyframe_add", "rpe_keyframe_add_host", "rpe_keyframe_info", "rpe_keyframe_download", "rpe_keyframes_count", "rpe_keyframes_clear",
     "rpe_keyframes_query", "rpe_keyframe_match", "rpe_relocalize_keyframes",
     "rpe_features_set_descriptor", "rpe_features_get_descriptor", "rpe_features_angles", "rpe_keyframes_descriptor",
+    "rpe_frame_set_filter", "rpe_frame_get_filter",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -79,6 +81,10 @@ class RpeFeatureOptions(C.Structure):
 
 class RpeMatchOptions(C.Structure):
     _fields_ = [("max_dist", C.c_int), ("ratio_num", C.c_int), ("ratio_den", C.c_int), ("cross_check", C.c_int)]
+
+
+class RpeDepthFilter(C.Structure):
+    _fields_ = [("radius", C.c_int), ("sigma_space", C.c_double), ("depth_cut", C.c_double), ("depth_cut_z2", C.c_double)]
 
 
 class RpeVolumeDesc(C.Structure):
@@ -194,6 +200,8 @@ def lib():
         L.rpe_icp.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_frame_set_depth_pyramid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RpeCamera), C.c_double, C.c_double, C.c_double,
                                                   C.c_double, C.c_int]
+        L.rpe_frame_set_filter.argtypes = [C.c_void_p, C.POINTER(RpeDepthFilter)]
+        L.rpe_frame_get_filter.argtypes = [C.c_void_p, C.POINTER(RpeDepthFilter)]
         L.rpe_frame_download_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rpe_frame_level_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(RpeCamera)]
         L.rpe_model_build_pyramid.argtypes = [C.c_void_p, C.c_int]

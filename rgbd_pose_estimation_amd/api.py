@@ -222,6 +222,20 @@ class Context:
         self._frame_hw = (k.height, k.width)
         return self
 
+    def frame_set_filter(self, radius: int = 3, sigma_space: float = 2.0, depth_cut: float = 0.01, depth_cut_z2: float = 0.02):
+        """Bilateral filter on the metric depth of every later frame_set_depth (rpe_frame_set_filter): a (2 radius + 1)^2 window,
+        Gaussian in space (sigma_space pixels), biweight in range with the cut-off depth_cut + depth_cut_z2 z^2 metres.
+        frame_set_filter(0) turns it off again; the current frame is not touched."""
+        f = L.RpeDepthFilter(int(radius), float(sigma_space), float(depth_cut), float(depth_cut_z2))
+        L.check(L.lib().rpe_frame_set_filter(self._h, C.byref(f)))
+        return self
+
+    def frame_filter(self):
+        """(radius, sigma_space, depth_cut, depth_cut_z2) of the depth filter; radius 0 = off."""
+        f = L.RpeDepthFilter()
+        L.check(L.lib().rpe_frame_get_filter(self._h, C.byref(f)))
+        return (f.radius, f.sigma_space, f.depth_cut, f.depth_cut_z2)
+
     def frame_download(self, which: int, level: int = 0) -> np.ndarray:
         """One map as (pixels, 3) float32 (MAP_DEPTH: (pixels,) metres) of pyramid level `level`; pixels of the model's view for the
         MAP_MODEL_* maps."""

@@ -159,6 +159,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
       rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
       rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_feature_oriented(); rpe::preload_keyframe();
+      rpe::preload_filter();
       loaded[device] = true;
     }
   }
@@ -198,6 +199,7 @@ void rpe_destroy(rpe_context* c) {
   for (float* m : c->fe.mmap) if (m) (void)hipFree(m);
   if (c->fe.d_count) (void)hipFree(c->fe.d_count);
   if (c->fe.fdepth) (void)hipFree(c->fe.fdepth);
+  if (c->fe.d_filt) (void)hipFree(c->fe.d_filt);
   if (c->vol.d) (void)hipFree(c->vol.d);
   if (c->vol.ws) (void)hipFree(c->vol.ws);
   for (void* m : {(void*)c->vol.mv, (void*)c->vol.mn, (void*)c->vol.mt}) if (m) (void)hipFree(m);

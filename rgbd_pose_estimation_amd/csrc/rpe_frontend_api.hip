@@ -94,9 +94,49 @@ int stage_depth(rpe_context* c, const void* depth, int depth_type, int64_t n) {
     F.depth_cap = bytes;
   }
   if (!F.d_count) HIP_TRY(hipMalloc((void**)&F.d_count, 64));
+  if (F.filter.radius > 0 && (!F.d_filt || F.filt_cap < (size_t)n * sizeof(float))) {   // the filtered depth: first use, or a larger frame
+    if (F.d_filt) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(F.d_filt)); F.d_filt = nullptr; F.filt_cap = 0; }
+    HIP_TRY(hipMalloc((void**)&F.d_filt, (size_t)n * sizeof(float)));
+    F.filt_cap = (size_t)n * sizeof(float);
+  }
+  return RPE_OK;
+}
+// what F1 / F1p read behind the upload: the raw depth as it came, or -- filter on -- F0's metric depth of it (float32, scale 1)
+struct DepthSource { const void* d; int type; float scale; };
+int depth_source(rpe_context* c, int depth_type, const rpe::Camera& k, float scale, float dmin, float dmax, DepthSource* src) {
+  auto& F = c->fe;
+  *src = DepthSource{F.d_depth, depth_type, scale};
+  if (F.filter.radius == 0) return RPE_OK;
+  HIP_TRY(rpe::launch_depth_filter(F.d_depth, depth_type, k.width, k.height, scale, dmin, dmax, F.fparams, F.d_filt, c->stream));
+  *src = DepthSource{F.d_filt, RPE_DEPTH_F32, 1.0f};
   return RPE_OK;
 }
 }  // namespace
+
+int rpe_frame_set_filter(rpe_context* c, const rpe_depth_filter* f) {
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  auto& F = c->fe;
+  if (!f || f->radius == 0) { F.filter = rpe_depth_filter{0, 0.0, 0.0, 0.0}; return RPE_OK; }
+  if (f->radius < 0 || f->radius > RPE_FILTER_MAX_RADIUS)
+    return fail(RPE_ERR_ARG, "rpe_frame_set_filter: radius must be 0 .. %d (got %d)", RPE_FILTER_MAX_RADIUS, f->radius);
+  if (!std::isfinite(f->sigma_space) || !(f->sigma_space > 0) || !std::isfinite(f->depth_cut) || !(f->depth_cut > 0) ||
+      !std::isfinite(f->depth_cut_z2) || f->depth_cut_z2 < 0)
+    return fail(RPE_ERR_ARG, "rpe_frame_set_filter: need sigma_space > 0, depth_cut > 0 and depth_cut_z2 >= 0, all finite");
+  rpe::FilterParams P{};
+  P.radius = f->radius; P.a = (float)f->depth_cut; P.b = (float)f->depth_cut_z2;
+  int i = 0;
+  for (int dy = -f->radius; dy <= f->radius; dy++)
+    for (int dx = -f->radius; dx <= f->radius; dx++)
+      P.ws[i++] = (float)std::exp(-(double)(dx * dx + dy * dy) / (2 * f->sigma_space * f->sigma_space));
+  F.filter = *f; F.fparams = P;
+  return RPE_OK;
+}
+
+int rpe_frame_get_filter(rpe_context* c, rpe_depth_filter* out) {
+  if (!c || !out) return fail(RPE_ERR_ARG, "rpe_frame_get_filter: bad argument");
+  *out = c->fe.filter;
+  return RPE_OK;
+}
 
 int rpe_frame_set_depth(rpe_context* c, const void* depth, int depth_type, const rpe_camera* cam, double depth_scale, double dmin,
                         double dmax, double max_jump) {
@@ -113,7 +153,9 @@ int rpe_frame_set_depth(rpe_context* c, const void* depth, int depth_type, const
   if ((rc = ensure_maps(c, F.fmap, 3, &F.fcap, n))) return rc;
   F.have_frame = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(rpe::launch_frame_maps(F.d_depth, depth_type, k, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fmap[0],
+  DepthSource src;
+  if ((rc = depth_source(c, depth_type, k, (float)depth_scale, (float)dmin, (float)dmax, &src))) return rc;
+  HIP_TRY(rpe::launch_frame_maps(src.d, src.type, k, src.scale, (float)dmin, (float)dmax, (float)max_jump, F.fmap[0],
       F.fmap[1],
                                  F.fmap[2], c->stream));
   F.cam = k; F.have_frame = true;
@@ -143,7 +185,9 @@ int rpe_frame_set_depth_pyramid(rpe_context* c, const void* depth, int depth_typ
   }
   F.have_frame = false; F.have_depth = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(rpe::launch_frame_pyramid(F.d_depth, depth_type, g, (float)depth_scale, (float)dmin, (float)dmax, (float)max_jump, F.fdepth,
+  DepthSource src;
+  if ((rc = depth_source(c, depth_type, g.cam[0], (float)depth_scale, (float)dmin, (float)dmax, &src))) return rc;
+  HIP_TRY(rpe::launch_frame_pyramid(src.d, src.type, g, src.scale, (float)dmin, (float)dmax, (float)max_jump, F.fdepth,
                                     F.fmap[0], F.fmap[1], F.fmap[2], c->stream));
   F.cam = g.cam[0]; F.fgeo = g;
   for (int l = 0; l < levels; l++) F.kcam[l] = kc[l];

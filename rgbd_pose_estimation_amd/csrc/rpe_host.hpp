@@ -5,7 +5,7 @@
 //   rpe_refine.hip        the Gauss-Newton loops (host-driven resident, autonomous, one launch per iteration), host-thread tuning
 //   rpe_session.hip       resident scoring sessions (K4r)
 //   rpe_dist.hip          sharded contexts: RCCL communicator, in-kernel peer-to-peer, host-side exchange, sharded steps
-//   rpe_frontend_api.hip  Part 3: depth-frame front end and ICP
+//   rpe_frontend_api.hip  Part 3: depth-frame front end (with its optional depth filter) and ICP
 //   rpe_volume_api.hip    Part 3: TSDF volume (integrate, raycast into the model, upload / download)
 //   rpe_mesh_api.hip      Part 3: mesh extraction from the TSDF volume (marching cubes) and its download
 //   rpe_color_api.hip     Part 3: frame colour, the colour volume beside the TSDF, model and mesh colours
@@ -160,6 +160,11 @@ struct rpe_context {
     rpe_camera kcam[RPE_MAX_LEVELS] = {}, mkcam[RPE_MAX_LEVELS] = {};
     float* fdepth = nullptr; size_t fdcap = 0;
     bool have_depth = false;
+    // depth filter (rpe_frame_set_filter): the setting as given (radius 0 = off), its fp32 form for the kernel, and the filtered
+    // level-0 depth the next rpe_frame_set_depth* hands to F1 / F1p in the raw depth's place (allocated on first use, reused)
+    rpe_depth_filter filter = {0, 0.0, 0.0, 0.0};
+    rpe::FilterParams fparams{};
+    float* d_filt = nullptr; size_t filt_cap = 0;
     // colour (rpe_color_api.hip): the frame's 3-byte staging upload and its RGBA8 map (level-0 pixels, dropped by a new depth), and
     // the model's RGBA8 colour map (level-0 pixels, sampled from the colour volume, dropped by any call that replaces the model)
     unsigned char* d_rgb = nullptr; size_t rgb_cap = 0;

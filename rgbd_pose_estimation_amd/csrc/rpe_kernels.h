@@ -232,6 +232,14 @@ hipError_t launch_associate(const float* vmap, const float* nmap, const float* b
                             const Camera& mcam, const PoseF& T, const PoseF& M, float dist_sq, float cos_thr, int use_normals,
                             const double* pose_dev, const int* done, float* xw, float* xc, float* bv, float* nw, float* nc, int* d_count,
                             hipStream_t s);
+// ---- depth filter (rpe_filter.hip): F0, the optional stage in front of F1 / F1p.  ws = the (2 radius + 1)^2 spatial weights in row
+// order (dy outer, dx inner), a / b = the range cut-off a + b z^2; all cast by the host once (include/rgbd_pose_hip.h Part 3)
+constexpr int kFilterMaxRadius = 4;
+struct FilterParams { int radius; float a, b; float ws[(2 * kFilterMaxRadius + 1) * (2 * kFilterMaxRadius + 1)]; };
+// out := the filtered metric depth of the width x height image (NaN = invalid), what F1 / F1p then read as float32 with scale 1
+hipError_t launch_depth_filter(const void* d_depth, int depth_type, int width, int height, float scale, float dmin, float dmax,
+                               const FilterParams& P, float* out, hipStream_t s);
+void preload_filter();
 // ---- TSDF volume (rpe_volume.hip): voxels are float2 {tsdf, weight} at (k * dim1 + j) * dim0 + i; geometry cast from the descriptor's
 // doubles once (include/rgbd_pose_hip.h Part 3)
 struct VolumeGeometry { int dim[3]; float o[3]; float s, tr, W; };

@@ -15,6 +15,7 @@
 //   fe.initVolume(desc);  fe.setDepthPyramid(d0, cam, 3);  fe.integrate(T0);
 //   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.raycast(T, cam, range, 3);  fe.icpPyramid(T, {6, 4, 3});  fe.integrate(T);
 //   rpe::Mesh m = fe.mesh();                                             // the surface: marching cubes on the GPU
+// A real sensor's depth is noisy (centimetres at room distances): fe.setDepthFilter(rpe::DepthFilter()) once, before the first frame
 // With a registered RGB image per frame (pixel (u, v) of colour and depth see the same ray), the volume also fuses colour:
 //   fe.setDepth(d, cam);  fe.setColor(rgb);  fe.integrateColor(T);  ...  fe.modelColor();  fe.meshColors();   // RGBA8, 4 bytes each
 // ... and tracking can use it: a photometric term beside ICP holds the pose where the view is one plane (a wall, a floor, a corridor)
@@ -55,6 +56,13 @@ struct IcpOptions {
   // true
   // keeps solve and update on the GPU instead (also one launch, the grid iterates by itself: 12 us per round; no busy host thread)
   bool use_normals = true, device_resident = false, fused = true;
+};
+// bilateral filter on the metric depth of every later setDepth / setDepthPyramid (rpe_frame_set_filter): a (2 radius + 1)^2 window,
+// Gaussian in space (sigma_space pixels), biweight in range with the cut-off depth_cut + depth_cut_z2 z^2 metres; radius 0 = off
+struct DepthFilter {
+  int radius = 3;
+  double sigma_space = 2.0, depth_cut = 0.01, depth_cut_z2 = 0.02;
+  static DepthFilter off() { DepthFilter f; f.radius = 0; return f; }
 };
 // TSDF volume (rpe_volume_init): dim[0] x dim[1] x dim[2] voxels of voxel_size metres from the world corner origin
 struct VolumeDesc {
@@ -114,6 +122,19 @@ class DepthFrontEnd {
       const DepthRange& r = DepthRange::millimetres()) { set(depth, RPE_DEPTH_U16, cam, r, levels); }
   void setDepthPyramid(const float* depth, const PinholeCamera& cam, int levels,
       const DepthRange& r = DepthRange::metres()) { set(depth, RPE_DEPTH_F32, cam, r, levels); }
+  // denoise the depth of every LATER frame before its maps are built (a sensor's noise is centimetres at room distances: the normals
+  // of raw depth are mostly noise); the current frame is not touched.  setDepthFilter(DepthFilter::off()) turns it off again
+  void setDepthFilter(const DepthFilter& f) {
+    const rpe_depth_filter d = {f.radius, f.sigma_space, f.depth_cut, f.depth_cut_z2};
+    check(rpe_frame_set_filter(_ctx, &d), "rpe_frame_set_filter");
+  }
+  DepthFilter depthFilter() const {
+    rpe_depth_filter d;
+    check(rpe_frame_get_filter(_ctx, &d), "rpe_frame_get_filter");
+    DepthFilter f;
+    f.radius = d.radius; f.sigma_space = d.sigma_space; f.depth_cut = d.depth_cut; f.depth_cut_z2 = d.depth_cut_z2;
+    return f;
+  }
   // levels 1 .. levels-1 of the model from its level 0 (for a model given by setModel)
   void buildModelPyramid(int levels) { check(rpe_model_build_pyramid(_ctx, levels), "rpe_model_build_pyramid"); }
   // the current frame, seen from T_cw, becomes the model the next frames are registered against

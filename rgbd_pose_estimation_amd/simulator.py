@@ -289,6 +289,25 @@ def render_depth(R, t, cam=DEFAULT_CAMERA, room=None, noise_sigma: float = 0.0, 
     return z.astype(np.float32)
 
 
+def sensor_depth_sigma(z):
+    """Axial noise of a depth camera at range z metres, head-on: axial_noise_kinect(0, z) = 0.0012 + 0.0019 (z - 0.4)^2."""
+    return 0.0012 + 0.0019 * (np.asarray(z, np.float64) - 0.4) ** 2
+
+
+def sensor_depth(R, t, cam=DEFAULT_CAMERA, rng=None, as_u16: bool = True, room=None):
+    """render_depth as a depth camera delivers it: Gaussian noise whose sigma grows with the square of the range
+    (sensor_depth_sigma: 1.2 mm at 0.4 m, 6 mm at 2 m, 4 cm at 5 m), quantised to millimetres.  (height, width) uint16 millimetres, or
+    (as_u16 = False) the same values as float32 metres; 0 = no return.  rng: a numpy Generator; one standard normal per pixel is drawn."""
+    w, h = cam[4], cam[5]
+    _, _, lam = _cast(R, t, cam, room)
+    z = np.where(np.isfinite(lam), lam, 0.0)
+    z = np.where(z > 0, z + sensor_depth_sigma(z) * rng.standard_normal(z.shape), 0.0)
+    mm = np.clip(np.rint(z.reshape(h, w) * 1000.0), 0, 65535)
+    if as_u16:
+        return mm.astype(np.uint16)
+    return (mm / 1000.0).astype(np.float32)
+
+
 # Colour of the room for the colour front end (rpe_frame_set_color): per channel a sinusoid of the world point with wavelengths of
 # 1.2 .. 1.6 m, so that a volume of 4-cm voxels holds it (30 or more voxels per period).  Wave vectors (rad / m) and phases of r, g, b.
 TEXTURE_K = ((1.0, 5.0, 0.6), (1.5, 0.0, 3.7), (0.0, 2.0, 4.5))
