@@ -753,7 +753,7 @@ int rpe_relocalize(rpe_context* ctx, const rpe_feature_options* fopt, const rpe_
  * rpe_model_from_frame + rpe_model_color_from_frame + rpe_features_detect(RPE_FEAT_MODEL) first.  Ids are 0, 1, ... in insertion order;
  * at most RPE_MAX_KEYFRAMES.  The store belongs to the context: it survives new frames, new models, rpe_volume_init and new detections
  * and is freed with the context; its memory grows in steps as keyframes are added.  Removing ONE keyframe is out of scope:
- * rpe_keyframes_clear empties the store (a saved map comes back through rpe_keyframe_add_host).  Keyframes of different cameras may
+ * rpe_keyframes_clear empties the store and drops its graph (a saved map comes back through rpe_keyframe_add_host).  Keyframes of different cameras may
  * share a store.  A store has ONE descriptor kind, that of its first keyframe (rpe_keyframe_add: the kind of the model's detection;
  * rpe_keyframe_add_host: the context's current kind); rpe_keyframes_clear forgets it.  RPE_ERR_STATE for a keyframe of the other kind
  * added to a non-empty store, for rpe_keyframes_query / rpe_keyframe_match with frame features of the other kind, and for
@@ -799,6 +799,58 @@ int rpe_relocalize_keyframes(rpe_context* ctx, const rpe_feature_options* fopt, 
                              double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence, uint64_t seed, int ls,
                              int min_matches, double* pose12, int* keyframe, int* matches, int* max_votes, short* mask_out);
 
+/* ---- Keyframe graph: close loops -- every keyframe pose of the store refined jointly from keyframe-to-keyframe matches.  The pose
+ * kept with a keyframe is the tracker's at the time; after a long path the keyframes around a loop disagree by the accumulated drift.
+ * Here the keyframes are linked by the matches of their own keypoints (nothing new is detected or uploaded), and a gated Gauss-Newton
+ * over ALL poses makes the matched world points agree.  tests/graph_oracle.py states every rule in numpy.
+ * Graph: an edge (j, i), j > i, is the match list rpe_features_match would give with keyframe j's descriptors as the frame's and
+ * keyframe i's as the model's (cross-check per pair of keyframes), kept when it has >= min_matches (>= 3) pairs.  Edges are ordered
+ * by (j, i), the pairs of an edge by j's keypoints; a pair is (a, b) = positions inside keyframe j / keyframe i.  rpe_keyframes_link
+ * drops the edges whose newer keyframe is >= first and builds them again (first = a new keyframe's id links it; first = 0 rebuilds
+ * all): per j one launch of the store's matcher against the keyframes 0 .. j - 1 and ONE host wait.  rpe_graph_add_edge_host puts a
+ * caller's own pairs (a solver's inliers) in an edge's place.  The graph lives beside the store, grows in steps as it does, and
+ * rpe_keyframes_clear drops it.
+ * Round: poses are Xc = R Xw + t; keyframe k sits in the store at T0_k with fp32 world points x.  At trial poses T_k a point's world
+ * position is X_k(x) = C_k x + c_k, C_k = R_k^T R0_k, c_k = R_k^T (t0_k - t_k): computed on the host in fp64 and handed to the device
+ * as 12 floats per keyframe (a pose with the store's own bits gives the identity exactly).  In fp32, every product and sum rounded on
+ * its own: X[r] = (((C[3r] x[0]) + (C[3r+1] x[1])) + (C[3r+2] x[2])) + c[r].  A pair's residual is r = X_j(x_a) - X_i(x_b); it counts
+ * iff the six coordinates are finite and ((r0 r0) + (r1 r1)) + (r2 r2) < gate^2, gate cast to fp32 and squared in fp32.  The update is
+ * T_k <- exp(delta_k) T_k as rpe_gn_apply does it, tangent order (upsilon, omega): dX_k/d upsilon = -R_k^T, dX_k/d omega =
+ * R_k^T [p]x, p = R_k X_k + t_k; the residual's row by keyframe i has the other sign.  ONE launch serves every edge (one workgroup per
+ * edge); behind the fp32 rows all arithmetic is fp64 in a fixed order (no atomics): the same call gives the same bits.
+ * Record, RPE_GRAPH_RECORD doubles per edge: [0] counted pairs | [1] cost = sum |r|^2 | [2..7] g_j | [8..13] g_i | [14..34] H_jj upper
+ * triangle row-major | [35..55] H_ii upper triangle | [56..91] H_ji row-major (rows: keyframe j's tangent).  The system is H delta = -g.
+ * Optimise: per round the corrections, the launch, one copy of the records to the host, rpe_graph_solve, the left update; it ends
+ * early when |delta| < tol.  Fixed: `anchor`, and the lowest id of every other connected component -- components over the edges with
+ * >= 1 counted pair in the FIRST round; a keyframe without such an edge keeps its pose.  RPE_ERR_STATE without an edge;
+ * RPE_ERR_DEGENERATE (nothing is changed) when the joint system is not positive definite.  With apply != 0 the store takes the result:
+ * rpe_keyframe_info's poses are the new ones and every keypoint's xw <- C_k xw + c_k, nw <- C_k nw in the fp32 order above (nw without
+ * the + c), so that relocalisation answers in the corrected world; edges are indices and stay valid.
+ * Out of scope: re-integrating the TSDF or colour volume at the corrected poses (the store keeps no depth: the caller fuses its own
+ * frames again with the poses of rpe_keyframe_info); relative-pose (odometry) edges; robust kernels other than the gate; removing a
+ * keyframe; a sparse or device-side solve (rpe_graph_solve is dense, K <= RPE_MAX_KEYFRAMES). */
+enum { RPE_GRAPH_RECORD = 92 };
+/* (re)build the edges of the keyframes >= first (0 .. the store's count); *edges / *pairs (may be NULL) = the graph's totals.
+ * RPE_ERR_STATE with an empty store, RPE_ERR_ARG for first out of range, min_matches outside 3 .. RPE_MAX_KEYPOINTS or bad options */
+int rpe_keyframes_link(rpe_context* ctx, int first, const rpe_match_options* mopt, int min_matches, int* edges, int64_t* pairs);
+/* edge (j, i) := the caller's `count` (1 .. RPE_MAX_KEYPOINTS) pairs, replacing an existing edge (j, i); RPE_ERR_ARG for j <= i, ids
+ * that are not in the store and positions outside the keyframes.  A replacement that fits reuses the old pairs' place; dead pairs of
+ * replaced edges are compacted away once they outweigh the live ones */
+int rpe_graph_add_edge_host(rpe_context* ctx, int j, int i, int count, const int32_t* a, const int32_t* b);
+int rpe_graph_info(rpe_context* ctx, int* edges, int64_t* pairs);
+/* (j, i, count) per edge: 3 x edges int32 */
+int rpe_graph_edges(rpe_context* ctx, int32_t* jic);
+/* the pairs of edge number `edge` (its position in rpe_graph_edges' order): `count` int32 each (either may be NULL) */
+int rpe_graph_edge_download(rpe_context* ctx, int edge, int32_t* a, int32_t* b);
+/* r of every pair at poses12 (K x 12 doubles; NULL = the store's), edges in order: pairs x 3 floats, NaN where the pair does not count */
+int rpe_graph_residuals(rpe_context* ctx, const double* poses12, double gate, float* r);
+/* the records of one round: edges x RPE_GRAPH_RECORD doubles */
+int rpe_graph_normal_eq(rpe_context* ctx, const double* poses12, double gate, double* records);
+/* gates: one per round; stats (may be NULL): 3 x rounds doubles, per round run {counted pairs, cost, |delta|}; *rounds_out (may be
+ * NULL) = the rounds run; poses12_out (may be NULL): K x 12 doubles */
+int rpe_keyframes_optimize(rpe_context* ctx, int anchor, int rounds, const double* gates, double tol, int apply, double* poses12_out,
+                           double* stats, int* rounds_out);
+
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.
  * 3 x K inputs are column-major doubles whose values are rounded to dtype before use. */
@@ -814,6 +866,11 @@ void rpe_host_shinji(int dtype, const double* xw, const double* xc, int K, doubl
 void rpe_host_se3_exp(const double* a6, double* R9, double* t3);                                  /* sophus/se3.hpp:321-342 */
 void rpe_host_svd3(const double* A9, double* U9, double* s3, double* V9);
 void rpe_host_calc_err(const double* Rgt9, const double* tgt3, const double* Rse9, const double* tse3, double* err2, double* pct2);
+/* the joint system of a keyframe graph: K poses, `edges` records of RPE_GRAPH_RECORD doubles, ji = (j, i) per edge (2 x edges int32),
+ * fixed_mask (K bytes, may be NULL) != 0 for the keyframes that stay.  Assembles the 6K x 6K system, removes the fixed keyframes and
+ * solves H delta = -g by a dense Cholesky factorisation; delta = 6 x K doubles, 0 for a fixed keyframe and for one on no edge.
+ * RPE_ERR_DEGENERATE when the matrix is not positive definite (a pivot at or below 1e-12 of its diagonal entry) */
+int rpe_graph_solve(int K, int edges, const int32_t* ji, const double* records, const uint8_t* fixed_mask, double* delta);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,7 @@ MAX_KEYPOINTS = 4096
 DESC_UPRIGHT, DESC_ORIENTED = 0, 1
 MAX_KEYFRAMES = 256
 FILTER_MAX_RADIUS = 4
+GRAPH_RECORD = 92
 
 # every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -52,6 +53,8 @@ SYMBOLS = [
     "rpe_keyframes_query", "rpe_keyframe_match", "rpe_relocalize_keyframes",
     "rpe_features_set_descriptor", "rpe_features_get_descriptor", "rpe_features_angles", "rpe_keyframes_descriptor",
     "rpe_frame_set_filter", "rpe_frame_get_filter",
+    "rpe_keyframes_link", "rpe_graph_add_edge_host", "rpe_graph_info", "rpe_graph_edges", "rpe_graph_edge_download", "rpe_graph_residuals",
+    "rpe_graph_normal_eq", "rpe_keyframes_optimize", "rpe_graph_solve",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -254,6 +257,15 @@ def lib():
         L.rpe_relocalize_keyframes.argtypes = [C.c_void_p, C.POINTER(RpeFeatureOptions), C.POINTER(RpeMatchOptions), C.c_int, C.c_int, C.c_double,
                                                C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_keyframes_link.argtypes = [C.c_void_p, C.c_int, C.POINTER(RpeMatchOptions), C.c_int, C.c_void_p, C.c_void_p]
+        L.rpe_graph_add_edge_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rpe_graph_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_graph_edges.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_graph_edge_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rpe_graph_residuals.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        L.rpe_graph_normal_eq.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        L.rpe_keyframes_optimize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_graph_solve.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

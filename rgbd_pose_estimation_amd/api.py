@@ -652,6 +652,73 @@ class Context:
         return dict(pose12=p, keyframe=kf.value, matches=m.value, iters=it.value, max_votes=mv.value,
                     masks=mask[:3 * m.value].reshape(3, m.value).copy())
 
+    # ---- keyframe graph (Part 3): the keyframes linked by their matches, every pose refined jointly
+    def keyframes_link(self, first: int = 0, min_matches: int = 12, max_dist: int = 64, ratio=(8, 10), cross_check: bool = False):
+        """(Re)build the edges of the keyframes >= first against every older keyframe; returns the graph's (edges, pairs)."""
+        o = L.RpeMatchOptions(int(max_dist), int(ratio[0]), int(ratio[1]), int(cross_check))
+        e, n = C.c_int(0), C.c_int64(0)
+        L.check(L.lib().rpe_keyframes_link(self._h, int(first), C.byref(o), int(min_matches), C.byref(e), C.byref(n)))
+        return e.value, n.value
+
+    def graph_info(self):
+        """(edges, pairs) of the graph."""
+        e, n = C.c_int(0), C.c_int64(0)
+        L.check(L.lib().rpe_graph_info(self._h, C.byref(e), C.byref(n)))
+        return e.value, n.value
+
+    def graph_edges(self) -> np.ndarray:
+        """(edges, 3) int32: newer keyframe j, older keyframe i and the number of pairs, ordered by (j, i)."""
+        out = np.zeros((self.graph_info()[0], 3), np.int32)
+        L.check(L.lib().rpe_graph_edges(self._h, _p(out) if len(out) else None))
+        return out
+
+    def graph_edge(self, edge: int):
+        """(a, b) of edge number `edge`: positions inside keyframe j / keyframe i, in the order of j's keypoints."""
+        jic = self.graph_edges()
+        if not 0 <= int(edge) < len(jic):
+            raise L.RpeError(L.RPE_ERR_ARG, f"no edge {edge} ({len(jic)} in the graph)")
+        a, b = np.zeros(jic[edge, 2], np.int32), np.zeros(jic[edge, 2], np.int32)
+        L.check(L.lib().rpe_graph_edge_download(self._h, int(edge), _p(a), _p(b)))
+        return a, b
+
+    def graph_add_edge(self, j: int, i: int, a, b):
+        """Edge (j, i) := the caller's pairs (a solver's inliers), replacing an existing one."""
+        a, b = np.ascontiguousarray(a, np.int32).reshape(-1), np.ascontiguousarray(b, np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("a and b need one entry per pair")
+        L.check(L.lib().rpe_graph_add_edge_host(self._h, int(j), int(i), len(a), _p(a), _p(b)))
+
+    def _graph_poses(self, poses12):
+        if poses12 is None:
+            return None
+        p = np.ascontiguousarray(poses12, np.float64).reshape(-1, 12)
+        if len(p) != self.keyframes_len():
+            raise ValueError("one pose per keyframe")
+        return p
+
+    def graph_residuals(self, poses12=None, gate: float = 0.1) -> np.ndarray:
+        """(pairs, 3) float32: r of every pair at the poses (None: the store's), NaN where the pair does not count."""
+        p = self._graph_poses(poses12)
+        out = np.zeros((self.graph_info()[1], 3), np.float32)
+        L.check(L.lib().rpe_graph_residuals(self._h, None if p is None else _p(p), float(gate), _p(out)))
+        return out
+
+    def graph_normal_eq(self, poses12=None, gate: float = 0.1) -> np.ndarray:
+        """(edges, GRAPH_RECORD) float64: the records of one round."""
+        p = self._graph_poses(poses12)
+        out = np.zeros((self.graph_info()[0], L.GRAPH_RECORD), np.float64)
+        L.check(L.lib().rpe_graph_normal_eq(self._h, None if p is None else _p(p), float(gate), _p(out)))
+        return out
+
+    def keyframes_optimize(self, gates, anchor: int = 0, tol: float = 0.0, apply: bool = True):
+        """Gated Gauss-Newton over every keyframe pose, one round per gate.  Returns (poses (K, 12), stats (rounds run, 3): counted
+        pairs, cost and |delta| per round).  apply: the store takes the poses and its world points move with them."""
+        g = np.ascontiguousarray(gates, np.float64).reshape(-1)
+        poses = np.zeros((max(self.keyframes_len(), 1), 12), np.float64)
+        stats, done = np.zeros((max(len(g), 1), 3), np.float64), C.c_int(0)
+        L.check(L.lib().rpe_keyframes_optimize(self._h, int(anchor), len(g), _p(g), float(tol), int(bool(apply)), _p(poses), _p(stats), C.byref(done)))
+        return poses[:self.keyframes_len()], stats[:done.value]
+
     def volume_mesh_colors(self) -> np.ndarray:
         """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh): the colour field there, as model_color samples it."""
         n = self._mesh_nv or 0
@@ -823,6 +890,22 @@ def gn_apply(delta6, pose):
     p = np.array(pose, np.float64).reshape(12).copy()
     L.check(L.lib().rpe_gn_apply(_p(d), _p(p)))
     return p
+
+
+def graph_solve(K: int, ji, records, fixed=None):
+    """The joint update of a keyframe graph from its records (host, no GPU): delta (K, 6); fixed = ids or a mask of K."""
+    ji = np.ascontiguousarray(ji, np.int32).reshape(-1, 2)
+    rec = np.ascontiguousarray(records, np.float64).reshape(len(ji), L.GRAPH_RECORD)
+    mask = np.zeros(int(K), np.uint8)
+    if fixed is not None:
+        f = np.asarray(fixed)
+        if f.dtype == bool:
+            mask[:] = f
+        else:
+            mask[f.astype(np.int64)] = 1
+    d = np.zeros((int(K), 6), np.float64)
+    L.check(L.lib().rpe_graph_solve(int(K), len(ji), _p(ji), _p(rec), _p(mask), _p(d)))
+    return d
 
 
 def ao(xw, xc):

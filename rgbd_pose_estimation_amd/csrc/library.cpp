@@ -8,6 +8,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <cmath>
+#include <vector>
 
 namespace rpe { int set_error(int code, const char* msg); }
 
@@ -291,6 +293,68 @@ void rpe_host_calc_err(const double* Rgt9, const double* tgt3, const double* Rse
   ad.setRcw(Rb); ad.sett(tb);
   const rpe::Point3<double> p = calc_percentage_err<double>(Ra, ta, &ad);
   pct2[0] = p[0]; pct2[1] = p[1];
+}
+
+// The joint Gauss-Newton system of a keyframe graph from its per-edge records (RPE_GRAPH_RECORD doubles: pairs | cost | g_j | g_i |
+// H_jj, H_ii upper triangles | H_ji full): the 6K x 6K matrix over all poses, the rows and columns of the fixed keyframes removed, a
+// dense Cholesky factorisation (row by row: the inner loops run along contiguous rows of L) and the two triangular solves.  A
+// keyframe that is neither fixed nor on any edge has no equation and keeps delta = 0.  A pivot at or below 1e-12 of its diagonal
+// entry is "not positive definite", as in the 6 x 6 solves.
+int rpe_graph_solve(int K, int edges, const int32_t* ji, const double* records, const uint8_t* fixed_mask, double* delta) {
+  if (K < 1 || edges < 0 || !delta || (edges > 0 && (!ji || !records))) return rpe::set_error(RPE_ERR_ARG, "rpe_graph_solve: bad argument");
+  std::vector<int> slot(K, -1);
+  std::vector<char> seen(K, 0);
+  for (int e = 0; e < edges; e++) {
+    const int j = ji[2 * e], i = ji[2 * e + 1];
+    if (j < 0 || j >= K || i < 0 || i >= K || i == j) return rpe::set_error(RPE_ERR_ARG, "rpe_graph_solve: an edge names a keyframe outside 0 .. K - 1");
+    seen[j] = seen[i] = 1;
+  }
+  int F = 0;
+  for (int k = 0; k < K; k++) if (seen[k] && !(fixed_mask && fixed_mask[k])) slot[k] = F++;
+  for (int k = 0; k < 6 * K; k++) delta[k] = 0.0;
+  if (F == 0) return RPE_OK;
+  const size_t n = (size_t)6 * F;
+  std::vector<double> A(n * n, 0.0), g(n, 0.0);        // the lower triangle of A is what the factorisation reads
+  auto add_sym = [&](int s, const double* up) {          // a diagonal block from its upper triangle
+    int k = 0;
+    for (int r = 0; r < 6; r++) for (int c = r; c < 6; c++, k++) {
+      A[(6 * (size_t)s + c) * n + 6 * s + r] += up[k];
+      if (c != r) A[(6 * (size_t)s + r) * n + 6 * s + c] += up[k];
+    }
+  };
+  for (int e = 0; e < edges; e++) {
+    const double* R = records + (size_t)e * RPE_GRAPH_RECORD;
+    const int sj = slot[ji[2 * e]], si = slot[ji[2 * e + 1]];
+    if (sj >= 0) { for (int r = 0; r < 6; r++) g[6 * (size_t)sj + r] += R[2 + r]; add_sym(sj, R + 14); }
+    if (si >= 0) { for (int r = 0; r < 6; r++) g[6 * (size_t)si + r] += R[8 + r]; add_sym(si, R + 35); }
+    if (sj >= 0 && si >= 0)
+      for (int r = 0; r < 6; r++) for (int c = 0; c < 6; c++) {          // H_ji: rows of j, columns of i -- and its transpose
+        A[(6 * (size_t)sj + r) * n + 6 * si + c] += R[56 + 6 * r + c];
+        A[(6 * (size_t)si + c) * n + 6 * sj + r] += R[56 + 6 * r + c];
+      }
+  }
+  std::vector<double> diag(n);
+  for (size_t r = 0; r < n; r++) diag[r] = A[r * n + r];
+  for (size_t r = 0; r < n; r++) {                       // A = L L^T, L over A's lower triangle
+    double* Lr = &A[r * n];
+    for (size_t c = 0; c < r; c++) {
+      const double* Lc = &A[c * n];
+      double s = Lr[c];
+      for (size_t k = 0; k < c; k++) s -= Lr[k] * Lc[k];
+      Lr[c] = s / Lc[c];
+    }
+    double d = Lr[r];
+    for (size_t k = 0; k < r; k++) d -= Lr[k] * Lr[k];
+    if (!(d > 1e-12 * diag[r]) || !(d < 1e300))
+      return rpe::set_error(RPE_ERR_DEGENERATE, "rpe_graph_solve: the joint normal equations are not positive definite");
+    Lr[r] = std::sqrt(d);
+  }
+  std::vector<double> y(n);
+  for (size_t r = 0; r < n; r++) { double s = -g[r]; const double* Lr = &A[r * n]; for (size_t k = 0; k < r; k++) s -= Lr[k] * y[k]; y[r] = s / Lr[r]; }
+  for (size_t r = n; r-- > 0;) { double s = y[r]; for (size_t k = r + 1; k < n; k++) s -= A[k * n + r] * y[k]; y[r] = s / A[r * n + r]; }
+  for (size_t r = 0; r < n; r++) if (!std::isfinite(y[r])) return rpe::set_error(RPE_ERR_DEGENERATE, "rpe_graph_solve: the update is not finite");
+  for (int k = 0; k < K; k++) if (slot[k] >= 0) for (int r = 0; r < 6; r++) delta[6 * k + r] = y[6 * (size_t)slot[k] + r];
+  return RPE_OK;
 }
 
 int rpe_run(int method, const rpe_problem* p, double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence,

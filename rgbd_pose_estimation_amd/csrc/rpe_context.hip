@@ -3,6 +3,7 @@
 // channel (status code + thread-local message).  There is NO CPU fallback: every entry point that computes fails with
 // RPE_ERR_NO_DEVICE when no HIP device is usable.
 #include "rpe_host.hpp"
+#include "rpe_graph.h"
 using namespace rpeh;
 namespace { thread_local std::string g_err; }
 namespace rpeh {
@@ -159,7 +160,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
       rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
       rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_feature_oriented(); rpe::preload_keyframe();
-      rpe::preload_filter();
+      rpe::preload_filter(); rpe::preload_graph();
       loaded[device] = true;
     }
   }
@@ -215,6 +216,7 @@ void rpe_destroy(rpe_context* c) {
     for (void* m : {(void*)K.st.off, (void*)K.st.desc, (void*)K.st.xw, (void*)K.st.nw, (void*)K.st.xy, (void*)K.back, (void*)K.d1, (void*)K.idx,
                     (void*)K.d2, (void*)K.rank}) if (m) (void)hipFree(m);
   }
+  graph_free(c);
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);

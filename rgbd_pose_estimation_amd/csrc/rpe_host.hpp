@@ -12,6 +12,7 @@
 //   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
 //   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
+//   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -205,6 +206,7 @@ struct rpe_context {
     int rows_cap = 0;
     int kind = -1;                       // the descriptor kind of every keyframe in the store: its first one's (-1: the store is empty)
   } kf;
+  struct rpe_graph* graph = nullptr;     // the keyframe graph beside the store (rpe_graph.h), made by the first call that needs it
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
   struct Volume {
     rpe::VolumeGeometry g{};

@@ -344,6 +344,27 @@ hipError_t launch_keyframe_gather(const int* mf, const int* mm, int matches, con
                                   const float* fb, const KeyframeStore& S, int base, float* xw, float* xc, float* bv, float* nw, float* nc,
                                   hipStream_t s);
 void preload_keyframe();
+// ---- keyframe graph (rpe_graph.hip): edges of keyframe-to-keyframe matches beside the store, and the joint Gauss-Newton round over
+// all of them.  An edge (j, i), j > i, owns `count` pairs from `off` of the pair arrays a / b (positions inside keyframe j / keyframe
+// i); `out` = the pairs of the edges before it in (j, i) order (where the row kernel writes).
+struct GraphEdgeDev { int j, i, off, count, out, pad; };
+constexpr int kGraphRaw = 40;           // doubles per edge the round kernel leaves (38 sums, layout in rpe_graph.hip)
+constexpr int kGraphCorr = 12;          // floats per keyframe: C row-major (9) | c (3), X = C x + c
+// G1: the accepted pairs of keyframe j's keypoints (na of them; d1 / idx / d2 = K2's rows over the segments 0 .. segs - 1), segment s
+// written from pair base.v[s] in the order of j's keypoints, at most counts[s] of them (base.v[s] < 0: the segment is dropped).
+// The bases travel as a kernel argument (1 KB)
+struct GraphBases { int v[kMaxKeyframes]; };
+hipError_t launch_graph_pack(const int* d1, const int* idx, const int* d2, int na, int segs, const int* off, const KeyframeAccept& acc,
+                             const int* counts, const GraphBases& base, int* a, int* b, hipStream_t s);
+// G2: one launch for every edge: the raw record of edge e at raw[e * kGraphRaw]
+hipError_t launch_graph_round(const GraphEdgeDev* edges, int n_edges, const int* a, const int* b, const KeyframeStore& S, const float* corr,
+                              float gate2, double* raw, hipStream_t s);
+// G3: r of every pair at rows[3 * (out + k)], NaN where the pair does not count
+hipError_t launch_graph_rows(const GraphEdgeDev* edges, int n_edges, const int* a, const int* b, const KeyframeStore& S, const float* corr,
+                             float gate2, float* rows, hipStream_t s);
+// G4: xw <- C_k xw + c_k, nw <- C_k nw for every keypoint of the K keyframes (`used` keypoints)
+hipError_t launch_graph_apply(const KeyframeStore& S, int K, int used, const float* corr, hipStream_t s);
+void preload_graph();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

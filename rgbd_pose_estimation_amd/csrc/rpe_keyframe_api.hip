@@ -2,7 +2,7 @@
 // vertex and normal at every keypoint -- kept in a packed store that belongs to the context; one frame matched against all of them in
 // one pass (rpe_keyframes_query: the host waits once, for the counts and the ranking); one keyframe's matches in the solver slots
 // (rpe_keyframe_match); and rpe_relocalize_keyframes: the best-ranked candidates through rpe_run, the one with the most votes kept.
-#include "rpe_host.hpp"
+#include "rpe_graph.h"
 using namespace rpeh;
 
 namespace {
@@ -251,6 +251,56 @@ int rpe_keyframes_clear(rpe_context* c) {
   c->kf.used = 0;                                  // the storage stays, for the next map
   c->kf.kind = -1;
   if (c->fe.match_kf >= 0) { c->fe.matches = -1; c->fe.match_kf = -1; }
+  graph_drop_from(c, 0);                           // the graph's edges named these keyframes
+  return RPE_OK;
+}
+
+// The graph's edges from the store's own matcher (the graph itself: rpe_graph_api.hip).  Per newer keyframe j: the cross-check (every
+// keypoint of the keyframes before j against j's list), K2 with A = j's rows of the store and the segments 0 .. j - 1 -- j rows of
+// d1 / idx / d2, never the whole K x K --, ONE host wait for the j counts, room for the kept pairs, and G1 that writes them at the offsets the host hands it.
+int rpe_keyframes_link(rpe_context* c, int first, const rpe_match_options* mopt, int min_matches, int* edges, int64_t* pairs) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  const rpe_match_options o = mopt ? *mopt : kMatchDefaults;
+  int rc = match_options(&o);
+  if (rc) return rc;
+  auto& K = c->kf;
+  const int n = (int)K.meta.size();
+  if (n == 0) return fail(RPE_ERR_STATE, "rpe_keyframes_link: the keyframe store is empty (rpe_keyframe_add)");
+  if (first < 0 || first > n || min_matches < 3 || min_matches > RPE_MAX_KEYPOINTS)
+    return fail(RPE_ERR_ARG, "rpe_keyframes_link: first 0 .. %d (got %d), min_matches 3 .. %d (got %d)", n, first, RPE_MAX_KEYPOINTS, min_matches);
+  HIP_TRY(hipSetDevice(c->device));
+  rpe_graph* G = graph_of(c);
+  graph_drop_from(c, first);
+  for (int j = std::max(first, 1); j < n; j++) {
+    const auto& M = K.meta[j];
+    if (M.count == 0 || M.off == 0) continue;      // no keypoint of its own, or none before it
+    if ((rc = ensure_rows(c, j))) return rc;
+    HIP_TRY(hipMemsetAsync(K.rank, 0, (size_t)j * sizeof(int), c->stream));
+    const unsigned int* dj = K.st.desc + 8 * (size_t)M.off;
+    if (o.cross_check)
+      HIP_TRY(rpe::launch_keyframe_best(K.st.desc, M.off, dj, nullptr, 0, 1, 0, M.count, rpe::KeyframeAccept{0, 1, 1, nullptr}, nullptr, K.back,
+                                        nullptr, nullptr, c->stream));
+    const rpe::KeyframeAccept acc{o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? K.back : nullptr};
+    HIP_TRY(rpe::launch_keyframe_best(dj, M.count, K.st.desc, K.st.off, 0, j, 0, 0, acc, K.d1, K.idx, K.d2, K.rank, c->stream));
+    int counts[rpe::kMaxKeyframes];
+    if ((rc = read_ints(c, K.rank, j, counts))) return rc;
+    int64_t total = 0;
+    for (int i = 0; i < j; i++) if (counts[i] >= min_matches) total += counts[i];
+    if (total == 0) continue;
+    if (G->used + total > kGraphMaxPairs) return fail(RPE_ERR_STATE, "rpe_keyframes_link: more than 2^30 pairs");
+    if ((rc = graph_reserve(c, total))) return rc;
+    // where each kept edge's pairs go (-1: the edge is dropped): handed to G1 by value, so nothing is uploaded or waited for
+    rpe::GraphBases base;
+    for (int i = 0; i < j; i++) {
+      base.v[i] = -1;
+      if (counts[i] >= min_matches) { base.v[i] = (int)G->used; G->edges.push_back(rpe_graph::Edge{j, i, (int)G->used, counts[i]}); G->used += counts[i]; }
+    }
+    HIP_TRY(rpe::launch_graph_pack(K.d1, K.idx, K.d2, M.count, j, K.st.off, acc, K.rank, base, G->a, G->b, c->stream));
+  }
+  G->dirty = true;
+  if (edges) *edges = (int)G->edges.size();
+  if (pairs) *pairs = G->pairs();
   return RPE_OK;
 }
 

@@ -29,6 +29,10 @@
 // ... against ALL the keyframes it has kept, without knowing which one the camera sees (the store lives in the context)
 //   at every keyframe: fe.setModelFromFrame(T);  fe.modelColorFromFrame();  fe.detectFeatures(RPE_FEAT_MODEL);  fe.addKeyframe();
 //   when lost:         rpe::KeyframeRelocResult r = fe.relocalizeKeyframes(6, 0.05, 3.0, 0.1);   // r.keyframe = the one it chose
+// ... and when a LOOP closes, the keyframes' poses are made consistent: linked by their own matches, refined jointly, the store rewritten
+//   after addKeyframe(): fe.linkKeyframes(id);   at a loop: rpe::GraphResult g = fe.optimizeKeyframes({0.1, 0.1, 0.05, 0.05, 0.03});
+//   (g.poses[k] = keyframe k's corrected pose.  Out of scope: the TSDF / colour volume is NOT re-integrated -- the store keeps no depth;
+//   fuse your own frames again with g.poses.  No odometry edges, no robust kernel but the gate, dense host solve.)
 //
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
@@ -97,6 +101,14 @@ struct RelocResult {
 struct KeyframeRelocResult : RelocResult { int keyframe = -1; };
 // queryKeyframes(): per keyframe the matches the frame would have against it, and the ids by (count descending, id ascending)
 struct KeyframeRanking { std::vector<int> counts, order; };
+// optimizeKeyframes(): the pose of every keyframe and, per round run, the counted pairs, the cost and |delta|; ok = false: the joint
+// system was not positive definite and nothing was changed
+struct GraphResult {
+  bool ok = false;
+  std::vector<SE3<double> > poses;
+  std::vector<int64_t> pairs;
+  std::vector<double> cost, step;
+};
 
 class DepthFrontEnd {
  public:
@@ -416,6 +428,37 @@ class DepthFrontEnd {
     r.masks.resize(r.ok ? (size_t)3 * r.matches : 0);
     if (r.ok) r.pose = pose_of(p);
     return r;
+  }
+  // (re)build the graph's edges of the keyframes >= first against every older keyframe (first = a new keyframe's id links it alone):
+  // an edge = the matches of the two keyframes' own keypoints, kept with >= min_matches pairs.  Returns the graph's edges
+  int linkKeyframes(int first = 0, int min_matches = 12, const MatchOptions& o = MatchOptions()) {
+    const rpe_match_options mo = {o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? 1 : 0};
+    int edges = 0;
+    check(rpe_keyframes_link(_ctx, first, &mo, min_matches, &edges, nullptr), "rpe_keyframes_link");
+    return edges;
+  }
+  Pose keyframePose(int id) {
+    double p[12];
+    check(rpe_keyframe_info(_ctx, id, nullptr, p, nullptr, nullptr), "rpe_keyframe_info");
+    return pose_of(p);
+  }
+  // gated Gauss-Newton over every keyframe pose, one round per gate (metres); `anchor` stays.  apply: the store takes the poses and
+  // its world points move with them, so that relocalizeKeyframes answers in the corrected world
+  GraphResult optimizeKeyframes(const std::vector<double>& gates, int anchor = 0, double tol = 0.0, bool apply = true) {
+    GraphResult g;
+    const int n = keyframes(), rounds = (int)gates.size();
+    std::vector<double> p((size_t)12 * std::max(n, 1)), stats((size_t)3 * std::max(rounds, 1));
+    int done = 0;
+    const int rc = rpe_keyframes_optimize(_ctx, anchor, rounds, gates.data(), tol, apply ? 1 : 0, p.data(), stats.data(), &done);
+    if (rc != RPE_ERR_DEGENERATE) check(rc, "rpe_keyframes_optimize");
+    g.ok = rc == RPE_OK;
+    if (!g.ok) return g;
+    for (int k = 0; k < n; k++) g.poses.push_back(pose_of(p.data() + 12 * k));
+    for (int r = 0; r < done; r++) {
+      const double* st = stats.data() + (size_t)3 * r;
+      g.pairs.push_back((int64_t)st[0]); g.cost.push_back(st[1]); g.step.push_back(st[2]);
+    }
+    return g;
   }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
