@@ -826,9 +826,10 @@ int rpe_relocalize_keyframes(rpe_context* ctx, const rpe_feature_options* fopt, 
  * RPE_ERR_DEGENERATE (nothing is changed) when the joint system is not positive definite.  With apply != 0 the store takes the result:
  * rpe_keyframe_info's poses are the new ones and every keypoint's xw <- C_k xw + c_k, nw <- C_k nw in the fp32 order above (nw without
  * the + c), so that relocalisation answers in the corrected world; edges are indices and stay valid.
- * Out of scope: re-integrating the TSDF or colour volume at the corrected poses (the store keeps no depth: the caller fuses its own
- * frames again with the poses of rpe_keyframe_info); relative-pose (odometry) edges; robust kernels other than the gate; removing a
- * keyframe; a sparse or device-side solve (rpe_graph_solve is dense, K <= RPE_MAX_KEYFRAMES). */
+ * The TSDF and colour volume follow through rpe_volume_fuse_keyframes ("Keyframe depth and rebuilding the volume" below): keyframes
+ * that carry their depth are fused again at the corrected poses in one launch.
+ * Out of scope: relative-pose (odometry) edges; robust kernels other than the gate; removing a keyframe; a sparse or device-side
+ * solve (rpe_graph_solve is dense, K <= RPE_MAX_KEYFRAMES). */
 enum { RPE_GRAPH_RECORD = 92 };
 /* (re)build the edges of the keyframes >= first (0 .. the store's count); *edges / *pairs (may be NULL) = the graph's totals.
  * RPE_ERR_STATE with an empty store, RPE_ERR_ARG for first out of range, min_matches outside 3 .. RPE_MAX_KEYPOINTS or bad options */
@@ -850,6 +851,52 @@ int rpe_graph_normal_eq(rpe_context* ctx, const double* poses12, double gate, do
  * NULL) = the rounds run; poses12_out (may be NULL): K x 12 doubles */
 int rpe_keyframes_optimize(rpe_context* ctx, int anchor, int rounds, const double* gates, double tol, int apply, double* poses12_out,
                            double* stats, int* rounds_out);
+
+/* ---- Keyframe depth and rebuilding the volume: after rpe_keyframes_optimize(apply = 1) the store answers in the corrected world, but
+ * the TSDF and colour volume still hold every frame fused at its drifted pose.  A keyframe may therefore carry an ATTACHMENT -- its
+ * level-0 metric depth, the camera it was taken with and, optionally, its colour -- and rpe_volume_fuse_keyframes fuses a list of
+ * attachments into the context's volume in ONE pass over the voxels.  tests/rebuild_oracle.py states the result in numpy.
+ * Attachment: the depth is a packed plane, one fp32 per pixel, NaN = invalid: exactly the values rpe_volume_integrate reads from the
+ * frame, the z of its level-0 vertex map (so an attached keyframe fuses as the frame itself would have, depth filter included); the
+ * colour is the frame's RGBA8 map.  The camera is kept as the rpe_camera given and as the fp32 camera the kernels use.  The memory
+ * belongs to the store: rpe_keyframes_clear drops every attachment (and keeps the memory for the next keyframes), rpe_destroy frees
+ * it.  Cost: 4 B per pixel for the depth plus 4 B per pixel for the colour -- 2.4 MB per keyframe at 640 x 480, about 630 MB for a
+ * full store of RPE_MAX_KEYFRAMES.  Attachments do not take part in rpe_keyframes_optimize, rpe_keyframes_link, rpe_keyframes_query
+ * or rpe_relocalize_keyframes: their outputs are the same bits with and without.
+ * Fuse, THE CONTRACT: after rpe_volume_fuse_keyframes the volume, the colour volume and every piece of volume state are, bit for
+ * bit, what this sequence leaves:
+ *   1. with RPE_FUSE_CLEAR: rpe_volume_init with the volume's own descriptor;
+ *   2. for each list entry in order: that keyframe's depth (and colour) as the current frame, then rpe_volume_integrate(pose) or,
+ *      with RPE_FUSE_COLOR, rpe_volume_integrate_color(pose), the pose cast to fp32 as every integrate casts it.
+ * The state this covers: a mesh extracted before stays valid without RPE_FUSE_CLEAR and is dropped with it; with RPE_FUSE_CLEAR
+ * but without RPE_FUSE_COLOR the colour volume is dropped, as rpe_volume_init drops it; with both it exists and untouched voxels are
+ * zero; without RPE_FUSE_CLEAR, RPE_FUSE_COLOR makes (and clears) a colour volume if there is none.  A voxel that no keyframe updates
+ * keeps its bits (without RPE_FUSE_CLEAR) or is zero (with it).  The current frame, the model and the store are not touched.  The
+ * host waits once, for the upload of the list's descriptor table.
+ * Cull: a workgroup of the kernel owns a brick of 32 x 8 x 4 voxels and skips the list entries that cannot update any of them (every
+ * voxel centre behind the camera, or all outside the same image edge).  The test is conservative: the result has the same bits
+ * with RPE_FUSE_NO_CULL, which switches it off (tests, timing).
+ * Out of scope: the frames BETWEEN keyframes (the rebuilt volume holds the keyframes only); de-integrating a single frame; fusing
+ * in any order but the list's; compressing the stored depth (16-bit or binary16 depth would break the bit contract); moving the
+ * volume; removing a keyframe; rpe_keyframe_add attaching by itself. */
+enum { RPE_FUSE_CLEAR = 1, RPE_FUSE_COLOR = 2, RPE_FUSE_NO_CULL = 4 };
+/* the CURRENT frame's level-0 depth (z of its vertex map), its camera and, if it has one, its colour become keyframe id's attachment
+ * (replacing an earlier one).  RPE_ERR_STATE without a frame; RPE_ERR_ARG for an id not in the store or a frame whose level-0 size is
+ * not the keyframe's width x height */
+int rpe_keyframe_attach_frame(rpe_context* ctx, int id);
+/* the same from host arrays: z = width*height floats (NaN = invalid; the bits are taken as given), rgba = 4*width*height bytes or NULL,
+ * cam as everywhere in Part 3 (its size must be the keyframe's) */
+int rpe_keyframe_attach_host(rpe_context* ctx, int id, const float* z, const uint8_t* rgba, const rpe_camera* cam);
+/* what is attached (any output may be NULL): *have_depth, *have_color 0 / 1, the camera (all zero without an attachment) */
+int rpe_keyframe_attachment_info(rpe_context* ctx, int id, int* have_depth, int* have_color, rpe_camera* cam);
+/* copy the attachment out (either may be NULL); RPE_ERR_STATE for what is not attached */
+int rpe_keyframe_attachment_download(rpe_context* ctx, int id, float* z, uint8_t* rgba);
+/* fuse the attachments of `count` (1 .. RPE_MAX_KEYFRAMES) keyframes into the context's volume, in list order; ids = NULL: every
+ * keyframe that has a depth attachment, by ascending id (count ignored).  poses12 = NULL: the store's poses (rpe_keyframe_info's);
+ * else one pose per LIST ENTRY (count x 12 doubles).  Repeated ids are allowed.
+ * RPE_ERR_STATE without a volume, for a listed keyframe without depth, with RPE_FUSE_COLOR for one without colour, and with ids = NULL
+ * when no keyframe has depth; RPE_ERR_ARG for ids not in the store, bad count or unknown flags. */
+int rpe_volume_fuse_keyframes(rpe_context* ctx, const int32_t* ids, int count, const double* poses12, int flags);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

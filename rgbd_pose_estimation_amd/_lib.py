@@ -32,6 +32,7 @@ DESC_UPRIGHT, DESC_ORIENTED = 0, 1
 MAX_KEYFRAMES = 256
 FILTER_MAX_RADIUS = 4
 GRAPH_RECORD = 92
+FUSE_CLEAR, FUSE_COLOR, FUSE_NO_CULL = 1, 2, 4
 
 # every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -55,6 +56,8 @@ SYMBOLS = [
     "rpe_frame_set_filter", "rpe_frame_get_filter",
     "rpe_keyframes_link", "rpe_graph_add_edge_host", "rpe_graph_info", "rpe_graph_edges", "rpe_graph_edge_download", "rpe_graph_residuals",
     "rpe_graph_normal_eq", "rpe_keyframes_optimize", "rpe_graph_solve",
+    "rpe_keyframe_attach_frame", "rpe_keyframe_attach_host", "rpe_keyframe_attachment_info", "rpe_keyframe_attachment_download",
+    "rpe_volume_fuse_keyframes",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -266,6 +269,11 @@ def lib():
         L.rpe_graph_normal_eq.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
         L.rpe_keyframes_optimize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_graph_solve.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_keyframe_attach_frame.argtypes = [C.c_void_p, C.c_int]
+        L.rpe_keyframe_attach_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(RpeCamera)]
+        L.rpe_keyframe_attachment_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(RpeCamera)]
+        L.rpe_keyframe_attachment_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rpe_volume_fuse_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

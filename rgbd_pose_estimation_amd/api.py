@@ -719,6 +719,55 @@ class Context:
         L.check(L.lib().rpe_keyframes_optimize(self._h, int(anchor), len(g), _p(g), float(tol), int(bool(apply)), _p(poses), _p(stats), C.byref(done)))
         return poses[:self.keyframes_len()], stats[:done.value]
 
+    # ---- keyframe depth (Part 3): a keyframe's depth and colour kept beside it, the volume rebuilt from a list of keyframes
+    def keyframe_attach_frame(self, kf: int):
+        """The current frame's level-0 depth (the z of its vertex map, NaN = invalid), its camera and, if it has one, its colour become
+        keyframe kf's attachment, replacing an earlier one."""
+        L.check(L.lib().rpe_keyframe_attach_frame(self._h, int(kf)))
+        return self
+
+    def keyframe_attach(self, kf: int, z, rgba=None, cam=(585.0, 585.0, 320.0, 240.0, 640, 480)):
+        """The same from host arrays: z (height, width) float32 metric depth, NaN = invalid (the bits are taken as given); rgba
+        (height, width, 4) uint8 or None; cam the camera they were taken with (its size must be the keyframe's)."""
+        k = self._camera(cam)
+        d = np.ascontiguousarray(z, np.float32)
+        if d.size != k.width * k.height:
+            raise ValueError(f"keyframe_attach: z has {d.size} values, the camera {k.width * k.height} pixels")
+        c = None
+        if rgba is not None:
+            c = np.ascontiguousarray(rgba, np.uint8)
+            if c.size != 4 * k.width * k.height:
+                raise ValueError(f"keyframe_attach: rgba has {c.size} bytes, the camera {4 * k.width * k.height}")
+        L.check(L.lib().rpe_keyframe_attach_host(self._h, int(kf), _p(d), None if c is None else _p(c), C.byref(k)))
+        return self
+
+    def keyframe_attachment(self, kf: int):
+        """dict(z (height, width) float32 or None, rgba (height, width, 4) uint8 or None, cam (fx, fy, cx, cy, width, height) or None)
+        of what keyframe kf carries."""
+        hd, hc, k = C.c_int(0), C.c_int(0), L.RpeCamera()
+        L.check(L.lib().rpe_keyframe_attachment_info(self._h, int(kf), C.byref(hd), C.byref(hc), C.byref(k)))
+        if not hd.value:
+            return dict(z=None, rgba=None, cam=None)
+        z = np.empty((k.height, k.width), np.float32)
+        c = np.empty((k.height, k.width, 4), np.uint8) if hc.value else None
+        L.check(L.lib().rpe_keyframe_attachment_download(self._h, int(kf), _p(z), None if c is None else _p(c)))
+        return dict(z=z, rgba=c, cam=(k.fx, k.fy, k.cx, k.cy, k.width, k.height))
+
+    def volume_fuse_keyframes(self, ids=None, poses=None, clear: bool = True, color: bool = False, cull: bool = True):
+        """Fuse the attachments of the keyframes `ids` (None: every keyframe that carries depth, by id) into the volume in list order,
+        one launch: bit for bit what volume_init (clear) and one volume_integrate / volume_integrate_color (color) per entry leave.
+        poses: one (12,) pose per list entry, None = the store's.  cull=False switches the per-workgroup cull off (the same bits)."""
+        flags = (L.FUSE_CLEAR if clear else 0) | (L.FUSE_COLOR if color else 0) | (0 if cull else L.FUSE_NO_CULL)
+        i = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        if p is not None and (i is None or len(p) != len(i)):
+            raise ValueError("volume_fuse_keyframes: poses need ids, and one pose per list entry")
+        L.check(L.lib().rpe_volume_fuse_keyframes(self._h, None if i is None else _p(i), 0 if i is None else len(i),
+                                                  None if p is None else _p(p), flags))
+        if clear:
+            self._mesh_nv = None
+        return self
+
     def volume_mesh_colors(self) -> np.ndarray:
         """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh): the colour field there, as model_color samples it."""
         n = self._mesh_nv or 0

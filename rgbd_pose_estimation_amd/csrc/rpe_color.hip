@@ -25,9 +25,7 @@ namespace {
 constexpr int kVolBlock = 256;    // C2: 4 voxels per lane, as V1
 constexpr int kColorBlock = 256;  // C1, C3: one pixel / point per lane
 
-// binary16 <-> fp32.  h(x): round to nearest even, subnormals kept, every NaN to the quiet NaN 0x7e00.
-__device__ __forceinline__ float h2f(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
-__device__ __forceinline__ unsigned f2h(float x) { return x == x ? (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x) : 0x7e00u; }
+// binary16 <-> fp32 (h2f, f2h) and the colour update of one voxel (blend): rpe_volume_field.hpp, shared with rpe_rebuild.hip.
 
 // ---------------------------------------------------------------------------------------------- C1
 __global__ __launch_bounds__(kColorBlock) void frame_color_kernel(const unsigned char* __restrict__ rgb, int64_t n, int bgr,
@@ -40,17 +38,7 @@ __global__ __launch_bounds__(kColorBlock) void frame_color_kernel(const unsigned
 }
 
 // ---------------------------------------------------------------------------------------------- C2
-// One voxel's colour {r, g, b, wc} as two words (rg = r | g << 16, bw = b | wc << 16) and the observation o (RGBA8): with w = (float)wc
-// before the update, each channel c := h(((float)c * w + o) / (w + 1.0f)), then wc := h(fminf(w + 1.0f, W)).
-__device__ __forceinline__ void blend(unsigned& rg, unsigned& bw, unsigned o, float W) {
-  const float w = h2f(bw >> 16);
-  const float r = (h2f(rg & 0xffffu) * w + (float)(o & 0xffu)) / (w + 1.0f);
-  const float g = (h2f(rg >> 16) * w + (float)((o >> 8) & 0xffu)) / (w + 1.0f);
-  const float b = (h2f(bw & 0xffffu) * w + (float)((o >> 16) & 0xffu)) / (w + 1.0f);
-  rg = f2h(r) | f2h(g) << 16;
-  bw = f2h(b) | f2h(fminf(w + 1.0f, W)) << 16;
-}
-
+// A voxel's colour update: blend (rpe_volume_field.hpp).
 // nvox <= 2^30 (dims <= 1024): the flat voxel index fits 32 bits, byte offsets do not
 __global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float* __restrict__ vol, unsigned short* __restrict__ cvol,
                                                                            VolumeGeometry G, int64_t nvox, const float* __restrict__ vmap,

@@ -160,7 +160,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
       rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
       rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_feature_oriented(); rpe::preload_keyframe();
-      rpe::preload_filter(); rpe::preload_graph();
+      rpe::preload_filter(); rpe::preload_graph(); rpe::preload_rebuild();
       loaded[device] = true;
     }
   }
@@ -214,7 +214,8 @@ void rpe_destroy(rpe_context* c) {
   {
     const auto& K = c->kf;
     for (void* m : {(void*)K.st.off, (void*)K.st.desc, (void*)K.st.xw, (void*)K.st.nw, (void*)K.st.xy, (void*)K.back, (void*)K.d1, (void*)K.idx,
-                    (void*)K.d2, (void*)K.rank}) if (m) (void)hipFree(m);
+                    (void*)K.d2, (void*)K.rank, (void*)K.d_table}) if (m) (void)hipFree(m);
+    for (const auto& A : K.att) for (void* m : {(void*)A.z, (void*)A.rgba}) if (m) (void)hipFree(m);
   }
   graph_free(c);
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }

@@ -13,6 +13,7 @@
 //   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
 //   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)
+//   rpe_rebuild_api.hip   Part 3: the volume rebuilt from the keyframes' attached depth (rpe_volume_fuse_keyframes; kernels in rpe_rebuild.hip)
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -205,6 +206,14 @@ struct rpe_context {
     int *back = nullptr, *d1 = nullptr, *idx = nullptr, *d2 = nullptr, *rank = nullptr;
     int rows_cap = 0;
     int kind = -1;                       // the descriptor kind of every keyframe in the store: its first one's (-1: the store is empty)
+    // attachments (rpe_keyframe_attach_*): per keyframe id its level-0 depth as a packed plane (NaN = invalid), optionally its RGBA8
+    // colour, and the camera both were taken with (fp32 for the kernels, the rpe_camera it was cast from).  att may be shorter than
+    // meta (a keyframe without an entry has nothing attached); rpe_keyframes_clear drops what is attached and keeps the memory for
+    // the next keyframe of that id.  d_table: the descriptor table of rpe_volume_fuse_keyframes (RPE_MAX_KEYFRAMES entries)
+    struct Attachment { float* z = nullptr; unsigned int* rgba = nullptr; size_t zcap = 0, ccap = 0; bool have_depth = false, have_color = false;
+                        rpe::Camera cam{}; rpe_camera kcam{}; };
+    std::vector<Attachment> att;
+    rpe::FuseEntry* d_table = nullptr;
   } kf;
   struct rpe_graph* graph = nullptr;     // the keyframe graph beside the store (rpe_graph.h), made by the first call that needs it
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM

@@ -365,6 +365,17 @@ hipError_t launch_graph_rows(const GraphEdgeDev* edges, int n_edges, const int* 
 // G4: xw <- C_k xw + c_k, nw <- C_k nw for every keypoint of the K keyframes (`used` keypoints)
 hipError_t launch_graph_apply(const KeyframeStore& S, int K, int used, const float* corr, hipStream_t s);
 void preload_graph();
+// ---- rebuilding the volume from keyframes (rpe_rebuild.hip).  A keyframe's attachment is its level-0 depth as a packed plane (one fp32
+// per pixel, NaN = invalid) and, optionally, its RGBA8 colour; a list entry of the fuse is one attachment with the camera it was taken
+// with and the pose it is fused at.  The table of a call lives in device memory (count <= kMaxKeyframes entries)
+struct FuseEntry { const float* z; const unsigned int* rgba; Camera cam; PoseF T; };
+// R1: z[i] = vmap[3 i + 2] for the n pixels of a vertex map; fcolor != nullptr: rgba[i] = fcolor[i] too
+hipError_t launch_attach_pack(const float* vmap, const unsigned int* fcolor, int64_t n, float* z, unsigned int* rgba, hipStream_t s);
+// R2: the entries fused in list order in one pass over the volume, each as V1 (color: as C2, cvol written too) would fuse it.  clear:
+// the volume (and cvol) is taken as all zero and every voxel is written; cull = false switches the per-workgroup cull off
+hipError_t launch_volume_fuse(float* vol, unsigned short* cvol, const VolumeGeometry& G, const FuseEntry* table, int count, bool clear,
+                              bool color, bool cull, hipStream_t s);
+void preload_rebuild();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

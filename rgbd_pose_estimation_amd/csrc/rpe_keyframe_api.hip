@@ -160,6 +160,26 @@ int match_from_row(rpe_context* c, int id, int row, const rpe_match_options& o, 
   if (matches) *matches = m;
   return RPE_OK;
 }
+// keyframe id's attachment slot with room for n pixels of depth (and of colour); what was attached is dropped
+int attachment_room(rpe_context* c, int id, size_t n, bool color) {
+  auto& K = c->kf;
+  if (K.att.size() < K.meta.size()) K.att.resize(K.meta.size());
+  auto& A = K.att[id];
+  A.have_depth = A.have_color = false;
+  const bool grow_z = !A.z || A.zcap < n * sizeof(float), grow_c = color && (!A.rgba || A.ccap < n * 4);
+  if (grow_z || grow_c) HIP_TRY(hipStreamSynchronize(c->stream));   // a fuse in flight may still read the old planes
+  if (grow_z) {
+    if (A.z) { HIP_TRY(hipFree(A.z)); A.z = nullptr; A.zcap = 0; }
+    HIP_TRY(hipMalloc((void**)&A.z, n * sizeof(float)));
+    A.zcap = n * sizeof(float);
+  }
+  if (grow_c) {
+    if (A.rgba) { HIP_TRY(hipFree(A.rgba)); A.rgba = nullptr; A.ccap = 0; }
+    HIP_TRY(hipMalloc((void**)&A.rgba, n * 4));
+    A.ccap = n * 4;
+  }
+  return RPE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -242,11 +262,86 @@ int rpe_keyframes_descriptor(rpe_context* c, int* kind) {
   return RPE_OK;
 }
 
+// ---- attachments: a keyframe's level-0 depth (and colour) kept beside it, for rpe_volume_fuse_keyframes (rpe_rebuild_api.hip)
+int rpe_keyframe_attach_frame(rpe_context* c, int id) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  auto& K = c->kf;
+  const auto& F = c->fe;
+  if (id < 0 || id >= (int)K.meta.size()) return fail(RPE_ERR_ARG, "rpe_keyframe_attach_frame: no keyframe %d (%d in the store)", id, (int)K.meta.size());
+  if (!F.have_frame) return fail(RPE_ERR_STATE, "rpe_keyframe_attach_frame: no frame (rpe_frame_set_depth)");
+  if (F.cam.width != K.meta[id].width || F.cam.height != K.meta[id].height)
+    return fail(RPE_ERR_ARG, "rpe_keyframe_attach_frame: the frame is %d x %d, keyframe %d is %d x %d", F.cam.width, F.cam.height, id,
+                K.meta[id].width, K.meta[id].height);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)F.cam.width * F.cam.height;
+  int rc = attachment_room(c, id, n, F.have_fcolor);
+  if (rc) return rc;
+  auto& A = K.att[id];
+  HIP_TRY(rpe::launch_attach_pack(F.fmap[0], F.have_fcolor ? F.fcolor : nullptr, (int64_t)n, A.z, A.rgba, c->stream));
+  A.cam = F.cam; A.kcam = F.kcam[0];
+  A.have_depth = true; A.have_color = F.have_fcolor;
+  return RPE_OK;
+}
+
+int rpe_keyframe_attach_host(rpe_context* c, int id, const float* z, const uint8_t* rgba, const rpe_camera* cam) {
+  session_end(c);
+  if (!c || !z) return fail(RPE_ERR_ARG, "rpe_keyframe_attach_host: bad argument");
+  auto& K = c->kf;
+  if (id < 0 || id >= (int)K.meta.size()) return fail(RPE_ERR_ARG, "rpe_keyframe_attach_host: no keyframe %d (%d in the store)", id, (int)K.meta.size());
+  rpe::Camera k;
+  int rc = camera_of(cam, &k);
+  if (rc) return rc;
+  if (k.width != K.meta[id].width || k.height != K.meta[id].height)
+    return fail(RPE_ERR_ARG, "rpe_keyframe_attach_host: the camera is %d x %d, keyframe %d is %d x %d", k.width, k.height, id, K.meta[id].width,
+                K.meta[id].height);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)k.width * k.height;
+  if ((rc = attachment_room(c, id, n, rgba != nullptr))) return rc;
+  auto& A = K.att[id];
+  HIP_TRY(hipMemcpyAsync(A.z, z, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (rgba) HIP_TRY(hipMemcpyAsync(A.rgba, rgba, n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));      // the caller's arrays are free again on return
+  A.cam = k; A.kcam = *cam;
+  A.have_depth = true; A.have_color = rgba != nullptr;
+  return RPE_OK;
+}
+
+int rpe_keyframe_attachment_info(rpe_context* c, int id, int* have_depth, int* have_color, rpe_camera* cam) {
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  const auto& K = c->kf;
+  if (id < 0 || id >= (int)K.meta.size()) return fail(RPE_ERR_ARG, "rpe_keyframe_attachment_info: no keyframe %d (%d in the store)", id, (int)K.meta.size());
+  const bool have = id < (int)K.att.size() && K.att[id].have_depth;
+  if (have_depth) *have_depth = have ? 1 : 0;
+  if (have_color) *have_color = have && K.att[id].have_color ? 1 : 0;
+  if (cam) *cam = have ? K.att[id].kcam : rpe_camera{0, 0, 0, 0, 0, 0};
+  return RPE_OK;
+}
+
+int rpe_keyframe_attachment_download(rpe_context* c, int id, float* z, uint8_t* rgba) {
+  session_end(c);
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  const auto& K = c->kf;
+  if (id < 0 || id >= (int)K.meta.size()) return fail(RPE_ERR_ARG, "rpe_keyframe_attachment_download: no keyframe %d (%d in the store)", id, (int)K.meta.size());
+  const bool have = id < (int)K.att.size() && K.att[id].have_depth;
+  if (z && !have) return fail(RPE_ERR_STATE, "rpe_keyframe_attachment_download: keyframe %d has no depth attached (rpe_keyframe_attach_frame)", id);
+  if (rgba && !(have && K.att[id].have_color)) return fail(RPE_ERR_STATE, "rpe_keyframe_attachment_download: keyframe %d has no colour attached", id);
+  if (!z && !rgba) return RPE_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const auto& A = K.att[id];
+  const size_t n = (size_t)A.cam.width * A.cam.height;
+  int rc;
+  if (z && (rc = copy_to_host(c, z, A.z, n * sizeof(float)))) return rc;
+  if (rgba && (rc = copy_to_host(c, rgba, A.rgba, n * 4))) return rc;
+  return RPE_OK;
+}
+
 int rpe_keyframes_clear(rpe_context* c) {
   session_end(c);
   if (!c) return fail(RPE_ERR_ARG, "null context");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  for (auto& A : c->kf.att) A.have_depth = A.have_color = false;   // the planes stay, for the next keyframe of that id
   c->kf.meta.clear();
   c->kf.used = 0;                                  // the storage stays, for the next map
   c->kf.kind = -1;

@@ -12,7 +12,9 @@ namespace {
 // Voxel (i, j, k), centre p = o + ((float)i + 0.5f) * s per axis; camera point pc = R p + t (rows left to right); pixel = nearest
 // (floorf(f * x / z + c + 0.5f)); d = z of the level-0 vertex map there (NaN = invalid depth); sdf = d - pc.z; updated iff pc.z > 0,
 // the pixel is in the image, d is valid and sdf >= -tr: f = fminf(1, sdf / tr), tsdf = (tsdf * w + f) / (w + 1), w = fminf(w + 1, W).
-// voxel_project also hands out sdf and the pixel's index (v * width + u) of an updated voxel.
+// voxel_project also hands out sdf and the pixel's index (v * width + u) of an updated voxel.  The depth of pixel `pix` is
+// vmap[STRIDE * pix + OFFSET]: the z of a vertex map by default, <1, 0> for a packed depth plane (rpe_rebuild.hip).
+template <int STRIDE = 3, int OFFSET = 2>
 __device__ __forceinline__ bool voxel_project(const VolumeGeometry& G, const float* __restrict__ vmap, const Camera& cam, const PoseF& T,
                                               int i, int j, int k, float& f, float& sdf, int64_t& pix) {
   const float px = G.o[0] + ((float)i + 0.5f) * G.s, py = G.o[1] + ((float)j + 0.5f) * G.s, pz = G.o[2] + ((float)k + 0.5f) * G.s;
@@ -23,7 +25,7 @@ __device__ __forceinline__ bool voxel_project(const VolumeGeometry& G, const flo
   const float uf = floorf(cam.fx * (cx / cz) + cam.cx + 0.5f), vf = floorf(cam.fy * (cy / cz) + cam.cy + 0.5f);
   if (!(uf >= 0.0f && uf <= (float)(cam.width - 1) && vf >= 0.0f && vf <= (float)(cam.height - 1))) return false;
   pix = (int64_t)(int)vf * cam.width + (int)uf;
-  const float d = vmap[3 * pix + 2];
+  const float d = vmap[STRIDE * pix + OFFSET];
   if (d != d) return false;
   sdf = d - cz;
   if (!(sdf >= -G.tr)) return false;
@@ -41,6 +43,22 @@ __device__ __forceinline__ bool voxel_sdf(const VolumeGeometry& G, const float* 
 __device__ __forceinline__ void fuse(float& tsdf, float& w, float f, float W) {
   tsdf = (tsdf * w + f) / (w + 1.0f);
   w = fminf(w + 1.0f, W);
+}
+
+// binary16 <-> fp32.  h(x): round to nearest even, subnormals kept, every NaN to the quiet NaN 0x7e00.
+__device__ __forceinline__ float h2f(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
+__device__ __forceinline__ unsigned f2h(float x) { return x == x ? (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x) : 0x7e00u; }
+
+// One voxel's colour {r, g, b, wc} as two words (rg = r | g << 16, bw = b | wc << 16) and the observation o (RGBA8): with w = (float)wc
+// before the update, each channel c := h(((float)c * w + o) / (w + 1.0f)), then wc := h(fminf(w + 1.0f, W)).  (The colour integrate
+// of rpe_color.hip and the keyframe fuse of rpe_rebuild.hip.)
+__device__ __forceinline__ void blend(unsigned& rg, unsigned& bw, unsigned o, float W) {
+  const float w = h2f(bw >> 16);
+  const float r = (h2f(rg & 0xffffu) * w + (float)(o & 0xffu)) / (w + 1.0f);
+  const float g = (h2f(rg >> 16) * w + (float)((o >> 8) & 0xffu)) / (w + 1.0f);
+  const float b = (h2f(bw & 0xffffu) * w + (float)((o >> 16) & 0xffu)) / (w + 1.0f);
+  rg = f2h(r) | f2h(g) << 16;
+  bw = f2h(b) | f2h(fminf(w + 1.0f, W)) << 16;
 }
 
 // F(p): g = (p - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; known iff 0 <= i0 <= dim - 2 on every axis and all eight corner

@@ -31,8 +31,10 @@
 //   when lost:         rpe::KeyframeRelocResult r = fe.relocalizeKeyframes(6, 0.05, 3.0, 0.1);   // r.keyframe = the one it chose
 // ... and when a LOOP closes, the keyframes' poses are made consistent: linked by their own matches, refined jointly, the store rewritten
 //   after addKeyframe(): fe.linkKeyframes(id);   at a loop: rpe::GraphResult g = fe.optimizeKeyframes({0.1, 0.1, 0.05, 0.05, 0.03});
-//   (g.poses[k] = keyframe k's corrected pose.  Out of scope: the TSDF / colour volume is NOT re-integrated -- the store keeps no depth;
-//   fuse your own frames again with g.poses.  No odometry edges, no robust kernel but the gate, dense host solve.)
+//   (g.poses[k] = keyframe k's corrected pose.  No odometry edges, no robust kernel but the gate, dense host solve.)
+// ... and the MAP follows: a keyframe that carries its depth is fused again at its corrected pose, all of them in one launch
+//   after addKeyframe(): fe.attachFrame(id);   after optimizeKeyframes(): fe.fuseKeyframes({}, {}, true, true);  rpe::Mesh m = fe.mesh();
+//   (the rebuilt volume holds the keyframes only, not the frames between them)
 //
 // Camera: the simulator's pinhole (Simulator.hpp:150-162).  Poses cross this interface as Sophus::SE3<double>.
 #ifndef RPE_DEPTH_FRONT_END_HEADER
@@ -108,6 +110,14 @@ struct GraphResult {
   std::vector<SE3<double> > poses;
   std::vector<int64_t> pairs;
   std::vector<double> cost, step;
+};
+// keyframeAttachment(): what a keyframe carries for fuseKeyframes -- its level-0 metric depth (NaN = invalid), the camera it was taken
+// with and, if color, its RGBA8 image; depth = false: nothing is attached
+struct KeyframeAttachment {
+  bool depth = false, color = false;
+  PinholeCamera cam;
+  std::vector<float> z;
+  std::vector<uint8_t> rgba;
 };
 
 class DepthFrontEnd {
@@ -459,6 +469,42 @@ class DepthFrontEnd {
       g.pairs.push_back((int64_t)st[0]); g.cost.push_back(st[1]); g.step.push_back(st[2]);
     }
     return g;
+  }
+  // the CURRENT frame's depth, camera and (if set) colour become keyframe id's attachment: what fuseKeyframes later fuses for it.
+  // Call it when the keyframe is made, while its frame is still the current one
+  void attachFrame(int id) { check(rpe_keyframe_attach_frame(_ctx, id), "rpe_keyframe_attach_frame"); }
+  // the same from host arrays: z = width*height metric depths (NaN = invalid), rgba = 4*width*height bytes or nullptr
+  void attachKeyframe(int id, const float* z, const uint8_t* rgba, const PinholeCamera& cam) {
+    const rpe_camera k = cam_of(cam);
+    check(rpe_keyframe_attach_host(_ctx, id, z, rgba, &k), "rpe_keyframe_attach_host");
+  }
+  KeyframeAttachment keyframeAttachment(int id) {
+    KeyframeAttachment a;
+    int hd = 0, hc = 0;
+    rpe_camera k;
+    check(rpe_keyframe_attachment_info(_ctx, id, &hd, &hc, &k), "rpe_keyframe_attachment_info");
+    a.depth = hd != 0; a.color = hc != 0;
+    if (!a.depth) return a;
+    a.cam.fx = k.fx; a.cam.fy = k.fy; a.cam.cx = k.cx; a.cam.cy = k.cy; a.cam.width = k.width; a.cam.height = k.height;
+    a.z.resize((size_t)k.width * k.height);
+    if (a.color) a.rgba.resize((size_t)4 * k.width * k.height);
+    check(rpe_keyframe_attachment_download(_ctx, id, a.z.data(), a.color ? a.rgba.data() : nullptr), "rpe_keyframe_attachment_download");
+    return a;
+  }
+  // the volume rebuilt from the keyframes' attachments in ONE launch, bit for bit what initVolume (clear) and one integrate /
+  // integrateColor (color) per list entry leave: ids empty = every keyframe that carries depth, by id; poses empty = the store's
+  // (after optimizeKeyframes: the corrected ones), else one per list entry.  The rebuilt volume holds the keyframes only, not the
+  // frames between them.  cull = false switches the per-workgroup cull off (the same bits)
+  void fuseKeyframes(const std::vector<int>& ids = std::vector<int>(), const std::vector<Pose>& poses = std::vector<Pose>(), bool clear = true,
+                     bool color = false, bool cull = true) {
+    if (!poses.empty() && poses.size() != ids.size()) throw DeviceError(RPE_ERR_ARG, "fuseKeyframes: one pose per list entry");
+    std::vector<int32_t> list(ids.begin(), ids.end());
+    std::vector<double> p((size_t)12 * poses.size());
+    for (size_t e = 0; e < poses.size(); e++) pose12(poses[e], p.data() + 12 * e);
+    const int flags = (clear ? RPE_FUSE_CLEAR : 0) | (color ? RPE_FUSE_COLOR : 0) | (cull ? 0 : RPE_FUSE_NO_CULL);
+    check(rpe_volume_fuse_keyframes(_ctx, list.empty() ? nullptr : list.data(), (int)list.size(), poses.empty() ? nullptr : p.data(), flags),
+          "rpe_volume_fuse_keyframes");
+    if (clear) _mesh_vertices = -1;
   }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
