@@ -11,7 +11,7 @@ the joint Gauss-Newton round over every edge, the store rewritten at the correct
 depth packed beside a keyframe, a list of keyframes fused in one pass over the voxels), csrc/rpe_hypotheses.hip (batched hypothesis generation),
 csrc/rpe_prosac.hip (PROSAC order: top-k select + sort); the host units behind include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp
 lists them: rpe_context.hip, rpe_receive.hip, rpe_capi.hip = the thin C-ABI shim, rpe_refine.hip, rpe_session.hip, rpe_dist.hip,
-rpe_frontend_api.hip, rpe_volume_api.hip, rpe_mesh_api.hip, rpe_color_api.hip, rpe_photo_api.hip, rpe_feature_api.hip, rpe_keyframe_api.hip, rpe_graph_api.hip, rpe_rebuild_api.hip), csrc/library.cpp (reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines),
+rpe_frontend_api.hip, rpe_volume_api.hip, rpe_mesh_api.hip, rpe_color_api.hip, rpe_photo_api.hip, rpe_feature_api.hip, rpe_keyframe_api.hip, rpe_graph_api.hip, rpe_rebuild_api.hip; csrc/rpe_devbuf.hpp owns their device memory, csrc/rpe_frontend_host.hpp holds what the Part 3 units share), csrc/library.cpp (reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines),
 csrc/rpe_hostex.cpp (host-side all-reduce between the rank processes of one node).  The units compile in parallel (RPE_BUILD_JOBS, default 6)."""
 from __future__ import annotations
 

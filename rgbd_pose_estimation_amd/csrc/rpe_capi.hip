@@ -481,11 +481,7 @@ int rpe_prosac_order(rpe_context* c, const float* weights, int n, int top_k, int
   if (top_k > rpe::kProsacMaxTopK) return fail(RPE_ERR_ARG,
       "rpe_prosac_order: top_k %d exceeds %d (sort the longer prefix on the host)", top_k, rpe::kProsacMaxTopK);
   HIP_TRY(hipSetDevice(c->device));
-  if (c->ps_w_cap < (size_t)n) {
-    if (c->ps_w) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->ps_w)); c->ps_w = nullptr; c->ps_w_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&c->ps_w, (size_t)n * sizeof(float)));
-    c->ps_w_cap = (size_t)n;
-  }
+  if (int rc = c->ps_w.reserve(c, (size_t)n * sizeof(float))) return rc;
   HIP_TRY(hipMemcpyAsync(c->ps_w, weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_prosac_order(c->ps_w, n, top_k, c->ps_hist, c->ps_hist + 2048, c->ps_cand, c->ps_order,
       c->ps_order + rpe::kProsacMaxTopK, c->stream));

@@ -1,33 +1,20 @@
 // Part 3 of include/rgbd_pose_hip.h: colour beside the TSDF volume (kernels in rpe_color.hip).  A registered RGB image becomes the
 // frame's RGBA8 map; the colour integrate fuses it into a binary16 colour volume at the tsdf's voxel index; the colour field is sampled
 // back at the model's level-0 vertices and at the last mesh's vertices.
-#include "rpe_host.hpp"
+#include "rpe_frontend_host.hpp"
 using namespace rpeh;
 
-namespace {
-// the colour volume of the current volume: allocated on first use after rpe_volume_init, cleared to 0 unless `clear` is false (an
-// upload overwrites every voxel)
+namespace rpeh {
 int ensure_color_volume(rpe_context* c, bool clear) {
   auto& V = c->vol;
   if (V.have_color) return RPE_OK;
   const size_t bytes = (size_t)V.g.dim[0] * V.g.dim[1] * V.g.dim[2] * 4 * sizeof(unsigned short);
-  if (!V.cd || V.ccap < bytes) {
-    if (V.cd) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.cd)); V.cd = nullptr; V.ccap = 0; }
-    HIP_TRY(hipMalloc((void**)&V.cd, bytes));
-    V.ccap = bytes;
-  }
+  if (int rc = V.cd.reserve(c, bytes)) return rc;
   if (clear) HIP_TRY(hipMemsetAsync(V.cd, 0, bytes, c->stream));
   V.have_color = true;
   return RPE_OK;
 }
-template <class T> int ensure_buffer(rpe_context* c, T** p, size_t* cap, size_t bytes) {
-  if (*p && *cap >= bytes) return RPE_OK;
-  if (*p) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(*p)); *p = nullptr; *cap = 0; }
-  HIP_TRY(hipMalloc((void**)p, bytes));
-  *cap = bytes;
-  return RPE_OK;
-}
-}  // namespace
+}  // namespace rpeh
 
 extern "C" {
 
@@ -39,8 +26,7 @@ int rpe_frame_set_color(rpe_context* c, const uint8_t* pixels, int format) {
   HIP_TRY(hipSetDevice(c->device));
   const int64_t n = (int64_t)F.cam.width * F.cam.height;
   int rc;
-  if ((rc = ensure_buffer(c, &F.d_rgb, &F.rgb_cap, (size_t)n * 3))) return rc;
-  if ((rc = ensure_buffer(c, &F.fcolor, &F.fccap, (size_t)n * 4))) return rc;
+  if ((rc = F.d_rgb.reserve(c, (size_t)n * 3)) || (rc = F.fcolor.reserve(c, (size_t)n * 4))) return rc;
   F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_rgb, pixels, (size_t)n * 3, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_color(F.d_rgb, n, format == RPE_COLOR_BGR8 ? 1 : 0, F.fcolor, c->stream));
@@ -71,7 +57,7 @@ int rpe_model_sample_color(rpe_context* c) {
   if (!c->vol.have_color) return fail(RPE_ERR_STATE, "no colour volume: call rpe_volume_integrate_color or rpe_volume_color_upload first");
   HIP_TRY(hipSetDevice(c->device));
   const int64_t n = (int64_t)F.mcam.width * F.mcam.height;
-  int rc = ensure_buffer(c, &F.mcolor, &F.mccap, (size_t)n * 4);
+  int rc = F.mcolor.reserve(c, (size_t)n * 4);
   if (rc) return rc;
   F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(rpe::launch_color_sample(c->vol.cd, c->vol.g, F.mmap[0], n, F.mcolor, c->stream));
@@ -104,7 +90,7 @@ int rpe_volume_mesh_colors(rpe_context* c, uint8_t* rgba) {
   if (V.nv > 0 && !rgba) return fail(RPE_ERR_ARG, "rpe_volume_mesh_colors: bad argument");
   if (V.nv == 0) return RPE_OK;
   HIP_TRY(hipSetDevice(c->device));
-  int rc = ensure_buffer(c, &V.mc, &V.mc_cap, (size_t)V.nv * 4);
+  int rc = V.mc.reserve(c, (size_t)V.nv * 4);
   if (rc) return rc;
   HIP_TRY(rpe::launch_color_sample(V.cd, V.g, V.mv, V.nv, V.mc, c->stream));
   HIP_TRY(hipMemcpyAsync(rgba, V.mc, (size_t)V.nv * 4, hipMemcpyDeviceToHost, c->stream));

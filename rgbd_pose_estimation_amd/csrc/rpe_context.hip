@@ -22,12 +22,8 @@ int set_error(int code, const char* msg) { g_err = msg ? msg : ""; return code; 
 namespace rpeh {
 int ensure_mask(rpe_context* c, int mod, bool fill_ones) {
   if (c->mask[mod]) return RPE_OK;
-  const size_t need = (size_t)c->n * sizeof(short);
-  if (!c->mask_store[mod] || c->mask_cap[mod] < need) {
-    if (c->mask_store[mod]) { HIP_TRY(hipFree(c->mask_store[mod])); c->mask_store[mod] = nullptr; c->mask_cap[mod] = 0; }
-    HIP_TRY(hipMalloc((void**)&c->mask_store[mod], need ? need : 2));
-    c->mask_cap[mod] = need;
-  }
+  int rc = c->mask_store[mod].reserve(c, (size_t)c->n * sizeof(short));
+  if (rc) return rc;
   c->mask[mod] = c->mask_store[mod];
   if (fill_ones && c->n)   // adapters start with all-ones masks (e.g. AOPoseAdapter.hpp:103-106): filled on the device, in stream order
     HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)c->mask[mod], (unsigned short)1, (size_t)c->n, c->stream));
@@ -98,42 +94,43 @@ int rpe_create(rpe_context** out, int device, void* stream) {
   if (const char* mb = getenv("RPE_BLOCK")) { int v = atoi(mb); if (v == 256 || v == 512) c->block = v; }
   if (const char* f = getenv("RPE_GUARD_ALWAYS")) c->guard_always = atoi(f) != 0;
   if (const char* f = getenv("RPE_HOST_CPU")) c->host_cpu_request = std::strcmp(f, "auto") == 0 ? -1 : (std::isdigit((unsigned char)f[0]) ? atoi(f) : -2);
-  hipError_t e = hipSuccess;
+  // plain device memory (zero: cleared) and pinned, device-mapped host memory, one after the other until the first failure
+  int rc = RPE_OK;
+  auto on_device = [&](auto& buf, size_t bytes, bool zero) {
+    if (rc == RPE_OK && (rc = buf.once(c, bytes)) == RPE_OK && zero) {
+      const hipError_t e = hipMemset(buf, 0, bytes);
+      if (e != hipSuccess) rc = fail(RPE_ERR_HIP, "hipMemset: %s", hipGetErrorString(e));
+    }
+  };
+  auto pinned = [&](void** p, size_t bytes) {
+    if (rc != RPE_OK) return;
+    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) { rc = fail(RPE_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); return; }
+    std::memset(*p, 0, bytes);
+  };
   // scratch of the cross-workgroup stages, whichever layout a launch uses: (4096 + 8 shard) records of kNlLd doubles, or 16-byte
   // granules [workgroup <= 4096][sums <= 44] followed by the autonomous loop's run records [2 parities][<= kAutoMaxRunSums = 1024]
   const size_t partial_doubles = std::max<size_t>((size_t)(4096 + 8) * rpe::kNlLd, (size_t)2 * 4096 * 44 + (size_t)2 * 2 * 1024);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_partials, partial_doubles * sizeof(double));
-  // granule tags start below every sequence value
-  if (e == hipSuccess) e = hipMemset(c->d_partials, 0, partial_doubles * sizeof(double));
+  on_device(c->d_partials, partial_doubles * sizeof(double), true);   // granule tags start below every sequence value
   // 64 doubles (a record for a collective, the solve probe) + the run records of a sharded step (rpe_dist.hip), zero between steps
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_out, (64 + 2 * rpe::kRunSlots * rpe::kRunLd) * sizeof(double));   // (two sets: chained steps alternate)
-  if (e == hipSuccess) e = hipMemset(c->d_out, 0, (64 + 2 * rpe::kRunSlots * rpe::kRunLd) * sizeof(double));
+  on_device(c->d_out, (64 + 2 * rpe::kRunSlots * rpe::kRunLd) * sizeof(double), true);   // (two sets: chained steps alternate)
   c->h_big_pairs = 8192 + 64;
-  if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_big, c->h_big_pairs * 16, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) std::memset(c->h_big, 0, c->h_big_pairs * 16);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_out, 80 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) { std::memset(c->h_out, 0, 80 * sizeof(double)); e = hipMalloc((void**)&c->d_ticket, 9 * 128); }
-  if (e == hipSuccess) e = hipMemset(c->d_ticket, 0, 9 * 128);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_gn_pose, 32 * sizeof(double));   // 12 (+ a second 12 at 16: chained steps alternate)
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_gn_state, sizeof(rpe::GnState));
-  if (e == hipSuccess) e = hipMalloc(&c->d_poses, (size_t)rpe::kMaxScoreH * 12 * sizeof(double));
-  // staging for pose uploads; also written directly by the hypothesis generator
-  if (e == hipSuccess) e = hipHostMalloc(&c->h_poses, (size_t)rpe::kMaxScoreH * 12 * sizeof(double),
-      hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d_votes, (size_t)rpe::kMaxScoreH * sizeof(int));
-  // the scoring kernels accumulate into zeroed counters
-  if (e == hipSuccess) e = hipMemset(c->d_votes, 0, (size_t)rpe::kMaxScoreH * sizeof(int));
+  pinned((void**)&c->h_big, c->h_big_pairs * 16);
+  pinned((void**)&c->h_out, 80 * sizeof(double));
+  on_device(c->d_ticket, 9 * 128, true);
+  on_device(c->d_gn_pose, 32 * sizeof(double), false);   // 12 (+ a second 12 at 16: chained steps alternate)
+  on_device(c->d_gn_state, sizeof(rpe::GnState), false);
+  on_device(c->d_poses, (size_t)rpe::kMaxScoreH * 12 * sizeof(double), false);
+  pinned(&c->h_poses, (size_t)rpe::kMaxScoreH * 12 * sizeof(double));   // staging for pose uploads; also written directly by the hypothesis generator
+  on_device(c->d_votes, (size_t)rpe::kMaxScoreH * sizeof(int), true);      // the scoring kernels accumulate into zeroed counters
   // pinned + device-mapped: the vote read-out kernel stores straight into it; the sequence word sits behind the counters
-  if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_votes, ((size_t)rpe::kMaxScoreH + 4) * sizeof(int),
-      hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) { std::memset(c->h_votes, 0, ((size_t)rpe::kMaxScoreH + 4) * sizeof(int));
-      c->h_flag2 = reinterpret_cast<unsigned long long*>(c->h_votes + rpe::kMaxScoreH); }
+  pinned((void**)&c->h_votes, ((size_t)rpe::kMaxScoreH + 4) * sizeof(int));
+  if (rc == RPE_OK) c->h_flag2 = reinterpret_cast<unsigned long long*>(c->h_votes + rpe::kMaxScoreH);
   // PROSAC order scratch (rpe_prosac_order): histogram + control words (zero between calls), candidate keys, order + status
-  if (e == hipSuccess) e = hipMalloc((void**)&c->ps_hist, (2048 + 8) * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMemset(c->ps_hist, 0, (2048 + 8) * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->ps_cand, (size_t)rpe::kProsacSortCap * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->ps_order, ((size_t)rpe::kProsacMaxTopK + 1) * sizeof(int));
-  if (e != hipSuccess) { rpe_destroy(c); return fail(RPE_ERR_HIP, "workspace allocation: %s", hipGetErrorString(e)); }
+  on_device(c->ps_hist, (2048 + 8) * sizeof(unsigned int), true);
+  on_device(c->ps_cand, (size_t)rpe::kProsacSortCap * sizeof(unsigned long long), false);
+  on_device(c->ps_order, ((size_t)rpe::kProsacMaxTopK + 1) * sizeof(int), false);
+  if (rc != RPE_OK) { const std::string why = g_err; rpe_destroy(c); return fail(RPE_ERR_HIP, "workspace allocation: %s", why.c_str()); }
   {  // Resident loops.  The co-residency cap is a property of the device (0: not even one workgroup of the resident kernels per
      // compute unit) and gates both forms; the AUTONOMOUS form (rpe_gn_refine_device, device_resident ICP) needs nothing else.  The
      // HOST-driven form also needs device memory the CPU can store into (large BAR: the control block); RPE_RESIDENT=0 switches that
@@ -173,58 +170,23 @@ void rpe_destroy(rpe_context* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (int i = 0; i < RPE_NUM_ARRAYS; i++) if (c->store[i]) (void)hipFree(c->store[i]);
-  for (int i = 0; i < 3; i++) { if (c->mask_store[i]) (void)hipFree(c->mask_store[i]);
-      if (c->weight_store[i]) (void)hipFree(c->weight_store[i]); }
-  if (c->d_partials) (void)hipFree(c->d_partials);
-  if (c->d_out) (void)hipFree(c->d_out);
-  if (c->d_ticket) (void)hipFree(c->d_ticket);
-  if (c->d_gn_pose) (void)hipFree(c->d_gn_pose);
-  if (c->d_gn_state) (void)hipFree(c->d_gn_state);
   if (c->h_out) (void)hipHostFree(c->h_out);
-  if (c->d_poses) (void)hipFree(c->d_poses);
   if (c->h_poses) (void)hipHostFree(c->h_poses);
-  if (c->d_votes) (void)hipFree(c->d_votes);
   if (c->h_votes) (void)hipHostFree(c->h_votes);
   (void)rpe_p2p_destroy(c);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->ctl) (void)hipFree((void*)c->ctl);
   if (c->h_big) (void)hipHostFree(c->h_big);
   if (c->hostex) rpe_host_exchange_close(c->hostex);
-  if (c->ps_w) (void)hipFree(c->ps_w);
-  if (c->ps_hist) (void)hipFree(c->ps_hist);
-  if (c->ps_cand) (void)hipFree(c->ps_cand);
-  if (c->ps_order) (void)hipFree(c->ps_order);
-  if (c->fe.d_depth) (void)hipFree(c->fe.d_depth);
-  for (float* m : c->fe.fmap) if (m) (void)hipFree(m);
-  for (float* m : c->fe.mmap) if (m) (void)hipFree(m);
-  if (c->fe.d_count) (void)hipFree(c->fe.d_count);
-  if (c->fe.fdepth) (void)hipFree(c->fe.fdepth);
-  if (c->fe.d_filt) (void)hipFree(c->fe.d_filt);
-  if (c->vol.d) (void)hipFree(c->vol.d);
-  if (c->vol.ws) (void)hipFree(c->vol.ws);
-  for (void* m : {(void*)c->vol.mv, (void*)c->vol.mn, (void*)c->vol.mt}) if (m) (void)hipFree(m);
-  for (void* m : {(void*)c->fe.d_rgb, (void*)c->fe.fcolor, (void*)c->fe.mcolor, (void*)c->vol.cd, (void*)c->vol.mc, (void*)c->fe.pint, (void*)c->fe.pmap}) if (m) (void)hipFree(m);
-  for (auto& f : c->fe.feat) for (void* m : {(void*)f.pix, (void*)f.score, (void*)f.xy, (void*)f.desc, (void*)f.bin}) if (m) (void)hipFree(m);
-  {
-    const auto& W = c->fe.fwork; const auto& M = c->fe.mlist;
-    for (void* m : {(void*)W.score, (void*)W.box, (void*)W.chunk, (void*)W.hist, (void*)W.ctl, (void*)W.spix, (void*)M.d1, (void*)M.idx, (void*)M.d2,
-                    (void*)M.back, (void*)M.mf, (void*)M.mm, (void*)M.md1, (void*)M.md2, (void*)M.mw}) if (m) (void)hipFree(m);
-  }
-  {
-    const auto& K = c->kf;
-    for (void* m : {(void*)K.st.off, (void*)K.st.desc, (void*)K.st.xw, (void*)K.st.nw, (void*)K.st.xy, (void*)K.back, (void*)K.d1, (void*)K.idx,
-                    (void*)K.d2, (void*)K.rank, (void*)K.d_table}) if (m) (void)hipFree(m);
-    for (const auto& A : K.att) for (void* m : {(void*)A.z, (void*)A.rgba}) if (m) (void)hipFree(m);
-  }
   graph_free(c);
   if (c->comm && rccl().ok) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
   for (hipEvent_t e : c->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev1) (void)hipEventDestroy(e);
   if (c->ev_stream2) (void)hipEventDestroy(c->ev_stream2);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  hipStream_t own = c->own_stream ? c->stream : nullptr;
+  delete c;   // every DevBuf of the context goes here, the stream still alive
+  if (own) (void)hipStreamDestroy(own);
 }
 
 int rpe_synchronize(rpe_context* c) {
@@ -253,12 +215,8 @@ int rpe_upload(rpe_context* c, int slot, const void* host) {
   if (c->n <= 0) return fail(RPE_ERR_STATE, "rpe_set_problem first");
   HIP_TRY(hipSetDevice(c->device));
   const size_t bytes = (size_t)c->n * 3 * elem_size(c->dtype);
-  if (!c->store[slot] || c->cap[slot] < bytes) {
-    if (c->store[slot]) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->store[slot])); c->store[slot] = nullptr;
-        c->cap[slot] = 0; }
-    HIP_TRY(hipMalloc(&c->store[slot], bytes));
-    c->cap[slot] = bytes;
-  }
+  int rc = c->store[slot].reserve(c, bytes);
+  if (rc) return rc;
   c->arr[slot] = c->store[slot];
   arrays_changed(c, slot, false);
   HIP_TRY(hipMemcpyAsync(c->arr[slot], host, bytes, hipMemcpyHostToDevice, c->stream));
@@ -300,12 +258,8 @@ int rpe_upload_weight(rpe_context* c, int mod, const void* host_weight) {
   HIP_TRY(hipSetDevice(c->device));
   if (!host_weight) { c->weight[mod] = nullptr; return RPE_OK; }
   const size_t need = (size_t)c->n * elem_size(c->dtype);
-  if (!c->weight_store[mod] || c->weight_cap[mod] < need) {
-    if (c->weight_store[mod]) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->weight_store[mod]));
-        c->weight_store[mod] = nullptr; }
-    HIP_TRY(hipMalloc(&c->weight_store[mod], need ? need : 8));
-    c->weight_cap[mod] = need;
-  }
+  int rc = c->weight_store[mod].reserve(c, need);
+  if (rc) return rc;
   c->weight[mod] = c->weight_store[mod];
   HIP_TRY(hipMemcpyAsync(c->weight[mod], host_weight, need, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

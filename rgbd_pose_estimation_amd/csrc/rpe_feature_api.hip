@@ -1,71 +1,10 @@
 // Part 3 of include/rgbd_pose_hip.h: features and relocalisation (kernels in rpe_feature.hip).  Keypoints and descriptors of the frame
 // and of the model view, their matches in the five solver slots, and rpe_relocalize: the matches through rpe_run -- a pose without a
 // pose guess, for ICP to refine.  The host waits for one count per detection and one per match list.
-#include "rpe_host.hpp"
+#include "rpe_frontend_host.hpp"
 using namespace rpeh;
 
-namespace {
-template <class T> int ensure(rpe_context* c, T** p, size_t count) {
-  if (*p) return RPE_OK;
-  HIP_TRY(hipMalloc((void**)p, count * sizeof(T)));
-  return RPE_OK;
-}
-// the counter a kernel left in device memory, through the pinned word every count of the front end takes
-int read_count(rpe_context* c, const int* d_word, int* out) {
-  const unsigned long long seq = ++c->vote_seq;
-  HIP_TRY(rpe::launch_publish_i32(d_word, 1, c->h_votes, c->h_flag2, seq, c->stream));
-  int rc = wait_flag(c, c->h_flag2, seq);
-  if (rc) return rc;
-  *out = c->h_votes[0];
-  return RPE_OK;
-}
-int ensure_work(rpe_context* c, int w, int h) {
-  auto& F = c->fe;
-  const int64_t n = (int64_t)w * h;
-  if (F.fwork_pixels < n) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    auto& W = F.fwork;
-    for (void* p : {(void*)W.score, (void*)W.box, (void*)W.chunk, (void*)W.spix}) if (p) HIP_TRY(hipFree(p));
-    W.score = nullptr; W.box = nullptr; W.chunk = nullptr; W.spix = nullptr; F.fwork_pixels = 0;
-    HIP_TRY(hipMalloc((void**)&W.score, n * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&W.box, n * sizeof(unsigned short)));
-    HIP_TRY(hipMalloc((void**)&W.chunk, (n / 256 + 2) * sizeof(int)));
-    // no two 8-neighbours both survive the suppression: at most ceil(w / 2) * ceil(h / 2) survivors
-    HIP_TRY(hipMalloc((void**)&W.spix, ((n + w + h + 1) / 4 + 1) * sizeof(int)));
-    F.fwork_pixels = n;
-  }
-  int rc;
-  if ((rc = ensure(c, &F.fwork.hist, rpe::kFeatScoreBins))) return rc;
-  if ((rc = ensure(c, &F.fwork.ctl, rpe::kFeatCtlWords))) return rc;
-  return RPE_OK;
-}
-int ensure_side(rpe_context* c, int which) {
-  auto& S = c->fe.feat[which];
-  int rc;
-  if ((rc = ensure(c, &S.pix, rpe::kMaxKeypoints))) return rc;
-  if ((rc = ensure(c, &S.score, rpe::kMaxKeypoints))) return rc;
-  if ((rc = ensure(c, &S.xy, 2 * rpe::kMaxKeypoints))) return rc;
-  if ((rc = ensure(c, &S.desc, 8 * rpe::kMaxKeypoints))) return rc;
-  return ensure(c, &S.bin, rpe::kMaxKeypoints);
-}
-int ensure_lists(rpe_context* c) {
-  auto& L = c->fe.mlist;
-  int rc;
-  for (int** p : {&L.d1, &L.idx, &L.d2, &L.back, &L.mf, &L.mm, &L.md1, &L.md2}) if ((rc = ensure(c, p, rpe::kMaxKeypoints))) return rc;
-  return ensure(c, &L.mw, rpe::kMaxKeypoints);
-}
-int side_ready(rpe_context* c, int which) {
-  auto& F = c->fe;
-  if (which == RPE_FEAT_FRAME) {
-    if (!F.have_frame) return fail(RPE_ERR_STATE, "no frame: call rpe_frame_set_depth first");
-    if (!F.have_fcolor) return fail(RPE_ERR_STATE, "no frame colour: call rpe_frame_set_color after the frame's depth");
-  } else {
-    if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_upload, rpe_model_from_frame or rpe_volume_raycast first");
-    if (!F.have_mcolor)
-      return fail(RPE_ERR_STATE, "no model colour: call rpe_model_sample_color, rpe_model_color_upload or rpe_model_color_from_frame");
-  }
-  return RPE_OK;
-}
+namespace rpeh {
 const rpe_feature_options kFeatureDefaults = {12, RPE_MAX_KEYPOINTS};
 const rpe_match_options kMatchDefaults = {64, 8, 10, 0};
 int feature_options(const rpe_feature_options* o) {
@@ -79,6 +18,86 @@ int match_options(const rpe_match_options* o) {
       (o->cross_check != 0 && o->cross_check != 1))
     return fail(RPE_ERR_ARG, "match options: max_dist 0 .. 256 (got %d), ratio_num / ratio_den 1 .. 65536 (got %d / %d), cross_check 0 or 1 (got %d)",
                 o->max_dist, o->ratio_num, o->ratio_den, o->cross_check);
+  return RPE_OK;
+}
+int ensure_lists(rpe_context* c) {
+  auto& L = c->fe.mlist;
+  int rc;
+  for (DevBuf<int>* p : {&L.d1, &L.idx, &L.d2, &L.back, &L.mf, &L.mm, &L.md1, &L.md2})
+    if ((rc = p->once(c, rpe::kMaxKeypoints * sizeof(int)))) return rc;
+  return L.mw.once(c, rpe::kMaxKeypoints * sizeof(float));
+}
+int read_ints(rpe_context* c, const int* d_words, int n, int* out) {
+  const unsigned long long seq = ++c->vote_seq;
+  HIP_TRY(rpe::launch_publish_i32(d_words, n, c->h_votes, c->h_flag2, seq, c->stream));
+  int rc = wait_flag(c, c->h_flag2, seq);
+  if (rc) return rc;
+  std::memcpy(out, c->h_votes, (size_t)n * sizeof(int));
+  return RPE_OK;
+}
+int detect_if_stale(rpe_context* c, int which, const rpe_feature_options& fo) {
+  const auto& S = c->fe.feat[which];
+  if (S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints && S.kind == c->fe.desc_kind) return RPE_OK;
+  return rpe_features_detect(c, which, &fo, nullptr);
+}
+int run_on_slots(rpe_context* c, int m, int method, double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence,
+                 uint64_t seed, int ls, double* pose12, int* max_votes, short* mask_out) {
+  const size_t n3 = (size_t)m * 3;
+  std::vector<float> host(5 * n3 + 3 * (size_t)m);
+  float* a[RPE_NUM_ARRAYS];
+  int rc;
+  for (int s = 0; s < RPE_NUM_ARRAYS; s++) {
+    a[s] = host.data() + s * n3;
+    if ((rc = copy_to_host(c, a[s], c->arr[s], n3 * sizeof(float)))) return rc;
+  }
+  float* wq = host.data() + 5 * n3;
+  if ((rc = copy_to_host(c, wq, c->fe.mlist.mw, (size_t)m * sizeof(float)))) return rc;
+  for (int k = 1; k < 3; k++) std::memcpy(wq + (size_t)k * m, wq, (size_t)m * sizeof(float));
+  rpe_problem p{};
+  p.n = m; p.dtype = RPE_F32;
+  p.xw = a[RPE_XW]; p.xc = a[RPE_XC]; p.bv = a[RPE_BV]; p.nw = a[RPE_NW]; p.nc = a[RPE_NC];
+  p.weights = wq; p.wcols = 3;
+  p.fx = c->fe.kcam[0].fx; p.fy = c->fe.kcam[0].fy;
+  double R9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t3[3] = {0, 0, 0};
+  if ((rc = rpe_run(method, &p, thre_3d, thre_2d, thre_nl, iter_io, confidence, seed, ls, RPE_SCORE_EXACT, nullptr, R9, t3, max_votes, mask_out)))
+    return rc;
+  for (int i = 0; i < 9; i++) pose12[i] = R9[i];
+  for (int i = 0; i < 3; i++) pose12[9 + i] = t3[i];
+  return RPE_OK;
+}
+}  // namespace rpeh
+
+namespace {
+// the detector's workspace for a w x h image, and one side's keypoint arrays (RPE_MAX_KEYPOINTS slots, allocated on first use)
+int ensure_work(rpe_context* c, int w, int h) {
+  auto& W = c->fe.fwork;
+  const size_t n = (size_t)w * h;
+  int rc;
+  if ((rc = W.score.reserve(c, n * sizeof(int))) || (rc = W.box.reserve(c, n * sizeof(unsigned short))) ||
+      (rc = W.chunk.reserve(c, (n / 256 + 2) * sizeof(int))) ||
+      // no two 8-neighbours both survive the suppression: at most ceil(w / 2) * ceil(h / 2) survivors
+      (rc = W.spix.reserve(c, ((n + w + h + 1) / 4 + 1) * sizeof(int)))) return rc;
+  if ((rc = W.hist.once(c, rpe::kFeatScoreBins * sizeof(unsigned int)))) return rc;
+  return W.ctl.once(c, rpe::kFeatCtlWords * sizeof(int));
+}
+int ensure_side(rpe_context* c, int which) {
+  auto& S = c->fe.feat[which];
+  const size_t k = rpe::kMaxKeypoints;
+  int rc;
+  if ((rc = S.pix.once(c, k * sizeof(int))) || (rc = S.score.once(c, k * sizeof(int))) || (rc = S.xy.once(c, 2 * k * sizeof(int))) ||
+      (rc = S.desc.once(c, 8 * k * sizeof(unsigned int)))) return rc;
+  return S.bin.once(c, k * sizeof(int));
+}
+int side_ready(rpe_context* c, int which) {
+  auto& F = c->fe;
+  if (which == RPE_FEAT_FRAME) {
+    if (!F.have_frame) return fail(RPE_ERR_STATE, "no frame: call rpe_frame_set_depth first");
+    if (!F.have_fcolor) return fail(RPE_ERR_STATE, "no frame colour: call rpe_frame_set_color after the frame's depth");
+  } else {
+    if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_upload, rpe_model_from_frame or rpe_volume_raycast first");
+    if (!F.have_mcolor)
+      return fail(RPE_ERR_STATE, "no model colour: call rpe_model_sample_color, rpe_model_color_upload or rpe_model_color_from_frame");
+  }
   return RPE_OK;
 }
 bool matches_current(const rpe_context* c) {
@@ -105,9 +124,9 @@ int rpe_features_detect(rpe_context* c, int which, const rpe_feature_options* op
   if ((rc = ensure_work(c, k.width, k.height)) || (rc = ensure_side(c, which))) return rc;
   S.have = false;
   HIP_TRY(rpe::launch_feature_detect(model ? F.mcolor : F.fcolor, model ? F.mmap[0] : F.fmap[0], model ? F.mmap[1] : F.fmap[1], k.width,
-                                     k.height, o.threshold, o.max_keypoints, F.fwork, F.desc_kind, S.pix, S.score, S.xy, S.desc, S.bin,
+                                     k.height, o.threshold, o.max_keypoints, F.fwork.view(), F.desc_kind, S.pix, S.score, S.xy, S.desc, S.bin,
                                      c->stream));
-  if ((rc = read_count(c, F.fwork.ctl + rpe::kFeatCtlCount, &S.count))) return rc;
+  if ((rc = read_ints(c, F.fwork.ctl + rpe::kFeatCtlCount, 1, &S.count))) return rc;
   S.have = true; S.gen++; S.threshold = o.threshold; S.max_keypoints = o.max_keypoints; S.kind = F.desc_kind;
   if (count) *count = S.count;
   return RPE_OK;
@@ -170,14 +189,14 @@ int rpe_features_match(rpe_context* c, const rpe_match_options* opt, int* matche
   if (!A.have || !B.have) return fail(RPE_ERR_STATE, "rpe_features_match: no features of the %s (rpe_features_detect)", A.have ? "model" : "frame");
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ensure_lists(c))) return rc;
-  const auto& L = F.mlist;
+  const rpe::MatchLists L = F.mlist.view();
   F.matches = -1; F.match_kf = -1;
   HIP_TRY(rpe::launch_feature_best(A.desc, A.count, B.desc, B.count, L.d1, L.idx, L.d2, c->stream));
   // the cross-check: the same pass with the roles swapped (its distances land in the match lists' slots, rewritten below)
   if (o.cross_check) HIP_TRY(rpe::launch_feature_best(B.desc, B.count, A.desc, A.count, L.md1, L.back, L.md2, c->stream));
   HIP_TRY(rpe::launch_feature_accept(L, A.count, o.max_dist, o.ratio_num, o.ratio_den, o.cross_check, F.fwork.ctl, c->stream));
   int m = 0;
-  if ((rc = read_count(c, F.fwork.ctl + rpe::kFeatCtlMatches, &m))) return rc;
+  if ((rc = read_ints(c, F.fwork.ctl + rpe::kFeatCtlMatches, 1, &m))) return rc;
   if (m > 0) {
     if ((rc = claim_slots(c, m))) return rc;
     HIP_TRY(rpe::launch_feature_gather(L, m, A.pix, B.pix, F.fmap[0], F.fmap[1], F.fmap[2], F.mmap[0], F.mmap[1], (float*)c->arr[RPE_XW],
@@ -216,39 +235,14 @@ int rpe_relocalize(rpe_context* c, const rpe_feature_options* fopt, const rpe_ma
   int rc;
   if ((rc = feature_options(&fo)) || (rc = match_options(&mo))) return rc;
   for (int which : {RPE_FEAT_FRAME, RPE_FEAT_MODEL}) {
-    if ((rc = side_ready(c, which))) return rc;
-    const auto& S = c->fe.feat[which];
-    if (S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints && S.kind == c->fe.desc_kind) continue;   // detected already, with these options and this descriptor
-    if ((rc = rpe_features_detect(c, which, &fo, nullptr))) return rc;
+    if ((rc = side_ready(c, which)) || (rc = detect_if_stale(c, which, fo))) return rc;
   }
   int m = 0;
   if ((rc = rpe_features_match(c, &mo, &m))) return rc;
   if (matches) *matches = m;
   if (m < min_matches) return fail(RPE_ERR_DEGENERATE, "rpe_relocalize: %d matches, %d needed (%d / %d keypoints)", m, min_matches,
                                    c->fe.feat[0].count, c->fe.feat[1].count);
-  // rpe_run's own path, on the host-pointer form of the problem: five arrays of 3 x m floats and the match quality as weight of
-  // every modality (m <= 4096: 240 KB at most)
-  const size_t n3 = (size_t)m * 3;
-  std::vector<float> host(5 * n3 + 3 * (size_t)m);
-  float* a[RPE_NUM_ARRAYS];
-  for (int s = 0; s < RPE_NUM_ARRAYS; s++) {
-    a[s] = host.data() + s * n3;
-    if ((rc = copy_to_host(c, a[s], c->arr[s], n3 * sizeof(float)))) return rc;
-  }
-  float* wq = host.data() + 5 * n3;
-  if ((rc = copy_to_host(c, wq, c->fe.mlist.mw, (size_t)m * sizeof(float)))) return rc;
-  for (int k = 1; k < 3; k++) std::memcpy(wq + (size_t)k * m, wq, (size_t)m * sizeof(float));
-  rpe_problem p{};
-  p.n = m; p.dtype = RPE_F32;
-  p.xw = a[RPE_XW]; p.xc = a[RPE_XC]; p.bv = a[RPE_BV]; p.nw = a[RPE_NW]; p.nc = a[RPE_NC];
-  p.weights = wq; p.wcols = 3;
-  p.fx = c->fe.kcam[0].fx; p.fy = c->fe.kcam[0].fy;
-  double R9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t3[3] = {0, 0, 0};
-  if ((rc = rpe_run(method, &p, thre_3d, thre_2d, thre_nl, iter_io, confidence, seed, ls, RPE_SCORE_EXACT, nullptr, R9, t3, max_votes, mask_out)))
-    return rc;
-  for (int i = 0; i < 9; i++) pose12[i] = R9[i];
-  for (int i = 0; i < 3; i++) pose12[9 + i] = t3[i];
-  return RPE_OK;
+  return run_on_slots(c, m, method, thre_3d, thre_2d, thre_nl, iter_io, confidence, seed, ls, pose12, max_votes, mask_out);
 }
 
 }  // extern "C"

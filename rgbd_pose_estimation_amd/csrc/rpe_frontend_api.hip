@@ -1,6 +1,6 @@
 // Part 3 of include/rgbd_pose_hip.h: the depth-frame front end (back-projection, normals, projective association: kernels in
 // rpe_frontend.hip) and ICP over it (fused rounds / resident grids: rpe_icp.hip).  No reference counterpart.
-#include "rpe_host.hpp"
+#include "rpe_frontend_host.hpp"
 #include <memory>
 using namespace rpeh;
 
@@ -8,20 +8,17 @@ namespace rpeh {
 // the solver slots the association writes: the context's own storage, n = pixels, fp32
 int claim_slots(rpe_context* c, int64_t n) {
   const size_t bytes = (size_t)n * 3 * sizeof(float);
-  for (int s = 0; s < RPE_NUM_ARRAYS; s++) {
-    if (!c->store[s] || c->cap[s] < bytes) {
-      if (c->store[s]) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->store[s])); c->store[s] = nullptr; c->cap[s] = 0;
-          }
-      HIP_TRY(hipMalloc(&c->store[s], bytes));
-      c->cap[s] = bytes;
-    }
-  }
+  for (auto& slot : c->store) if (int rc = slot.reserve(c, bytes)) return rc;
   if (c->n != n || c->dtype != RPE_F32) {  // a different problem was loaded before: its masks / weights do not apply
     for (int i = 0; i < 3; i++) { c->mask[i] = nullptr; c->weight[i] = nullptr; }
   }
   c->n = n; c->dtype = RPE_F32;
   // (the association kernel rewrites them every round, NaN-marking the pixels without a partner: never promoted to "verified")
   for (int s = 0; s < RPE_NUM_ARRAYS; s++) { c->arr[s] = c->store[s]; arrays_changed(c, s, true); }
+  return RPE_OK;
+}
+int model_room(rpe_context* c, int64_t n) {
+  for (auto& m : c->fe.mmap) if (int rc = m.reserve(c, (size_t)n * 3 * sizeof(float))) return rc;
   return RPE_OK;
 }
 }  // namespace rpeh
@@ -84,21 +81,14 @@ int plan_levels(const rpe_camera& k0, int levels, rpe_camera* kc, rpe::PyramidGe
   for (int l = levels + 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = g->off[levels];
   return RPE_OK;
 }
-// raw depth of n pixels to the device (and the pair counter)
-int stage_depth(rpe_context* c, const void* depth, int depth_type, int64_t n) {
+// room for the raw depth of n pixels (and the pair counter; filter on: the filtered depth, on first use or for a larger frame) and
+// for `maps` pixels in each of the frame's three maps
+int stage_depth(rpe_context* c, int depth_type, int64_t n, int64_t maps) {
   auto& F = c->fe;
-  const size_t bytes = (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4);
-  if (!F.d_depth || F.depth_cap < bytes) {
-    if (F.d_depth) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(F.d_depth)); F.d_depth = nullptr; F.depth_cap = 0; }
-    HIP_TRY(hipMalloc(&F.d_depth, bytes));
-    F.depth_cap = bytes;
-  }
-  if (!F.d_count) HIP_TRY(hipMalloc((void**)&F.d_count, 64));
-  if (F.filter.radius > 0 && (!F.d_filt || F.filt_cap < (size_t)n * sizeof(float))) {   // the filtered depth: first use, or a larger frame
-    if (F.d_filt) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(F.d_filt)); F.d_filt = nullptr; F.filt_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&F.d_filt, (size_t)n * sizeof(float)));
-    F.filt_cap = (size_t)n * sizeof(float);
-  }
+  int rc;
+  if ((rc = F.d_depth.reserve(c, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4))) || (rc = F.d_count.once(c, 64))) return rc;
+  if (F.filter.radius > 0 && (rc = F.d_filt.reserve(c, (size_t)n * sizeof(float)))) return rc;
+  for (auto& m : F.fmap) if ((rc = m.reserve(c, (size_t)maps * 3 * sizeof(float)))) return rc;
   return RPE_OK;
 }
 // what F1 / F1p read behind the upload: the raw depth as it came, or -- filter on -- F0's metric depth of it (float32, scale 1)
@@ -149,8 +139,7 @@ int rpe_frame_set_depth(rpe_context* c, const void* depth, int depth_type, const
   HIP_TRY(hipSetDevice(c->device));
   auto& F = c->fe;
   const int64_t n = (int64_t)k.width * k.height;
-  if ((rc = stage_depth(c, depth, depth_type, n))) return rc;
-  if ((rc = ensure_maps(c, F.fmap, 3, &F.fcap, n))) return rc;
+  if ((rc = stage_depth(c, depth_type, n, n))) return rc;
   F.have_frame = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   DepthSource src;
@@ -176,13 +165,7 @@ int rpe_frame_set_depth_pyramid(rpe_context* c, const void* depth, int depth_typ
   HIP_TRY(hipSetDevice(c->device));
   auto& F = c->fe;
   const int64_t n = (int64_t)g.cam[0].width * g.cam[0].height, total = g.off[levels];
-  if ((rc = stage_depth(c, depth, depth_type, n))) return rc;
-  if ((rc = ensure_maps(c, F.fmap, 3, &F.fcap, total))) return rc;
-  if (!F.fdepth || F.fdcap < (size_t)total * sizeof(float)) {
-    if (F.fdepth) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(F.fdepth)); F.fdepth = nullptr; F.fdcap = 0; }
-    HIP_TRY(hipMalloc((void**)&F.fdepth, (size_t)total * sizeof(float)));
-    F.fdcap = (size_t)total * sizeof(float);
-  }
+  if ((rc = stage_depth(c, depth_type, n, total)) || (rc = F.fdepth.reserve(c, (size_t)total * sizeof(float)))) return rc;
   F.have_frame = false; F.have_depth = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   DepthSource src;
@@ -247,7 +230,7 @@ int rpe_model_from_frame(rpe_context* c, const double* pose12) {
   if (!F.have_frame) return fail(RPE_ERR_STATE, "no frame: call rpe_frame_set_depth first");
   HIP_TRY(hipSetDevice(c->device));
   const int64_t n = F.fgeo.off[F.fgeo.levels];   // every level (one level: width * height)
-  int rc = ensure_maps(c, F.mmap, 2, &F.mcap, n);
+  int rc = model_room(c, n);
   if (rc) return rc;
   F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(rpe::launch_to_world(F.fmap[0], F.fmap[1], n, pose_f(pose12), F.mmap[0], F.mmap[1], c->stream));
@@ -268,7 +251,7 @@ int rpe_model_upload(rpe_context* c, const float* vertex_w, const float* normal_
   HIP_TRY(hipSetDevice(c->device));
   auto& F = c->fe;
   const int64_t n = (int64_t)k.width * k.height;
-  if ((rc = ensure_maps(c, F.mmap, 2, &F.mcap, n))) return rc;
+  if ((rc = model_room(c, n))) return rc;
   F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.mmap[0], vertex_w, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(F.mmap[1], normal_w, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
@@ -291,16 +274,10 @@ int rpe_model_build_pyramid(rpe_context* c, int levels) {
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const size_t bytes = (size_t)g.off[levels] * 3 * sizeof(float);
-  if (F.mcap < bytes) {   // grow, keeping level 0
-    float* fresh[2] = {nullptr, nullptr};
-    for (int k = 0; k < 2; k++) {
-      HIP_TRY(hipMalloc((void**)&fresh[k], bytes));
-      HIP_TRY(hipMemcpyAsync(fresh[k], F.mmap[k], (size_t)g.cam[0].width * g.cam[0].height * 3 * sizeof(float), hipMemcpyDeviceToDevice,
-                             c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 2; k++) { HIP_TRY(hipFree(F.mmap[k])); F.mmap[k] = fresh[k]; }
-    F.mcap = bytes;
+  if (F.mmap[0].bytes() < bytes) {   // grow, keeping level 0
+    const size_t keep = (size_t)g.cam[0].width * g.cam[0].height * 3 * sizeof(float);
+    const DevMem::Grow grow[] = {{&F.mmap[0], keep, bytes}, {&F.mmap[1], keep, bytes}};
+    if ((rc = DevMem::regrow(c, "model pyramid", grow))) return rc;
   }
   F.photo_levels = 0;   // the model's levels move: the photometric map is laid out by them
   HIP_TRY(rpe::launch_model_pyramid(g, F.mmap[0], F.mmap[1], c->stream));

@@ -1,0 +1,56 @@
+// What the Part 3 units of the C ABI share on the host (rpe_host.hpp lists the units): camera and pose casts, the solver slots a
+// device-side producer writes, and the single copies of what the feature, keyframe, colour and rebuild units have in common, each
+// defined in the unit that owns it.  Everything is internal to the library (namespace rpeh, hidden visibility).
+#pragma once
+#include "rpe_host.hpp"
+
+namespace rpeh __attribute__((visibility("hidden"))) {
+
+// an rpe_camera validated and cast to the kernels' fp32 camera
+inline int camera_of(const rpe_camera* cam, rpe::Camera* out) {
+  if (!cam || cam->width < 1 || cam->height < 1 || !(cam->fx > 0) || !(cam->fy > 0)
+      || (int64_t)cam->width * cam->height > (int64_t)1 << 28)
+    return fail(RPE_ERR_ARG, "bad camera (need width, height >= 1 and fx, fy > 0)");
+  out->fx = (float)cam->fx; out->fy = (float)cam->fy; out->cx = (float)cam->cx; out->cy = (float)cam->cy;
+  out->width = cam->width; out->height = cam->height;
+  return RPE_OK;
+}
+inline rpe::PoseF pose_f(const double* p12) {
+  rpe::PoseF T;
+  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
+  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
+  return T;
+}
+// the solver slots a device-side producer writes (association, feature matches): the context's own storage, n columns, fp32
+// (rpe_frontend_api.hip)
+int claim_slots(rpe_context* c, int64_t n);
+// room for n pixels in each of the model's two maps, content not kept (rpe_frontend_api.hip)
+int model_room(rpe_context* c, int64_t n);
+// the one-level pyramid of a single image (rpe_frame_set_depth, rpe_model_upload, rpe_volume_raycast)
+inline void one_level(const rpe_camera& k, const rpe::Camera& f, rpe_camera* kc, rpe::PyramidGeometry* g) {
+  *g = rpe::PyramidGeometry{};
+  g->levels = 1; g->cam[0] = f; kc[0] = k;
+  for (int l = 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = (int64_t)f.width * f.height;
+}
+
+// ---- rpe_color_api.hip
+// the colour volume of the current volume: allocated on first use after rpe_volume_init, cleared to 0 unless `clear` is false (the
+// caller overwrites every voxel)
+int ensure_color_volume(rpe_context* c, bool clear);
+
+// ---- rpe_feature_api.hip
+extern const rpe_feature_options kFeatureDefaults;
+extern const rpe_match_options kMatchDefaults;
+int feature_options(const rpe_feature_options* o);   // the range check of either option struct (RPE_ERR_ARG)
+int match_options(const rpe_match_options* o);
+int ensure_lists(rpe_context* c);                    // c->fe.mlist, allocated on first use
+// n ints a kernel left in device memory, through the pinned words every count of the front end takes: one host wait
+int read_ints(rpe_context* c, const int* d_words, int n, int* out);
+// rpe_features_detect on one side, unless that side was already detected with these options and the context's descriptor kind
+int detect_if_stale(rpe_context* c, int which, const rpe_feature_options& fo);
+// the m matches in the solver slots through rpe_run's own path, on the host-pointer form of the problem: five arrays of 3 x m floats
+// down, the match quality as weight of every modality (m <= 4096: 240 KB at most).  pose12 is written on success only
+int run_on_slots(rpe_context* c, int m, int method, double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence,
+                 uint64_t seed, int ls, double* pose12, int* max_votes, short* mask_out);
+
+}  // namespace rpeh

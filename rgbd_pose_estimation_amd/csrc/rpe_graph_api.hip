@@ -17,23 +17,12 @@ rpe_graph* graph_of(rpe_context* c) {
 int graph_reserve(rpe_context* c, int64_t more) {
   rpe_graph* G = graph_of(c);
   const int64_t need = G->used + more;
-  if (need <= G->cap) return RPE_OK;
-  int64_t cap = std::max<int64_t>(G->cap, 16 * (int64_t)rpe::kMaxKeypoints);
+  if (need <= G->cap()) return RPE_OK;
+  int64_t cap = std::max<int64_t>(G->cap(), 16 * (int64_t)rpe::kMaxKeypoints);
   while (cap < need) cap *= 2;
-  int* q[2] = {nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipMalloc((void**)&q[k], (size_t)cap * sizeof(int));
-  int* old[2] = {G->a, G->b};
-  for (int k = 0; k < 2 && e == hipSuccess; k++)
-    if (old[k] && G->used) e = hipMemcpyAsync(q[k], old[k], (size_t)G->used * sizeof(int), hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    for (int* m : q) if (m) (void)hipFree(m);
-    return fail(RPE_ERR_HIP, "graph storage: %s", hipGetErrorString(e));
-  }
-  for (int* m : old) if (m) (void)hipFree(m);
-  G->a = q[0]; G->b = q[1]; G->cap = cap;
-  return RPE_OK;
+  const size_t keep = (size_t)G->used * sizeof(int), bytes = (size_t)cap * sizeof(int);
+  const DevMem::Grow g[] = {{&G->a, keep, bytes}, {&G->b, keep, bytes}};
+  return DevMem::regrow(c, "graph storage", g);
 }
 
 void graph_drop_from(rpe_context* c, int first) {
@@ -48,10 +37,11 @@ void graph_drop_from(rpe_context* c, int first) {
 // the live edges' pairs moved together, in edge order, into fresh arrays of the same size (the dead ranges of replaced edges go)
 int graph_compact(rpe_context* c) {
   rpe_graph* G = c->graph;
-  if (!G || !G->cap) return RPE_OK;
-  int* q[2] = {nullptr, nullptr};
+  if (!G || !G->cap()) return RPE_OK;
+  DevBuf<int> q[2];   // swapped in on success, gone with this scope otherwise
+  int rc;
+  if ((rc = q[0].once(c, G->a.bytes())) || (rc = q[1].once(c, G->b.bytes()))) return rc;
   hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipMalloc((void**)&q[k], (size_t)G->cap * sizeof(int));
   int64_t at = 0;
   std::vector<int> off(G->edges.size());
   for (size_t n = 0; n < G->edges.size() && e == hipSuccess; n++) {
@@ -63,21 +53,14 @@ int graph_compact(rpe_context* c) {
     at += E.count;
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    for (int* m : q) if (m) (void)hipFree(m);
-    return fail(RPE_ERR_HIP, "graph storage: %s", hipGetErrorString(e));
-  }
-  (void)hipFree(G->a); (void)hipFree(G->b);
-  G->a = q[0]; G->b = q[1]; G->used = at; G->dirty = true;
+  if (e != hipSuccess) return fail(RPE_ERR_HIP, "graph storage: %s", hipGetErrorString(e));
+  G->a = std::move(q[0]); G->b = std::move(q[1]); G->used = at; G->dirty = true;
   for (size_t n = 0; n < G->edges.size(); n++) G->edges[n].off = off[n];
   return RPE_OK;
 }
 
 void graph_free(rpe_context* c) {
-  rpe_graph* G = c->graph;
-  if (!G) return;
-  for (void* m : {(void*)G->a, (void*)G->b, (void*)G->d_edges, (void*)G->d_raw, (void*)G->d_corr}) if (m) (void)hipFree(m);
-  delete G;
+  delete c->graph;
   c->graph = nullptr;
 }
 
@@ -98,19 +81,13 @@ int graph_ready(rpe_context* c, const char* who) {
 int graph_device(rpe_context* c) {
   rpe_graph* G = c->graph;
   const int n = (int)G->edges.size();
-  if (!G->d_corr) HIP_TRY(hipMalloc((void**)&G->d_corr, (size_t)rpe::kMaxKeyframes * rpe::kGraphCorr * sizeof(float)));
-  if (n > G->edges_cap) {
-    int cap = std::max(G->edges_cap, 64);
-    while (cap < n) cap *= 2;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (G->d_edges) { HIP_TRY(hipFree(G->d_edges)); G->d_edges = nullptr; }
-    if (G->d_raw) { HIP_TRY(hipFree(G->d_raw)); G->d_raw = nullptr; }
-    G->edges_cap = 0;
-    HIP_TRY(hipMalloc((void**)&G->d_edges, (size_t)cap * sizeof(rpe::GraphEdgeDev)));
-    HIP_TRY(hipMalloc((void**)&G->d_raw, (size_t)cap * rpe::kGraphRaw * sizeof(double)));
-    G->edges_cap = cap;
-    G->dirty = true;
-  }
+  int rc;
+  if ((rc = G->d_corr.once(c, (size_t)rpe::kMaxKeyframes * rpe::kGraphCorr * sizeof(float)))) return rc;
+  int cap = std::max(G->edges_cap(), 64);
+  while (cap < n) cap *= 2;
+  if (n > G->edges_cap()) G->dirty = true;
+  if ((rc = G->d_edges.reserve(c, (size_t)cap * sizeof(rpe::GraphEdgeDev))) ||
+      (rc = G->d_raw.reserve(c, (size_t)cap * rpe::kGraphRaw * sizeof(double)))) return rc;
   if (G->dirty) {
     std::vector<rpe::GraphEdgeDev> t(n);
     int out = 0;
@@ -223,7 +200,7 @@ int graph_round(rpe_context* c, const std::vector<Pose>& P, double gate, std::ve
   const int n = (int)G->edges.size();
   int rc;
   if ((rc = upload_corrections(c, P))) return rc;
-  HIP_TRY(rpe::launch_graph_round(G->d_edges, n, G->a, G->b, c->kf.st, G->d_corr, gate_sq(gate), G->d_raw, c->stream));
+  HIP_TRY(rpe::launch_graph_round(G->d_edges, n, G->a, G->b, c->kf.store(), G->d_corr, gate_sq(gate), G->d_raw, c->stream));
   raw->resize((size_t)n * rpe::kGraphRaw);
   if ((rc = copy_to_host(c, raw->data(), G->d_raw, raw->size() * sizeof(double)))) return rc;
   for (int e = 0; e < n; e++)
@@ -314,12 +291,11 @@ int rpe_graph_residuals(rpe_context* c, const double* poses12, double gate, floa
   if ((rc = graph_device(c)) || (rc = upload_corrections(c, P))) return rc;
   rpe_graph* G = c->graph;
   const size_t bytes = (size_t)G->pairs() * 3 * sizeof(float);
-  float* d_rows = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_rows, bytes));
-  hipError_t e = rpe::launch_graph_rows(G->d_edges, (int)G->edges.size(), G->a, G->b, c->kf.st, G->d_corr, gate_sq(gate), d_rows, c->stream);
+  DevBuf<float> d_rows;
+  if ((rc = d_rows.once(c, bytes))) return rc;
+  hipError_t e = rpe::launch_graph_rows(G->d_edges, (int)G->edges.size(), G->a, G->b, c->kf.store(), G->d_corr, gate_sq(gate), d_rows, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(r, d_rows, bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_rows);
   if (e != hipSuccess) return fail(RPE_ERR_HIP, "rpe_graph_residuals: %s", hipGetErrorString(e));
   return RPE_OK;
 }
@@ -389,7 +365,7 @@ int rpe_keyframes_optimize(rpe_context* c, int anchor, int rounds, const double*
   if (poses12_out) for (int k = 0; k < n; k++) std::memcpy(poses12_out + 12 * k, P[k].data(), sizeof(Pose));
   if (apply) {
     if ((rc = upload_corrections(c, P))) return rc;
-    HIP_TRY(rpe::launch_graph_apply(K.st, n, (int)K.used, G->d_corr, c->stream));
+    HIP_TRY(rpe::launch_graph_apply(K.store(), n, (int)K.used, G->d_corr, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int k = 0; k < n; k++) std::memcpy(K.meta[k].pose, P[k].data(), sizeof(Pose));
     if (c->fe.match_kf >= 0) { c->fe.matches = -1; c->fe.match_kf = -1; }   // a keyframe match list's slots held the old points

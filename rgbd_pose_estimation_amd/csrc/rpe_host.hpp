@@ -14,10 +14,14 @@
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
 //   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)
 //   rpe_rebuild_api.hip   Part 3: the volume rebuilt from the keyframes' attached depth (rpe_volume_fuse_keyframes; kernels in rpe_rebuild.hip)
+// Two headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
+// host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create) and rpe_frontend_host.hpp (what the
+// Part 3 units share: camera and pose casts, the solver slots, feature / match options, the relocalisers' common steps).
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
 #include "rpe_kernels.h"
+#include "rpe_devbuf.hpp"
 #include "../include/rpe/linalg.hpp"
 
 #include <dlfcn.h>
@@ -69,12 +73,9 @@ struct rpe_context {
   void* weight[3] = {nullptr, nullptr, nullptr};
   // ... and the storage this context owns; it survives rpe_set_problem so that a pooled context (rpe/device.hpp) serving
   // one frame after another does not pay hipMalloc/hipFree per call
-  void* store[RPE_NUM_ARRAYS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t cap[RPE_NUM_ARRAYS] = {0, 0, 0, 0, 0};
-  short* mask_store[3] = {nullptr, nullptr, nullptr};
-  size_t mask_cap[3] = {0, 0, 0};
-  void* weight_store[3] = {nullptr, nullptr, nullptr};
-  size_t weight_cap[3] = {0, 0, 0};
+  rpeh::DevBuf<void> store[RPE_NUM_ARRAYS];
+  rpeh::DevBuf<short> mask_store[3];
+  rpeh::DevBuf<void> weight_store[3];
   int max_blocks = 256;          // reduction kernels: cap on workgroups = one per CU (multiples of 256 only: 320 or 384 lose 20-30 %)
   int score_blocks = 2048;       // scoring / mask kernels (256-thread workgroups)
   int block = 0;                 // reduction workgroup size override (RPE_BLOCK), 0 = default
@@ -86,16 +87,16 @@ struct rpe_context {
   bool guard_always = false;     // RPE_GUARD_ALWAYS=1: never launch the CLEAN flavour (experiments, A/B)
   int host_cpu_request = -2;     // RPE_HOST_CPU at rpe_create: -2 none, -1 auto (rpe_tune_host_thread at the first resident refinement), >= 0 that CPU
   bool host_cpu_done = false;
-  double* d_partials = nullptr;  // max_blocks * kNlLd doubles
-  double* d_out = nullptr;       // 64 doubles + kRunSlots x kRunLd doubles of run records (rpe_dist.hip)
+  rpeh::DevBuf<double> d_partials;   // max_blocks * kNlLd doubles
+  rpeh::DevBuf<double> d_out;    // 64 doubles + kRunSlots x kRunLd doubles of run records (rpe_dist.hip)
   double* h_out = nullptr;       // pinned + device-mapped, 64 doubles + sequence word: kernels publish straight into it
-  unsigned int* d_ticket = nullptr;
+  rpeh::DevBuf<unsigned int> d_ticket;
   unsigned long long seq = 0;
-  double* d_gn_pose = nullptr;          // device-resident Gauss-Newton: pose (12 doubles) ...
-  rpe::GnState* d_gn_state = nullptr;   // ... and loop state, both in HBM
-  void* d_poses = nullptr;       // kMaxScoreH * 12 doubles
+  rpeh::DevBuf<double> d_gn_pose;       // device-resident Gauss-Newton: pose (12 doubles) ...
+  rpeh::DevBuf<rpe::GnState> d_gn_state;   // ... and loop state, both in HBM
+  rpeh::DevBuf<void> d_poses;    // kMaxScoreH * 12 doubles
   void* h_poses = nullptr;       // pinned staging
-  int* d_votes = nullptr;        // kMaxScoreH ints
+  rpeh::DevBuf<int> d_votes;     // kMaxScoreH ints
   int* h_votes = nullptr;        // pinned
   // optional HIP-event timing of the stage-1 normal-equation kernel (bench.py roofline leg)
   std::vector<hipEvent_t> ev0, ev1;
@@ -135,10 +136,10 @@ struct rpe_context {
   // two ranks on one GPU: no resident kernels (they would wait for each other's hosts without both being resident)
   bool hostex_shared_gpu = false;
   // PROSAC order on the device (rpe_prosac_order): scratch
-  float* ps_w = nullptr; size_t ps_w_cap = 0;
-  unsigned int* ps_hist = nullptr;        // 2048 + 8 uints (histogram | control words)
-  unsigned long long* ps_cand = nullptr;  // kProsacSortCap keys
-  int* ps_order = nullptr;                // kProsacMaxTopK + 1 ints (order | status)
+  rpeh::DevBuf<float> ps_w;                 // the weights of the last call (grown to the largest n seen)
+  rpeh::DevBuf<unsigned int> ps_hist;       // 2048 + 8 uints (histogram | control words)
+  rpeh::DevBuf<unsigned long long> ps_cand; // kProsacSortCap keys
+  rpeh::DevBuf<int> ps_order;               // kProsacMaxTopK + 1 ints (order | status)
   // optional host-clock profile of the resident loop (rpe_debug_loop_profile): time spent waiting for records vs the host's own turn
   bool loop_prof = false;
   double prof_wait_us = 0, prof_host_us = 0;
@@ -149,89 +150,90 @@ struct rpe_context {
   struct Frontend {
     rpe::Camera cam{}, mcam{};
     bool have_frame = false, have_model = false;
-    void* d_depth = nullptr; size_t depth_cap = 0;
-    float* fmap[3] = {nullptr, nullptr, nullptr};   // vertex, normal, bearing (camera frame)
-    size_t fcap = 0;
-    float* mmap[2] = {nullptr, nullptr};            // model vertex, normal (world frame)
-    size_t mcap = 0;
+    rpeh::DevBuf<void> d_depth;
+    rpeh::DevBuf<float> fmap[3];                    // vertex, normal, bearing (camera frame)
+    rpeh::DevBuf<float> mmap[2];                    // model vertex, normal (world frame)
     double mpose[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    int* d_count = nullptr;
+    rpeh::DevBuf<int> d_count;
     // coarse-to-fine pyramid: fp32 level cameras, level offsets into the maps above and level counts (cam / mcam = level 0), the fp64
     // level cameras they were cast from, and the metric depth of every level (rpe_frame_set_depth_pyramid only: have_depth)
     rpe::PyramidGeometry fgeo{}, mgeo{};
     rpe_camera kcam[RPE_MAX_LEVELS] = {}, mkcam[RPE_MAX_LEVELS] = {};
-    float* fdepth = nullptr; size_t fdcap = 0;
+    rpeh::DevBuf<float> fdepth;
     bool have_depth = false;
     // depth filter (rpe_frame_set_filter): the setting as given (radius 0 = off), its fp32 form for the kernel, and the filtered
     // level-0 depth the next rpe_frame_set_depth* hands to F1 / F1p in the raw depth's place (allocated on first use, reused)
     rpe_depth_filter filter = {0, 0.0, 0.0, 0.0};
     rpe::FilterParams fparams{};
-    float* d_filt = nullptr; size_t filt_cap = 0;
+    rpeh::DevBuf<float> d_filt;
     // colour (rpe_color_api.hip): the frame's 3-byte staging upload and its RGBA8 map (level-0 pixels, dropped by a new depth), and
     // the model's RGBA8 colour map (level-0 pixels, sampled from the colour volume, dropped by any call that replaces the model)
-    unsigned char* d_rgb = nullptr; size_t rgb_cap = 0;
-    unsigned int* fcolor = nullptr; size_t fccap = 0;
-    unsigned int* mcolor = nullptr; size_t mccap = 0;
+    rpeh::DevBuf<unsigned char> d_rgb;
+    rpeh::DevBuf<unsigned int> fcolor, mcolor;
     bool have_fcolor = false, have_mcolor = false;
     // photometric term (rpe_photo_api.hip): the frame's intensity pyramid (one float per pixel, the frame's level offsets) and the
     // model's photometric map (float4 {I, gx, gy, zm} per pixel, the model's level offsets), prepared for photo_levels levels
     // (0 = not prepared: whatever replaces the frame's depth or colour, the model or the model colour resets it)
-    float* pint = nullptr; size_t pint_cap = 0;
-    float* pmap = nullptr; size_t pmap_cap = 0;
+    rpeh::DevBuf<float> pint, pmap;
     int photo_levels = 0;
     // features (rpe_feature_api.hip): per side (RPE_FEAT_FRAME / RPE_FEAT_MODEL) the keypoints of the last detection -- pixel index,
     // score, xy and 8 descriptor words each, RPE_MAX_KEYPOINTS slots, allocated on first use -- valid while `have` (whatever replaces
     // the side's depth, model or colour resets it); gen counts the side's detections so that a match list knows what it was made of
     // kind / bin: the descriptor kind the detection was made with and, for RPE_DESC_ORIENTED, the keypoints' angle bins.  desc_kind is
     // the context's kind (rpe_features_set_descriptor): what the next detection on either side uses
-    struct Features { int *pix = nullptr, *score = nullptr, *xy = nullptr; unsigned int* desc = nullptr; int count = 0; bool have = false;
-                      unsigned long long gen = 0; int threshold = 0, max_keypoints = 0; int kind = 0; int* bin = nullptr; } feat[2];
+    struct Features { rpeh::DevBuf<int> pix, score, xy, bin; rpeh::DevBuf<unsigned int> desc; int count = 0; bool have = false;
+                      unsigned long long gen = 0; int threshold = 0, max_keypoints = 0; int kind = 0; } feat[2];
     int desc_kind = 0;
-    rpe::FeatureWork fwork{};            // the detector's workspace, sized for fwork_pixels pixels (shared by both sides)
-    int64_t fwork_pixels = 0;
-    rpe::MatchLists mlist{};             // best / second best per keypoint and the accepted matches (RPE_MAX_KEYPOINTS slots)
+    // the detector's workspace, sized for the largest image seen (shared by both sides), and the match lists: best / second best per
+    // keypoint and the accepted matches (RPE_MAX_KEYPOINTS slots).  view(): the plain pointer struct a launch takes by value
+    struct Work { rpeh::DevBuf<int> score, chunk, ctl, spix; rpeh::DevBuf<unsigned short> box; rpeh::DevBuf<unsigned int> hist;
+                  rpe::FeatureWork view() const { return {score, box, chunk, hist, ctl, spix}; } } fwork;
+    struct Lists { rpeh::DevBuf<int> d1, idx, d2, back, mf, mm, md1, md2; rpeh::DevBuf<float> mw;
+                   rpe::MatchLists view() const { return {d1, idx, d2, back, mf, mm, md1, md2, mw}; } } mlist;
     int matches = -1;                    // accepted matches of the last rpe_features_match (-1: none) ...
     unsigned long long match_gen[2] = {0, 0};   // ... made of these detections
     int match_kf = -1;                   // ... against this keyframe of the store in the model's place (-1: against the model side)
   } fe;
-  // keyframes (rpe_keyframe_api.hip): the packed store (rpe::KeyframeStore, room for `cap` keypoints, grown in steps), per keyframe
-  // what the host keeps, and the query's workspace: back = per store keypoint its best frame keypoint (cap ints), d1 / idx / d2 =
-  // one row of RPE_MAX_KEYPOINTS ints per keyframe (rows_cap rows), rank = counts | order (2 x RPE_MAX_KEYFRAMES ints).  The store
-  // belongs to the context: nothing but rpe_keyframes_clear and rpe_destroy touches it.
+  // keyframes (rpe_keyframe_api.hip): the packed store (off / desc / xw / nw / xy, room for cap() keypoints, grown in steps; store() =
+  // the kernels' rpe::KeyframeStore of it), per keyframe what the host keeps, and the query's workspace: back = per store keypoint its
+  // best frame keypoint (cap() ints), d1 / idx / d2 = one row of RPE_MAX_KEYPOINTS ints per keyframe (rows_cap() rows), rank = counts |
+  // order (2 x RPE_MAX_KEYFRAMES ints).  The store belongs to the context: nothing but rpe_keyframes_clear and rpe_destroy touches it.
   struct Keyframes {
     struct Meta { int off = 0, count = 0, width = 0, height = 0; double pose[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}; };
     std::vector<Meta> meta;
-    rpe::KeyframeStore st{};
-    int64_t cap = 0, used = 0;
-    int *back = nullptr, *d1 = nullptr, *idx = nullptr, *d2 = nullptr, *rank = nullptr;
-    int rows_cap = 0;
+    rpeh::DevBuf<int> off, xy; rpeh::DevBuf<unsigned int> desc; rpeh::DevBuf<float> xw, nw;
+    rpe::KeyframeStore store() const { return {off, desc, xw, nw, xy}; }
+    int64_t used = 0;
+    rpeh::DevBuf<int> back, d1, idx, d2, rank;
+    int64_t cap() const { return (int64_t)(back.bytes() / sizeof(int)); }
+    int rows_cap() const { return (int)(d1.bytes() / ((size_t)RPE_MAX_KEYPOINTS * sizeof(int))); }
     int kind = -1;                       // the descriptor kind of every keyframe in the store: its first one's (-1: the store is empty)
     // attachments (rpe_keyframe_attach_*): per keyframe id its level-0 depth as a packed plane (NaN = invalid), optionally its RGBA8
     // colour, and the camera both were taken with (fp32 for the kernels, the rpe_camera it was cast from).  att may be shorter than
     // meta (a keyframe without an entry has nothing attached); rpe_keyframes_clear drops what is attached and keeps the memory for
     // the next keyframe of that id.  d_table: the descriptor table of rpe_volume_fuse_keyframes (RPE_MAX_KEYFRAMES entries)
-    struct Attachment { float* z = nullptr; unsigned int* rgba = nullptr; size_t zcap = 0, ccap = 0; bool have_depth = false, have_color = false;
+    struct Attachment { rpeh::DevBuf<float> z; rpeh::DevBuf<unsigned int> rgba; bool have_depth = false, have_color = false;
                         rpe::Camera cam{}; rpe_camera kcam{}; };
     std::vector<Attachment> att;
-    rpe::FuseEntry* d_table = nullptr;
+    rpeh::DevBuf<rpe::FuseEntry> d_table;
   } kf;
   struct rpe_graph* graph = nullptr;     // the keyframe graph beside the store (rpe_graph.h), made by the first call that needs it
   // TSDF volume (Part 3, rpe_volume_api.hip): one per context, dim0 x dim1 x dim2 float2 {tsdf, weight} voxels in HBM
   struct Volume {
     rpe::VolumeGeometry g{};
-    float* d = nullptr; size_t cap = 0;   // bytes allocated
+    rpeh::DevBuf<float> d;
     bool have = false;
     // mesh extraction (rpe_mesh_api.hip): the workspace (allocated on the first extraction, freed when the volume grows) and the
     // last mesh, 3 x nv vertex / normal floats and 3 x nt int32 ids (valid while have_mesh)
-    void* ws = nullptr; size_t ws_cap = 0;
-    float *mv = nullptr, *mn = nullptr; int32_t* mt = nullptr; size_t mv_cap = 0, mt_cap = 0;
+    rpeh::DevBuf<void> ws;
+    rpeh::DevBuf<float> mv, mn; rpeh::DevBuf<int32_t> mt;
     int64_t nv = 0, nt = 0;
     bool have_mesh = false;
     // colour volume (rpe_color_api.hip): 4 binary16 {r, g, b, wc} per voxel at the tsdf's index, allocated and cleared on the first
     // colour integrate or upload after rpe_volume_init (have_color); mc = the RGBA8 colours of the last mesh's vertices
-    unsigned short* cd = nullptr; size_t ccap = 0;
+    rpeh::DevBuf<unsigned short> cd;
     bool have_color = false;
-    unsigned int* mc = nullptr; size_t mc_cap = 0;
+    rpeh::DevBuf<unsigned int> mc;
   } vol;
 
   rpe::DeviceArrays arrays() const {
@@ -383,43 +385,6 @@ struct SlotHold {
 ResidentSlot& resident_mutex(int device);
 int resident_run_shape(int grid, int nacc, int max_rows, int rows_auto, rpe::ReduceTarget* rt);
 void note_lost_grid(rpe_context* c);
-
-// ---- front-end helpers shared by rpe_frontend_api.hip and rpe_volume_api.hip
-// an rpe_camera validated and cast to the kernels' fp32 camera
-inline int camera_of(const rpe_camera* cam, rpe::Camera* out) {
-  if (!cam || cam->width < 1 || cam->height < 1 || !(cam->fx > 0) || !(cam->fy > 0)
-      || (int64_t)cam->width * cam->height > (int64_t)1 << 28)
-    return fail(RPE_ERR_ARG, "bad camera (need width, height >= 1 and fx, fy > 0)");
-  out->fx = (float)cam->fx; out->fy = (float)cam->fy; out->cx = (float)cam->cx; out->cy = (float)cam->cy;
-  out->width = cam->width; out->height = cam->height;
-  return RPE_OK;
-}
-inline rpe::PoseF pose_f(const double* p12) {
-  rpe::PoseF T;
-  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
-  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
-  return T;
-}
-// (re)allocate `count` float maps of n pixels each
-inline int ensure_maps(rpe_context* c, float** maps, int count, size_t* cap, int64_t n) {
-  const size_t bytes = (size_t)n * 3 * sizeof(float);
-  if (maps[0] && *cap >= bytes) return RPE_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < count; i++) { if (maps[i]) { HIP_TRY(hipFree(maps[i])); maps[i] = nullptr; } }
-  *cap = 0;
-  for (int i = 0; i < count; i++) HIP_TRY(hipMalloc((void**)&maps[i], bytes));
-  *cap = bytes;
-  return RPE_OK;
-}
-// the solver slots a device-side producer writes (association, feature matches): the context's own storage, n columns, fp32
-// (rpe_frontend_api.hip)
-int claim_slots(rpe_context* c, int64_t n);
-// the one-level pyramid of a single image (rpe_frame_set_depth, rpe_model_upload, rpe_volume_raycast)
-inline void one_level(const rpe_camera& k, const rpe::Camera& f, rpe_camera* kc, rpe::PyramidGeometry* g) {
-  *g = rpe::PyramidGeometry{};
-  g->levels = 1; g->cam[0] = f; kc[0] = k;
-  for (int l = 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = (int64_t)f.width * f.height;
-}
 
 // ---- rpe_session.hip
 void session_end(rpe_context* c);      // every entry point that queues work behind the context's stream, reads the masks or reuses the host-side record area calls this first

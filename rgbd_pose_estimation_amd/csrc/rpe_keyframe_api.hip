@@ -8,66 +8,35 @@ using namespace rpeh;
 namespace {
 constexpr int64_t kStoreStep = 8 * (int64_t)rpe::kMaxKeypoints;                        // the store's first allocation, keypoints
 constexpr int64_t kStoreMax = (int64_t)rpe::kMaxKeyframes * rpe::kMaxKeypoints;
-const rpe_match_options kMatchDefaults = {64, 8, 10, 0};
 
-int match_options(const rpe_match_options* o) {
-  if (o->max_dist < 0 || o->max_dist > 256 || o->ratio_num < 1 || o->ratio_den < 1 || o->ratio_num > 65536 || o->ratio_den > 65536 ||
-      (o->cross_check != 0 && o->cross_check != 1))
-    return fail(RPE_ERR_ARG, "match options: max_dist 0 .. 256 (got %d), ratio_num / ratio_den 1 .. 65536 (got %d / %d), cross_check 0 or 1 (got %d)",
-                o->max_dist, o->ratio_num, o->ratio_den, o->cross_check);
-  return RPE_OK;
-}
-// larger arrays with the first `keep` elements of each kept: every new array first, the copies behind one another, ONE wait, then
-// the old arrays go.  A failure on the way frees what was new and leaves every array, and the capacity beside them, as it was
-struct Grow { void** p; size_t keep, bytes; };    // keep and bytes in bytes
-template <size_t N> int regrow(rpe_context* c, const Grow (&g)[N]) {
-  void* q[N] = {};
-  hipError_t e = hipSuccess;
-  for (size_t i = 0; i < N && e == hipSuccess; i++) e = hipMalloc(&q[i], g[i].bytes);
-  for (size_t i = 0; i < N && e == hipSuccess; i++)
-    if (*g[i].p && g[i].keep) e = hipMemcpyAsync(q[i], *g[i].p, g[i].keep, hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    for (void* m : q) if (m) (void)hipFree(m);
-    return fail(RPE_ERR_HIP, "keyframe storage: %s", hipGetErrorString(e));
-  }
-  for (size_t i = 0; i < N; i++) { if (*g[i].p) (void)hipFree(*g[i].p); *g[i].p = q[i]; }
-  return RPE_OK;
-}
 // room for `more` keypoints behind the store's last: the store doubles (from kStoreStep keypoints, up to its bound)
 int ensure_store(rpe_context* c, int more) {
   auto& K = c->kf;
-  if (!K.st.off) HIP_TRY(hipMalloc((void**)&K.st.off, (rpe::kMaxKeyframes + 1) * sizeof(int)));
-  if (!K.rank) HIP_TRY(hipMalloc((void**)&K.rank, 2 * rpe::kMaxKeyframes * sizeof(int)));
+  int rc;
+  if ((rc = K.off.once(c, (rpe::kMaxKeyframes + 1) * sizeof(int))) || (rc = K.rank.once(c, 2 * rpe::kMaxKeyframes * sizeof(int)))) return rc;
   const int64_t need = K.used + more;
-  if (need <= K.cap) return RPE_OK;
-  int64_t cap = std::max(K.cap, kStoreStep);
+  if (need <= K.cap()) return RPE_OK;
+  int64_t cap = std::max(K.cap(), kStoreStep);
   while (cap < need) cap *= 2;
   cap = std::min(cap, kStoreMax);
   const size_t u = (size_t)K.used, n = (size_t)cap;
-  const Grow g[] = {{(void**)&K.st.desc, 8 * u * sizeof(unsigned int), 8 * n * sizeof(unsigned int)},
-                    {(void**)&K.st.xw, 3 * u * sizeof(float), 3 * n * sizeof(float)},
-                    {(void**)&K.st.nw, 3 * u * sizeof(float), 3 * n * sizeof(float)},
-                    {(void**)&K.st.xy, 2 * u * sizeof(int), 2 * n * sizeof(int)},
-                    {(void**)&K.back, 0, n * sizeof(int)}};
-  int rc = regrow(c, g);
-  if (rc) return rc;
-  K.cap = cap;
-  return RPE_OK;
+  const DevMem::Grow g[] = {{&K.desc, 8 * u * sizeof(unsigned int), 8 * n * sizeof(unsigned int)},
+                            {&K.xw, 3 * u * sizeof(float), 3 * n * sizeof(float)},
+                            {&K.nw, 3 * u * sizeof(float), 3 * n * sizeof(float)},
+                            {&K.xy, 2 * u * sizeof(int), 2 * n * sizeof(int)},
+                            {&K.back, 0, n * sizeof(int)}};
+  return DevMem::regrow(c, "keyframe storage", g);
 }
 // `rows` rows of RPE_MAX_KEYPOINTS ints in each of d1 / idx / d2 (nothing in them outlives a call that asks for more)
 int ensure_rows(rpe_context* c, int rows) {
   auto& K = c->kf;
-  if (rows <= K.rows_cap) return RPE_OK;
-  int cap = std::max(K.rows_cap, 8);
+  if (rows <= K.rows_cap()) return RPE_OK;
+  int cap = std::max(K.rows_cap(), 8);
   while (cap < rows) cap *= 2;
   cap = std::min(cap, rpe::kMaxKeyframes);
   const size_t bytes = (size_t)cap * rpe::kMaxKeypoints * sizeof(int);
-  const Grow g[] = {{(void**)&K.d1, 0, bytes}, {(void**)&K.idx, 0, bytes}, {(void**)&K.d2, 0, bytes}};
-  int rc = regrow(c, g);
-  if (rc) return rc;
-  K.rows_cap = cap;
-  return RPE_OK;
+  const DevMem::Grow g[] = {{&K.d1, 0, bytes}, {&K.idx, 0, bytes}, {&K.d2, 0, bytes}};
+  return DevMem::regrow(c, "keyframe storage", g);
 }
 int new_keyframe(rpe_context* c, int kind, int count, const double* pose12, int width, int height, int* id) {
   auto& K = c->kf;
@@ -78,8 +47,8 @@ int new_keyframe(rpe_context* c, int kind, int count, const double* pose12, int 
   K.meta.push_back(m);
   K.used += count;
   const int k = (int)K.meta.size(), end = (int)K.used;
-  if (k == 1) { const int zero = 0; HIP_TRY(hipMemcpyAsync(K.st.off, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream)); }
-  HIP_TRY(hipMemcpyAsync(K.st.off + k, &end, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (k == 1) { const int zero = 0; HIP_TRY(hipMemcpyAsync(K.off, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream)); }
+  HIP_TRY(hipMemcpyAsync(K.off + k, &end, sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));      // `end` and the caller's arrays are the host's again
   if (id) *id = k - 1;
   return RPE_OK;
@@ -99,19 +68,20 @@ int kind_fits(rpe_context* c, int kind, const char* who) {
                 c->kf.kind);
   return RPE_OK;
 }
-int ensure_lists(rpe_context* c) {
-  auto& L = c->fe.mlist;
-  for (int** p : {&L.d1, &L.idx, &L.d2, &L.back, &L.mf, &L.mm, &L.md1, &L.md2}) if (!*p) HIP_TRY(hipMalloc((void**)p, rpe::kMaxKeypoints * sizeof(int)));
-  if (!L.mw) HIP_TRY(hipMalloc((void**)&L.mw, rpe::kMaxKeypoints * sizeof(float)));
-  return RPE_OK;
-}
-// several ints a kernel left in device memory, through the pinned words every count of the front end takes: one host wait
-int read_ints(rpe_context* c, const int* d_words, int n, int* out) {
-  const unsigned long long seq = ++c->vote_seq;
-  HIP_TRY(rpe::launch_publish_i32(d_words, n, c->h_votes, c->h_flag2, seq, c->stream));
-  int rc = wait_flag(c, c->h_flag2, seq);
-  if (rc) return rc;
-  std::memcpy(out, c->h_votes, (size_t)n * sizeof(int));
+// list A (na descriptors) against the store's keyframes 0 .. segs - 1: behind a cross-check the pass of the store's first `before`
+// keypoints against A first (K.back), then K2 with the acceptance test `acc` -- rows of d1 / idx / d2, the pairs that pass counted
+// per keyframe in K.rank
+int best_with_counts(rpe_context* c, const unsigned int* desc_a, int na, int before, int segs, const rpe_match_options& o,
+                     rpe::KeyframeAccept* acc) {
+  auto& K = c->kf;
+  int rc;
+  if ((rc = ensure_rows(c, segs))) return rc;
+  HIP_TRY(hipMemsetAsync(K.rank, 0, (size_t)segs * sizeof(int), c->stream));
+  if (o.cross_check)
+    HIP_TRY(rpe::launch_keyframe_best(K.desc, before, desc_a, nullptr, 0, 1, 0, na, rpe::KeyframeAccept{0, 1, 1, nullptr}, nullptr, K.back,
+                                      nullptr, nullptr, c->stream));
+  *acc = rpe::KeyframeAccept{o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? K.back.get() : nullptr};
+  HIP_TRY(rpe::launch_keyframe_best(desc_a, na, K.desc, K.off, 0, segs, 0, 0, *acc, K.d1, K.idx, K.d2, K.rank, c->stream));
   return RPE_OK;
 }
 // the frame's keypoints against every keyframe: row k of d1 / idx / d2 = keyframe k's, counts | order in K.rank and on the host
@@ -120,14 +90,8 @@ int query(rpe_context* c, const rpe_match_options& o, int* counts, int* order) {
   const auto& A = c->fe.feat[RPE_FEAT_FRAME];
   const int n = (int)K.meta.size();
   int rc;
-  if ((rc = ensure_rows(c, n))) return rc;
-  HIP_TRY(hipMemsetAsync(K.rank, 0, (size_t)n * sizeof(int), c->stream));
-  // the cross-check first: every keypoint of the store against the frame's list, one launch
-  if (o.cross_check)
-    HIP_TRY(rpe::launch_keyframe_best(K.st.desc, (int)K.used, A.desc, nullptr, 0, 1, 0, A.count, rpe::KeyframeAccept{0, 1, 1, nullptr}, nullptr,
-                                      K.back, nullptr, nullptr, c->stream));
-  const rpe::KeyframeAccept acc{o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? K.back : nullptr};
-  HIP_TRY(rpe::launch_keyframe_best(A.desc, A.count, K.st.desc, K.st.off, 0, n, 0, 0, acc, K.d1, K.idx, K.d2, K.rank, c->stream));
+  rpe::KeyframeAccept acc;
+  if ((rc = best_with_counts(c, A.desc, A.count, (int)K.used, n, o, &acc))) return rc;   // (the cross-check: the whole store against the frame)
   HIP_TRY(rpe::launch_keyframe_rank(K.rank, n, K.rank + n, c->stream));            // the order directly behind the n counts
   int host[2 * rpe::kMaxKeyframes];
   if ((rc = read_ints(c, K.rank, 2 * n, host))) return rc;
@@ -144,7 +108,7 @@ int match_from_row(rpe_context* c, int id, int row, const rpe_match_options& o, 
   const auto& M = K.meta[id];
   int rc;
   if ((rc = ensure_lists(c))) return rc;
-  rpe::MatchLists L = F.mlist;
+  rpe::MatchLists L = F.mlist.view();
   const size_t r = (size_t)row * A.count;
   L.d1 = K.d1 + r; L.idx = K.idx + r; L.d2 = K.d2 + r; L.back = K.back + M.off;
   F.matches = -1;
@@ -153,7 +117,7 @@ int match_from_row(rpe_context* c, int id, int row, const rpe_match_options& o, 
   if ((rc = read_ints(c, F.fwork.ctl + rpe::kFeatCtlMatches, 1, &m))) return rc;
   if (m > 0) {
     if ((rc = claim_slots(c, m))) return rc;
-    HIP_TRY(rpe::launch_keyframe_gather(L.mf, L.mm, m, A.pix, F.fmap[0], F.fmap[1], F.fmap[2], K.st, M.off, (float*)c->arr[RPE_XW],
+    HIP_TRY(rpe::launch_keyframe_gather(L.mf, L.mm, m, A.pix, F.fmap[0], F.fmap[1], F.fmap[2], K.store(), M.off, (float*)c->arr[RPE_XW],
                                         (float*)c->arr[RPE_XC], (float*)c->arr[RPE_BV], (float*)c->arr[RPE_NW], (float*)c->arr[RPE_NC], c->stream));
   } else if ((rc = rpe_set_problem(c, 0, RPE_F32))) return rc;
   F.matches = m; F.match_gen[0] = A.gen; F.match_kf = id;
@@ -166,18 +130,8 @@ int attachment_room(rpe_context* c, int id, size_t n, bool color) {
   if (K.att.size() < K.meta.size()) K.att.resize(K.meta.size());
   auto& A = K.att[id];
   A.have_depth = A.have_color = false;
-  const bool grow_z = !A.z || A.zcap < n * sizeof(float), grow_c = color && (!A.rgba || A.ccap < n * 4);
-  if (grow_z || grow_c) HIP_TRY(hipStreamSynchronize(c->stream));   // a fuse in flight may still read the old planes
-  if (grow_z) {
-    if (A.z) { HIP_TRY(hipFree(A.z)); A.z = nullptr; A.zcap = 0; }
-    HIP_TRY(hipMalloc((void**)&A.z, n * sizeof(float)));
-    A.zcap = n * sizeof(float);
-  }
-  if (grow_c) {
-    if (A.rgba) { HIP_TRY(hipFree(A.rgba)); A.rgba = nullptr; A.ccap = 0; }
-    HIP_TRY(hipMalloc((void**)&A.rgba, n * 4));
-    A.ccap = n * 4;
-  }
+  int rc;   // (a fuse in flight may still read the old planes: reserve waits for the stream before one goes)
+  if ((rc = A.z.reserve(c, n * sizeof(float))) || (color && (rc = A.rgba.reserve(c, n * 4)))) return rc;
   return RPE_OK;
 }
 }  // namespace
@@ -195,7 +149,7 @@ int rpe_keyframe_add(rpe_context* c, int* id) {
   if ((rc = kind_fits(c, S.kind, "rpe_keyframe_add"))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ensure_store(c, S.count))) return rc;
-  HIP_TRY(rpe::launch_keyframe_snapshot(S.count, S.pix, S.xy, S.desc, F.mmap[0], F.mmap[1], c->kf.st, (int)c->kf.used, c->stream));
+  HIP_TRY(rpe::launch_keyframe_snapshot(S.count, S.pix, S.xy, S.desc, F.mmap[0], F.mmap[1], c->kf.store(), (int)c->kf.used, c->stream));
   return new_keyframe(c, S.kind, S.count, F.mpose, F.mcam.width, F.mcam.height, id);
 }
 
@@ -216,10 +170,10 @@ int rpe_keyframe_add_host(rpe_context* c, int count, const int32_t* xy, const ui
   auto& K = c->kf;
   const size_t o = (size_t)K.used, n = (size_t)count;
   if (n) {
-    HIP_TRY(hipMemcpyAsync(K.st.desc + 8 * o, desc, 8 * n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(K.st.xw + 3 * o, xw, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(K.st.nw + 3 * o, nw, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(K.st.xy + 2 * o, xy, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(K.desc + 8 * o, desc, 8 * n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(K.xw + 3 * o, xw, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(K.nw + 3 * o, nw, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(K.xy + 2 * o, xy, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   }
   return new_keyframe(c, c->fe.desc_kind, count, pose12, width, height, id);
 }
@@ -243,10 +197,10 @@ int rpe_keyframe_download(rpe_context* c, int id, int32_t* xy, uint32_t* desc, f
   const auto& K = c->kf;
   const size_t o = (size_t)K.meta[id].off, n = (size_t)K.meta[id].count;
   int rc;
-  if (n && xy && (rc = copy_to_host(c, xy, K.st.xy + 2 * o, 2 * n * sizeof(int)))) return rc;
-  if (n && desc && (rc = copy_to_host(c, desc, K.st.desc + 8 * o, 8 * n * sizeof(unsigned int)))) return rc;
-  if (n && xw && (rc = copy_to_host(c, xw, K.st.xw + 3 * o, 3 * n * sizeof(float)))) return rc;
-  if (n && nw && (rc = copy_to_host(c, nw, K.st.nw + 3 * o, 3 * n * sizeof(float)))) return rc;
+  if (n && xy && (rc = copy_to_host(c, xy, K.xy + 2 * o, 2 * n * sizeof(int)))) return rc;
+  if (n && desc && (rc = copy_to_host(c, desc, K.desc + 8 * o, 8 * n * sizeof(unsigned int)))) return rc;
+  if (n && xw && (rc = copy_to_host(c, xw, K.xw + 3 * o, 3 * n * sizeof(float)))) return rc;
+  if (n && nw && (rc = copy_to_host(c, nw, K.nw + 3 * o, 3 * n * sizeof(float)))) return rc;
   return RPE_OK;
 }
 
@@ -278,7 +232,7 @@ int rpe_keyframe_attach_frame(rpe_context* c, int id) {
   int rc = attachment_room(c, id, n, F.have_fcolor);
   if (rc) return rc;
   auto& A = K.att[id];
-  HIP_TRY(rpe::launch_attach_pack(F.fmap[0], F.have_fcolor ? F.fcolor : nullptr, (int64_t)n, A.z, A.rgba, c->stream));
+  HIP_TRY(rpe::launch_attach_pack(F.fmap[0], F.have_fcolor ? F.fcolor.get() : nullptr, (int64_t)n, A.z, A.rgba, c->stream));
   A.cam = F.cam; A.kcam = F.kcam[0];
   A.have_depth = true; A.have_color = F.have_fcolor;
   return RPE_OK;
@@ -370,14 +324,8 @@ int rpe_keyframes_link(rpe_context* c, int first, const rpe_match_options* mopt,
   for (int j = std::max(first, 1); j < n; j++) {
     const auto& M = K.meta[j];
     if (M.count == 0 || M.off == 0) continue;      // no keypoint of its own, or none before it
-    if ((rc = ensure_rows(c, j))) return rc;
-    HIP_TRY(hipMemsetAsync(K.rank, 0, (size_t)j * sizeof(int), c->stream));
-    const unsigned int* dj = K.st.desc + 8 * (size_t)M.off;
-    if (o.cross_check)
-      HIP_TRY(rpe::launch_keyframe_best(K.st.desc, M.off, dj, nullptr, 0, 1, 0, M.count, rpe::KeyframeAccept{0, 1, 1, nullptr}, nullptr, K.back,
-                                        nullptr, nullptr, c->stream));
-    const rpe::KeyframeAccept acc{o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? K.back : nullptr};
-    HIP_TRY(rpe::launch_keyframe_best(dj, M.count, K.st.desc, K.st.off, 0, j, 0, 0, acc, K.d1, K.idx, K.d2, K.rank, c->stream));
+    rpe::KeyframeAccept acc;
+    if ((rc = best_with_counts(c, K.desc + 8 * (size_t)M.off, M.count, M.off, j, o, &acc))) return rc;
     int counts[rpe::kMaxKeyframes];
     if ((rc = read_ints(c, K.rank, j, counts))) return rc;
     int64_t total = 0;
@@ -391,7 +339,7 @@ int rpe_keyframes_link(rpe_context* c, int first, const rpe_match_options* mopt,
       base.v[i] = -1;
       if (counts[i] >= min_matches) { base.v[i] = (int)G->used; G->edges.push_back(rpe_graph::Edge{j, i, (int)G->used, counts[i]}); G->used += counts[i]; }
     }
-    HIP_TRY(rpe::launch_graph_pack(K.d1, K.idx, K.d2, M.count, j, K.st.off, acc, K.rank, base, G->a, G->b, c->stream));
+    HIP_TRY(rpe::launch_graph_pack(K.d1, K.idx, K.d2, M.count, j, K.off, acc, K.rank, base, G->a, G->b, c->stream));
   }
   G->dirty = true;
   if (edges) *edges = (int)G->edges.size();
@@ -423,10 +371,10 @@ int rpe_keyframe_match(rpe_context* c, int id, const rpe_match_options* mopt, in
   const auto& A = c->fe.feat[RPE_FEAT_FRAME];
   const auto& M = K.meta[id];
   c->fe.matches = -1;
-  HIP_TRY(rpe::launch_keyframe_best(A.desc, A.count, K.st.desc, K.st.off, id, 1, 0, 0, rpe::KeyframeAccept{0, 1, 1, nullptr}, K.d1, K.idx, K.d2,
+  HIP_TRY(rpe::launch_keyframe_best(A.desc, A.count, K.desc, K.off, id, 1, 0, 0, rpe::KeyframeAccept{0, 1, 1, nullptr}, K.d1, K.idx, K.d2,
                                     nullptr, c->stream));
   if (o.cross_check)
-    HIP_TRY(rpe::launch_keyframe_best(K.st.desc + 8 * (size_t)M.off, M.count, A.desc, nullptr, 0, 1, 0, A.count, rpe::KeyframeAccept{0, 1, 1, nullptr},
+    HIP_TRY(rpe::launch_keyframe_best(K.desc + 8 * (size_t)M.off, M.count, A.desc, nullptr, 0, 1, 0, A.count, rpe::KeyframeAccept{0, 1, 1, nullptr},
                                       nullptr, K.back + M.off, nullptr, nullptr, c->stream));
   return match_from_row(c, id, 0, o, matches);
 }
@@ -439,23 +387,16 @@ int rpe_relocalize_keyframes(rpe_context* c, const rpe_feature_options* fopt, co
     return fail(RPE_ERR_ARG, "rpe_relocalize_keyframes: bad argument (method 0 .. 9, candidates >= 1, pose12 and iter_io not NULL)");
   if (min_matches < 4 || min_matches > RPE_MAX_KEYPOINTS) return fail(RPE_ERR_ARG, "rpe_relocalize_keyframes: min_matches 4 .. %d (got %d)",
                                                                      RPE_MAX_KEYPOINTS, min_matches);
-  const rpe_feature_options fo = fopt ? *fopt : rpe_feature_options{12, RPE_MAX_KEYPOINTS};
+  const rpe_feature_options fo = fopt ? *fopt : kFeatureDefaults;
   const rpe_match_options mo = mopt ? *mopt : kMatchDefaults;
-  int rc = match_options(&mo);
-  if (rc) return rc;
-  if (fo.threshold < 1 || fo.threshold > 255 || fo.max_keypoints < 1 || fo.max_keypoints > RPE_MAX_KEYPOINTS)
-    return fail(RPE_ERR_ARG, "feature options: threshold 1 .. 255 (got %d), max_keypoints 1 .. %d (got %d)", fo.threshold, RPE_MAX_KEYPOINTS,
-                fo.max_keypoints);
+  int rc;
+  if ((rc = match_options(&mo)) || (rc = feature_options(&fo))) return rc;
   auto& K = c->kf;
   if (K.meta.empty()) return fail(RPE_ERR_STATE, "rpe_relocalize_keyframes: the keyframe store is empty (rpe_keyframe_add)");
   if (c->fe.desc_kind != K.kind)
     return fail(RPE_ERR_STATE, "rpe_relocalize_keyframes: the context describes with kind %d, the store's descriptors are of kind %d "
                 "(rpe_features_set_descriptor)", c->fe.desc_kind, K.kind);
-  {
-    const auto& S = c->fe.feat[RPE_FEAT_FRAME];
-    if (!(S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints && S.kind == c->fe.desc_kind) &&
-        (rc = rpe_features_detect(c, RPE_FEAT_FRAME, &fo, nullptr))) return rc;
-  }
+  if ((rc = detect_if_stale(c, RPE_FEAT_FRAME, fo))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const int n = (int)K.meta.size();
   std::vector<int> counts(n), order(n);
@@ -470,38 +411,21 @@ int rpe_relocalize_keyframes(rpe_context* c, const rpe_feature_options* fopt, co
   int win = -1, win_votes = -1, win_iter = iter_in, win_m = 0, last = -1;
   double win_pose[12];
   std::vector<short> win_mask, mask;
-  std::vector<float> host;
   for (int r = 0; r < n && r < candidates && counts[order[r]] >= min_matches; r++) {
     const int id = order[r];
     int m = 0;
     if ((rc = match_from_row(c, id, id, mo, &m))) return rc;
     last = id;
     // rpe_relocalize's own run: the downloaded arrays through rpe_run, the match quality as weight of every modality
-    const size_t n3 = (size_t)m * 3;
-    host.resize(5 * n3 + n3);
-    float* a[RPE_NUM_ARRAYS];
-    for (int s = 0; s < RPE_NUM_ARRAYS; s++) {
-      a[s] = host.data() + s * n3;
-      if ((rc = copy_to_host(c, a[s], c->arr[s], n3 * sizeof(float)))) return rc;
-    }
-    float* wq = host.data() + 5 * n3;
-    if ((rc = copy_to_host(c, wq, c->fe.mlist.mw, (size_t)m * sizeof(float)))) return rc;
-    for (int k = 1; k < 3; k++) std::memcpy(wq + (size_t)k * m, wq, (size_t)m * sizeof(float));
-    rpe_problem p{};
-    p.n = m; p.dtype = RPE_F32;
-    p.xw = a[RPE_XW]; p.xc = a[RPE_XC]; p.bv = a[RPE_BV]; p.nw = a[RPE_NW]; p.nc = a[RPE_NC];
-    p.weights = wq; p.wcols = 3;
-    p.fx = c->fe.kcam[0].fx; p.fy = c->fe.kcam[0].fy;
-    double R9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t3[3] = {0, 0, 0};
+    double pose[12];
     int it = iter_in, votes = 0;
-    mask.assign(n3, 0);
-    rc = rpe_run(method, &p, thre_3d, thre_2d, thre_nl, &it, confidence, seed, ls, RPE_SCORE_EXACT, nullptr, R9, t3, &votes, mask.data());
+    mask.assign((size_t)m * 3, 0);
+    rc = run_on_slots(c, m, method, thre_3d, thre_2d, thre_nl, &it, confidence, seed, ls, pose, &votes, mask.data());
     if (rc == RPE_ERR_DEGENERATE) continue;        // refused as rank-deficient: the next candidate
     if (rc) return rc;
     if (votes > win_votes) {                       // a tie stays with the better rank
       win = id; win_votes = votes; win_iter = it; win_m = m;
-      for (int i = 0; i < 9; i++) win_pose[i] = R9[i];
-      for (int i = 0; i < 3; i++) win_pose[9 + i] = t3[i];
+      std::memcpy(win_pose, pose, sizeof(win_pose));
       win_mask.swap(mask);
     }
   }

@@ -1,6 +1,6 @@
 // Part 3 of include/rgbd_pose_hip.h: the mesh of the TSDF volume (kernels in rpe_mesh.hip).  Marching cubes over the context's volume
 // into device buffers the context owns: three launches, one host wait for the totals, two launches; the download copies them out.
-#include "rpe_host.hpp"
+#include "rpe_frontend_host.hpp"
 #include <cmath>
 using namespace rpeh;
 
@@ -18,11 +18,8 @@ int rpe_volume_mesh(rpe_context* c, double min_weight, int64_t* n_vertices, int6
   HIP_TRY(hipSetDevice(c->device));
   const int64_t nvox = (int64_t)V.g.dim[0] * V.g.dim[1] * V.g.dim[2];
   const size_t ws = rpe::mesh_workspace_bytes(nvox);
-  if (!V.ws || V.ws_cap < ws) {
-    if (V.ws) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.ws)); V.ws = nullptr; V.ws_cap = 0; }
-    HIP_TRY(hipMalloc(&V.ws, ws));
-    V.ws_cap = ws;
-  }
+  int rc;
+  if ((rc = V.ws.reserve(c, ws))) return rc;
   const rpe::MeshWorkspace W = rpe::mesh_workspace(V.ws, nvox);
   HIP_TRY(rpe::launch_mesh_count(V.d, V.g, wmin, W, c->stream));
   long long tot[2] = {0, 0};
@@ -31,19 +28,8 @@ int rpe_volume_mesh(rpe_context* c, double min_weight, int64_t* n_vertices, int6
   if (tot[0] >= ((long long)1 << 31))
     return fail(RPE_ERR_ARG, "rpe_volume_mesh: %lld vertices; the int32 triangle ids hold fewer than 2^31", tot[0]);
   const size_t vb = (size_t)tot[0] * 3 * sizeof(float), tb = (size_t)tot[1] * 3 * sizeof(int32_t);
-  if (V.mv_cap < vb) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (float** m : {&V.mv, &V.mn}) if (*m) { HIP_TRY(hipFree(*m)); *m = nullptr; }
-    V.mv_cap = 0;
-    HIP_TRY(hipMalloc((void**)&V.mv, vb));
-    HIP_TRY(hipMalloc((void**)&V.mn, vb));
-    V.mv_cap = vb;
-  }
-  if (V.mt_cap < tb) {
-    if (V.mt) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.mt)); V.mt = nullptr; V.mt_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&V.mt, tb));
-    V.mt_cap = tb;
-  }
+  if (vb && ((rc = V.mv.reserve(c, vb)) || (rc = V.mn.reserve(c, vb)))) return rc;   // (an empty mesh asks for nothing)
+  if (tb && (rc = V.mt.reserve(c, tb))) return rc;
   if (tot[0] > 0) HIP_TRY(rpe::launch_mesh_emit(V.d, V.g, W, V.mv, V.mn, V.mt, c->stream));
   V.nv = tot[0]; V.nt = tot[1];
   V.have_mesh = true;

@@ -1,17 +1,10 @@
 // Part 3 of include/rgbd_pose_hip.h: the photometric term beside ICP (kernels in rpe_photo.hip).  A model colour without a volume, the
 // photometric maps of frame and model, the photometric normal equations and per-pixel rows, and the RGB-D ICP loops: per round ONE
 // launch whose record carries the geometric and the photometric rows, one host wait, the host solve and left update of rpe_icp.
-#include "rpe_host.hpp"
+#include "rpe_frontend_host.hpp"
 using namespace rpeh;
 
 namespace {
-template <class T> int ensure_buffer(rpe_context* c, T** p, size_t* cap, size_t bytes) {
-  if (*p && *cap >= bytes) return RPE_OK;
-  if (*p) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(*p)); *p = nullptr; *cap = 0; }
-  HIP_TRY(hipMalloc((void**)p, bytes));
-  *cap = bytes;
-  return RPE_OK;
-}
 // one level of what a round reads: frame vertex / normal / intensity, model vertex / normal / photometric map, pixels, model camera
 struct PhotoLevel { const float *fv, *fn, *fi, *mv, *mn, *pm; int64_t n; rpe::Camera mcam; };
 PhotoLevel photo_level(rpe_context* c, int l) {
@@ -90,7 +83,7 @@ int rpe_model_color_upload(rpe_context* c, const uint8_t* rgba) {
   if (!F.have_model) return fail(RPE_ERR_STATE, "no model: call rpe_model_upload, rpe_model_from_frame or rpe_volume_raycast first");
   HIP_TRY(hipSetDevice(c->device));
   const size_t bytes = (size_t)F.mcam.width * F.mcam.height * 4;
-  int rc = ensure_buffer(c, &F.mcolor, &F.mccap, bytes);
+  int rc = F.mcolor.reserve(c, bytes);
   if (rc) return rc;
   F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.mcolor, rgba, bytes, hipMemcpyHostToDevice, c->stream));
@@ -110,7 +103,7 @@ int rpe_model_color_from_frame(rpe_context* c) {
                 F.cam.width, F.cam.height);
   HIP_TRY(hipSetDevice(c->device));
   const size_t bytes = (size_t)F.mcam.width * F.mcam.height * 4;
-  int rc = ensure_buffer(c, &F.mcolor, &F.mccap, bytes);
+  int rc = F.mcolor.reserve(c, bytes);
   if (rc) return rc;
   F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.mcolor, F.fcolor, bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -136,8 +129,8 @@ int rpe_photo_prepare(rpe_context* c, int levels) {
   rpe::PyramidGeometry fg = F.fgeo, mg = F.mgeo;
   fg.levels = levels; mg.levels = levels;
   int rc;
-  if ((rc = ensure_buffer(c, &F.pint, &F.pint_cap, (size_t)fg.off[levels] * sizeof(float)))) return rc;
-  if ((rc = ensure_buffer(c, &F.pmap, &F.pmap_cap, (size_t)mg.off[levels] * 4 * sizeof(float)))) return rc;
+  if ((rc = F.pint.reserve(c, (size_t)fg.off[levels] * sizeof(float)))) return rc;
+  if ((rc = F.pmap.reserve(c, (size_t)mg.off[levels] * 4 * sizeof(float)))) return rc;
   F.photo_levels = 0;
   HIP_TRY(rpe::launch_frame_intensity(F.fcolor, fg, F.pint, c->stream));
   HIP_TRY(rpe::launch_model_photo(F.mcolor, mg, F.mmap[0], F.mmap[1], pose_f(F.mpose), F.pmap, c->stream));
@@ -184,12 +177,11 @@ int rpe_photo_rows(rpe_context* c, int level, const double* pose12, double dist_
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const PhotoLevel lv = photo_level(c, level);
-  float* d_rows = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_rows, (size_t)lv.n * 7 * sizeof(float)));
+  DevBuf<float> d_rows;
+  if ((rc = d_rows.once(c, (size_t)lv.n * 7 * sizeof(float)))) return rc;
   hipError_t e = rpe::launch_photo_rows(lv.fv, lv.fi, lv.n, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr, pose12, d_rows, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, (size_t)lv.n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_rows);
   if (e != hipSuccess) return fail(RPE_ERR_HIP, "rpe_photo_rows: %s", hipGetErrorString(e));
   return RPE_OK;
 }

@@ -1,7 +1,7 @@
 // Part 3 of include/rgbd_pose_hip.h: the volume rebuilt from the keyframes (kernels in rpe_rebuild.hip).  The attachments themselves
 // -- a keyframe's depth plane, colour and camera -- are the store's (rpe_keyframe_api.hip); here a list of them is fused into the
 // context's volume in one launch, leaving what volume_init + one integrate per keyframe would leave, bit for bit.
-#include "rpe_host.hpp"
+#include "rpe_frontend_host.hpp"
 using namespace rpeh;
 
 extern "C" {
@@ -39,22 +39,13 @@ int rpe_volume_fuse_keyframes(rpe_context* c, const int32_t* ids, int count, con
     table[e].z = A.z; table[e].rgba = color ? A.rgba : nullptr; table[e].cam = A.cam;
     table[e].T = pose_f(poses12 ? poses12 + 12 * (size_t)e : K.meta[ids[e]].pose);
   }
-  if (!K.d_table) HIP_TRY(hipMalloc((void**)&K.d_table, RPE_MAX_KEYFRAMES * sizeof(rpe::FuseEntry)));
+  if (int rc = K.d_table.once(c, RPE_MAX_KEYFRAMES * sizeof(rpe::FuseEntry))) return rc;
   // the call's one host wait: the table is the host's again (and an earlier fuse has read the table it was given)
   HIP_TRY(hipMemcpyAsync(K.d_table, table.data(), table.size() * sizeof(rpe::FuseEntry), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   // the volume's state, as rpe_volume_init (clear) and rpe_volume_integrate_color (color) leave it
-  const size_t cbytes = (size_t)V.g.dim[0] * V.g.dim[1] * V.g.dim[2] * 4 * sizeof(unsigned short);
   if (clear) { V.have_mesh = false; V.have_color = false; }
-  if (color && !V.have_color) {
-    if (!V.cd || V.ccap < cbytes) {
-      if (V.cd) { HIP_TRY(hipFree(V.cd)); V.cd = nullptr; V.ccap = 0; }
-      HIP_TRY(hipMalloc((void**)&V.cd, cbytes));
-      V.ccap = cbytes;
-    }
-    if (!clear) HIP_TRY(hipMemsetAsync(V.cd, 0, cbytes, c->stream));   // with clear the kernel writes every colour voxel itself
-    V.have_color = true;
-  }
+  if (color) if (int rc = ensure_color_volume(c, !clear)) return rc;   // with clear the kernel writes every colour voxel itself
   HIP_TRY(rpe::launch_volume_fuse(V.d, color ? V.cd : nullptr, V.g, K.d_table, count, clear, color, cull, c->stream));
   return RPE_OK;
 }

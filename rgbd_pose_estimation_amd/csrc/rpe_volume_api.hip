@@ -1,7 +1,7 @@
 // Part 3 of include/rgbd_pose_hip.h: the TSDF volume of the front end (kernels in rpe_volume.hip).  Frames are fused into the
 // context's volume; a raycast of the volume becomes the model the next frame is registered against, through the same allocation and
 // model state rpe_model_upload leaves (one level, the raycast's pose and camera).
-#include "rpe_host.hpp"
+#include "rpe_frontend_host.hpp"
 #include <cmath>
 using namespace rpeh;
 
@@ -27,13 +27,11 @@ int rpe_volume_init(rpe_context* c, const rpe_volume_desc* d) {
   V.have = false;
   V.have_mesh = false;
   V.have_color = false;
-  if (!V.d || V.cap < bytes) {
-    if (V.d) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(V.d)); V.d = nullptr; V.cap = 0; }
-    if (V.ws) { HIP_TRY(hipFree(V.ws)); V.ws = nullptr; V.ws_cap = 0; }   // the mesh workspace follows the volume's size
-    if (V.cd) { HIP_TRY(hipFree(V.cd)); V.cd = nullptr; V.ccap = 0; }     // ... and so does the colour volume
-    HIP_TRY(hipMalloc((void**)&V.d, bytes));
-    V.cap = bytes;
+  if (V.d.bytes() < bytes) {   // the mesh workspace and the colour volume follow the volume's size: they go before it grows
+    if (V.d) HIP_TRY(hipStreamSynchronize(c->stream));
+    V.ws = {}; V.cd = {};
   }
+  if (int rc = V.d.reserve(c, bytes)) return rc;
   HIP_TRY(hipMemsetAsync(V.d, 0, bytes, c->stream));
   V.g = g;
   V.have = true;
@@ -65,7 +63,7 @@ int rpe_volume_raycast(rpe_context* c, const double* pose12, const rpe_camera* c
   HIP_TRY(hipSetDevice(c->device));
   auto& F = c->fe;
   const int64_t n = (int64_t)k.width * k.height;
-  if ((rc = ensure_maps(c, F.mmap, 2, &F.mcap, n))) return rc;
+  if ((rc = model_room(c, n))) return rc;
   F.have_model = false;
   F.have_mcolor = false; F.feat[1].have = false; F.photo_levels = 0;
   HIP_TRY(rpe::launch_volume_raycast(c->vol.d, c->vol.g, k, pose_f(pose12), (float)dmin, (float)dmax, F.mmap[0], F.mmap[1], c->stream));

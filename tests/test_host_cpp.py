@@ -43,3 +43,14 @@ def test_resident_slot_policy_cpp(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "resident_slot.cpp"), "-lpthread", "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "resident_slot: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_device_buffer_cpp(tmp_path):
+    """rpeh::DevBuf, the one owner of plain device memory in the host units (csrc/rpe_devbuf.hpp), against a fake runtime over
+    malloc / free: reserve / once, the all-or-nothing regrow with a failure injected at every malloc, copy and the wait, moves inside a
+    std::vector.  g++ with AddressSanitizer (leak detection on) and UBSan; a stand-alone program that links no HIP runtime."""
+    exe = str(tmp_path / "devbuf_host")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "cpp", "devbuf_host.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0 and "devbuf_host: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

@@ -53,5 +53,6 @@ def test_units_without_device_code_have_none():
 def test_no_host_unit_outgrows_its_job():
     """The C-ABI side is split by job (rpe_host.hpp lists the units); none of them may grow back into a catch-all file."""
     csrc = os.path.join(os.path.dirname(LIB), "csrc")
-    for u in ("rpe_capi.hip", "rpe_context.hip", "rpe_receive.hip", "rpe_refine.hip", "rpe_session.hip", "rpe_dist.hip", "rpe_frontend_api.hip", "rpe_host.hpp"):
+    for u in ("rpe_capi.hip", "rpe_context.hip", "rpe_receive.hip", "rpe_refine.hip", "rpe_session.hip", "rpe_dist.hip", "rpe_frontend_api.hip", "rpe_host.hpp",
+              "rpe_devbuf.hpp", "rpe_frontend_host.hpp"):
         assert os.path.getsize(os.path.join(csrc, u)) < 40 * 1024, u
