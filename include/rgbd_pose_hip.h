@@ -566,13 +566,15 @@ int rpe_volume_mesh_download(rpe_context* ctx, float* vertices, float* normals, 
  * Conventions, followed bit for bit (fp32, the written order, no FMA contraction; tests/color_oracle.py states them in numpy).
  * h(x) = fp32 -> IEEE binary16, round to nearest even, subnormals kept, overflow to +-Inf, every NaN to the quiet NaN 0x7e00.
  * Frame colour: width*height*3 bytes, row-major, at the current frame's level-0 size, REGISTERED to the depth image: pixel (u, v) of
- * both images sees the same ray (a separate colour camera must be reprojected by the caller).  Stored on the device as RGBA8 with
- * A = 255.  rpe_frame_set_depth and rpe_frame_set_depth_pyramid drop it.
+ * both images sees the same ray (a separate colour camera: rpe_frame_register_color, "Colour registration" below).  Stored on the
+ * device as RGBA8 with A = 255; A = 0 (only rpe_frame_register_color writes it) means "this pixel has no colour".  rpe_frame_set_depth
+ * and rpe_frame_set_depth_pyramid drop it.
  * Colour volume: beside {tsdf, weight}, at the same voxel index; a voxel is four binary16 {r, g, b, wc} (8 bytes, channels on the
  * 0..255 scale), wc = 0: no colour observed.  It comes into being, all zeros, on the first rpe_volume_integrate_color or
  * rpe_volume_color_upload after rpe_volume_init; rpe_volume_init drops it; the plain rpe_volume_integrate never touches it.
  * Integrate with colour (pose12): {tsdf, weight} are updated exactly as rpe_volume_integrate does it (same voxels, same bits).  A voxel
- * that this rule updates AND whose sdf <= tr (inside the truncation band) also gets a colour update: the observation o = the frame
+ * that this rule updates AND whose sdf <= tr (inside the truncation band) AND whose frame pixel (uf, vf) has A != 0 also gets a colour
+ * update (the same gate in rpe_volume_fuse_keyframes; the tsdf update does not look at A): the observation o = the frame
  * colour at the same (uf, vf), each channel (float)byte; with w = (float)wc before the update, each channel
  * c := h(((float)c * w + o) / (w + 1.0f)), then wc := h(fminf(w + 1.0f, W)) (for W > 2048 the weight stops at 2048: 2049 rounds to
  * 2048; a NaN weight becomes W, as in the tsdf rule).  A voxel without a colour update is never stored (its 16-byte pair may be loaded).
@@ -601,6 +603,47 @@ int rpe_volume_mesh_colors(rpe_context* ctx, uint8_t* rgba);
 int rpe_volume_color_download(rpe_context* ctx, uint16_t* rgbw);
 /* the inverse of rpe_volume_color_download (the bits are taken as given); RPE_ERR_STATE without a volume */
 int rpe_volume_color_upload(rpe_context* ctx, const uint16_t* rgbw);
+
+/* ---- Colour registration: a SEPARATE colour camera reprojected onto the depth frame on the device.  An RGB-D sensor's colour camera
+ * sits a few centimetres beside the depth camera, with its own resolution, focal length and lens distortion, and sees around foreground
+ * objects differently.  rpe_frame_register_color takes its image as delivered and leaves the current frame's colour where
+ * rpe_frame_set_color leaves it (same buffer, same state changes): RGBA8 at the depth frame's level-0 size, A = 255 where a colour was
+ * found and 0x00000000 elsewhere -- outside the colour image, without depth, or HIDDEN from the colour camera by something nearer (the
+ * naive per-pixel lookup paints the occluder's colour there).  Everywhere colour is consumed, A = 0 means "no colour".
+ * Conventions, followed bit for bit (fp32, the written order, no FMA contraction; tests/register_oracle.py states them in numpy).
+ * Casts, once: the colour camera (fx fy cx cy; wc x hc pixels), dist = k1 k2 p1 p2 k3, pose12 = (R, t) as every pose12 is cast,
+ * a = (float)occl_tol, b = (float)occl_tol_z2, r2_max.  Grid: gw = (wc + cell - 1) / cell, gh = (hc + cell - 1) / cell.
+ * Projection of depth pixel i with the level-0 vertex X (all three components finite):
+ *   Xk = R X + t, each row summed left to right; needs Xk.z > 0.  x = Xk.x / Xk.z, y = Xk.y / Xk.z, r2 = x*x + y*y; needs
+ *   r2 <= r2_max when r2_max > 0.  rad = 1.0f + r2 * (k1 + r2 * (k2 + r2 * k3));
+ *   xd = x * rad + ((2.0f * p1) * (x * y) + p2 * (r2 + 2.0f * (x * x)));  yd = y * rad + (p1 * (r2 + 2.0f * (y * y)) + (2.0f * p2) * (x * y));
+ *   px = fx * xd + cx, py = fy * yd + cy, both finite; x0 = floorf(px), y0 = floorf(py); needs 0 <= x0 <= wc - 2, 0 <= y0 <= hc - 2.
+ *   A pixel that fails any of these has no colour and casts no shadow.
+ * Z-buffer (cell >= 1): gw x gh unsigned words, cleared to 0xffffffff per call.  gx = (px + 0.5f) / (float)cell - 0.5f, i0 = floorf(gx);
+ *   gy, j0 likewise.  The pixel takes the minimum of the bits of Xk.z (a positive float: ordered as unsigned) into those of the four
+ *   cells (i0 + di, j0 + dj), di, dj = 0, 1, that lie inside the grid.  Its own cell is ci = floorf(gx + 0.5f), cj = floorf(gy + 0.5f):
+ *   one of the four, inside the grid.  With zmin that cell's value after ALL pixels have written, the pixel is visible iff
+ *   (Xk.z - zmin) <= a + b * (zmin * zmin).  An integer minimum does not depend on arrival order: the output is repeatable bit for bit.
+ *   (The device keeps the minima per base cell (i0, j0) and takes the minimum of four of them when it reads a cell: the same value.)
+ *   (The z^2 term, as in rpe_depth_filter: one constant cannot fit a floor at a grazing angle at 4 m and a table edge at 1 m.)
+ * Sample (visible pixels; with cell = 0 every pixel that passed the projection): s = px - x0, u = py - y0; each channel on (float)byte
+ *   with lerp(p, q, s) = p + (q - p) * s along x for the rows y0 and y0 + 1, then along y by u; then the colour block's q(x); A = 255.
+ * Out of scope: depth registered INTO the colour camera, rolling-shutter or time offsets, distortion of the DEPTH camera, distortion
+ * models other than the five coefficients, and the fold-over of a strongly distorted model beyond r2_max when no limit is given. */
+typedef struct {
+  rpe_camera cam;        /* the colour camera: its own width x height and pinhole */
+  double dist[5];        /* k1 k2 p1 p2 k3 (Brown-Conrady, the usual order); all 0 = none */
+  double pose12[12];     /* depth camera -> colour camera, Xk = R Xd + t, the layout of every pose12 */
+  double r2_max;         /* skip points with x^2 + y^2 > r2_max before distortion; 0 = no limit */
+  int cell;              /* z-buffer cell in colour pixels, 1 .. 16; 0 = no occlusion test */
+  double occl_tol, occl_tol_z2;   /* hidden iff z - zmin > occl_tol + occl_tol_z2 * zmin^2 (metres) */
+} rpe_color_rig;
+/* the current frame's colour from a separate colour camera: `pixels` = rig->cam.width * height * 3 bytes in `format` order
+ * (RPE_COLOR_*8).  known may be NULL (no host wait); otherwise it receives the number of A = 255 pixels (one host wait).
+ * RPE_ERR_STATE without a frame; RPE_ERR_ARG for a bad format, cell outside 0 .. 16, a colour camera of fewer than 2 x 2 pixels or
+ * with a non-finite or non-positive focal length or a non-finite centre, non-finite dist, pose or tolerances, negative tolerances or
+ * r2_max.  After an error the frame colour is what it was */
+int rpe_frame_register_color(rpe_context* ctx, const uint8_t* pixels, int format, const rpe_color_rig* rig, int64_t* known);
 
 /* ---- Photometric term: tracking against the model's colour beside its geometry.  Point-to-plane ICP has nothing to hold three of
  * the six degrees of freedom with wherever the view is one plane (a wall, a floor, a corridor); the intensity of a textured plane

@@ -46,7 +46,7 @@ SYMBOLS = [
     "rpe_volume_init", "rpe_volume_integrate", "rpe_volume_raycast", "rpe_volume_download",
     "rpe_volume_upload", "rpe_volume_mesh", "rpe_volume_mesh_download",
     "rpe_frame_set_color", "rpe_volume_integrate_color", "rpe_model_sample_color", "rpe_color_download", "rpe_volume_mesh_colors",
-    "rpe_volume_color_download", "rpe_volume_color_upload",
+    "rpe_volume_color_download", "rpe_volume_color_upload", "rpe_frame_register_color",
     "rpe_model_color_upload", "rpe_model_color_from_frame", "rpe_photo_prepare", "rpe_photo_download", "rpe_photo_normal_eq", "rpe_photo_rows",
     "rpe_icp_rgbd", "rpe_icp_pyramid_rgbd",
     "rpe_features_detect", "rpe_features_download", "rpe_features_match", "rpe_matches_download", "rpe_relocalize",
@@ -91,6 +91,12 @@ class RpeMatchOptions(C.Structure):
 
 class RpeDepthFilter(C.Structure):
     _fields_ = [("radius", C.c_int), ("sigma_space", C.c_double), ("depth_cut", C.c_double), ("depth_cut_z2", C.c_double)]
+
+
+class ColorRig(C.Structure):
+    """rpe_color_rig: a separate colour camera beside the depth camera (rpe_frame_register_color)"""
+    _fields_ = [("cam", RpeCamera), ("dist", C.c_double * 5), ("pose12", C.c_double * 12), ("r2_max", C.c_double), ("cell", C.c_int),
+                ("occl_tol", C.c_double), ("occl_tol_z2", C.c_double)]
 
 
 class RpeVolumeDesc(C.Structure):
@@ -227,6 +233,7 @@ def lib():
         L.rpe_volume_mesh_colors.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_volume_color_download.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_volume_color_upload.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_frame_register_color.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ColorRig), C.POINTER(C.c_int64)]
         L.rpe_model_color_upload.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_model_color_from_frame.argtypes = [C.c_void_p]
         L.rpe_photo_prepare.argtypes = [C.c_void_p, C.c_int]

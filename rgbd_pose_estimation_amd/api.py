@@ -388,6 +388,34 @@ class Context:
         L.check(L.lib().rpe_frame_set_color(self._h, _p(a), fmt))
         return self
 
+    @staticmethod
+    def color_rig(cam, dist=(0.0, 0.0, 0.0, 0.0, 0.0), pose12=(1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0), r2_max: float = 0.0, cell: int = 2,
+                  occl_tol: float = 0.02, occl_tol_z2: float = 0.01) -> "L.ColorRig":
+        """An rpe_color_rig: the colour camera (fx, fy, cx, cy, width, height), its distortion (k1, k2, p1, p2, k3), the pose depth
+        camera -> colour camera (Xk = R Xd + t), the limit on x^2 + y^2 before distortion (0 = none), the z-buffer cell in colour
+        pixels (0 = no occlusion test) and the occlusion tolerance occl_tol + occl_tol_z2 z^2 metres."""
+        d = np.asarray(dist, np.float64).reshape(5)
+        p = np.asarray(pose12, np.float64).reshape(12)
+        return L.ColorRig(Context._camera(cam), (C.c_double * 5)(*d), (C.c_double * 12)(*p), float(r2_max), int(cell), float(occl_tol),
+                          float(occl_tol_z2))
+
+    def frame_register_color(self, pixels, rig, format: str = "rgb", want_known: bool = False):
+        """The current frame's colour from a SEPARATE colour camera (rpe_frame_register_color): `pixels` is that camera's own
+        (height, width, 3) uint8 image, `rig` a color_rig(...).  Every depth pixel gets the colour its vertex projects to, A = 255, or
+        0 0 0 0 where it has none: outside the image, no depth, or hidden from the colour camera.  want_known: returns the number of
+        A = 255 pixels (one host wait); otherwise returns self and waits for nothing."""
+        fmt = {"rgb": L.COLOR_RGB8, "bgr": L.COLOR_BGR8}.get(str(format).lower())
+        if fmt is None:
+            raise ValueError(f"frame_register_color: format must be 'rgb' or 'bgr', got {format!r}")
+        a = np.ascontiguousarray(pixels)
+        if a.dtype != np.uint8:
+            raise TypeError("frame_register_color: the image must be uint8")
+        if a.shape != (rig.cam.height, rig.cam.width, 3):
+            raise ValueError(f"frame_register_color: expected shape {(rig.cam.height, rig.cam.width, 3)}, got {a.shape}")
+        known = C.c_int64(0)
+        L.check(L.lib().rpe_frame_register_color(self._h, _p(a), fmt, C.byref(rig), C.byref(known) if want_known else None))
+        return known.value if want_known else self
+
     def volume_integrate_color(self, pose12):
         """volume_integrate plus the colour of the frame fused into the voxels inside the truncation band."""
         p = np.array(pose12, np.float64).reshape(12)

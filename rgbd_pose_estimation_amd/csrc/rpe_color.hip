@@ -5,7 +5,7 @@
 //   C2  volume_integrate_color_kernel   V1 (rpe_volume.hip) plus the colour: the tsdf half is V1's code (voxel_project / fuse of
 //                                       rpe_volume_field.hpp) and touches the same voxels with the same bits; a voxel that V1 updates
 //                                       and that lies inside the truncation band (sdf <= tr) also blends the frame colour of its pixel
-//                                       into its four binary16 {r, g, b, wc}.  A lane owns 4 voxels: two 16-byte {tsdf, w} pairs and two
+//                                       into its four binary16 {r, g, b, wc}, unless that pixel has A = 0 (no colour).  A lane owns 4 voxels: two 16-byte {tsdf, w} pairs and two
 //                                       16-byte colour pairs, each loaded and stored only where one of its voxels is updated, plus one
 //                                       4-byte frame-colour gather per band voxel.
 //   C3  color_sample_kernel             RGBA8 of the colour field C at N world points (stride 3 floats), one lane per point, eight 8-byte
@@ -77,6 +77,9 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float
   }
 #pragma unroll
   for (int q = 0; q < 4; q++) o[q] = band[q] ? rgba[pix[q]] : 0u;
+  // A = 0: the pixel has no colour (rpe_frame_register_color), so the voxel gets no colour update and no colour store
+#pragma unroll
+  for (int q = 0; q < 4; q++) band[q] = band[q] && (o[q] >> 24) != 0u;
 #pragma unroll
   for (int p = 0; p < 2; p++) {
     const bool lo = up[2 * p], hi = up[2 * p + 1];

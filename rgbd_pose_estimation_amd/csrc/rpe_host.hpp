@@ -9,6 +9,7 @@
 //   rpe_volume_api.hip    Part 3: TSDF volume (integrate, raycast into the model, upload / download)
 //   rpe_mesh_api.hip      Part 3: mesh extraction from the TSDF volume (marching cubes) and its download
 //   rpe_color_api.hip     Part 3: frame colour, the colour volume beside the TSDF, model and mesh colours
+//   rpe_register_api.hip  Part 3: colour registration (a separate colour camera reprojected onto the depth frame; kernels in rpe_register.hip)
 //   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
 //   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
@@ -171,6 +172,10 @@ struct rpe_context {
     rpeh::DevBuf<unsigned char> d_rgb;
     rpeh::DevBuf<unsigned int> fcolor, mcolor;
     bool have_fcolor = false, have_mcolor = false;
+    // colour registration (rpe_register_api.hip): a separate colour camera's 3-byte staging upload, its RGBA8 image at its own size, and
+    // the z-buffer over it with the count words behind; allocated on first use, regrown when a call needs more
+    rpeh::DevBuf<unsigned char> rg_rgb;
+    rpeh::DevBuf<unsigned int> rg_rgba, rg_zbuf;
     // photometric term (rpe_photo_api.hip): the frame's intensity pyramid (one float per pixel, the frame's level offsets) and the
     // model's photometric map (float4 {I, gx, gy, zm} per pixel, the model's level offsets), prepared for photo_levels levels
     // (0 = not prepared: whatever replaces the frame's depth or colour, the model or the model colour resets it)

@@ -275,6 +275,19 @@ hipError_t launch_volume_integrate_color(float* vol, unsigned short* cvol, const
 // C3: RGBA8 of the colour field C at n world points (stride 3 floats)
 hipError_t launch_color_sample(const unsigned short* cvol, const VolumeGeometry& G, const float* pts, int64_t n, unsigned int* rgba,
                                hipStream_t s);
+// ---- colour registration (rpe_register.hip): a separate colour camera reprojected onto the depth frame.  Everything cast by the host
+// once (include/rgbd_pose_hip.h Part 3): the colour camera, T = depth camera -> colour camera, the distortion k1 k2 p1 p2 k3, r2_max
+// (0 = no limit), the z-buffer cell in colour pixels (0 = no occlusion test) with its grid gw x gh, the tolerance a + b zmin^2
+struct RegisterRig { Camera cam; PoseF T; float k1, k2, p1, p2, k3, r2_max; int cell, gw, gh; float a, b; };
+// R1: the z-buffer in its factored form ((gw + 1) * (gh + 1) words of base-cell minima, cleared to 0xffffffff by the caller; a cell's
+// value is the minimum of four of them, rpe_register.hip) takes the bits of Xk.z of the n depth pixels of vmap
+hipError_t launch_register_splat(const float* vmap, int64_t n, const RegisterRig& G, unsigned int* zbuf, hipStream_t s);
+// R2: out[i] = RGBA8 of depth pixel i from the colour camera's RGBA8 image crgba, 0 where it has none; count (may be null):
+// kRegCountWords words, cleared by the caller, whose SUM grows by the pixels with A = 255.  zbuf is not read with cell = 0
+constexpr int kRegCountWords = 64;
+hipError_t launch_register_gather(const float* vmap, int64_t n, const RegisterRig& G, const unsigned int* zbuf, const unsigned int* crgba,
+                                  unsigned int* out, unsigned int* count, hipStream_t s);
+void preload_register();
 // ---- photometric term (rpe_photo.hip).  P1: the frame's intensity pyramid (one float per pixel, levels concatenated as G says) from
 // its level-0 RGBA8 colour.  P2: the model's photometric map (float4 {I, gx, gy, zm} per pixel, levels concatenated) from its level-0
 // RGBA8 colour and its world vertex / normal maps; M = world -> model camera

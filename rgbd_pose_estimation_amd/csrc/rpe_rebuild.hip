@@ -159,6 +159,9 @@ __global__ __launch_bounds__(kFuseBlock) void volume_fuse_kernel(float* __restri
     if (COLOR) {
 #pragma unroll
       for (int q = 0; q < 4; q++) o[q] = band[q] ? E.rgba[pix[q]] : 0u;
+      // A = 0: the pixel has no colour (as C2)
+#pragma unroll
+      for (int q = 0; q < 4; q++) band[q] = band[q] && (o[q] >> 24) != 0u;
     }
 #pragma unroll
     for (int q = 0; q < 4; q++) {

@@ -18,6 +18,7 @@
 // A real sensor's depth is noisy (centimetres at room distances): fe.setDepthFilter(rpe::DepthFilter()) once, before the first frame
 // With a registered RGB image per frame (pixel (u, v) of colour and depth see the same ray), the volume also fuses colour:
 //   fe.setDepth(d, cam);  fe.setColor(rgb);  fe.integrateColor(T);  ...  fe.modelColor();  fe.meshColors();   // RGBA8, 4 bytes each
+// A sensor's colour camera is a separate one (beside the depth camera, its own size and lens): fe.registerColor(rgb, rig) in setColor's place
 // ... and tracking can use it: a photometric term beside ICP holds the pose where the view is one plane (a wall, a floor, a corridor)
 //   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.setColor(rgb);  fe.raycast(T, cam, range, 3);  fe.modelColor();
 //                   fe.preparePhoto(3);  fe.icpPyramidRgbd(T, 0.01, {6, 4, 3});  fe.integrateColor(T);
@@ -69,6 +70,17 @@ struct DepthFilter {
   int radius = 3;
   double sigma_space = 2.0, depth_cut = 0.01, depth_cut_z2 = 0.02;
   static DepthFilter off() { DepthFilter f; f.radius = 0; return f; }
+};
+// a SEPARATE colour camera beside the depth camera (rpe_color_rig, for DepthFrontEnd::registerColor): its own pinhole and size, its lens
+// distortion k1 k2 p1 p2 k3, the pose depth camera -> colour camera (Xk = R Xd + t), the limit on x^2 + y^2 before distortion (0 = none),
+// the z-buffer cell of the occlusion test in colour pixels (0 = no test) and its tolerance occl_tol + occl_tol_z2 z^2 metres
+struct ColorRig {
+  PinholeCamera cam;
+  double dist[5] = {0, 0, 0, 0, 0};
+  SE3<double> T_kd;
+  double r2_max = 0;
+  int cell = 2;
+  double occl_tol = 0.02, occl_tol_z2 = 0.01;
 };
 // TSDF volume (rpe_volume_init): dim[0] x dim[1] x dim[2] voxels of voxel_size metres from the world corner origin
 struct VolumeDesc {
@@ -270,6 +282,19 @@ class DepthFrontEnd {
   // the current frame's colour: width*height*3 bytes (RPE_COLOR_RGB8 or RPE_COLOR_BGR8 order) registered to its depth; a new depth
   // drops it
   void setColor(const uint8_t* rgb, int format = RPE_COLOR_RGB8) { check(rpe_frame_set_color(_ctx, rgb, format), "rpe_frame_set_color"); }
+  // the current frame's colour from a SEPARATE colour camera: rgb = rig.cam.width * height * 3 bytes as that camera delivers them.  Every
+  // depth pixel gets the colour its vertex projects to (A = 255), or 0 0 0 0 where it has none: outside the image, without depth, or
+  // hidden from the colour camera by something nearer.  count = true: returns the number of A = 255 pixels (one host wait), else -1
+  int64_t registerColor(const uint8_t* rgb, const ColorRig& rig, int format = RPE_COLOR_RGB8, bool count = false) {
+    rpe_color_rig r;
+    r.cam = cam_of(rig.cam);
+    for (int i = 0; i < 5; i++) r.dist[i] = rig.dist[i];
+    pose12(rig.T_kd, r.pose12);
+    r.r2_max = rig.r2_max; r.cell = rig.cell; r.occl_tol = rig.occl_tol; r.occl_tol_z2 = rig.occl_tol_z2;
+    int64_t known = -1;
+    check(rpe_frame_register_color(_ctx, rgb, format, &r, count ? &known : nullptr), "rpe_frame_register_color");
+    return known;
+  }
   // integrate(T_cw) plus the frame's colour fused into the voxels inside the truncation band
   void integrateColor(const Pose& T_cw) {
     double p[12]; pose12(T_cw, p);

@@ -241,17 +241,20 @@ def default_room():
     return np.array([-2.5, -1.6, -1.0]), np.array([2.7, 1.5, 5.0]), spheres
 
 
-def _cast(R, t, cam, room):
+def _cast(R, t, cam, room, d_cam=None):
     """(camera centre C0 in the world, world ray direction of every pixel (h*w, 3), ray parameter of the first hit (inf = none)):
-    the ray of pixel (u, v) is C0 + lambda * d with camera z = lambda."""
+    the ray of pixel (u, v) is C0 + lambda * d with camera z = lambda.  d_cam: ray directions in the camera frame, (n, 3) with z = 1, in
+    the pinhole's place -- one per pixel for a distorted camera (undistort_rays), or any n rays from the camera centre (cam's
+    intrinsics and size are then not used)."""
     fx, fy, cx, cy, w, h = cam
     lo, hi, spheres = room if room is not None else default_room()
     R = np.asarray(R, np.float64)
     t = np.asarray(t, np.float64)
     C0 = -R.T @ t                                    # camera centre in the world
-    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
-    d_cam = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1).reshape(-1, 3)
-    d = d_cam @ R                                    # world direction of each pixel's ray (rows: R^T d_cam); z_cam = lambda
+    if d_cam is None:
+        u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+        d_cam = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1).reshape(-1, 3)
+    d = np.asarray(d_cam, np.float64).reshape(-1, 3) @ R                                    # world direction of each pixel's ray (rows: R^T d_cam); z_cam = lambda
     lam = np.full(len(d), np.inf)
     with np.errstate(divide="ignore", invalid="ignore"):
         for ax in range(3):                          # the six walls, seen from inside
@@ -336,12 +339,36 @@ def cell_texture(P, cell=0.15):
     return out
 
 
-def render_rgb(R, t, cam=DEFAULT_CAMERA, room=None, texture=None):
+def distort(x, y, dist):
+    """Brown-Conrady, dist = (k1, k2, p1, p2, k3): the distorted normalised coordinates of the ideal ones (x, y)"""
+    k1, k2, p1, p2, k3 = dist
+    r2 = x * x + y * y
+    rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    return (x * rad + (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)), y * rad + (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y))
+
+
+def undistort_rays(cam, dist, iters=30):
+    """Camera-frame ray direction (x, y, 1) of every pixel of a camera with lens distortion `dist`, (h*w, 3) float64: the model
+    inverted per pixel by the fixed-point iteration x <- (xd - tangential(x, y)) / radial(x, y) from x = xd."""
+    fx, fy, cx, cy, w, h = cam
+    k1, k2, p1, p2, k3 = dist
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    xd, yd = ((u - cx) / fx).reshape(-1), ((v - cy) / fy).reshape(-1)
+    x, y = xd.copy(), yd.copy()
+    for _ in range(iters):
+        r2 = x * x + y * y
+        rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+        x, y = (xd - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) / rad, (yd - (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)) / rad
+    return np.stack([x, y, np.ones_like(x)], -1)
+
+
+def render_rgb(R, t, cam=DEFAULT_CAMERA, room=None, texture=None, dist=None):
     """Colour image (height, width, 3) uint8 of the room seen by the camera Xc = R Xw + t, registered to render_depth's image: each
     pixel is texture (default room_texture) at the pixel's noise-free hit point, rounded to the nearest integer and clipped to
-    0 .. 255; black where the ray hits nothing."""
+    0 .. 255; black where the ray hits nothing.  dist = (k1, k2, p1, p2, k3): the camera's lens distorts (Brown-Conrady); the image is
+    then what such a colour camera delivers, and is registered to nothing."""
     w, h = cam[4], cam[5]
-    C0, d, lam = _cast(R, t, cam, room)
+    C0, d, lam = _cast(R, t, cam, room, None if dist is None else undistort_rays(cam, dist))
     hit = np.isfinite(lam)
     out = np.zeros((len(d), 3), np.uint8)
     P = C0 + lam[hit, None] * d[hit]
