@@ -65,16 +65,22 @@ void gn_normal_eq(int kind, const Tin* a, const Tin* b, const Tin* c, const shor
     if (bx != bx && by != by && bz != bz) continue;
     double w = weight ? (double)weight[i] : 1.0;
     double x = a[3 * i], y = a[3 * i + 1], z = a[3 * i + 2];
-    double p[3] = {R[0] * x + R[1] * y + R[2] * z + t[0], R[3] * x + R[4] * y + R[5] * z + t[1], R[6] * x + R[7] * y + R[8] * z + t[2]};
+    // p and the residuals that cancel against it (p - Xc is 1e-4 of |p| near the optimum) are formed in long double and rounded once, so
+    // that g and the cost carry fp64 rounding of their OWN size (tests/test_solver_rows_oracle.py holds them to 1e-12 of the sum of the
+    // products' magnitudes); everything else is plain fp64
+    typedef long double XL;
+    const XL pl[3] = {(XL)R[0] * x + (XL)R[1] * y + (XL)R[2] * z + t[0], (XL)R[3] * x + (XL)R[4] * y + (XL)R[5] * z + t[1],
+                      (XL)R[6] * x + (XL)R[7] * y + (XL)R[8] * z + t[2]};
+    double p[3] = {(double)pl[0], (double)pl[1], (double)pl[2]};
     // Jp = [I | -[p]x] : rows of dp/ddelta
     const double Jp[3][6] = {{1, 0, 0, 0, p[2], -p[1]}, {0, 1, 0, -p[2], 0, p[0]}, {0, 0, 1, p[1], -p[0], 0}};
     if (kind == GN_P2P) {
-      double r[3] = {p[0] - bx, p[1] - by, p[2] - bz};
+      double r[3] = {(double)(pl[0] - bx), (double)(pl[1] - by), (double)(pl[2] - bz)};
       w *= robust_weight(robust, robust_k, std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]));
       for (int k = 0; k < 3; k++) ne->add_row(Jp[k], r[k], w);
     } else if (kind == GN_P2PLANE) {
       double nx = c[3 * i], ny = c[3 * i + 1], nz = c[3 * i + 2];
-      double r = nx * (p[0] - bx) + ny * (p[1] - by) + nz * (p[2] - bz);
+      double r = (double)(nx * (pl[0] - bx) + ny * (pl[1] - by) + nz * (pl[2] - bz));
       w *= robust_weight(robust, robust_k, std::fabs(r));
       double J[6];
       for (int k = 0; k < 6; k++) J[k] = nx * Jp[0][k] + ny * Jp[1][k] + nz * Jp[2][k];
@@ -93,8 +99,9 @@ void gn_normal_eq(int kind, const Tin* a, const Tin* b, const Tin* c, const shor
       }
     } else if (kind == GN_NORMAL) {
       // a = Nw, b = Nc ; q = R Nw ; r = q - Nc ; dq/ddelta = [0 | -[q]x]
-      double q[3] = {R[0] * x + R[1] * y + R[2] * z, R[3] * x + R[4] * y + R[5] * z, R[6] * x + R[7] * y + R[8] * z};
-      double r[3] = {q[0] - bx, q[1] - by, q[2] - bz};
+      const XL ql[3] = {(XL)R[0] * x + (XL)R[1] * y + (XL)R[2] * z, (XL)R[3] * x + (XL)R[4] * y + (XL)R[5] * z, (XL)R[6] * x + (XL)R[7] * y + (XL)R[8] * z};
+      double q[3] = {(double)ql[0], (double)ql[1], (double)ql[2]};
+      double r[3] = {(double)(ql[0] - bx), (double)(ql[1] - by), (double)(ql[2] - bz)};
       w *= robust_weight(robust, robust_k, std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]));
       const double Jq[3][6] = {{0, 0, 0, 0, q[2], -q[1]}, {0, 0, 0, -q[2], 0, q[0]}, {0, 0, 0, q[1], -q[0], 0}};
       for (int k = 0; k < 3; k++) ne->add_row(Jq[k], r[k], w);

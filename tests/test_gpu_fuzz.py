@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from rgbd_pose_estimation_amd import _lib as L, api
+import solver_rows as SR
 import util
 
 pytestmark = pytest.mark.gpu
@@ -86,6 +87,7 @@ def test_fuzz_normal_equations_and_moments(gpu_ctx_factory, oracle, seed):
             assert np.abs(got[:29] - ref).max() <= tol * max(scale, np.abs(ref).max()), (n, f64, kind, mask is not None, weight is not None)
             if weight is None:
                 assert got[28] == ref[28]                 # number of contributing correspondences: exact
+            SR.check_record(kind, got, (sc.Q, b, c), p, n, dt, mask, weight, ("fuzz", seed))   # every entry within its rounding bound
         m = ctx.p2p_moments(flags | L.SKIP_INVALID)
         valid = ~np.isnan(np.asarray(sc.P, np.float64)).all(1)
         sel = valid & ((mask == 1) if mask is not None else True)

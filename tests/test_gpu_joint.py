@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from rgbd_pose_estimation_amd import _lib as L, api
+import solver_rows as SR
 import util
 
 pytestmark = pytest.mark.gpu
@@ -25,6 +26,19 @@ def _oracle_sum(oracle, sc, terms, pose, masks=None, weights=None, f64=False):
         tot[:28] += scale * rec[:28]
         tot[28] += rec[28]
     return tot
+
+
+_term_refs = {}
+
+
+def _term_ref(sc, kind, pose, masks, weights, n, f64):
+    """tests/solver_rows.py reference of one term (record, majorant, bound); the scene is the same for every term set of a size"""
+    key = (kind, n, f64)
+    if key not in _term_refs:
+        a, b, c, mod = ARR[kind]
+        _term_refs[key] = SR.reference(kind, (getattr(sc, a), getattr(sc, b), None if c is None else getattr(sc, c)), pose, n,
+                                       np.float64 if f64 else np.float32, masks[mod], weights[mod])
+    return _term_refs[key]
 
 
 COMBOS = [(L.RES_P2P,), (L.RES_NORMAL,), (L.RES_P2P, L.RES_BEARING), (L.RES_P2PLANE, L.RES_BEARING), (L.RES_P2P, L.RES_NORMAL),
@@ -50,6 +64,8 @@ def test_joint_record_equals_sum_of_terms(gpu_ctx_factory, oracle, n, combo, f64
     tol = 1e-11 if f64 else 3e-6
     assert abs(rec[28] - ref[28]) <= tol * max(1.0, ref[28])
     assert np.max(np.abs(rec[:28] - ref[:28])) <= tol * np.max(np.abs(ref[:28]))
+    # and every entry within the sum of its terms' rounding bounds (the permuted, signed columns of TermSums land where they belong)
+    SR.assert_within(rec, SR.joint_reference([(_term_ref(sc, k, pose, masks, weights, n, f64), s) for k, s, _, _ in terms]), dt, True, (combo, n, f64))
 
 
 @pytest.mark.parametrize("robust", [L.ROBUST_HUBER, L.ROBUST_CAUCHY])

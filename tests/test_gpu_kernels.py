@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from rgbd_pose_estimation_amd import _lib as L, api
+import solver_rows as SR
 import util
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +78,11 @@ def test_normal_eq_matches_oracle(gpu_ctx_factory, oracle, n, kind, f64):
     tolH = 1e-11 if f64 else 2e-6
     assert np.max(np.abs(H - Ho)) <= tolH * np.max(np.abs(Ho))
     assert abs(cost - costo) <= (tolH if n >= 1000 or f64 else 1e-4) * abs(costo) + 1e-12
+    # every entry on its own scale (tests/solver_rows.py: the derived rounding bound), and g against the oracle at every n -- the step
+    # comparison below starts at 1000, and the max-norm above holds a gradient entry to a percent of itself
+    rows = SR.reference(kind, (a, b, c), used, n, dt)
+    SR.assert_within(rec, rows, dt, False, ("normal_eq", kind, n, f64))
+    assert (np.abs(g - go) <= np.asarray(rows[2][21:27] + 1e-12 * rows[1][21:27], np.float64)).all(), (g - go, rows[2][21:27])
     # the step the normal equations imply is what matters for the pose: compare solutions
     if n >= 1000:
         d, do = api.gn_solve(rec), oracle.gn_solve(ref)[0]
@@ -97,6 +103,7 @@ def test_normal_eq_mask_weight(gpu_ctx_factory, oracle, n, kind):
     a, b, c = (getattr(sc, k) if k else None for k in KIND_ARR[kind])
     ref = oracle.gn_normal_eq(kind, a, b, c, mask=mask, weight=w, pose=used)
     assert np.max(np.abs(rec[:29] - ref)) <= 3e-6 * np.max(np.abs(ref))
+    SR.check_record(kind, rec, (a, b, c), used, n, np.float32, mask, w, "mask + weight")     # entrywise, the weight sum included
 
 
 @pytest.mark.parametrize("n", [1000, 307200])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from rgbd_pose_estimation_amd import _lib as L, api
+import solver_rows as SR
 import util
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +55,7 @@ def test_normal_equations_match_the_oracle(gpu_ctx_factory, oracle, n, flags, f6
     tol = 1e-11 if f64 else 3e-6
     assert np.max(np.abs(H - Ho)) <= tol * np.max(np.abs(Ho))
     assert abs(cost - costo) <= (tol if n >= 1000 or f64 else 1e-4) * abs(costo) + 1e-12
+    SR.check_record(L.RES_REPROJ, rec, (sc.Q, sc.U, None), used, n, dt, mask, w, "reproj")      # every entry within its rounding bound
     if n >= 1000:
         d, do = api.gn_solve(rec), oracle.gn_solve(ref)[0]
         assert np.linalg.norm(d - do) <= (1e-11 if f64 else 3e-7) * max(1.0, np.linalg.norm(do))
