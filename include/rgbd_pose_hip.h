@@ -553,7 +553,8 @@ int rpe_volume_upload(rpe_context* ctx, const float* tsdf_weight);
  * alone, so neighbouring cubes agree and the mesh has no cracks).  Segments chain into closed loops; each loop is fan-triangulated
  * from its vertex with the lowest edge number, in the direction the winding requires; loops in the order of that edge.  At most 5
  * triangles per case.
- * The mesh lives until the next rpe_volume_mesh (whether or not it succeeds) or rpe_volume_init.  Workspace: 6 bytes per voxel,
+ * The mesh lives until the next rpe_volume_mesh / rpe_volume_mesh_box (whether or not it succeeds), rpe_volume_init or a non-zero
+ * rpe_volume_shift.  Workspace: 6 bytes per voxel,
  * allocated on the first extraction and kept with the volume. */
 /* marching cubes over the volume: builds the mesh in device buffers the context owns and returns its size (one host wait);
  * RPE_ERR_STATE without a volume, RPE_ERR_ARG for a bad min_weight or a mesh of 2^31 or more vertices (the ids are int32) */
@@ -920,8 +921,8 @@ int rpe_keyframes_optimize(rpe_context* ctx, int anchor, int rounds, const doubl
  * voxel centre behind the camera, or all outside the same image edge).  The test is conservative: the result has the same bits
  * with RPE_FUSE_NO_CULL, which switches it off (tests, timing).
  * Out of scope: the frames BETWEEN keyframes (the rebuilt volume holds the keyframes only); de-integrating a single frame; fusing
- * in any order but the list's; compressing the stored depth (16-bit or binary16 depth would break the bit contract); moving the
- * volume; removing a keyframe; rpe_keyframe_add attaching by itself. */
+ * in any order but the list's; compressing the stored depth (16-bit or binary16 depth would break the bit contract); removing a
+ * keyframe; rpe_keyframe_add attaching by itself.  (Moving the volume: "Moving volume" below.) */
 enum { RPE_FUSE_CLEAR = 1, RPE_FUSE_COLOR = 2, RPE_FUSE_NO_CULL = 4 };
 /* the CURRENT frame's level-0 depth (z of its vertex map), its camera and, if it has one, its colour become keyframe id's attachment
  * (replacing an earlier one).  RPE_ERR_STATE without a frame; RPE_ERR_ARG for an id not in the store or a frame whose level-0 size is
@@ -940,6 +941,52 @@ int rpe_keyframe_attachment_download(rpe_context* ctx, int id, float* z, uint8_t
  * RPE_ERR_STATE without a volume, for a listed keyframe without depth, with RPE_FUSE_COLOR for one without colour, and with ids = NULL
  * when no keyframe has depth; RPE_ERR_ARG for ids not in the store, bad count or unknown flags. */
 int rpe_volume_fuse_keyframes(rpe_context* ctx, const int32_t* ids, int count, const double* poses12, int flags);
+
+/* ---- Moving volume: the window of the TSDF and colour volume follows the camera.  rpe_volume_init fixes a cube; a camera that walks
+ * out of it gets no raycast hits and the session is over.  rpe_volume_shift moves the window by WHOLE VOXELS on the device,
+ * rpe_volume_follow proposes the shift that re-centres it in front of the camera, rpe_volume_geometry says where it is now, and
+ * rpe_volume_mesh_box extracts the surface of the cubes that are about to leave.  tests/shift_oracle.py states all four in numpy.
+ * Shift by (di, dj, dk) voxels along +x, +y, +z.  Content: new voxel (i, j, k) := old voxel (i+di, j+dj, k+dk) where that lies inside
+ * the old window, with the bits as they are (NaN payloads, -0 and denormals stay); every other voxel is cleared to {0, 0}.  A colour
+ * volume, if there is one, moves by the same rule and its cleared voxels are all-zero bits; if there is none, none comes into being.
+ * Geometry: the context keeps the descriptor rpe_volume_init was given (origin and voxel_size as doubles) and an int64 total shift per
+ * axis, zeroed by rpe_volume_init.  After a shift origin_now[a] = origin[a] + (double)total[a] * voxel_size, in double as written,
+ * and the kernels' fp32 origin is o[a] = (float)origin_now[a]: ONE rounding from the exact value every time, so nothing drifts over
+ * many shifts, and at total 0 the origin is the init's again.  Every other call (integrate, raycast, mesh, colour, the keyframe fuse)
+ * then sees an ordinary volume at that origin: the shifted context behaves, bit for bit, like a fresh rpe_volume_init at origin_now
+ * followed by rpe_volume_upload / rpe_volume_color_upload of the moved content.
+ * Edge rules: shift = (0, 0, 0) changes nothing at all (the last mesh stays).  |shift[a]| >= dim[a] on any axis is legal and clears
+ * the whole window.  A total shift beyond 2^30 voxels either way on any axis, or an o[a] that is not finite, is RPE_ERR_ARG and
+ * nothing has changed.  Any non-zero shift drops the last mesh (rpe_volume_mesh_download and rpe_volume_mesh_colors then return
+ * RPE_ERR_STATE).  The frame, the model, the model colour, the keyframes and the graph are in world coordinates and are not touched.
+ * Memory: the shift is out of place.  The context keeps a spare of the tsdf volume and, if there is a colour volume, of that too,
+ * reserved on the first shift and swapped with the live arrays by each one: 8 B + 8 B per voxel more, 2 GB at 512^3 with colour.
+ * rpe_volume_init drops the spares when the volume grows.  The host does not wait.
+ * Follow (pose12 with Xc = R Xw + t, look_ahead metres, granule voxels), all in double, in this order: p = (0, 0, look_ahead) - t;
+ * c[a] = R[0][a]*p[0] + R[1][a]*p[1] + R[2][a]*p[2], summed left to right (the world point look_ahead metres in front of the camera);
+ * centre[a] = origin_now[a] + 0.5 * dim[a] * voxel_size; v[a] = (c[a] - centre[a]) / voxel_size;
+ * shift[a] = granule * (int)trunc(v[a] / granule).  So an axis moves only when the target is at least granule voxels off centre, and
+ * in multiples of granule.  The shift is computed, not applied.
+ * Mesh of a box: exactly rpe_volume_mesh with one more condition on a cube: cube (i, j, k) takes part only if lo[a] <= index[a] <
+ * hi[a] on every axis; a cube outside has case 0.  Vertex rule and order (owner voxel index, then axis), triangle order, the normals
+ * (the raycast's normal from the field of the WHOLE volume, not of the box), the mesh's lifetime, rpe_volume_mesh_download and
+ * rpe_volume_mesh_colors are unchanged; rpe_volume_mesh is the full box (0, dim-1).  Cubes partition along a cut: for a shift di > 0
+ * the cubes with i < di are exactly those whose surface is lost and the cubes with i >= di exactly the cubes of the window after the
+ * shift, so mesh_box of what leaves, download, shift loses or doubles no triangle.  The extraction still sweeps the whole volume.
+ * The tracking loop: follow -> if non-zero: mesh_box of what leaves, download, shift -> raycast -> ICP -> integrate.  What comes IN
+ * is empty until frames are fused into it; rpe_volume_fuse_keyframes with RPE_FUSE_CLEAR rebuilds the new window from the store. */
+/* move the window by shift[0..2] voxels; RPE_ERR_STATE without a volume, RPE_ERR_ARG for a total beyond 2^30 or a non-finite origin */
+int rpe_volume_shift(rpe_context* ctx, const int32_t shift[3]);
+/* the init-time descriptor with origin replaced by origin_now; total_shift (may be NULL) = the voxels moved since rpe_volume_init;
+ * RPE_ERR_STATE without a volume */
+int rpe_volume_geometry(rpe_context* ctx, rpe_volume_desc* desc, int64_t total_shift[3]);
+/* the shift that re-centres the window on the point look_ahead metres in front of the camera at pose12; granule >= 1 and a finite
+ * look_ahead >= 0 are required and |v[a]| <= 2^30, otherwise RPE_ERR_ARG; RPE_ERR_STATE without a volume */
+int rpe_volume_follow(rpe_context* ctx, const double* pose12, double look_ahead, int granule, int32_t shift[3]);
+/* rpe_volume_mesh over the cubes lo <= (i, j, k) < hi only: 0 <= lo[a] <= hi[a] <= dim[a] - 1, otherwise RPE_ERR_ARG; an empty box
+ * gives an empty mesh */
+int rpe_volume_mesh_box(rpe_context* ctx, double min_weight, const int32_t lo[3], const int32_t hi[3], int64_t* n_vertices,
+                        int64_t* n_triangles);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

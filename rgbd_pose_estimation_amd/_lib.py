@@ -58,6 +58,7 @@ SYMBOLS = [
     "rpe_graph_normal_eq", "rpe_keyframes_optimize", "rpe_graph_solve",
     "rpe_keyframe_attach_frame", "rpe_keyframe_attach_host", "rpe_keyframe_attachment_info", "rpe_keyframe_attachment_download",
     "rpe_volume_fuse_keyframes",
+    "rpe_volume_shift", "rpe_volume_geometry", "rpe_volume_follow", "rpe_volume_mesh_box",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -281,6 +282,10 @@ def lib():
         L.rpe_keyframe_attachment_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(RpeCamera)]
         L.rpe_keyframe_attachment_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rpe_volume_fuse_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.rpe_volume_shift.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_volume_geometry.argtypes = [C.c_void_p, C.POINTER(RpeVolumeDesc), C.c_void_p]
+        L.rpe_volume_follow.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]
+        L.rpe_volume_mesh_box.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -360,18 +360,49 @@ class Context:
         L.check(L.lib().rpe_volume_upload(self._h, _p(a)))
         return self
 
-    def volume_mesh(self, min_weight: float = 1.0):
+    def volume_mesh(self, min_weight: float = 1.0, box=None):
         """Marching cubes over the volume (corners with weight >= min_weight): (vertices (V, 3) float32, normals (V, 3) float32, NaN
-        where the field is unknown, triangles (T, 3) int32), wound so that (v1 - v0) x (v2 - v0) points to free space."""
+        where the field is unknown, triangles (T, 3) int32), wound so that (v1 - v0) x (v2 - v0) points to free space.  box = (lo, hi):
+        only the cubes with lo <= (i, j, k) < hi per axis (rpe_volume_mesh_box; 0 <= lo <= hi <= dim - 1), everything else unchanged."""
         nv, nt = C.c_int64(0), C.c_int64(0)
         self._mesh_nv = None
-        L.check(L.lib().rpe_volume_mesh(self._h, float(min_weight), C.byref(nv), C.byref(nt)))
+        if box is None:
+            L.check(L.lib().rpe_volume_mesh(self._h, float(min_weight), C.byref(nv), C.byref(nt)))
+        else:
+            lo, hi = (np.ascontiguousarray(b, np.int32).reshape(3) for b in box)
+            L.check(L.lib().rpe_volume_mesh_box(self._h, float(min_weight), _p(lo), _p(hi), C.byref(nv), C.byref(nt)))
         self._mesh_nv = nv.value
         V = np.empty((nv.value, 3), np.float32)
         N = np.empty((nv.value, 3), np.float32)
         T = np.empty((nt.value, 3), np.int32)
         L.check(L.lib().rpe_volume_mesh_download(self._h, _p(V), _p(N), _p(T)))
         return V, N, T
+
+    # ---- moving volume (Part 3): the window shifted by whole voxels, where it is, and the shift that follows the camera
+    def volume_shift(self, shift):
+        """Move the volume's window by shift = (di, dj, dk) whole voxels along +x, +y, +z: new voxel (i, j, k) := old voxel
+        (i + di, j + dj, k + dk) where that was inside, cleared elsewhere; the colour volume (if any) likewise; the origin follows.  A
+        non-zero shift drops the last mesh."""
+        d = np.ascontiguousarray(shift, np.int32).reshape(3)
+        L.check(L.lib().rpe_volume_shift(self._h, _p(d)))
+        if d.any():
+            self._mesh_nv = None
+        return self
+
+    def volume_geometry(self):
+        """dict(dims, voxel_size, origin (3,) float64 -- where the window is NOW --, trunc, max_weight, total_shift (3,) int64)."""
+        d, tot = L.RpeVolumeDesc(), np.zeros(3, np.int64)
+        L.check(L.lib().rpe_volume_geometry(self._h, C.byref(d), _p(tot)))
+        return dict(dims=tuple(d.dim), voxel_size=d.voxel_size, origin=np.array(list(d.origin), np.float64), trunc=d.trunc,
+                    max_weight=d.max_weight, total_shift=tot)
+
+    def volume_follow(self, pose12, look_ahead: float, granule: int = 1) -> np.ndarray:
+        """The shift (3,) int32, in multiples of `granule` voxels, that brings the world point look_ahead metres in front of the camera
+        at pose12 (Xc = R Xw + t) back towards the window's centre (rpe_volume_follow).  Nothing is applied: hand it to volume_shift."""
+        p = np.array(pose12, np.float64).reshape(12)
+        out = np.zeros(3, np.int32)
+        L.check(L.lib().rpe_volume_follow(self._h, _p(p), float(look_ahead), int(granule), _p(out)))
+        return out
 
     # ---- colour (Part 3): a registered RGB frame fused beside the depth, sampled back at the model's and the mesh's vertices
     def frame_set_color(self, rgb, order: str = "rgb"):

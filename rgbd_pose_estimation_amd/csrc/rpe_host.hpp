@@ -15,6 +15,7 @@
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
 //   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)
 //   rpe_rebuild_api.hip   Part 3: the volume rebuilt from the keyframes' attached depth (rpe_volume_fuse_keyframes; kernels in rpe_rebuild.hip)
+//   rpe_shift_api.hip     Part 3: the moving volume (rpe_volume_shift / _geometry / _follow; kernel in rpe_shift.hip)
 // Two headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
 // host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create) and rpe_frontend_host.hpp (what the
 // Part 3 units share: camera and pose casts, the solver slots, feature / match options, the relocalisers' common steps).
@@ -239,6 +240,13 @@ struct rpe_context {
     rpeh::DevBuf<unsigned short> cd;
     bool have_color = false;
     rpeh::DevBuf<unsigned int> mc;
+    // moving volume (rpe_shift_api.hip): the descriptor rpe_volume_init was given, the voxels the window has moved since, per axis
+    // (g.o = (float)(desc.origin + total * desc.voxel_size)), and the spares rpe_volume_shift writes into before it swaps them with
+    // d / cd (reserved on the first shift, dropped when the volume grows)
+    rpe_volume_desc desc{};
+    int64_t total[3] = {0, 0, 0};
+    rpeh::DevBuf<float> d_spare;
+    rpeh::DevBuf<unsigned short> cd_spare;
   } vol;
 
   rpe::DeviceArrays arrays() const {

@@ -261,8 +261,10 @@ struct MeshWorkspace {
 };
 size_t mesh_workspace_bytes(int64_t nvox);
 MeshWorkspace mesh_workspace(void* ws, int64_t nvox);
-// M1-M3: cases, used edges, chunk counts, their scan and the totals (min weight wmin > 0)
-hipError_t launch_mesh_count(const float* vol, const VolumeGeometry& G, float wmin, const MeshWorkspace& W, hipStream_t s);
+// M1-M3: cases, used edges, chunk counts, their scan and the totals (min weight wmin > 0).  Only the cubes with lo <= (i, j, k) < hi per
+// axis take part (rpe_volume_mesh_box); the full box is lo = 0, hi = dim - 1
+struct MeshBox { int lo[3], hi[3]; };
+hipError_t launch_mesh_count(const float* vol, const VolumeGeometry& G, float wmin, const MeshBox& B, const MeshWorkspace& W, hipStream_t s);
 // M4-M5 after launch_mesh_count: 3 x V vertex and normal floats, 3 x T int32 triangle ids
 hipError_t launch_mesh_emit(const float* vol, const VolumeGeometry& G, const MeshWorkspace& W, float* vertices, float* normals,
                             int* triangles, hipStream_t s);
@@ -389,6 +391,12 @@ hipError_t launch_attach_pack(const float* vmap, const unsigned int* fcolor, int
 hipError_t launch_volume_fuse(float* vol, unsigned short* cvol, const VolumeGeometry& G, const FuseEntry* table, int count, bool clear,
                               bool color, bool cull, hipStream_t s);
 void preload_rebuild();
+// ---- moving the volume (rpe_shift.hip).  S1: out voxel (i, j, k) := voxel (i + shift[0], j + shift[1], k + shift[2]) of vol where that
+// lies inside dim, zero bits elsewhere; cvol != nullptr: the colour volume likewise into cvol_out, in the same launch.  Out of place:
+// vol_out / cvol_out must not overlap vol / cvol.  |shift[a]| <= dim[a] (the caller clears the volume itself for a larger one)
+hipError_t launch_volume_shift(const float* vol, float* vol_out, const unsigned short* cvol, unsigned short* cvol_out, const int dim[3],
+                               const int shift[3], hipStream_t s);
+void preload_shift();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

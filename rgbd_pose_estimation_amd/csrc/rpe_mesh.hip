@@ -72,12 +72,16 @@ __device__ __forceinline__ unsigned cube_case(const float* __restrict__ vol, con
 
 // one cube per lane, so that each of the 8 corner loads of a wave reads 512 contiguous bytes; `padded` = the chunks' voxels: the case
 // bytes past the volume are written as 0
-__global__ __launch_bounds__(kMeshBlock) void mesh_classify_kernel(const float* __restrict__ vol, VolumeGeometry G, float wmin,
+// a cube outside the box [B.lo, B.hi) has case 0, as an inactive one: it emits nothing and marks no edge (hi <= dim - 1 keeps the
+// box's cubes inside cube_case's own range test)
+__global__ __launch_bounds__(kMeshBlock) void mesh_classify_kernel(const float* __restrict__ vol, VolumeGeometry G, float wmin, MeshBox B,
                                                                    unsigned padded, unsigned char* __restrict__ cases) {
   const unsigned flat = blockIdx.x * kMeshBlock + threadIdx.x;
   if (flat >= padded) return;
   const unsigned d0 = (unsigned)G.dim[0], d1 = (unsigned)G.dim[1];
-  cases[flat] = (unsigned char)cube_case(vol, G, wmin, flat, (int)(flat % d0), (int)((flat / d0) % d1), (int)(flat / d0 / d1));
+  const int i = (int)(flat % d0), j = (int)((flat / d0) % d1), k = (int)(flat / d0 / d1);
+  const bool in_box = i >= B.lo[0] && i < B.hi[0] && j >= B.lo[1] && j < B.hi[1] && k >= B.lo[2] && k < B.hi[2];
+  cases[flat] = in_box ? (unsigned char)cube_case(vol, G, wmin, flat, i, j, k) : (unsigned char)0;
 }
 
 // ---------------------------------------------------------------------------------------------- M2
@@ -242,9 +246,10 @@ MeshWorkspace mesh_workspace(void* ws, int64_t nvox) {
   return W;
 }
 
-hipError_t launch_mesh_count(const float* vol, const VolumeGeometry& G, float wmin, const MeshWorkspace& W, hipStream_t s) {
+hipError_t launch_mesh_count(const float* vol, const VolumeGeometry& G, float wmin, const MeshBox& B, const MeshWorkspace& W,
+                             hipStream_t s) {
   const unsigned nvox = (unsigned)((int64_t)G.dim[0] * G.dim[1] * G.dim[2]), padded = (unsigned)W.chunks * kMeshChunk;
-  hipLaunchKernelGGL(mesh_classify_kernel, dim3(padded / kMeshBlock), dim3(kMeshBlock), 0, s, vol, G, wmin, padded, W.cases);
+  hipLaunchKernelGGL(mesh_classify_kernel, dim3(padded / kMeshBlock), dim3(kMeshBlock), 0, s, vol, G, wmin, B, padded, W.cases);
   hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)W.chunks), dim3(kMeshBlock), 0, s, W.cases, G, nvox, W.used, W.chunk_v, W.chunk_t);
   hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, W.chunk_v, W.chunk_t, W.chunks, W.off_v, W.off_t, W.totals);
   return hipGetLastError();

@@ -27,13 +27,15 @@ int rpe_volume_init(rpe_context* c, const rpe_volume_desc* d) {
   V.have = false;
   V.have_mesh = false;
   V.have_color = false;
-  if (V.d.bytes() < bytes) {   // the mesh workspace and the colour volume follow the volume's size: they go before it grows
+  if (V.d.bytes() < bytes) {   // the mesh workspace, the colour volume and the shift's spares follow the volume's size: they go before it grows
     if (V.d) HIP_TRY(hipStreamSynchronize(c->stream));
-    V.ws = {}; V.cd = {};
+    V.ws = {}; V.cd = {}; V.d_spare = {}; V.cd_spare = {};
   }
   if (int rc = V.d.reserve(c, bytes)) return rc;
   HIP_TRY(hipMemsetAsync(V.d, 0, bytes, c->stream));
   V.g = g;
+  V.desc = *d;
+  V.total[0] = V.total[1] = V.total[2] = 0;
   V.have = true;
   return RPE_OK;
 }

@@ -34,6 +34,7 @@
 //   after addKeyframe(): fe.linkKeyframes(id);   at a loop: rpe::GraphResult g = fe.optimizeKeyframes({0.1, 0.1, 0.05, 0.05, 0.03});
 //   (g.poses[k] = keyframe k's corrected pose.  No odometry edges, no robust kernel but the gate, dense host solve.)
 // ... and the MAP follows: a keyframe that carries its depth is fused again at its corrected pose, all of them in one launch
+//   int32_t d[3]; fe.followShift(T, 1.5, 8, d);  if (d[0] | d[1] | d[2]) { rpe::Mesh gone = fe.mesh(1, lo, hi); fe.shiftVolume(d); }   // moving volume
 //   after addKeyframe(): fe.attachFrame(id);   after optimizeKeyframes(): fe.fuseKeyframes({}, {}, true, true);  rpe::Mesh m = fe.mesh();
 //   (the rebuilt volume holds the keyframes only, not the frames between them)
 //
@@ -278,6 +279,40 @@ class DepthFrontEnd {
     M.triangles.resize((size_t)nt * 3);
     check(rpe_volume_mesh_download(_ctx, M.vertices.data(), M.normals.data(), M.triangles.data()), "rpe_volume_mesh_download");
     return M;
+  }
+  // the same over the cubes lo <= (i, j, k) < hi only (rpe_volume_mesh_box; 0 <= lo <= hi <= dim - 1): what a shift is about to lose
+  Mesh mesh(double min_weight, const int32_t lo[3], const int32_t hi[3]) const {
+    int64_t nv = 0, nt = 0;
+    _mesh_vertices = -1;
+    check(rpe_volume_mesh_box(_ctx, min_weight, lo, hi, &nv, &nt), "rpe_volume_mesh_box");
+    _mesh_vertices = nv;
+    Mesh M;
+    M.vertices.resize(3, (int)nv);
+    M.normals.resize(3, (int)nv);
+    M.triangles.resize((size_t)nt * 3);
+    check(rpe_volume_mesh_download(_ctx, M.vertices.data(), M.normals.data(), M.triangles.data()), "rpe_volume_mesh_download");
+    return M;
+  }
+  // move the volume's window by (di, dj, dk) whole voxels along +x, +y, +z (rpe_volume_shift): new voxel (i, j, k) := old voxel
+  // (i + di, j + dj, k + dk) where that was inside, cleared elsewhere, the colour volume likewise; a non-zero shift drops the last mesh
+  void shiftVolume(const int32_t shift[3]) {
+    check(rpe_volume_shift(_ctx, shift), "rpe_volume_shift");
+    if (shift[0] || shift[1] || shift[2]) _mesh_vertices = -1;
+  }
+  // where the window is now: the descriptor of initVolume with its origin moved by the total shift (total, if given, receives it)
+  VolumeDesc volumeGeometry(int64_t total[3] = nullptr) const {
+    rpe_volume_desc v;
+    check(rpe_volume_geometry(_ctx, &v, total), "rpe_volume_geometry");
+    VolumeDesc d;
+    for (int a = 0; a < 3; a++) { d.dim[a] = v.dim[a]; d.origin[a] = v.origin[a]; }
+    d.voxel_size = v.voxel_size; d.trunc = v.trunc; d.max_weight = v.max_weight;
+    return d;
+  }
+  // the shift, in multiples of `granule` voxels, that re-centres the window on the point look_ahead metres in front of the camera at
+  // T_cw (rpe_volume_follow); nothing is applied: hand it to shiftVolume
+  void followShift(const Pose& T_cw, double look_ahead, int granule, int32_t shift[3]) const {
+    double p[12]; pose12(T_cw, p);
+    check(rpe_volume_follow(_ctx, p, look_ahead, granule, shift), "rpe_volume_follow");
   }
   // the current frame's colour: width*height*3 bytes (RPE_COLOR_RGB8 or RPE_COLOR_BGR8 order) registered to its depth; a new depth
   // drops it
