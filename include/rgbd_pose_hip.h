@@ -922,7 +922,9 @@ int rpe_keyframes_optimize(rpe_context* ctx, int anchor, int rounds, const doubl
  * with RPE_FUSE_NO_CULL, which switches it off (tests, timing).
  * Out of scope: the frames BETWEEN keyframes (the rebuilt volume holds the keyframes only); de-integrating a single frame; fusing
  * in any order but the list's; compressing the stored depth (16-bit or binary16 depth would break the bit contract); removing a
- * keyframe; rpe_keyframe_add attaching by itself.  (Moving the volume: "Moving volume" below.) */
+ * keyframe; rpe_keyframe_add attaching by itself.  (Moving the volume: "Moving volume" below.)
+ * The volume archive ("Volume archive" below) is not touched by this call: bricks archived before a correction keep the old poses'
+ * surface; rpe_volume_archive_clear forgets them. */
 enum { RPE_FUSE_CLEAR = 1, RPE_FUSE_COLOR = 2, RPE_FUSE_NO_CULL = 4 };
 /* the CURRENT frame's level-0 depth (z of its vertex map), its camera and, if it has one, its colour become keyframe id's attachment
  * (replacing an earlier one).  RPE_ERR_STATE without a frame; RPE_ERR_ARG for an id not in the store or a frame whose level-0 size is
@@ -987,6 +989,50 @@ int rpe_volume_follow(rpe_context* ctx, const double* pose12, double look_ahead,
  * gives an empty mesh */
 int rpe_volume_mesh_box(rpe_context* ctx, double min_weight, const int32_t lo[3], const int32_t hi[3], int64_t* n_vertices,
                         int64_t* n_triangles);
+
+/* ---- Volume archive: what leaves the moving window is kept, bit for bit, on the device, and put back when the window returns over it.
+ * Without it a voxel that a shift pushes out is destroyed ("What comes IN is empty", above); with it the window plus the archive is a
+ * map.  tests/archive_oracle.py states the section in numpy.
+ * Brick: 8 x 8 x 8 voxels, aligned in WORLD voxel coordinates.  World voxel = total shift + window index, per axis; world brick =
+ * world voxel / 8, an int64 triple (bx, by, bz).  The archive therefore requires every dim and every component of the total shift,
+ * and with it on of every shift, to be a multiple of 8 (rpe_volume_follow with granule = 8 proposes such shifts).
+ * THE INVARIANT: there is one unbounded store of bricks, keyed by world brick.  A shift (1) writes into it every LEAVING brick -- a
+ * brick of the window that has no destination inside the window after the move; for |shift[a]| >= dim[a] on any axis that is every
+ * brick -- of which ANY 32-bit word is non-zero in the tsdf or the colour volume, (2) moves the window as rpe_volume_shift always does,
+ * (3) takes out of the store every ENTERING brick -- a brick of the new window that was not in the old one -- that the store holds,
+ * and writes it over the zeros step 2 left there.  After any sequence of shifts, uploads and integrates, the window and the archive
+ * (rpe_volume_archive_download) are what this model gives, bit for bit; the window is always the only holder of what it covers; and
+ * shift(d) followed by shift(-d) is the identity on both volumes.  The occupancy rule of step 1 is about BITS, not weights: NaN
+ * payloads, -0, and a voxel of weight 0 that has a tsdf all make their brick non-zero, so the round trip is exact for any content.
+ * An all-zero brick is not kept, and restores as the zeros it was.
+ * Colour: a brick is archived with the colour volume's brick if there is a colour volume, with all-zero colour otherwise, and restores
+ * its colour into the colour volume if there is one at that time (into a window without a colour volume only the tsdf brick returns).
+ * Memory: a slot is 4 KB for {tsdf, weight} plus 4 KB for colour; the colour plane of the pool is reserved (and zeroed) the first time
+ * a brick is archived while a colour volume exists.  The index world brick -> slot lives on the host.
+ * Shift with the archive on: a component that is not a multiple of 8 is RPE_ERR_ARG; more non-zero leaving bricks than free slots
+ * (capacity - held; the slots of the bricks that enter in the same shift do not count) is RPE_ERR_STATE with both numbers in the
+ * message.  Both are decided before anything is written: window, archive and geometry are unchanged.  The host waits ONCE per shift,
+ * for the flags that say which leaving bricks are non-zero.  With the archive off rpe_volume_shift is what it was, call for call, and
+ * does not wait.
+ * Lifetimes: rpe_volume_init drops the archive (pool and content).  rpe_volume_fuse_keyframes does not touch it: after a loop closure
+ * has rebuilt the window at corrected poses, the archived bricks still hold the OLD poses' surface -- call rpe_volume_archive_clear.
+ * rpe_volume_upload, rpe_volume_integrate and the colour calls write the window only.
+ * The tracking loop: follow(granule = 8) -> if non-zero: shift -> raycast -> ICP -> integrate.
+ * Out of scope: shifts or dims that are not multiples of 8 with the archive on; a device-side index (no host wait); spilling the pool
+ * to host memory; meshing or raycasting the archive directly; moving the archived bricks under a loop-closure correction. */
+/* capacity_bricks > 0: switch the archive on with a pool of that many slots, or grow the pool to it (the content stays; a capacity
+ * between the number of held bricks and the current capacity changes nothing: the pool does not shrink); 0: switch it off and free
+ * everything.  RPE_ERR_ARG for a capacity below the number of held bricks, negative or above 2^24; RPE_ERR_STATE (nothing changed)
+ * without a volume or when a dim or a component of the total shift is not a multiple of 8 */
+int rpe_volume_archive(rpe_context* ctx, int64_t capacity_bricks);
+/* the number of held bricks and the capacity (0 and 0 with the archive off); either may be NULL */
+int rpe_volume_archive_info(rpe_context* ctx, int64_t* held, int64_t* capacity);
+/* the held bricks sorted by (bz, by, bx): coords = held x 3 int64 (bx, by, bz); tsdf = held x 8 x 8 x 8 x 2 floats in (z, y, x) order,
+ * as rpe_volume_download lays a window out; colour (may be NULL) = held x 8 x 8 x 8 x 4 binary16, zeros where none was kept.  Slot
+ * numbers are not part of the contract.  With nothing held nothing is written */
+int rpe_volume_archive_download(rpe_context* ctx, int64_t* coords, float* tsdf, uint16_t* colour);
+/* forget every brick, keep the pool: for use after rpe_volume_fuse_keyframes has rebuilt the map at corrected poses */
+int rpe_volume_archive_clear(rpe_context* ctx);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

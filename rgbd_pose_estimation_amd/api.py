@@ -404,6 +404,35 @@ class Context:
         L.check(L.lib().rpe_volume_follow(self._h, _p(p), float(look_ahead), int(granule), _p(out)))
         return out
 
+    # ---- volume archive (Part 3): what a shift pushes out of the window is kept in bricks on the device and put back on return
+    def volume_archive(self, capacity: int):
+        """Switch the archive on with a pool of `capacity` bricks (8 x 8 x 8 voxels, 4 KB + 4 KB with colour), grow it to that, or, with
+        0, switch it off and free it (rpe_volume_archive).  While it is on, volume_shift takes multiples of 8 only, keeps every
+        non-zero brick that leaves and restores every archived brick the window returns over."""
+        L.check(L.lib().rpe_volume_archive(self._h, int(capacity)))
+        return self
+
+    def volume_archive_info(self):
+        """dict(held, capacity): the bricks the archive holds and the slots of its pool (0, 0 with the archive off)."""
+        held, cap = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().rpe_volume_archive_info(self._h, C.byref(held), C.byref(cap)))
+        return dict(held=held.value, capacity=cap.value)
+
+    def volume_archive_download(self):
+        """The held bricks sorted by (bz, by, bx): (coords (n, 3) int64 world bricks (bx, by, bz), tsdf (n, 8, 8, 8, 2) float32 in
+        (z, y, x) order, colour (n, 8, 8, 8, 4) float16, or None where no held brick has a colour bit set)."""
+        n = self.volume_archive_info()["held"]
+        coords = np.zeros((n, 3), np.int64)
+        tsdf = np.zeros((n, 8, 8, 8, 2), np.float32)
+        colour = np.zeros((n, 8, 8, 8, 4), np.float16)
+        L.check(L.lib().rpe_volume_archive_download(self._h, _p(coords), _p(tsdf), _p(colour)))
+        return coords, tsdf, colour if colour.view(np.uint16).any() else None
+
+    def volume_archive_clear(self):
+        """Forget every archived brick and keep the pool (after volume_fuse_keyframes rebuilt the map at corrected poses)."""
+        L.check(L.lib().rpe_volume_archive_clear(self._h))
+        return self
+
     # ---- colour (Part 3): a registered RGB frame fused beside the depth, sampled back at the model's and the mesh's vertices
     def frame_set_color(self, rgb, order: str = "rgb"):
         """The current frame's colour: (height, width, 3) uint8 registered to its depth (pixel (u, v) of both sees the same ray), channels

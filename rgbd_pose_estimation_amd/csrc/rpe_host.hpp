@@ -16,6 +16,8 @@
 //   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)
 //   rpe_rebuild_api.hip   Part 3: the volume rebuilt from the keyframes' attached depth (rpe_volume_fuse_keyframes; kernels in rpe_rebuild.hip)
 //   rpe_shift_api.hip     Part 3: the moving volume (rpe_volume_shift / _geometry / _follow; kernel in rpe_shift.hip)
+//   rpe_archive_api.hip   Part 3: the volume archive (rpe_volume_archive / _info / _download / _clear and the two halves of a shift with the
+//                         archive on: the bricks that leave kept in a pool, the ones that return put back; kernels in rpe_archive.hip)
 // Two headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
 // host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create) and rpe_frontend_host.hpp (what the
 // Part 3 units share: camera and pose casts, the solver slots, feature / match options, the relocalisers' common steps).
@@ -42,6 +44,8 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <array>
+#include <map>
 #include <cctype>
 #include <sched.h>
 #include <unistd.h>
@@ -247,6 +251,22 @@ struct rpe_context {
     int64_t total[3] = {0, 0, 0};
     rpeh::DevBuf<float> d_spare;
     rpeh::DevBuf<unsigned short> cd_spare;
+    // volume archive (rpe_archive_api.hip): a pool of `capacity` slots of rpe::kArchiveSlotBytes for the tsdf bricks and, from the first
+    // brick archived while a colour volume exists, as many for the colour bricks (cpool); the index world brick -> slot, keyed (bz, by,
+    // bx) so that it iterates in the download's order, and the free slots.  flags / pairs_out / pairs_in: the occupancy flags of a
+    // shift's leaving bricks and its two (window brick, slot) lists on the device, h_pairs their host copy, which the upload may still
+    // be reading until the next wait on the stream
+    struct Archive {
+      bool on = false;
+      int64_t capacity = 0;
+      rpeh::DevBuf<unsigned int> pool, cpool;
+      std::map<std::array<int64_t, 3>, int32_t> index;
+      std::vector<int32_t> free;
+      rpeh::DevBuf<unsigned int> flags;
+      rpeh::DevBuf<int> pairs;
+      std::vector<unsigned int> h_flags;
+      std::vector<int32_t> h_pairs;
+    } arc;
   } vol;
 
   rpe::DeviceArrays arrays() const {
@@ -398,6 +418,16 @@ struct SlotHold {
 ResidentSlot& resident_mutex(int device);
 int resident_run_shape(int grid, int nacc, int max_rows, int rows_auto, rpe::ReduceTarget* rt);
 void note_lost_grid(rpe_context* c);
+
+// ---- rpe_archive_api.hip: the two halves of rpe_volume_shift with the archive on (c->vol.arc.on).  archive_leave, BEFORE the window
+// moves: finds the non-zero leaving bricks (the shift's one host wait), checks the free slots (RPE_ERR_STATE and nothing changed if
+// they do not suffice), copies the bricks into their slots and looks up the entering bricks at the new total.  archive_enter, AFTER the
+// shift's kernel or memsets: writes the entering bricks over the zeros and commits the plan to the index.  archive_drop: the archive
+// goes (rpe_volume_init, capacity 0)
+struct ArchivePlan { std::vector<std::array<int64_t, 3>> leave_key, enter_key; std::vector<int32_t> enter_slot; };
+int archive_leave(rpe_context* c, const int32_t shift[3], const int64_t total_new[3], ArchivePlan* plan);
+int archive_enter(rpe_context* c, const ArchivePlan& plan);
+int archive_drop(rpe_context* c);
 
 // ---- rpe_session.hip
 void session_end(rpe_context* c);      // every entry point that queues work behind the context's stream, reads the masks or reuses the host-side record area calls this first

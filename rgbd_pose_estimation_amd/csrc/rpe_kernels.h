@@ -397,6 +397,21 @@ void preload_rebuild();
 hipError_t launch_volume_shift(const float* vol, float* vol_out, const unsigned short* cvol, unsigned short* cvol_out, const int dim[3],
                                const int shift[3], hipStream_t s);
 void preload_shift();
+// ---- the volume archive (rpe_archive.hip): bricks of 8 x 8 x 8 voxels kept in a pool of slots, kArchiveSlotBytes per slot and volume,
+// a brick's 64 rows of 8 voxels back to back in (z, y, x) order.  Every dim is a multiple of 8.
+constexpr int kArchiveSlotBytes = 4096;
+// up to three disjoint boxes of bricks: box b covers lo[b][a] .. lo[b][a] + n[b][a] - 1 on axis a; its bricks are numbered from
+// first[b], x fastest; first[3] = the number of bricks of all boxes
+struct ArchiveBoxes { int lo[3][3], n[3][3], first[4]; };
+// A1: flags[g] = 1 if any 32-bit word of brick g of the boxes is non-zero in vol or (cvol != nullptr) in cvol, else 0
+hipError_t launch_brick_occupancy(const float* vol, const unsigned short* cvol, const int dim[3], const ArchiveBoxes& B, unsigned int* flags,
+                                  hipStream_t s);
+// A2: n pairs {window brick = bx + nb0 * (by + nb1 * bz), slot}.  to_pool: slot := brick (cpool without cvol: the slot's colour is
+// zeroed); else brick := slot (the colour only where cvol and cpool both exist).  A pair whose brick is not in the window or whose slot
+// is not below capacity is skipped
+hipError_t launch_brick_copy(bool to_pool, float* vol, unsigned short* cvol, unsigned int* pool, unsigned int* cpool, const int dim[3],
+                             const int* pairs, int n, int capacity, hipStream_t s);
+void preload_archive();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

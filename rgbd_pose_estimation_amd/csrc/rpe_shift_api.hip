@@ -5,7 +5,8 @@
 // Memory: the shift is OUT OF PLACE.  The context keeps a spare of the tsdf volume (8 B per voxel) and, when there is a colour volume,
 // of that too (8 B per voxel), reserved on the first shift and swapped with the live arrays after each: 16 B per voxel more, 2 GB at
 // 512^3 with colour, for a kernel whose every voxel is read once and written once with no ordering between workgroups to rely on.
-// rpe_volume_init drops the spares when the volume grows.
+// rpe_volume_init drops the spares when the volume grows.  With the volume archive on (rpe_archive_api.hip) a shift is bracketed by
+// archive_leave and archive_enter; with it off the path below is what it was, call for call, and the host does not wait.
 #include "rpe_frontend_host.hpp"
 #include <cmath>
 #include <utility>
@@ -43,6 +44,15 @@ int rpe_volume_shift(rpe_context* c, const int32_t shift[3]) {
   HIP_TRY(hipSetDevice(c->device));
   const size_t nvox = (size_t)V.g.dim[0] * V.g.dim[1] * V.g.dim[2];
   const size_t bytes = nvox * 2 * sizeof(float), cbytes = nvox * 4 * sizeof(unsigned short);
+  // the archive (rpe_archive_api.hip), if it is on: the non-zero bricks that leave go into the pool before the window moves, the ones
+  // that return are written over the zeros behind it.  Everything that can refuse the shift does so before the first brick is copied
+  ArchivePlan plan;
+  if (V.arc.on) {
+    int rc;
+    if (!all_out && (rc = V.d_spare.reserve(c, bytes))) return rc;
+    if (!all_out && V.have_color && (rc = V.cd_spare.reserve(c, cbytes))) return rc;
+    if ((rc = archive_leave(c, shift, total, &plan))) return rc;
+  }
   if (all_out) {   // no voxel stays: the window is cleared where it is
     HIP_TRY(hipMemsetAsync(V.d, 0, bytes, c->stream));
     if (V.have_color) HIP_TRY(hipMemsetAsync(V.cd, 0, cbytes, c->stream));
@@ -59,6 +69,7 @@ int rpe_volume_shift(rpe_context* c, const int32_t shift[3]) {
   }
   for (int a = 0; a < 3; a++) { V.total[a] = total[a]; V.g.o[a] = o[a]; }
   V.have_mesh = false;
+  if (V.arc.on) return archive_enter(c, plan);
   return RPE_OK;
 }
 

@@ -24,6 +24,7 @@ int rpe_volume_init(rpe_context* c, const rpe_volume_desc* d) {
   HIP_TRY(hipSetDevice(c->device));
   auto& V = c->vol;
   const size_t bytes = (size_t)g.dim[0] * g.dim[1] * g.dim[2] * 2 * sizeof(float);
+  if (V.arc.on) if (int rc = archive_drop(c)) return rc;   // the archive belongs to the volume it was switched on for
   V.have = false;
   V.have_mesh = false;
   V.have_color = false;

@@ -299,6 +299,28 @@ class DepthFrontEnd {
     check(rpe_volume_shift(_ctx, shift), "rpe_volume_shift");
     if (shift[0] || shift[1] || shift[2]) _mesh_vertices = -1;
   }
+  // the volume archive (rpe_volume_archive): a pool of `capacity` bricks of 8 x 8 x 8 voxels on the device; while it is on, shiftVolume
+  // takes multiples of 8, keeps every non-zero brick that leaves and restores every archived brick the window returns over.  A larger
+  // capacity grows the pool, 0 switches the archive off and frees it
+  void archiveVolume(int64_t capacity) { check(rpe_volume_archive(_ctx, capacity), "rpe_volume_archive"); }
+  // the bricks held; capacity, if given, receives the pool's slots
+  int64_t archiveHeld(int64_t* capacity = nullptr) const {
+    int64_t held = 0;
+    check(rpe_volume_archive_info(_ctx, &held, capacity), "rpe_volume_archive_info");
+    return held;
+  }
+  // the held bricks sorted by (bz, by, bx): coords = 3 per brick (bx, by, bz), tsdf = 8 x 8 x 8 x 2 floats per brick in (z, y, x) order,
+  // colour (may be null) = 8 x 8 x 8 x 4 binary16 per brick, zeros where none was kept; returns the number of bricks
+  int64_t archiveDownload(std::vector<int64_t>& coords, std::vector<float>& tsdf, std::vector<uint16_t>* colour = nullptr) const {
+    const int64_t n = archiveHeld();
+    coords.assign((size_t)n * 3, 0);
+    tsdf.assign((size_t)n * 1024, 0.f);
+    if (colour) colour->assign((size_t)n * 2048, 0);
+    check(rpe_volume_archive_download(_ctx, coords.data(), tsdf.data(), colour ? colour->data() : nullptr), "rpe_volume_archive_download");
+    return n;
+  }
+  // forget every archived brick, keep the pool (after fuseKeyframes rebuilt the map at corrected poses)
+  void archiveClear() { check(rpe_volume_archive_clear(_ctx), "rpe_volume_archive_clear"); }
   // where the window is now: the descriptor of initVolume with its origin moved by the total shift (total, if given, receives it)
   VolumeDesc volumeGeometry(int64_t total[3] = nullptr) const {
     rpe_volume_desc v;
