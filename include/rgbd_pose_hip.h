@@ -1019,7 +1019,7 @@ int rpe_volume_mesh_box(rpe_context* ctx, double min_weight, const int32_t lo[3]
  * rpe_volume_upload, rpe_volume_integrate and the colour calls write the window only.
  * The tracking loop: follow(granule = 8) -> if non-zero: shift -> raycast -> ICP -> integrate.
  * Out of scope: shifts or dims that are not multiples of 8 with the archive on; a device-side index (no host wait); spilling the pool
- * to host memory; meshing or raycasting the archive directly; moving the archived bricks under a loop-closure correction. */
+ * to host memory; raycasting the archive directly; moving the archived bricks under a loop-closure correction. */
 /* capacity_bricks > 0: switch the archive on with a pool of that many slots, or grow the pool to it (the content stays; a capacity
  * between the number of held bricks and the current capacity changes nothing: the pool does not shrink); 0: switch it off and free
  * everything.  RPE_ERR_ARG for a capacity below the number of held bricks, negative or above 2^24; RPE_ERR_STATE (nothing changed)
@@ -1033,6 +1033,40 @@ int rpe_volume_archive_info(rpe_context* ctx, int64_t* held, int64_t* capacity);
 int rpe_volume_archive_download(rpe_context* ctx, int64_t* coords, float* tsdf, uint16_t* colour);
 /* forget every brick, keep the pool: for use after rpe_volume_fuse_keyframes has rebuilt the map at corrected poses */
 int rpe_volume_archive_clear(rpe_context* ctx);
+
+/* ---- Map mesh: the window and the archived bricks meshed in one extraction.  The MAP is a sparse grid of world voxels (world voxel =
+ * total shift + window index, as above): a voxel holds the window's bits where the window covers it, the held brick's bits where the
+ * archive holds its world brick, and {0, 0} with all-zero colour -- weight 0, unknown -- everywhere else.  The colour of a window voxel
+ * is the colour volume's (zeros without one), of a held voxel the pool's colour plane's (zeros without one).
+ * A box of world voxels lo <= w < hi (int64 per axis, multiples of 8, 8 <= hi - lo <= 2^20) defines a VIRTUAL VOLUME: dim = hi - lo,
+ * origin = origin_init + (double)lo * voxel_size in double as written, o = (float) of that (rpe_volume_shift's single rounding);
+ * voxel_size, trunc and max_weight are the init descriptor's.
+ * THE CONTRACT: rpe_volume_map_mesh gives the mesh rpe_volume_mesh gives on a fresh rpe_volume_init of the virtual volume with the
+ * map's content uploaded into it, with the same min_weight: the same cubes, known and active rules, cases and tables, the vertex rule
+ * o + (((float)i + 0.5f) + t) * s with i the index inside the box, normals from the field of the whole virtual volume (weight > 0,
+ * 0 <= i0 <= dim - 2 of the box), winding, and colours C(p) of the virtual colour volume -- the same bits.  Only the ORDER differs,
+ * and it is fixed: bricks ascend by (bz, by, bx), as rpe_volume_archive_download sorts them; inside a brick voxels go in (z, y, x)
+ * order, x fastest; vertices follow their owner voxel in that order, then axis x < y < z; triangles follow their cube (named by its
+ * corner-0 voxel) in that order, then table order.  So the map mesh is a stated permutation of the dense one; with the box equal to
+ * the window's extent it is a permutation of rpe_volume_mesh's mesh of the window.  tests/mapmesh_oracle.py states it in numpy.
+ * A brick outside the box is absent: cubes that reach over the box's faces are inactive, as at the faces of any volume.
+ * The archive does not have to be on: without it the map is the window.  Every dim and every component of the total shift must be a
+ * multiple of 8 (the archive's own precondition).  Nothing is written to the window, the archive or the geometry.
+ * The result is the last mesh: rpe_volume_mesh_download serves it and it has the same lifetime (dropped by the next extraction of
+ * either kind, rpe_volume_init and a non-zero rpe_volume_shift).  Colours are sampled DURING the extraction, when the window has a
+ * colour volume or the pool a colour plane; rpe_volume_mesh_colors returns them for a map mesh, RPE_ERR_STATE if neither existed at
+ * extraction time (for a window mesh it is unchanged).  Only the bricks of the map that lie in the box are visited, one workgroup per
+ * brick; the workspace is 3 KB per such brick, nothing scales with the box.  The host waits once, for the two totals.
+ * Out of scope: boxes that are not multiples of 8; raycasting or tracking against the archive; simplifying or welding the mesh; a
+ * device-side brick index; dense order for the map mesh. */
+/* the world-voxel bounding box of the window and every held brick, in multiples of 8; RPE_ERR_STATE without a volume or when a dim or
+ * a component of the total shift is not a multiple of 8 */
+int rpe_volume_map_bounds(rpe_context* ctx, int64_t lo[3], int64_t hi[3]);
+/* marching cubes over the map inside the box lo <= w < hi (lo = hi = NULL: the bounds); min_weight, n_vertices and n_triangles as in
+ * rpe_volume_mesh.  RPE_ERR_STATE as rpe_volume_map_bounds; RPE_ERR_ARG for a box that is unaligned, empty or larger than 2^20 voxels
+ * on an axis, a bad min_weight, or 2^31 or more vertices */
+int rpe_volume_map_mesh(rpe_context* ctx, double min_weight, const int64_t lo[3], const int64_t hi[3], int64_t* n_vertices,
+                        int64_t* n_triangles);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

@@ -60,6 +60,7 @@ SYMBOLS = [
     "rpe_volume_fuse_keyframes",
     "rpe_volume_shift", "rpe_volume_geometry", "rpe_volume_follow", "rpe_volume_mesh_box",
     "rpe_volume_archive", "rpe_volume_archive_info", "rpe_volume_archive_download", "rpe_volume_archive_clear",
+    "rpe_volume_map_bounds", "rpe_volume_map_mesh",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -291,6 +292,8 @@ def lib():
         L.rpe_volume_archive_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.rpe_volume_archive_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_volume_archive_clear.argtypes = [C.c_void_p]
+        L.rpe_volume_map_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_volume_map_mesh.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

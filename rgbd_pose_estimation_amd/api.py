@@ -433,6 +433,32 @@ class Context:
         L.check(L.lib().rpe_volume_archive_clear(self._h))
         return self
 
+    # ---- map mesh (Part 3): the window and the archived bricks meshed in one extraction
+    def volume_map_bounds(self):
+        """(lo, hi), (3,) int64 each: the world-voxel bounding box of the window and every archived brick, in multiples of 8
+        (world voxel = total shift + window index)."""
+        lo, hi = np.zeros(3, np.int64), np.zeros(3, np.int64)
+        L.check(L.lib().rpe_volume_map_bounds(self._h, _p(lo), _p(hi)))
+        return lo, hi
+
+    def volume_map_mesh(self, min_weight: float = 1.0, box=None):
+        """Marching cubes over the MAP -- the window plus the archived bricks -- inside box = (lo, hi) in world voxels (multiples of 8;
+        None: volume_map_bounds): (vertices, normals, triangles) as volume_mesh returns them, bit for bit the mesh of a dense volume
+        of the box holding the map's content, in brick order (rpe_volume_map_mesh).  volume_mesh_colors works after it."""
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        self._mesh_nv = None
+        if box is None:
+            L.check(L.lib().rpe_volume_map_mesh(self._h, float(min_weight), None, None, C.byref(nv), C.byref(nt)))
+        else:
+            lo, hi = (np.ascontiguousarray(b, np.int64).reshape(3) for b in box)
+            L.check(L.lib().rpe_volume_map_mesh(self._h, float(min_weight), _p(lo), _p(hi), C.byref(nv), C.byref(nt)))
+        self._mesh_nv = nv.value
+        V = np.empty((nv.value, 3), np.float32)
+        N = np.empty((nv.value, 3), np.float32)
+        T = np.empty((nt.value, 3), np.int32)
+        L.check(L.lib().rpe_volume_mesh_download(self._h, _p(V), _p(N), _p(T)))
+        return V, N, T
+
     # ---- colour (Part 3): a registered RGB frame fused beside the depth, sampled back at the model's and the mesh's vertices
     def frame_set_color(self, rgb, order: str = "rgb"):
         """The current frame's colour: (height, width, 3) uint8 registered to its depth (pixel (u, v) of both sees the same ray), channels
@@ -857,7 +883,8 @@ class Context:
         return self
 
     def volume_mesh_colors(self) -> np.ndarray:
-        """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh): the colour field there, as model_color samples it."""
+        """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh, volume_map_mesh): the colour field there, as model_color samples
+        it."""
         n = self._mesh_nv or 0
         out = np.empty((n, 4), np.uint8)
         L.check(L.lib().rpe_volume_mesh_colors(self._h, _p(out) if n else None))

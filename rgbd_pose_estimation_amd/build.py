@@ -9,10 +9,10 @@ descriptors and matches for relocalisation), csrc/rpe_feature_oriented.hip (the 
 against every keyframe, count and rank, gather), csrc/rpe_graph.hip (the keyframe graph: pair lists of keyframe-to-keyframe matches,
 the joint Gauss-Newton round over every edge, the store rewritten at the corrected poses), csrc/rpe_rebuild.hip (the volume rebuilt from the keyframes: the
 depth packed beside a keyframe, a list of keyframes fused in one pass over the voxels), csrc/rpe_register.hip (colour registration: a separate colour
-camera reprojected onto the depth frame through a z-buffer), csrc/rpe_shift.hip (the moving volume: the TSDF and colour volume shifted by whole voxels into a spare), csrc/rpe_archive.hip (the volume archive: which leaving bricks are non-zero, bricks gathered into a pool of slots and scattered back), csrc/rpe_hypotheses.hip (batched hypothesis generation),
+camera reprojected onto the depth frame through a z-buffer), csrc/rpe_shift.hip (the moving volume: the TSDF and colour volume shifted by whole voxels into a spare), csrc/rpe_archive.hip (the volume archive: which leaving bricks are non-zero, bricks gathered into a pool of slots and scattered back), csrc/rpe_mapmesh.hip (the map mesh: marching cubes over the listed bricks of the window and the archive, a workgroup per brick), csrc/rpe_hypotheses.hip (batched hypothesis generation),
 csrc/rpe_prosac.hip (PROSAC order: top-k select + sort); the host units behind include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp
 lists them: rpe_context.hip, rpe_receive.hip, rpe_capi.hip = the thin C-ABI shim, rpe_refine.hip, rpe_session.hip, rpe_dist.hip,
-rpe_frontend_api.hip, rpe_volume_api.hip, rpe_mesh_api.hip, rpe_color_api.hip, rpe_photo_api.hip, rpe_feature_api.hip, rpe_keyframe_api.hip, rpe_graph_api.hip, rpe_rebuild_api.hip, rpe_register_api.hip, rpe_shift_api.hip, rpe_archive_api.hip; csrc/rpe_devbuf.hpp owns their device memory, csrc/rpe_frontend_host.hpp holds what the Part 3 units share), csrc/library.cpp (reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines),
+rpe_frontend_api.hip, rpe_volume_api.hip, rpe_mesh_api.hip, rpe_color_api.hip, rpe_photo_api.hip, rpe_feature_api.hip, rpe_keyframe_api.hip, rpe_graph_api.hip, rpe_rebuild_api.hip, rpe_register_api.hip, rpe_shift_api.hip, rpe_archive_api.hip, rpe_mapmesh_api.hip; csrc/rpe_devbuf.hpp owns their device memory, csrc/rpe_frontend_host.hpp holds what the Part 3 units share), csrc/library.cpp (reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines),
 csrc/rpe_hostex.cpp (host-side all-reduce between the rank processes of one node).  The units compile in parallel (RPE_BUILD_JOBS, default 6)."""
 from __future__ import annotations
 
@@ -25,7 +25,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "librgbdpose_hip.so")
-SOURCES = ["rpe_normal_eq.hip", "rpe_icp.hip", "rpe_joint.hip", "rpe_score.hip", "rpe_nl.hip", "rpe_frontend.hip", "rpe_filter.hip", "rpe_volume.hip", "rpe_mesh.hip", "rpe_color.hip", "rpe_photo.hip", "rpe_feature.hip", "rpe_feature_oriented.hip", "rpe_keyframe.hip", "rpe_graph.hip", "rpe_rebuild.hip", "rpe_register.hip", "rpe_shift.hip", "rpe_archive.hip", "rpe_hypotheses.hip", "rpe_prosac.hip", "rpe_context.hip", "rpe_receive.hip", "rpe_capi.hip", "rpe_refine.hip", "rpe_session.hip", "rpe_dist.hip", "rpe_frontend_api.hip", "rpe_volume_api.hip", "rpe_mesh_api.hip", "rpe_color_api.hip", "rpe_photo_api.hip", "rpe_feature_api.hip", "rpe_keyframe_api.hip", "rpe_graph_api.hip", "rpe_rebuild_api.hip", "rpe_register_api.hip", "rpe_shift_api.hip", "rpe_archive_api.hip", "library.cpp", "rpe_hostex.cpp"]
+SOURCES = ["rpe_normal_eq.hip", "rpe_icp.hip", "rpe_joint.hip", "rpe_score.hip", "rpe_nl.hip", "rpe_frontend.hip", "rpe_filter.hip", "rpe_volume.hip", "rpe_mesh.hip", "rpe_color.hip", "rpe_photo.hip", "rpe_feature.hip", "rpe_feature_oriented.hip", "rpe_keyframe.hip", "rpe_graph.hip", "rpe_rebuild.hip", "rpe_register.hip", "rpe_shift.hip", "rpe_archive.hip", "rpe_mapmesh.hip", "rpe_hypotheses.hip", "rpe_prosac.hip", "rpe_context.hip", "rpe_receive.hip", "rpe_capi.hip", "rpe_refine.hip", "rpe_session.hip", "rpe_dist.hip", "rpe_frontend_api.hip", "rpe_volume_api.hip", "rpe_mesh_api.hip", "rpe_color_api.hip", "rpe_photo_api.hip", "rpe_feature_api.hip", "rpe_keyframe_api.hip", "rpe_graph_api.hip", "rpe_rebuild_api.hip", "rpe_register_api.hip", "rpe_shift_api.hip", "rpe_archive_api.hip", "rpe_mapmesh_api.hip", "library.cpp", "rpe_hostex.cpp"]
 ARCH = "gfx950"
 LINK_RT = "--rtlib=libgcc"
 

@@ -106,9 +106,8 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float
 
 // ---------------------------------------------------------------------------------------------- C3
 // C(p): F's g, i0, a and in-range rule; known iff in range and all eight corner colour weights are > 0; each channel with F's lerp
-// order on (float) of the binary16 values.  q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f).
-__device__ __forceinline__ unsigned quantise(float x) { return (unsigned)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f); }
-
+// order on (float) of the binary16 values.  q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f) (quantise: rpe_volume_field.hpp,
+// shared with the map mesh of rpe_mapmesh.hip).
 __device__ __forceinline__ float trilerp(float v000, float v100, float v010, float v110, float v001, float v101, float v011, float v111,
                                          float ax, float ay, float az) {
   const float c00 = lerp(v000, v100, ax), c10 = lerp(v010, v110, ax), c01 = lerp(v001, v101, ax), c11 = lerp(v011, v111, ax);

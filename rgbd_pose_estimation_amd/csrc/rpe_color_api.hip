@@ -86,10 +86,17 @@ int rpe_volume_mesh_colors(rpe_context* c, uint8_t* rgba) {
   auto& V = c->vol;
   if (!V.have) return fail(RPE_ERR_STATE, "no volume: call rpe_volume_init first");
   if (!V.have_mesh) return fail(RPE_ERR_STATE, "no mesh: call rpe_volume_mesh first (rpe_volume_init drops the mesh)");
-  if (!V.have_color) return fail(RPE_ERR_STATE, "no colour volume: call rpe_volume_integrate_color or rpe_volume_color_upload first");
+  if (V.mesh_is_map ? !V.map_color : !V.have_color)
+    return fail(RPE_ERR_STATE, V.mesh_is_map ? "no colour: the map had neither a colour volume nor a colour plane in the archive when rpe_volume_map_mesh ran"
+                                             : "no colour volume: call rpe_volume_integrate_color or rpe_volume_color_upload first");
   if (V.nv > 0 && !rgba) return fail(RPE_ERR_ARG, "rpe_volume_mesh_colors: bad argument");
   if (V.nv == 0) return RPE_OK;
   HIP_TRY(hipSetDevice(c->device));
+  if (V.mesh_is_map) {   // sampled during the extraction (rpe_mapmesh.hip P3)
+    HIP_TRY(hipMemcpyAsync(rgba, V.mc, (size_t)V.nv * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RPE_OK;
+  }
   int rc = V.mc.reserve(c, (size_t)V.nv * 4);
   if (rc) return rc;
   HIP_TRY(rpe::launch_color_sample(V.cd, V.g, V.mv, V.nv, V.mc, c->stream));

@@ -412,6 +412,34 @@ hipError_t launch_brick_occupancy(const float* vol, const unsigned short* cvol, 
 hipError_t launch_brick_copy(bool to_pool, float* vol, unsigned short* cvol, unsigned int* pool, unsigned int* cpool, const int dim[3],
                              const int* pairs, int n, int capacity, hipStream_t s);
 void preload_archive();
+// ---- the map mesh (rpe_mapmesh.hip): marching cubes over the LISTED bricks of the map -- the window's and the archive's that lie in a
+// box of world voxels -- one workgroup per brick.  The list is one upload of kMapListBytes per brick: key (ascending: the brick's
+// coordinates in the box, bz << 34 | by << 17 | bx), src (>= 0: the window brick bx + nb0 * (by + nb1 * bz); < 0: ~slot of the pool)
+// and nbr (27 list positions, entry (dz + 1) * 9 + (dy + 1) * 3 + dx + 1, -1 = absent).
+constexpr int kMapKeyBits = 17;
+constexpr size_t kMapListBytes = 8 + 4 + 27 * 4;
+struct MapMeshView {
+  const unsigned int *vol, *cvol, *pool, *cpool;   // the window's two volumes and the pool's two planes as words; null = all zeros
+  int wdim0, wdim1, wnb[3], capacity;              // the window's row and plane lengths, its bricks per axis, the pool's slots
+  int n;                                           // listed bricks
+  const unsigned long long* key; const int* src; const int* nbr;
+};
+// per listed brick: 512 case bytes, 512 used-edge bytes, 512 first ids, the two counts and their offsets; totals behind
+struct MapMeshWorkspace {
+  unsigned char *cases = nullptr, *used = nullptr;
+  int* first = nullptr;
+  unsigned *brick_v = nullptr, *brick_t = nullptr;
+  long long *off_v = nullptr, *off_t = nullptr, *totals = nullptr;
+};
+size_t map_mesh_workspace_bytes(int64_t bricks);
+MapMeshWorkspace map_mesh_workspace(void* ws, int64_t bricks);
+// P1-P2: the counts per listed brick (min weight wmin > 0), their scan, the totals
+hipError_t launch_map_mesh_count(const MapMeshView& M, float wmin, const MapMeshWorkspace& W, hipStream_t s);
+// P3-P4 after launch_map_mesh_count: G = the geometry of the box (dim = its voxels, o = its fp32 origin); colours (may be null: not
+// sampled) = one RGBA8 per vertex
+hipError_t launch_map_mesh_emit(const MapMeshView& M, const VolumeGeometry& G, const MapMeshWorkspace& W, float* vertices, float* normals,
+                                int* triangles, unsigned int* colours, hipStream_t s);
+void preload_mapmesh();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

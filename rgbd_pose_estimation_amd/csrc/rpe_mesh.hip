@@ -16,6 +16,7 @@
 // tests/mesh_oracle.py is their numpy statement.  Workspace: 6 bytes per voxel (case, used bits, first id) plus 24 per chunk.
 #include "rpe_volume_field.hpp"
 #include "rpe_mc_tables.h"
+#include "rpe_scan.hpp"
 
 namespace rpe {
 
@@ -27,29 +28,7 @@ constexpr int kScanBlock = 1024;
 
 __device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
 
-// exclusive scan of x over the workgroup (NT threads): wave prefix by shuffles, the wave totals through LDS; `total` = the sum
-template <int NT, typename T>
-__device__ __forceinline__ T block_exclusive_scan(T x, T* lds, T& total) {
-  const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
-  T inc = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += y;
-  }
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    T run = 0;
-    for (int w = 0; w < NT / 64; w++) { const T t = lds[w]; lds[w] = run; run += t; }
-    lds[NT / 64] = run;
-  }
-  __syncthreads();
-  const T r = lds[wave] + inc - x;
-  total = lds[NT / 64];
-  __syncthreads();   // lds is reused by the next call
-  return r;
-}
+// block_exclusive_scan<NT>(x, lds, total): rpe_scan.hpp, shared with rpe_mapmesh.hip
 
 // ---------------------------------------------------------------------------------------------- M1
 // cube (i, j, k), 0 <= i <= d0 - 2 etc.: corner n = di + 2 dj + 4 dk is voxel (i + di, j + dj, k + dk); known iff weight >= wmin and

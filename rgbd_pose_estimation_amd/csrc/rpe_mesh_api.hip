@@ -11,7 +11,7 @@ namespace {
 int mesh_of_box(rpe_context* c, const char* who, double min_weight, const int32_t* lo, const int32_t* hi, bool boxed, int64_t* n_vertices,
                 int64_t* n_triangles) {
   session_end(c);
-  if (c) c->vol.have_mesh = false;   // the last mesh lives until this call, whatever it returns
+  if (c) c->vol.have_mesh = c->vol.mesh_is_map = false;   // the last mesh lives until this call, whatever it returns
   if (!c || !n_vertices || !n_triangles || (boxed && (!lo || !hi))) return fail(RPE_ERR_ARG, "%s: bad argument", who);
   auto& V = c->vol;
   if (!V.have) return fail(RPE_ERR_STATE, "no volume: call rpe_volume_init first");

@@ -65,6 +65,9 @@ __device__ __forceinline__ void blend(unsigned& rg, unsigned& bw, unsigned o, fl
 // weights are > 0; trilinear with lerp(x, y, t) = x + (y - x) * t along x for (j, k) = (0,0) (1,0) (0,1) (1,1), then y, then z.
 __device__ __forceinline__ float lerp(float x, float y, float t) { return x + (y - x) * t; }
 
+// the colour field's RGBA8 byte (rpe_color.hip C3, rpe_mapmesh.hip P3): q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f)
+__device__ __forceinline__ unsigned quantise(float x) { return (unsigned)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f); }
+
 __device__ __forceinline__ bool field(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz, float& F) {
   const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
   const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);

@@ -321,6 +321,23 @@ class DepthFrontEnd {
   }
   // forget every archived brick, keep the pool (after fuseKeyframes rebuilt the map at corrected poses)
   void archiveClear() { check(rpe_volume_archive_clear(_ctx), "rpe_volume_archive_clear"); }
+  // the world-voxel bounding box of the window and every archived brick, in multiples of 8 (rpe_volume_map_bounds)
+  void mapBounds(int64_t lo[3], int64_t hi[3]) const { check(rpe_volume_map_bounds(_ctx, lo, hi), "rpe_volume_map_bounds"); }
+  // marching cubes over the map -- the window plus the archived bricks -- inside the box lo <= w < hi of world voxels (multiples of 8;
+  // both null: the bounds), brought to the host: bit for bit the mesh of a dense volume of the box, in brick order
+  // (rpe_volume_map_mesh).  meshColors() works after it
+  Mesh meshMap(double min_weight = 1, const int64_t* lo = nullptr, const int64_t* hi = nullptr) const {
+    int64_t nv = 0, nt = 0;
+    _mesh_vertices = -1;
+    check(rpe_volume_map_mesh(_ctx, min_weight, lo, hi, &nv, &nt), "rpe_volume_map_mesh");
+    _mesh_vertices = nv;
+    Mesh M;
+    M.vertices.resize(3, (int)nv);
+    M.normals.resize(3, (int)nv);
+    M.triangles.resize((size_t)nt * 3);
+    check(rpe_volume_mesh_download(_ctx, M.vertices.data(), M.normals.data(), M.triangles.data()), "rpe_volume_mesh_download");
+    return M;
+  }
   // where the window is now: the descriptor of initVolume with its origin moved by the total shift (total, if given, receives it)
   VolumeDesc volumeGeometry(int64_t total[3] = nullptr) const {
     rpe_volume_desc v;
