@@ -53,6 +53,7 @@ SYMBOLS = [
     "rpe_keyframe_add", "rpe_keyframe_add_host", "rpe_keyframe_info", "rpe_keyframe_download", "rpe_keyframes_count", "rpe_keyframes_clear",
     "rpe_keyframes_query", "rpe_keyframe_match", "rpe_relocalize_keyframes",
     "rpe_features_set_descriptor", "rpe_features_get_descriptor", "rpe_features_angles", "rpe_keyframes_descriptor",
+    "rpe_features_set_levels", "rpe_features_get_levels", "rpe_features_scale",
     "rpe_frame_set_filter", "rpe_frame_get_filter",
     "rpe_keyframes_link", "rpe_graph_add_edge_host", "rpe_graph_info", "rpe_graph_edges", "rpe_graph_edge_download", "rpe_graph_residuals",
     "rpe_graph_normal_eq", "rpe_keyframes_optimize", "rpe_graph_solve",
@@ -253,6 +254,9 @@ def lib():
         L.rpe_features_set_descriptor.argtypes = [C.c_void_p, C.c_int]
         L.rpe_features_get_descriptor.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_features_angles.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rpe_features_set_levels.argtypes = [C.c_void_p, C.c_int]
+        L.rpe_features_get_levels.argtypes = [C.c_void_p, C.c_void_p]
+        L.rpe_features_scale.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rpe_keyframes_descriptor.argtypes = [C.c_void_p, C.c_void_p]
         L.rpe_matches_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_relocalize.argtypes = [C.c_void_p, C.POINTER(RpeFeatureOptions), C.POINTER(RpeMatchOptions), C.c_int, C.c_double, C.c_double,

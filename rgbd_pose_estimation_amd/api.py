@@ -623,7 +623,8 @@ class Context:
         return n.value
 
     def features(self, which: int = L.FEAT_FRAME):
-        """(xy (k, 2) int32, score (k,) int32, desc (k, 8) uint32) of the side's last detection, in pixel order."""
+        """(xy (k, 2) int32, score (k,) int32, desc (k, 8) uint32) of the side's last detection, in pixel order (with scale levels: in
+        (level, level pixel) order, xy the level-0 pixel a keypoint stands at; features_scale gives the rest)."""
         cap = L.MAX_KEYPOINTS
         xy, sc, de = np.zeros((cap, 2), np.int32), np.zeros(cap, np.int32), np.zeros((cap, 8), np.uint32)
         L.check(L.lib().rpe_features_download(self._h, int(which), _p(xy), _p(sc), _p(de)))
@@ -646,6 +647,25 @@ class Context:
         bins = np.full(L.MAX_KEYPOINTS, -1, np.int32)
         L.check(L.lib().rpe_features_angles(self._h, int(which), _p(bins)))
         return bins[:int(np.count_nonzero(bins >= 0))].copy()
+
+    def features_set_levels(self, levels: int):
+        """The number of scale levels (1 .. 4; scale 1, 2/3, 1/2, 1/3) of every later detection: with more than one a frame taken
+        closer to the scene than its keyframe still matches it.  1 is the default; a change drops both sides' features and the match
+        list."""
+        L.check(L.lib().rpe_features_set_levels(self._h, int(levels)))
+
+    def features_levels(self) -> int:
+        n = C.c_int(-1)
+        L.check(L.lib().rpe_features_get_levels(self._h, C.byref(n)))
+        return n.value
+
+    def features_scale(self, which: int = L.FEAT_FRAME):
+        """(level (k,) int32, lxy (k, 2) int32): the level and the level pixel of the side's keypoints (features()' xy is the level-0
+        pixel a keypoint stands at).  With one level: zeros, and lxy = xy."""
+        level, lxy = np.full(L.MAX_KEYPOINTS, -1, np.int32), np.zeros((L.MAX_KEYPOINTS, 2), np.int32)
+        L.check(L.lib().rpe_features_scale(self._h, int(which), _p(level), _p(lxy)))
+        k = int(np.count_nonzero(level >= 0))
+        return level[:k].copy(), lxy[:k].copy()
 
     def features_match(self, max_dist: int = 64, ratio=(8, 10), cross_check: bool = False) -> int:
         """Match the frame's keypoints against the model's; XW XC BV NW NC of this context become the matches.  Returns their number."""

@@ -5,7 +5,7 @@ csrc/rpe_normal_eq.hip (K1-K3 Gauss-Newton normal equations + the resident form)
 csrc/rpe_joint.hip (joint normal equations), csrc/rpe_score.hip (K4 scoring, K4b masks), csrc/rpe_nl.hip (K1' moments, K5, publish
 kernels), csrc/rpe_frontend.hip (depth-frame front end), csrc/rpe_filter.hip (the bilateral depth filter in front of it), csrc/rpe_volume.hip (TSDF volume: integrate, raycast), csrc/rpe_mesh.hip (marching cubes over the volume), csrc/rpe_color.hip (colour of the volume: frame
 colour, colour integrate, colour sampling), csrc/rpe_photo.hip (photometric term beside ICP: intensity maps, the RGB-D round), csrc/rpe_feature.hip (keypoints,
-descriptors and matches for relocalisation), csrc/rpe_feature_oriented.hip (the oriented descriptor: moments, angle bin, steered tests), csrc/rpe_keyframe.hip (the keyframe store: snapshot, the batched match of a frame
+descriptors and matches for relocalisation), csrc/rpe_feature_oriented.hip (the oriented descriptor: moments, angle bin, steered tests), csrc/rpe_feature_scale.hip (the scale levels: the detector and both descriptors over a ladder of resampled images in one index space), csrc/rpe_keyframe.hip (the keyframe store: snapshot, the batched match of a frame
 against every keyframe, count and rank, gather), csrc/rpe_graph.hip (the keyframe graph: pair lists of keyframe-to-keyframe matches,
 the joint Gauss-Newton round over every edge, the store rewritten at the corrected poses), csrc/rpe_rebuild.hip (the volume rebuilt from the keyframes: the
 depth packed beside a keyframe, a list of keyframes fused in one pass over the voxels), csrc/rpe_register.hip (colour registration: a separate colour
@@ -25,7 +25,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "librgbdpose_hip.so")
-SOURCES = ["rpe_normal_eq.hip", "rpe_icp.hip", "rpe_joint.hip", "rpe_score.hip", "rpe_nl.hip", "rpe_frontend.hip", "rpe_filter.hip", "rpe_volume.hip", "rpe_mesh.hip", "rpe_color.hip", "rpe_photo.hip", "rpe_feature.hip", "rpe_feature_oriented.hip", "rpe_keyframe.hip", "rpe_graph.hip", "rpe_rebuild.hip", "rpe_register.hip", "rpe_shift.hip", "rpe_archive.hip", "rpe_mapmesh.hip", "rpe_hypotheses.hip", "rpe_prosac.hip", "rpe_context.hip", "rpe_receive.hip", "rpe_capi.hip", "rpe_refine.hip", "rpe_session.hip", "rpe_dist.hip", "rpe_frontend_api.hip", "rpe_volume_api.hip", "rpe_mesh_api.hip", "rpe_color_api.hip", "rpe_photo_api.hip", "rpe_feature_api.hip", "rpe_keyframe_api.hip", "rpe_graph_api.hip", "rpe_rebuild_api.hip", "rpe_register_api.hip", "rpe_shift_api.hip", "rpe_archive_api.hip", "rpe_mapmesh_api.hip", "library.cpp", "rpe_hostex.cpp"]
+SOURCES = ["rpe_normal_eq.hip", "rpe_icp.hip", "rpe_joint.hip", "rpe_score.hip", "rpe_nl.hip", "rpe_frontend.hip", "rpe_filter.hip", "rpe_volume.hip", "rpe_mesh.hip", "rpe_color.hip", "rpe_photo.hip", "rpe_feature.hip", "rpe_feature_oriented.hip", "rpe_feature_scale.hip", "rpe_keyframe.hip", "rpe_graph.hip", "rpe_rebuild.hip", "rpe_register.hip", "rpe_shift.hip", "rpe_archive.hip", "rpe_mapmesh.hip", "rpe_hypotheses.hip", "rpe_prosac.hip", "rpe_context.hip", "rpe_receive.hip", "rpe_capi.hip", "rpe_refine.hip", "rpe_session.hip", "rpe_dist.hip", "rpe_frontend_api.hip", "rpe_volume_api.hip", "rpe_mesh_api.hip", "rpe_color_api.hip", "rpe_photo_api.hip", "rpe_feature_api.hip", "rpe_keyframe_api.hip", "rpe_graph_api.hip", "rpe_rebuild_api.hip", "rpe_register_api.hip", "rpe_shift_api.hip", "rpe_archive_api.hip", "rpe_mapmesh_api.hip", "library.cpp", "rpe_hostex.cpp"]
 ARCH = "gfx950"
 LINK_RT = "--rtlib=libgcc"
 

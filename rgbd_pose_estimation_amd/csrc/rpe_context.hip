@@ -156,7 +156,7 @@ int rpe_create(rpe_context** out, int device, void* stream) {
     if (device < 64 && !loaded[device]) {
       rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
       rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
-      rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_feature_oriented(); rpe::preload_keyframe();
+      rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_feature_oriented(); rpe::preload_feature_scale(); rpe::preload_keyframe();
       rpe::preload_filter(); rpe::preload_graph(); rpe::preload_rebuild(); rpe::preload_register(); rpe::preload_shift(); rpe::preload_archive(); rpe::preload_mapmesh();
       loaded[device] = true;
     }

@@ -318,6 +318,16 @@ hipError_t launch_feature_detect(const unsigned int* rgba, const float* vmap, co
   return hipGetLastError();
 }
 
+hipError_t launch_feature_scan(const FeatureWork& W, int nchunks, int max_keypoints, hipStream_t s) {
+  hipLaunchKernelGGL(feat_scan_kernel, dim3(1), dim3(kWide), 0, s, W.chunk, nchunks, W.hist, max_keypoints, W.ctl);
+  return hipGetLastError();
+}
+
+hipError_t launch_feature_select(const FeatureWork& W, int max_keypoints, int* kp_idx, int* kp_score, hipStream_t s) {
+  hipLaunchKernelGGL(feat_select_kernel, dim3(1), dim3(kWide), 0, s, W.score, W.spix, max_keypoints, W.ctl, kp_idx, kp_score);
+  return hipGetLastError();
+}
+
 hipError_t launch_feature_best(const unsigned int* desc_a, int na, const unsigned int* desc_b, int nb, int* d1, int* idx, int* d2, hipStream_t s) {
   if (na <= 0) return hipSuccess;
   hipLaunchKernelGGL(feat_best_kernel, dim3((na + 256 / kGroup - 1) / (256 / kGroup)), dim3(256), 0, s, desc_a, na, desc_b, nb, d1, idx, d2);

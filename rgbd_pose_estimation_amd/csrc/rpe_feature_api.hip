@@ -37,7 +37,8 @@ int read_ints(rpe_context* c, const int* d_words, int n, int* out) {
 }
 int detect_if_stale(rpe_context* c, int which, const rpe_feature_options& fo) {
   const auto& S = c->fe.feat[which];
-  if (S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints && S.kind == c->fe.desc_kind) return RPE_OK;
+  if (S.have && S.threshold == fo.threshold && S.max_keypoints == fo.max_keypoints && S.kind == c->fe.desc_kind && S.levels == c->fe.levels)
+    return RPE_OK;
   return rpe_features_detect(c, which, &fo, nullptr);
 }
 int run_on_slots(rpe_context* c, int m, int method, double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence,
@@ -68,25 +69,34 @@ int run_on_slots(rpe_context* c, int m, int method, double thre_3d, double thre_
 }  // namespace rpeh
 
 namespace {
-// the detector's workspace for a w x h image, and one side's keypoint arrays (RPE_MAX_KEYPOINTS slots, allocated on first use)
-int ensure_work(rpe_context* c, int w, int h) {
+// the detector's workspace for the levels L of an image (one level: the image itself), and one side's keypoint arrays
+// (RPE_MAX_KEYPOINTS slots, allocated on first use)
+int ensure_work(rpe_context* c, const rpe::FeatLevels& L) {
   auto& W = c->fe.fwork;
-  const size_t n = (size_t)w * h;
+  const size_t n = (size_t)L.base[rpe::kFeatMaxLevels];
+  // no two 8-neighbours both survive the suppression, and nothing is suppressed across levels: at most ceil(w / 2) * ceil(h / 2)
+  // survivors per level
+  size_t survivors = 0;
+  for (int l = 0; l < L.n; l++) survivors += ((size_t)L.w[l] * L.h[l] + L.w[l] + L.h[l] + 1) / 4 + 1;
   int rc;
   if ((rc = W.score.reserve(c, n * sizeof(int))) || (rc = W.box.reserve(c, n * sizeof(unsigned short))) ||
-      (rc = W.chunk.reserve(c, (n / 256 + 2) * sizeof(int))) ||
-      // no two 8-neighbours both survive the suppression: at most ceil(w / 2) * ceil(h / 2) survivors
-      (rc = W.spix.reserve(c, ((n + w + h + 1) / 4 + 1) * sizeof(int)))) return rc;
+      (rc = W.chunk.reserve(c, (n / 256 + 2) * sizeof(int))) || (rc = W.spix.reserve(c, survivors * sizeof(int)))) return rc;
+  if (L.n > 1 && ((rc = W.lum.reserve(c, n * sizeof(unsigned short))) || (rc = W.kidx.once(c, rpe::kMaxKeypoints * sizeof(int))))) return rc;
   if ((rc = W.hist.once(c, rpe::kFeatScoreBins * sizeof(unsigned int)))) return rc;
   return W.ctl.once(c, rpe::kFeatCtlWords * sizeof(int));
 }
-int ensure_side(rpe_context* c, int which) {
+int ensure_side(rpe_context* c, int which, int levels) {
   auto& S = c->fe.feat[which];
   const size_t k = rpe::kMaxKeypoints;
   int rc;
   if ((rc = S.pix.once(c, k * sizeof(int))) || (rc = S.score.once(c, k * sizeof(int))) || (rc = S.xy.once(c, 2 * k * sizeof(int))) ||
       (rc = S.desc.once(c, 8 * k * sizeof(unsigned int)))) return rc;
+  if (levels > 1 && ((rc = S.level.once(c, k * sizeof(int))) || (rc = S.lxy.once(c, 2 * k * sizeof(int))))) return rc;
   return S.bin.once(c, k * sizeof(int));
+}
+int no_features(int which) {
+  return fail(RPE_ERR_STATE, "no features of the %s: call rpe_features_detect (a new depth, colour or model drops them)",
+              which == RPE_FEAT_MODEL ? "model" : "frame");
 }
 int side_ready(rpe_context* c, int which) {
   auto& F = c->fe;
@@ -121,13 +131,19 @@ int rpe_features_detect(rpe_context* c, int which, const rpe_feature_options* op
   auto& S = F.feat[which];
   const bool model = which == RPE_FEAT_MODEL;
   const rpe::Camera& k = model ? F.mcam : F.cam;
-  if ((rc = ensure_work(c, k.width, k.height)) || (rc = ensure_side(c, which))) return rc;
+  const rpe::FeatLevels lv = rpe::feature_levels(k.width, k.height, F.levels);
+  if ((rc = ensure_work(c, lv)) || (rc = ensure_side(c, which, F.levels))) return rc;
   S.have = false;
-  HIP_TRY(rpe::launch_feature_detect(model ? F.mcolor : F.fcolor, model ? F.mmap[0] : F.fmap[0], model ? F.mmap[1] : F.fmap[1], k.width,
-                                     k.height, o.threshold, o.max_keypoints, F.fwork.view(), F.desc_kind, S.pix, S.score, S.xy, S.desc, S.bin,
-                                     c->stream));
+  const unsigned int* rgba = model ? F.mcolor : F.fcolor;
+  const float *vmap = model ? F.mmap[0] : F.fmap[0], *nmap = model ? F.mmap[1] : F.fmap[1];
+  if (F.levels == 1)      // one level is the stage as it was: the same six kernels on the image itself
+    HIP_TRY(rpe::launch_feature_detect(rgba, vmap, nmap, k.width, k.height, o.threshold, o.max_keypoints, F.fwork.view(), F.desc_kind, S.pix,
+                                       S.score, S.xy, S.desc, S.bin, c->stream));
+  else
+    HIP_TRY(rpe::launch_feature_detect_levels(rgba, vmap, nmap, lv, o.threshold, o.max_keypoints, F.fwork.view(), F.desc_kind, S.pix, S.score,
+                                              S.xy, S.desc, S.bin, S.level, S.lxy, c->stream));
   if ((rc = read_ints(c, F.fwork.ctl + rpe::kFeatCtlCount, 1, &S.count))) return rc;
-  S.have = true; S.gen++; S.threshold = o.threshold; S.max_keypoints = o.max_keypoints; S.kind = F.desc_kind;
+  S.have = true; S.gen++; S.threshold = o.threshold; S.max_keypoints = o.max_keypoints; S.kind = F.desc_kind; S.levels = F.levels;
   if (count) *count = S.count;
   return RPE_OK;
 }
@@ -136,8 +152,7 @@ int rpe_features_download(rpe_context* c, int which, int32_t* xy, int32_t* score
   session_end(c);
   if (!c || (which != RPE_FEAT_FRAME && which != RPE_FEAT_MODEL)) return fail(RPE_ERR_ARG, "rpe_features_download: bad argument");
   auto& S = c->fe.feat[which];
-  if (!S.have) return fail(RPE_ERR_STATE, "no features of the %s: call rpe_features_detect (a new depth, colour or model drops them)",
-                           which == RPE_FEAT_MODEL ? "model" : "frame");
+  if (!S.have) return no_features(which);
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = (size_t)S.count;
   int rc;
@@ -164,12 +179,45 @@ int rpe_features_get_descriptor(rpe_context* c, int* kind) {
   return RPE_OK;
 }
 
+int rpe_features_set_levels(rpe_context* c, int levels) {
+  session_end(c);
+  if (!c || levels < 1 || levels > rpe::kFeatMaxLevels)
+    return fail(RPE_ERR_ARG, "rpe_features_set_levels: levels 1 .. %d (got %d)", rpe::kFeatMaxLevels, levels);
+  auto& F = c->fe;
+  if (levels == F.levels) return RPE_OK;
+  F.levels = levels;                     // ids and yields differ between ladders: both sides and the match list go
+  F.feat[0].have = false; F.feat[1].have = false; F.matches = -1; F.match_kf = -1;
+  return RPE_OK;
+}
+
+int rpe_features_get_levels(rpe_context* c, int* levels) {
+  if (!c || !levels) return fail(RPE_ERR_ARG, "rpe_features_get_levels: bad argument");
+  *levels = c->fe.levels;
+  return RPE_OK;
+}
+
+int rpe_features_scale(rpe_context* c, int which, int32_t* level, int32_t* lxy) {
+  session_end(c);
+  if (!c || (which != RPE_FEAT_FRAME && which != RPE_FEAT_MODEL)) return fail(RPE_ERR_ARG, "rpe_features_scale: bad argument");
+  auto& S = c->fe.feat[which];
+  if (!S.have) return no_features(which);
+  const size_t n = (size_t)S.count;
+  if (!n) return RPE_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if (S.levels == 1) {                   // the image itself: level 0, and the level pixel is the keypoint's pixel
+    if (level) std::memset(level, 0, n * sizeof(int32_t));
+    return lxy ? copy_to_host(c, lxy, S.xy, n * 2 * sizeof(int)) : RPE_OK;
+  }
+  if (level && (rc = copy_to_host(c, level, S.level, n * sizeof(int)))) return rc;
+  return lxy ? copy_to_host(c, lxy, S.lxy, n * 2 * sizeof(int)) : RPE_OK;
+}
+
 int rpe_features_angles(rpe_context* c, int which, int32_t* bins) {
   session_end(c);
   if (!c || (which != RPE_FEAT_FRAME && which != RPE_FEAT_MODEL)) return fail(RPE_ERR_ARG, "rpe_features_angles: bad argument");
   auto& S = c->fe.feat[which];
-  if (!S.have) return fail(RPE_ERR_STATE, "no features of the %s: call rpe_features_detect (a new depth, colour or model drops them)",
-                           which == RPE_FEAT_MODEL ? "model" : "frame");
+  if (!S.have) return no_features(which);
   const size_t n = (size_t)S.count;
   if (!n || !bins) return RPE_OK;
   if (S.kind != RPE_DESC_ORIENTED) { std::memset(bins, 0, n * sizeof(int32_t)); return RPE_OK; }   // an upright patch is not turned

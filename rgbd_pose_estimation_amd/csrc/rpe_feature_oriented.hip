@@ -13,33 +13,11 @@
 // to what they were.
 #include "rpe_assoc.h"
 #include "rpe_brief_table.h"
+#include "rpe_feature_disc.h"   // the angle table and the disc, shared with the scale levels' D6os
 
 namespace rpe {
 
 namespace {
-
-constexpr int kAngleBins = 32, kDiscRadius = 13, kDiscPixels = 529;
-
-// round(1024 cos(2 pi k / 32)) as the header states them; the sine is the cosine a quarter turn back: S[k] = C[(k + 24) % 32]
-__constant__ int kAngleCos[kAngleBins] = {1024, 1004, 946, 851, 724, 569, 392, 200, 0, -200, -392, -569, -724, -851, -946, -1004,
-                                          -1024, -1004, -946, -851, -724, -569, -392, -200, 0, 200, 392, 569, 724, 851, 946, 1004};
-
-// the offsets of the disc dx^2 + dy^2 <= 169 in row order, listed by the compiler
-struct Disc {
-  signed char d[kDiscPixels][2] = {};
-  int count = 0;
-  constexpr Disc() {
-    for (int dy = -kDiscRadius; dy <= kDiscRadius; dy++)
-      for (int dx = -kDiscRadius; dx <= kDiscRadius; dx++)
-        if (dx * dx + dy * dy <= kDiscRadius * kDiscRadius) {
-          if (count < kDiscPixels) { d[count][0] = (signed char)dx; d[count][1] = (signed char)dy; }
-          count++;
-        }
-  }
-};
-constexpr Disc kDiscHost{};
-static_assert(kDiscHost.count == kDiscPixels, "the disc of radius 13 has 529 pixels");
-__device__ const Disc kDisc = kDiscHost;
 
 __global__ __launch_bounds__(256) void feat_describe_oriented_kernel(const unsigned int* __restrict__ rgba,
                                                                     const unsigned short* __restrict__ box, int w, int h,

@@ -193,13 +193,18 @@ struct rpe_context {
     // the side's depth, model or colour resets it); gen counts the side's detections so that a match list knows what it was made of
     // kind / bin: the descriptor kind the detection was made with and, for RPE_DESC_ORIENTED, the keypoints' angle bins.  desc_kind is
     // the context's kind (rpe_features_set_descriptor): what the next detection on either side uses
-    struct Features { rpeh::DevBuf<int> pix, score, xy, bin; rpeh::DevBuf<unsigned int> desc; int count = 0; bool have = false;
-                      unsigned long long gen = 0; int threshold = 0, max_keypoints = 0; int kind = 0; } feat[2];
+    // levels / level / lxy: the number of scale levels the detection was made with (rpe_features_set_levels) and, with more than one,
+    // the keypoints' level and level pixel (with one, pix and xy ARE the level pixel: level and lxy are not written).  `levels` below
+    // is the context's number, as desc_kind is its kind
+    struct Features { rpeh::DevBuf<int> pix, score, xy, bin, level, lxy; rpeh::DevBuf<unsigned int> desc; int count = 0; bool have = false;
+                      unsigned long long gen = 0; int threshold = 0, max_keypoints = 0; int kind = 0; int levels = 1; } feat[2];
     int desc_kind = 0;
+    int levels = 1;
     // the detector's workspace, sized for the largest image seen (shared by both sides), and the match lists: best / second best per
     // keypoint and the accepted matches (RPE_MAX_KEYPOINTS slots).  view(): the plain pointer struct a launch takes by value
-    struct Work { rpeh::DevBuf<int> score, chunk, ctl, spix; rpeh::DevBuf<unsigned short> box; rpeh::DevBuf<unsigned int> hist;
-                  rpe::FeatureWork view() const { return {score, box, chunk, hist, ctl, spix}; } } fwork;
+    // (lum, kidx: the levels' luma bytes and the kept survivors' indices, allocated by the first detection with more than one level)
+    struct Work { rpeh::DevBuf<int> score, chunk, ctl, spix, kidx; rpeh::DevBuf<unsigned short> box, lum; rpeh::DevBuf<unsigned int> hist;
+                  rpe::FeatureWork view() const { return {score, box, chunk, hist, ctl, spix, lum, kidx}; } } fwork;
     struct Lists { rpeh::DevBuf<int> d1, idx, d2, back, mf, mm, md1, md2; rpeh::DevBuf<float> mw;
                    rpe::MatchLists view() const { return {d1, idx, d2, back, mf, mm, md1, md2, mw}; } } mlist;
     int matches = -1;                    // accepted matches of the last rpe_features_match (-1: none) ...

@@ -312,7 +312,8 @@ constexpr int kFeatScoreBins = 4096;    // a score is at most 16 * 255
 enum { kFeatCtlSurvivors = 0, kFeatCtlCut = 1, kFeatCtlTies = 2, kFeatCtlCount = 3, kFeatCtlMatches = 4, kFeatCtlWords = 8 };
 // the detector's workspace for an image of n pixels: score (n ints), box sums (n u16), per-chunk survivor counts -> offsets
 // (n / 256 + 2 ints), the score histogram, the control words above and the survivors' pixel indices ((n + w + h + 1) / 4 + 1 ints)
-struct FeatureWork { int* score; unsigned short* box; int* chunk; unsigned int* hist; int* ctl; int* spix; };
+// (scale levels only: lum = Y | K << 8 of every level's pixels, kidx = the kept survivors' indices in the levels' index space)
+struct FeatureWork { int* score; unsigned short* box; int* chunk; unsigned int* hist; int* ctl; int* spix; unsigned short* lum; int* kidx; };
 // F1: detect + describe one view.  rgba / vmap / nmap: the view's RGBA8 colour, vertex and normal maps (w x h).  Leaves the number of
 // keypoints in W.ctl[kFeatCtlCount] and pixel index, score, xy and descriptor of keypoint k at slot k, in pixel order.  Six kernels, no
 // host wait.  kind = kDescUpright: D6, kp_bin untouched; kDescOriented: the sixth kernel is launch_feature_describe_oriented, which
@@ -326,6 +327,35 @@ hipError_t launch_feature_describe_oriented(const unsigned int* rgba, const unsi
                                             const int* ctl, const int* kp_pix, int* kp_xy, unsigned int* kp_desc, int* kp_bin,
                                             hipStream_t s);
 void preload_feature_oriented();
+// D3 / D5 on their own (rpe_feature.hip), for a detection whose other stages are not launch_feature_detect's: both work on a linear
+// index -- chunk counts of nchunks chunks and W.hist in, W.ctl and the kept survivors' indices (in W.spix's order) and scores out
+hipError_t launch_feature_scan(const FeatureWork& W, int nchunks, int max_keypoints, hipStream_t s);
+hipError_t launch_feature_select(const FeatureWork& W, int max_keypoints, int* kp_idx, int* kp_score, hipStream_t s);
+// ---- scale levels (rpe_feature_scale.hip): the detector on a fixed ladder of up to four levels of scale p / q = 1, 2/3, 1/2, 1/3, the
+// levels' pixels laid end to end in ONE index space: index = base[l] + v * w[l] + u.  tile[l] = the first 32 x 8 tile of level l in
+// D1s' grid, tiles_x[l] its tiles per row; entries from n on are empty levels (w = h = 0, base = base[4] = all pixels, tile = tile[4])
+constexpr int kFeatMaxLevels = 4;
+struct FeatLevels { int n; int w[kFeatMaxLevels], h[kFeatMaxLevels], base[kFeatMaxLevels + 1], tile[kFeatMaxLevels + 1], tiles_x[kFeatMaxLevels]; };
+inline FeatLevels feature_levels(int w, int h, int n) {
+  constexpr int P[kFeatMaxLevels] = {1, 2, 1, 1}, Q[kFeatMaxLevels] = {1, 3, 2, 3};
+  FeatLevels L{};
+  L.n = n;
+  for (int l = 0; l < kFeatMaxLevels; l++) {
+    L.w[l] = l < n ? w * P[l] / Q[l] : 0;
+    L.h[l] = l < n ? h * P[l] / Q[l] : 0;
+    L.tiles_x[l] = (L.w[l] + 31) / 32;
+    L.base[l + 1] = L.base[l] + L.w[l] * L.h[l];
+    L.tile[l + 1] = L.tile[l] + L.tiles_x[l] * ((L.h[l] + 7) / 8);
+  }
+  return L;
+}
+// F1 with L.n > 1 levels: eight launches (the histogram's memset, D0 resample, D1s, D2s, D3, D4s, D5, D6s or D6os), every stage once
+// over all levels, no host wait.  Leaves what launch_feature_detect leaves -- the keypoints in (level, level pixel) order, kp_pix /
+// kp_xy = the LEVEL-0 pixel a keypoint stands at -- and per keypoint its level and level pixel (kp_level, kp_lxy)
+hipError_t launch_feature_detect_levels(const unsigned int* rgba, const float* vmap, const float* nmap, const FeatLevels& L, int threshold,
+                                        int max_keypoints, const FeatureWork& W, int kind, int* kp_pix, int* kp_score, int* kp_xy,
+                                        unsigned int* kp_desc, int* kp_bin, int* kp_level, int* kp_lxy, hipStream_t s);
+void preload_feature_scale();
 // per keypoint of the list A: d1, index and d2 over the list B (ties to the lower index; d1 = d2 = 257, index -1 without any)
 struct MatchLists { int *d1, *idx, *d2, *back; int *mf, *mm, *md1, *md2; float* mw; };
 hipError_t launch_feature_best(const unsigned int* desc_a, int na, const unsigned int* desc_b, int nb, int* d1, int* idx, int* d2, hipStream_t s);

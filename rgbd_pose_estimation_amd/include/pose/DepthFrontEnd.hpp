@@ -464,6 +464,26 @@ class DepthFrontEnd {
     bins.resize(n);
     return bins;
   }
+  // the number of scale levels (1 .. 4: scale 1, 2/3, 1/2, 1/3) of every later detection on either side, relocalize's own included:
+  // with more than one a frame taken CLOSER to the scene than its keyframe still matches it, at the price of a smaller share of correct
+  // matches on a pair of one scale.  1 is the default; a change drops both sides' features and the match list.  A keyframe store may be
+  // filled at one number and queried at another
+  void setLevels(int levels) { check(rpe_features_set_levels(_ctx, levels), "rpe_features_set_levels"); }
+  int levels() const {
+    int n = 0;
+    check(rpe_features_get_levels(_ctx, &n), "rpe_features_get_levels");
+    return n;
+  }
+  // per keypoint of the side its level and its level pixel (u, v interleaved); the keypoint's own xy is the level-0 pixel it stands at
+  void featureScale(int which, std::vector<int32_t>& level, std::vector<int32_t>& lxy) {
+    level.assign((size_t)RPE_MAX_KEYPOINTS, -1);
+    lxy.assign(2 * (size_t)RPE_MAX_KEYPOINTS, 0);
+    check(rpe_features_scale(_ctx, which, level.data(), lxy.data()), "rpe_features_scale");
+    size_t n = 0;
+    while (n < level.size() && level[n] >= 0) n++;
+    level.resize(n);
+    lxy.resize(2 * n);
+  }
   // match the frame's keypoints against the model's; the solver slots become the matches (n = their number, returned)
   int matchFeatures(const MatchOptions& o = MatchOptions()) {
     const rpe_match_options mo = {o.max_dist, o.ratio_num, o.ratio_den, o.cross_check ? 1 : 0};
