@@ -1,6 +1,7 @@
 """Compile the HIP backend for gfx950 in-tree: rgbd_pose_estimation_amd/lib/librgbdpose_hip.so.
 
-hipcc cross-compiles without a GPU.  Kernel units (shared device code in csrc/rpe_reduce.hpp and csrc/rpe_residuals.hpp):
+hipcc cross-compiles without a GPU.  Kernel units (shared device code in csrc/rpe_reduce.hpp and csrc/rpe_residuals.hpp; the front end's
+bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp):
 csrc/rpe_normal_eq.hip (K1-K3 Gauss-Newton normal equations + the resident form), csrc/rpe_icp.hip (fused ICP rounds),
 csrc/rpe_joint.hip (joint normal equations), csrc/rpe_score.hip (K4 scoring, K4b masks), csrc/rpe_nl.hip (K1' moments, K5, publish
 kernels), csrc/rpe_frontend.hip (depth-frame front end), csrc/rpe_filter.hip (the bilateral depth filter in front of it), csrc/rpe_volume.hip (TSDF volume: integrate, raycast), csrc/rpe_mesh.hip (marching cubes over the volume), csrc/rpe_color.hip (colour of the volume: frame

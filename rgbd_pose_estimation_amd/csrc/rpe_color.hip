@@ -2,8 +2,8 @@
 // sampled back at world points (the model's vertices, the mesh's vertices).
 //
 //   C1  frame_color_kernel              the 3-byte staging upload of one frame into its RGBA8 map (A = 255), RGB or BGR order.
-//   C2  volume_integrate_color_kernel   V1 (rpe_volume.hip) plus the colour: the tsdf half is V1's code (voxel_project / fuse of
-//                                       rpe_volume_field.hpp) and touches the same voxels with the same bits; a voxel that V1 updates
+//   C2  volume_integrate_color_kernel   V1 (rpe_volume.hip) plus the colour: the tsdf half is V1's code (voxel_project / fuse and
+//                                       the {tsdf, w} pairs of rpe_volume_field.hpp) and touches the same voxels with the same bits; a voxel that V1 updates
 //                                       and that lies inside the truncation band (sdf <= tr) also blends the frame colour of its pixel
 //                                       into its four binary16 {r, g, b, wc}, unless that pixel has A = 0 (no colour).  A lane owns 4 voxels: two 16-byte {tsdf, w} pairs and two
 //                                       16-byte colour pairs, each loaded and stored only where one of its voxels is updated, plus one
@@ -64,11 +64,7 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float
 #pragma unroll
   for (int p = 0; p < 2; p++) {
     const int64_t a = first + 2 * p;
-    v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (up[2 * p] || up[2 * p + 1]) {
-      if (a + 1 < nvox) v[p] = *reinterpret_cast<const float4*>(vol + 2 * a);
-      else { const float2 h = *reinterpret_cast<const float2*>(vol + 2 * a); v[p].x = h.x; v[p].y = h.y; }
-    }
+    v[p] = load_pair(vol, a, nvox, up[2 * p] || up[2 * p + 1]);
     c[p] = make_uint4(0u, 0u, 0u, 0u);
     if (band[2 * p] || band[2 * p + 1]) {
       if (a + 1 < nvox) c[p] = *reinterpret_cast<const uint4*>(cvol + 4 * a);
@@ -83,13 +79,9 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float
 #pragma unroll
   for (int p = 0; p < 2; p++) {
     const bool lo = up[2 * p], hi = up[2 * p + 1];
-    if (!lo && !hi) continue;
-    float* q = vol + 2 * (first + 2 * p);
     if (lo) fuse(v[p].x, v[p].y, f[2 * p], G.W);
     if (hi) fuse(v[p].z, v[p].w, f[2 * p + 1], G.W);
-    if (lo && hi) *reinterpret_cast<float4*>(q) = v[p];
-    else if (lo) *reinterpret_cast<float2*>(q) = make_float2(v[p].x, v[p].y);
-    else *reinterpret_cast<float2*>(q + 2) = make_float2(v[p].z, v[p].w);
+    store_pair(vol, first + 2 * p, v[p], lo, hi);
   }
 #pragma unroll
   for (int p = 0; p < 2; p++) {
@@ -105,16 +97,9 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float
 }
 
 // ---------------------------------------------------------------------------------------------- C3
-// C(p): F's g, i0, a and in-range rule; known iff in range and all eight corner colour weights are > 0; each channel with F's lerp
-// order on (float) of the binary16 values.  q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f) (quantise: rpe_volume_field.hpp,
-// shared with the map mesh of rpe_mapmesh.hip).
-__device__ __forceinline__ float trilerp(float v000, float v100, float v010, float v110, float v001, float v101, float v011, float v111,
-                                         float ax, float ay, float az) {
-  const float c00 = lerp(v000, v100, ax), c10 = lerp(v010, v110, ax), c01 = lerp(v001, v101, ax), c11 = lerp(v011, v111, ax);
-  const float c0 = lerp(c00, c10, ay), c1 = lerp(c01, c11, ay);
-  return lerp(c0, c1, az);
-}
-
+// C(p): F's cell (g, i0, a and the in-range rule: cell); known iff in range and all eight corner colour weights are > 0; each channel
+// with F's lerp chain (trilerp) on (float) of the binary16 values.  q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f)
+// (quantise).  All three: rpe_volume_field.hpp, shared with the map mesh of rpe_mapmesh.hip.
 __global__ __launch_bounds__(kColorBlock) void color_sample_kernel(const unsigned short* __restrict__ cvol, VolumeGeometry G,
                                                                    const float* __restrict__ pts, int64_t n,
                                                                    unsigned int* __restrict__ rgba) {
@@ -122,13 +107,11 @@ __global__ __launch_bounds__(kColorBlock) void color_sample_kernel(const unsigne
   if (e >= n) return;
   const float px = pts[3 * e], py = pts[3 * e + 1], pz = pts[3 * e + 2];
   unsigned out = 0u;
-  const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
-  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
-  if (fx >= 0.0f && fx <= (float)(G.dim[0] - 2) && fy >= 0.0f && fy <= (float)(G.dim[1] - 2) && fz >= 0.0f &&
-      fz <= (float)(G.dim[2] - 2)) {
-    const float ax = gx - fx, ay = gy - fy, az = gz - fz;
+  int i0[3];
+  float a[3];
+  if (cell(G, px, py, pz, i0, a)) {
     const int64_t sy = 4 * (int64_t)G.dim[0], sz = sy * G.dim[1];
-    const unsigned short* b = cvol + (int64_t)(int)fz * sz + (int64_t)(int)fy * sy + 4 * (int64_t)(int)fx;
+    const unsigned short* b = cvol + (int64_t)i0[2] * sz + (int64_t)i0[1] * sy + 4 * (int64_t)i0[0];
     uint2 v[8];   // corner n = di + 2 dj + 4 dk
 #pragma unroll
     for (int m = 0; m < 8; m++) v[m] = *reinterpret_cast<const uint2*>(b + ((m & 4) ? sz : 0) + ((m & 2) ? sy : 0) + ((m & 1) ? 4 : 0));
@@ -138,11 +121,11 @@ __global__ __launch_bounds__(kColorBlock) void color_sample_kernel(const unsigne
     if (known) {
       float ch[3];
 #pragma unroll
-      for (int a = 0; a < 3; a++) {
+      for (int c = 0; c < 3; c++) {
         float x[8];
 #pragma unroll
-        for (int m = 0; m < 8; m++) x[m] = h2f(a == 0 ? v[m].x & 0xffffu : a == 1 ? v[m].x >> 16 : v[m].y & 0xffffu);
-        ch[a] = trilerp(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], ax, ay, az);
+        for (int m = 0; m < 8; m++) x[m] = h2f(c == 0 ? v[m].x & 0xffffu : c == 1 ? v[m].x >> 16 : v[m].y & 0xffffu);
+        ch[c] = trilerp(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], a[0], a[1], a[2]);
       }
       out = quantise(ch[0]) | quantise(ch[1]) << 8 | quantise(ch[2]) << 16 | 0xff000000u;
     }

@@ -23,14 +23,12 @@
 // The conventions (include/rgbd_pose_hip.h Part 3, "Features and relocalisation") are integer arithmetic and comparisons throughout;
 // tests/feature_oracle.py is their numpy statement and the results are its bits.  Nothing is placed by an atomic: ids come from scans.
 #include "rpe_assoc.h"
-#include "rpe_brief_table.h"
+#include "rpe_feature_rules.hpp"   // the rules the scale levels share: luma, the segment test, survives
 
 namespace rpe {
 
 namespace {
 
-constexpr int kTileX = 32, kTileY = 8, kHalo = 3, kBorder = 16;
-constexpr int kLdsX = kTileX + 2 * kHalo, kLdsY = kTileY + 2 * kHalo;
 constexpr int kChunk = 256;      // D2, D4: pixels per workgroup
 constexpr int kWide = 1024;      // D3, D5, M2: the single workgroup
 constexpr int kGroup = 16;       // M1: lanes per keypoint
@@ -56,7 +54,7 @@ template <int B> __device__ __forceinline__ int block_scan(int v, int* lds, int&
 __global__ __launch_bounds__(kTileX * kTileY) void feat_score_kernel(const unsigned int* __restrict__ rgba, const float* __restrict__ vmap,
                                                                     const float* __restrict__ nmap, int w, int h, int thr,
                                                                     int* __restrict__ score, unsigned short* __restrict__ box) {
-  __shared__ unsigned short t[kLdsY][kLdsX + 2];
+  __shared__ FeatTile t;
   const int u0 = blockIdx.x * kTileX, v0 = blockIdx.y * kTileY;
   for (int i = threadIdx.x; i < kLdsX * kLdsY; i += kTileX * kTileY) {
     const int ly = i / kLdsX, lx = i - ly * kLdsX;
@@ -64,7 +62,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void feat_score_kernel(const unsig
     unsigned px = 0;
     if (gu >= 0 && gu < w && gv >= 0 && gv < h) px = rgba[gv * w + gu];
     const unsigned known = (px >> 24) != 0;
-    const unsigned y = (77u * (px & 0xffu) + 150u * ((px >> 8) & 0xffu) + 29u * ((px >> 16) & 0xffu) + 128u) >> 8;
+    const unsigned y = luma(px);
     t[ly][lx] = (unsigned short)(known ? (y | 0x100u) : 0u);
   }
   __syncthreads();
@@ -72,58 +70,22 @@ __global__ __launch_bounds__(kTileX * kTileY) void feat_score_kernel(const unsig
   const int u = u0 + tx, v = v0 + ty;
   if (u >= w || v >= h) return;
   const int cx = tx + kHalo, cy = ty + kHalo, idx = v * w + u;
-  int S = 0;
+  int S = 0;   // the 5 x 5 box sum, what the descriptor compares (stated in D1 and D1s: rpe_feature_rules.hpp, header)
 #pragma unroll
   for (int dy = -2; dy <= 2; dy++)
 #pragma unroll
     for (int dx = -2; dx <= 2; dx++) S += t[cy + dy][cx + dx] & 0xff;
   box[idx] = (unsigned short)S;
-  int sc = 0;
-  const int c = t[cy][cx];
-  if (u >= kBorder && u < w - kBorder && v >= kBorder && v < h - kBorder && (c & 0x100)) {
-    constexpr int RX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
-    constexpr int RY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
-    const int Y = c & 0xff;
-    unsigned hi = 0, lo = 0, known = 0x100;
-    int sum = 0;
+  score[idx] = segment_score(t, cx, cy, u, v, w, h, thr, [=] {
+    bool fin = true;
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const int r = t[cy + RY[k]][cx + RX[k]], yr = r & 0xff;
-      known &= (unsigned)r;
-      hi |= (unsigned)(yr > Y + thr) << k;
-      lo |= (unsigned)(yr < Y - thr) << k;
-      const int d = yr > Y ? yr - Y : Y - yr;
-      sum += d > thr ? d - thr : 0;
-    }
-    // nine contiguous ring pixels: bit i of run9(m) is set iff bits i .. i + 8 of the doubled 16-bit mask are
-    auto run9 = [](unsigned m16) { unsigned m = m16 | m16 << 16; unsigned r = m & (m >> 1); r &= r >> 2; r &= r >> 4; return r & (m >> 8) & 0xffffu; };
-    if (known && (run9(hi) | run9(lo))) {
-      bool fin = true;
-#pragma unroll
-      for (int k = 0; k < 3; k++) fin = fin && __builtin_isfinite(vmap[3 * (int64_t)idx + k]) && __builtin_isfinite(nmap[3 * (int64_t)idx + k]);
-      sc = fin ? sum : 0;
-    }
-  }
-  score[idx] = sc;
+    for (int k = 0; k < 3; k++) fin = fin && __builtin_isfinite(vmap[3 * (int64_t)idx + k]) && __builtin_isfinite(nmap[3 * (int64_t)idx + k]);
+    return fin;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- D2, D4
-// a positive score lies at least kBorder pixels inside the image: all eight neighbours exist
-__device__ __forceinline__ bool survives(const int* __restrict__ score, int i, int w) {
-  const int s = score[i];
-  if (s <= 0) return false;
-  bool ok = true;
-#pragma unroll
-  for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-    for (int dx = -1; dx <= 1; dx++) {
-      if (dx == 0 && dy == 0) continue;
-      const int nb = score[i + dy * w + dx];
-      ok = ok && ((dy < 0 || (dy == 0 && dx < 0)) ? s > nb : s >= nb);   // a tie goes to the lower pixel index
-    }
-  return ok;
-}
-
+// survives(score, i, w): rpe_feature_rules.hpp
 __global__ __launch_bounds__(kChunk) void feat_nms_kernel(const int* __restrict__ score, int n, int w, int* __restrict__ chunk,
                                                          unsigned int* __restrict__ hist) {
   const int i = blockIdx.x * kChunk + threadIdx.x;
@@ -204,6 +166,7 @@ __global__ __launch_bounds__(256) void feat_describe_kernel(const unsigned short
   if (k >= ctl[kFeatCtlCount]) return;
   const int p = kp_pix[k];
   unsigned long long m[4];
+  // the tests and the word store: stated here and in rpe_feature_scale.hip (see rpe_feature_rules.hpp)
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const signed char* q = kBriefPairs[j * 64 + lane];

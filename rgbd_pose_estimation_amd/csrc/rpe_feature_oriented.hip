@@ -12,8 +12,7 @@
 // sums, so the order of the reduction does not matter.  The unit is its own so that rpe_feature.hip, and the upright D6 in it, compile
 // to what they were.
 #include "rpe_assoc.h"
-#include "rpe_brief_table.h"
-#include "rpe_feature_disc.h"   // the angle table and the disc, shared with the scale levels' D6os
+#include "rpe_feature_rules.hpp"   // luma; the tables (rpe_brief_table.h, rpe_feature_disc.h: the angle table and the disc, shared with D6os)
 
 namespace rpe {
 
@@ -28,12 +27,13 @@ __global__ __launch_bounds__(256) void feat_describe_oriented_kernel(const unsig
   if (k >= ctl[kFeatCtlCount]) return;
   const int p = kp_pix[k];
   const int u = p % w, v = p / w;
+  // moments, angle bin, steered tests and word store: stated here and in rpe_feature_scale.hip (see rpe_feature_rules.hpp)
   // the moments: a keypoint lies 16 px inside the image, the whole disc with it
   int m10 = 0, m01 = 0;
   for (int i = lane; i < kDiscPixels; i += 64) {
     const int dx = kDisc.d[i][0], dy = kDisc.d[i][1];
     const unsigned px = rgba[p + dy * w + dx];
-    const int y = (px >> 24) != 0 ? (int)((77u * (px & 0xffu) + 150u * ((px >> 8) & 0xffu) + 29u * ((px >> 16) & 0xffu) + 128u) >> 8) : 0;
+    const int y = (px >> 24) != 0 ? (int)luma(px) : 0;
     m10 += dx * y; m01 += dy * y;
   }
 #pragma unroll

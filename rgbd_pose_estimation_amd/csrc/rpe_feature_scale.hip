@@ -19,16 +19,13 @@
 // The rule (include/rgbd_pose_hip.h Part 3, "Scale levels") is integer arithmetic and comparisons throughout; tests/scale_oracle.py is
 // its numpy statement and the results are its bits.  Nothing is placed by an atomic: ids come from scans.
 #include "rpe_assoc.h"
-#include "rpe_brief_table.h"
-#include "rpe_feature_disc.h"
+#include "rpe_feature_rules.hpp"   // luma, the segment test, survives: shared with rpe_feature.hip / rpe_feature_oriented.hip
 #include "rpe_scan.hpp"
 
 namespace rpe {
 
 namespace {
 
-constexpr int kTileX = 32, kTileY = 8, kHalo = 3, kBorder = 16;
-constexpr int kLdsX = kTileX + 2 * kHalo, kLdsY = kTileY + 2 * kHalo;
 constexpr int kChunk = 256;
 
 // a[l] by comparisons (l is a register value: an indexed read of a kernel argument could go through scratch)
@@ -55,7 +52,7 @@ __global__ __launch_bounds__(256) void feat_resample_kernel(const unsigned int* 
       const int sx = (q * u + k) / p;
       const unsigned px = rgba[sy * w0 + sx];
       const unsigned a = (px >> 24) != 0;
-      const unsigned y = (77u * (px & 0xffu) + 150u * ((px >> 8) & 0xffu) + 29u * ((px >> 16) & 0xffu) + 128u) >> 8;
+      const unsigned y = luma(px);
       sum += a ? y : 0u;
       known &= a;
     }
@@ -69,7 +66,7 @@ __global__ __launch_bounds__(kTileX * kTileY) void feat_score_levels_kernel(cons
                                                                            const float* __restrict__ vmap, const float* __restrict__ nmap,
                                                                            FeatLevels L, int thr, int* __restrict__ score,
                                                                            unsigned short* __restrict__ box) {
-  __shared__ unsigned short t[kLdsY][kLdsX + 2];
+  __shared__ FeatTile t;
   const int b = blockIdx.x, l = level_of(L.tile, b), tb = b - at(L.tile, l), tiles_x = at(L.tiles_x, l);
   const int w = at(L.w, l), h = at(L.h, l), base = at(L.base, l);
   const int by = tb / tiles_x, bx = tb - by * tiles_x;
@@ -84,61 +81,26 @@ __global__ __launch_bounds__(kTileX * kTileY) void feat_score_levels_kernel(cons
   const int u = u0 + tx, v = v0 + ty;
   if (u >= w || v >= h) return;
   const int cx = tx + kHalo, cy = ty + kHalo, idx = base + v * w + u;
-  int S = 0;
+  int S = 0;   // the 5 x 5 box sum, what the descriptor compares (stated in D1 and D1s: rpe_feature_rules.hpp, header)
 #pragma unroll
   for (int dy = -2; dy <= 2; dy++)
 #pragma unroll
     for (int dx = -2; dx <= 2; dx++) S += t[cy + dy][cx + dx] & 0xff;
   box[idx] = (unsigned short)S;
-  int sc = 0;
-  const int c = t[cy][cx];
-  if (u >= kBorder && u < w - kBorder && v >= kBorder && v < h - kBorder && (c & 0x100)) {
-    constexpr int RX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
-    constexpr int RY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
-    const int Y = c & 0xff;
-    unsigned hi = 0, lo = 0, known = 0x100;
-    int sum = 0;
+  const int w0 = L.w[0];
+  score[idx] = segment_score(t, cx, cy, u, v, w, h, thr, [=] {
+    // the geometry of a level keypoint is that of the level-0 pixel it stands at (inside the image: see centre())
+    const int p = level_p(l), q = level_q(l);
+    const int64_t g = (int64_t)centre(v, p, q) * w0 + centre(u, p, q);
+    bool fin = true;
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const int r = t[cy + RY[k]][cx + RX[k]], yr = r & 0xff;
-      known &= (unsigned)r;
-      hi |= (unsigned)(yr > Y + thr) << k;
-      lo |= (unsigned)(yr < Y - thr) << k;
-      const int d = yr > Y ? yr - Y : Y - yr;
-      sum += d > thr ? d - thr : 0;
-    }
-    // nine contiguous ring pixels: bit i of run9(m) is set iff bits i .. i + 8 of the doubled 16-bit mask are
-    auto run9 = [](unsigned m16) { unsigned m = m16 | m16 << 16; unsigned r = m & (m >> 1); r &= r >> 2; r &= r >> 4; return r & (m >> 8) & 0xffffu; };
-    if (known && (run9(hi) | run9(lo))) {
-      // the geometry of a level keypoint is that of the level-0 pixel it stands at (inside the image: see centre())
-      const int p = level_p(l), q = level_q(l);
-      const int64_t g = (int64_t)centre(v, p, q) * L.w[0] + centre(u, p, q);
-      bool fin = true;
-#pragma unroll
-      for (int k = 0; k < 3; k++) fin = fin && __builtin_isfinite(vmap[3 * g + k]) && __builtin_isfinite(nmap[3 * g + k]);
-      sc = fin ? sum : 0;
-    }
-  }
-  score[idx] = sc;
+    for (int k = 0; k < 3; k++) fin = fin && __builtin_isfinite(vmap[3 * g + k]) && __builtin_isfinite(nmap[3 * g + k]);
+    return fin;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- D2s, D4s
-// a positive score lies at least kBorder pixels inside ITS LEVEL: all eight neighbours exist, in the same level (w = its row width)
-__device__ __forceinline__ bool survives(const int* __restrict__ score, int i, int w) {
-  const int s = score[i];
-  if (s <= 0) return false;
-  bool ok = true;
-#pragma unroll
-  for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-    for (int dx = -1; dx <= 1; dx++) {
-      if (dx == 0 && dy == 0) continue;
-      const int nb = score[i + dy * w + dx];
-      ok = ok && ((dy < 0 || (dy == 0 && dx < 0)) ? s > nb : s >= nb);   // a tie goes to the lower pixel index
-    }
-  return ok;
-}
-
+// survives (rpe_feature_rules.hpp) with w = the row width of the pixel's level: its eight neighbours lie in the same level
 __global__ __launch_bounds__(kChunk) void feat_nms_levels_kernel(const int* __restrict__ score, FeatLevels L, int* __restrict__ chunk,
                                                                 unsigned int* __restrict__ hist) {
   const int i = blockIdx.x * kChunk + threadIdx.x;
@@ -176,6 +138,7 @@ __device__ __forceinline__ void report(const FeatLevels& L, const LevelKeypoint&
   kp_level[k] = K.l;
   kp_lxy[2 * k] = K.u; kp_lxy[2 * k + 1] = K.v;
 }
+// the word store of D6s and D6os; D6 (rpe_feature.hip) and D6o (rpe_feature_oriented.hip) state it too (see rpe_feature_rules.hpp)
 __device__ __forceinline__ void store_words(const unsigned long long (&m)[4], int lane, int k, unsigned int* __restrict__ kp_desc) {
   if (lane < 8) {
     const int j = lane >> 1;
@@ -196,7 +159,7 @@ __global__ __launch_bounds__(256) void feat_describe_levels_kernel(const unsigne
   unsigned long long m[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    // the offsets lie within +-13 and the keypoint 16 pixels inside its level: both samples are pixels of the level
+    // D6's tests, stated here and in rpe_feature.hip (see rpe_feature_rules.hpp); both samples are pixels of the level (16 px inside)
     const signed char* q = kBriefPairs[j * 64 + lane];
     const int a = box[g + q[1] * K.w + q[0]], b = box[g + q[3] * K.w + q[2]];
     m[j] = __ballot(a < b);
@@ -215,6 +178,7 @@ __global__ __launch_bounds__(256) void feat_describe_oriented_levels_kernel(cons
   if (k >= ctl[kFeatCtlCount]) return;
   const int g = kidx[k];
   const LevelKeypoint K = level_keypoint(L, g);
+  // moments, angle bin and steered tests: stated here and in D6o of rpe_feature_oriented.hip (see rpe_feature_rules.hpp)
   // the moments: a keypoint lies 16 px inside its level, the whole disc with it
   int m10 = 0, m01 = 0;
   for (int i = lane; i < kDiscPixels; i += 64) {

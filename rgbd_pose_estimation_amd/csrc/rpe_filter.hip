@@ -30,8 +30,6 @@ constexpr int kFilterStride = kFilterSpan + 1;                        // 41: see
 static_assert(kFilterStride % 4 == 1, "LDS row stride must be 1 (mod 4) for conflict-free ds_read_b32");
 static_assert(kFilterBlock * 4 == kFilterTile * kFilterTile, "4 pixels per thread");
 
-__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
-
 template <class D>
 __global__ __launch_bounds__(kFilterBlock) void depth_filter_kernel(const D* __restrict__ raw, int w, int h, float scale, float dmin,
                                                                     float dmax, FilterParams P, float* __restrict__ out) {

@@ -28,8 +28,6 @@ namespace {
 
 constexpr int kFeBlock = 256;
 
-__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
-
 template <class D> __device__ __forceinline__ float depth_at(const D* __restrict__ d, int idx,
     float scale) { return (float)d[idx] * scale; }
 

@@ -15,6 +15,8 @@ constexpr int kMaxScoreH = 8192;     // hypotheses per scoring launch (LDS vote 
 constexpr int kRunSlots = 8;
 constexpr int kRunLd = 32;
 
+__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }   // what the front end writes for "invalid"
+
 // Correspondence arrays resident in HBM.  3 x n column-major (xyz interleaved), dtype 0 = f32, 1 = f64.
 struct DeviceArrays {
   const void* a[5];        // RPE_XW, RPE_XC, RPE_BV, RPE_NW, RPE_NC

@@ -40,6 +40,7 @@
 // the box.  No address is formed for an absent neighbour, a slot at or above the capacity or a brick index outside the window.
 #include "rpe_volume_field.hpp"
 #include "rpe_mc_tables.h"
+#include "rpe_mc_rules.hpp"
 #include "rpe_scan.hpp"
 
 namespace rpe {
@@ -56,7 +57,6 @@ constexpr int kStVox = kStY * kStY * kStX;
 constexpr int kCases = 9 * 9 * 9;                    // cubes at local -1 .. 7
 constexpr unsigned long long kKeyMask = (1ull << kMapKeyBits) - 1ull;
 
-__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
 __device__ __forceinline__ int stage_index(int lx, int ly, int lz) { return ((lz + 2) * kStY + (ly + 2)) * kStX + (lx + 2); }
 __device__ __forceinline__ int case_index(int lx, int ly, int lz) { return ((lz + 1) * 9 + (ly + 1)) * 9 + (lx + 1); }
 
@@ -143,8 +143,6 @@ __device__ __forceinline__ void stage(const MapMeshView& M, const int* s_pos, co
   }
 }
 
-__device__ __forceinline__ unsigned crossed(unsigned c, int a, int b) { return ((c >> a) ^ (c >> b)) & 1u; }
-
 // ---------------------------------------------------------------------------------------------- P1
 __global__ __launch_bounds__(kMapBlock) void map_count_kernel(MapMeshView M, float wmin, MapMeshWorkspace W) {
   __shared__ __align__(16) uint2 st[kStVox];
@@ -168,34 +166,25 @@ __global__ __launch_bounds__(kMapBlock) void map_count_kernel(MapMeshView M, flo
   __syncthreads();
   stage<-1, 8, 6>(M, s_pos, s_src, st);   // x: -2 .. 9
   __syncthreads();
-  // cube at local (x, y, z) in -1 .. 7: corner n = di + 2 dj + 4 dk; known iff weight >= wmin and the tsdf is finite; case bit n iff
-  // tsdf <= 0; 0 unless all 8 corners are known.  A cube that reaches outside the box has an absent corner: weight 0, inactive
+  // cube at local (x, y, z) in -1 .. 7: corner n = di + 2 dj + 4 dk from the staged region, its case by mc::cube_case (rpe_mc_rules.hpp).
+  // A cube that reaches outside the box has an absent corner: weight 0, inactive
   for (int c = t; c < kCases; c += kMapBlock) {
     const int x = c % 9 - 1, y = (c / 9) % 9 - 1, z = c / 81 - 1;
-    unsigned m = 0;
-    bool active = true;
-#pragma unroll
-    for (int n = 0; n < 8; n++) {
+    cs[c] = (unsigned char)mc::cube_case([&](int n) {
       const uint2 v = st[stage_index(x + (n & 1), y + ((n >> 1) & 1), z + (n >> 2))];
-      const float f = __uint_as_float(v.x);
-      active = active && __uint_as_float(v.y) >= wmin && __builtin_isfinite(f);
-      m |= (f <= 0.0f ? 1u : 0u) << n;
-    }
-    cs[c] = (unsigned char)(active ? m : 0u);
+      return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+    }, wmin);
   }
   __syncthreads();
   unsigned nv = 0, nt = 0;
 #pragma unroll
   for (int r = 0; r < kBrickVox / kMapBlock; r++) {
     const int v = r * kMapBlock + t, x = v & 7, y = (v >> 3) & 7, z = v >> 6;
-    // cDDD = the case of the cube at (x - di, y - dj, z - dk), as used_bits of rpe_mesh.hip
+    // cDDD = the case of the cube at (x - di, y - dj, z - dk)
     const unsigned c000 = cs[case_index(x, y, z)], c100 = cs[case_index(x - 1, y, z)], c010 = cs[case_index(x, y - 1, z)];
     const unsigned c110 = cs[case_index(x - 1, y - 1, z)], c001 = cs[case_index(x, y, z - 1)], c101 = cs[case_index(x - 1, y, z - 1)];
     const unsigned c011 = cs[case_index(x, y - 1, z - 1)];
-    const unsigned ux = crossed(c000, 0, 1) | crossed(c010, 2, 3) | crossed(c001, 4, 5) | crossed(c011, 6, 7);
-    const unsigned uy = crossed(c000, 0, 2) | crossed(c100, 1, 3) | crossed(c001, 4, 6) | crossed(c101, 5, 7);
-    const unsigned uz = crossed(c000, 0, 4) | crossed(c100, 1, 5) | crossed(c010, 2, 6) | crossed(c110, 3, 7);
-    const unsigned u = ux | (uy << 1) | (uz << 2);
+    const unsigned u = mc::used_edges(c000, c100, c010, c110, c001, c101, c011);
     W.cases[(int64_t)pos * kBrickVox + v] = (unsigned char)c000;
     W.used[(int64_t)pos * kBrickVox + v] = (unsigned char)u;
     nv += __popc(u);
@@ -242,21 +231,9 @@ __global__ __launch_bounds__(kMapScanBlock) void map_scan_kernel(int n, MapMeshW
 }
 
 // ---------------------------------------------------------------------------------------------- P3
-// g, i0, a of rpe_volume_field.hpp's field and its in-range rule, on the box
-__device__ __forceinline__ bool box_cell(const VolumeGeometry& G, float px, float py, float pz, int i0[3], float a[3]) {
-  const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
-  const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
-  if (!(fx >= 0.0f && fx <= (float)(G.dim[0] - 2) && fy >= 0.0f && fy <= (float)(G.dim[1] - 2) && fz >= 0.0f &&
-        fz <= (float)(G.dim[2] - 2)))
-    return false;
-  a[0] = gx - fx; a[1] = gy - fy; a[2] = gz - fz;
-  i0[0] = (int)fx; i0[1] = (int)fy; i0[2] = (int)fz;
-  return true;
-}
-
 // ---- the two fields
-// The trilinear value of NCH channels in F's lerp order -- along x for (dj, dk) = (0,0) (1,0) (0,1) (1,1), then y, then z -- with the
-// corners taken a pair at a time: corner(di, dj, dk, x) gives a corner's channels and whether its weight is > 0.  The loop is
+// The trilinear value of NCH channels in F's lerp chain (trilerp of rpe_volume_field.hpp: along x for (dj, dk) = (0,0) (1,0) (0,1)
+// (1,1), then bilerp along y and z) with the corners taken a pair at a time: corner(di, dj, dk, x) gives a corner's channels and whether its weight is > 0.  The loop is
 // NOT unrolled: a corner may come from global memory through the table or a search of the keys (map_voxel), and eight copies of that
 // per sample cost more scalar registers than the kernel has
 template <int NCH, class Corner>
@@ -277,17 +254,17 @@ __device__ __forceinline__ bool trilinear(Corner corner, const float a[3], float
     }
   }
 #pragma unroll
-  for (int c = 0; c < NCH; c++) out[c] = lerp(lerp(x00[c], x10[c], a[1]), lerp(x01[c], x11[c], a[1]), a[2]);
+  for (int c = 0; c < NCH; c++) out[c] = bilerp(x00[c], x10[c], x01[c], x11[c], a[1], a[2]);
   return known;
 }
 
-// F(p) of the box's virtual volume (rpe_volume_field.hpp field, bit for bit): the eight corners from the staged region where they
+// F(p) of the box's virtual volume (rpe_volume_field.hpp field, bit for bit; the cell is the BOX's): the eight corners from the staged region where they
 // all lie in it, from global memory otherwise
 __device__ __forceinline__ bool map_field(const uint2* st, const MapMeshView& M, const int* s_pos, const int* s_src,
                                           const VolumeGeometry& G, const int ob[3], float px, float py, float pz, float& F) {
   int i0[3];
   float a[3];
-  if (!box_cell(G, px, py, pz, i0, a)) return false;
+  if (!cell(G, px, py, pz, i0, a)) return false;
   const int lx = i0[0] - 8 * ob[0], ly = i0[1] - 8 * ob[1], lz = i0[2] - 8 * ob[2];
   const bool staged = lx >= -2 && lx <= 9 && ly >= -2 && ly <= 9 && lz >= -2 && lz <= 9;
   float out[1];
@@ -305,7 +282,7 @@ __device__ __forceinline__ unsigned map_colour(const MapMeshView& M, const int* 
                                                const int ob[3], float px, float py, float pz) {
   int i0[3];
   float a[3];
-  if (!box_cell(G, px, py, pz, i0, a)) return 0u;
+  if (!cell(G, px, py, pz, i0, a)) return 0u;
   float ch[3];
   const bool known = trilinear<3>([&](int di, int dj, int dk, float x[3]) {
     const uint2 v = map_voxel<true>(M, s_pos, s_src, ob, i0[0] + di, i0[1] + dj, i0[2] + dk);
@@ -316,8 +293,8 @@ __device__ __forceinline__ unsigned map_colour(const MapMeshView& M, const int* 
   return quantise(ch[0]) | quantise(ch[1]) << 8 | quantise(ch[2]) << 16 | 0xff000000u;
 }
 
-// vertex on the edge of voxel a along an axis, Fa, Fb its tsdf values: t = Fa / (Fa - Fb); along the axis o + (((float)i + 0.5f) + t) * s
-// with i the index INSIDE THE BOX, across it the voxel centre's.  Normal: field_normal's six samples (NaN where unknown)
+// the vertex on a used edge of a voxel: mc::edge_vertex (rpe_mc_rules.hpp) with the voxel's index INSIDE THE BOX.  Normal:
+// field_normal's six samples on map_field and its finish, unit_normal (NaN where unknown)
 __global__ __launch_bounds__(kMapBlock) void map_vertex_kernel(MapMeshView M, VolumeGeometry G, MapMeshWorkspace W, float* __restrict__ vout,
                                                                float* __restrict__ nout) {
   __shared__ __align__(16) uint2 st[kStVox];
@@ -347,11 +324,9 @@ __global__ __launch_bounds__(kMapBlock) void map_vertex_kernel(MapMeshView M, Vo
     for (int a = 0; a < 3; a++) {
       if (!((u >> a) & 1u)) continue;
       const float Fb = __uint_as_float(st[stage_index(l[0] + (a == 0), l[1] + (a == 1), l[2] + (a == 2))].x);
-      const float tt = Fa / (Fa - Fb);
       float p[3];
-#pragma unroll
-      for (int q = 0; q < 3; q++) p[q] = q == a ? G.o[q] + (((float)ijk[q] + 0.5f) + tt) * G.s : G.o[q] + ((float)ijk[q] + 0.5f) * G.s;
-      // field_normal of rpe_volume_field.hpp, an axis per turn: F(p + s e) - F(p - s e)
+      mc::edge_vertex(G, ijk, a, Fa, Fb, p);
+      // field_normal's differences, an axis per turn: F(p + s e) - F(p - s e)
       float g[3] = {0.0f, 0.0f, 0.0f};
       bool ok = true;
 #pragma unroll 1
@@ -365,10 +340,7 @@ __global__ __launch_bounds__(kMapBlock) void map_vertex_kernel(MapMeshView M, Vo
         if (q == 0) g[0] = d; else if (q == 1) g[1] = d; else g[2] = d;
       }
       float nx = qnan(), ny = qnan(), nz = qnan();
-      if (ok) {
-        const float len = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-        if (len > 0.0f) { nx = g[0] / len; ny = g[1] / len; nz = g[2] / len; }
-      }
+      if (ok) (void)unit_normal(g[0], g[1], g[2], nx, ny, nz);
       float* o = vout + 3 * (int64_t)id;
       o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
       float* n = nout + 3 * (int64_t)id;
@@ -399,7 +371,7 @@ __global__ __launch_bounds__(kMapBlock) void map_colour_kernel(MapMeshView M, Vo
 
 // ---------------------------------------------------------------------------------------------- P4
 // triangles of the cube at voxel v of the brick, in table order; the vertex of table edge e is on the edge its owner voxel
-// v + kEdgeOwner[e] owns along kEdgeAxis[e]: the owner's first id plus its used edges of lower axis.  An owner at local 8 is a voxel of
+// v + kEdgeOwner[e] owns along kEdgeAxis[e]: mc::corner_id of the owner's first id and used bits.  An owner at local 8 is a voxel of
 // the neighbour brick; the cube is active, so that voxel is known, its brick is listed and P1 / P3 wrote its bytes and its id
 __global__ __launch_bounds__(kMapBlock) void map_triangle_kernel(MapMeshView M, MapMeshWorkspace W, int* __restrict__ tout) {
   __shared__ unsigned lds[kMapBlock / 64 + 1];
@@ -424,7 +396,7 @@ __global__ __launch_bounds__(kMapBlock) void map_triangle_kernel(MapMeshView M, 
       int id = 0;
       if (p >= 0) {
         const int64_t w = (int64_t)p * kBrickVox + ((oz & 7) * 8 + (oy & 7)) * 8 + (ox & 7);
-        id = W.first[w] + (int)__popc(W.used[w] & ((1u << axis) - 1u));
+        id = mc::corner_id(W.first[w], W.used[w], axis);
       }
       tout[3 * t0 + q] = id;
     }

@@ -16,6 +16,7 @@
 // tests/mesh_oracle.py is their numpy statement.  Workspace: 6 bytes per voxel (case, used bits, first id) plus 24 per chunk.
 #include "rpe_volume_field.hpp"
 #include "rpe_mc_tables.h"
+#include "rpe_mc_rules.hpp"
 #include "rpe_scan.hpp"
 
 namespace rpe {
@@ -26,27 +27,17 @@ constexpr int kMeshBlock = 256;
 constexpr int kMeshRounds = kMeshChunk / kMeshBlock;   // a workgroup walks its chunk in rounds of one voxel per lane
 constexpr int kScanBlock = 1024;
 
-__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
-
 // block_exclusive_scan<NT>(x, lds, total): rpe_scan.hpp, shared with rpe_mapmesh.hip
 
 // ---------------------------------------------------------------------------------------------- M1
-// cube (i, j, k), 0 <= i <= d0 - 2 etc.: corner n = di + 2 dj + 4 dk is voxel (i + di, j + dj, k + dk); known iff weight >= wmin and
-// the tsdf is finite; case bit n iff tsdf <= 0; 0 unless all 8 corners are known (or when the cube does not exist)
+// cube (i, j, k), 0 <= i <= d0 - 2 etc.: corner n = di + 2 dj + 4 dk is voxel (i + di, j + dj, k + dk); its case by mc::cube_case
+// (rpe_mc_rules.hpp), 0 when the cube does not exist
 __device__ __forceinline__ unsigned cube_case(const float* __restrict__ vol, const VolumeGeometry& G, float wmin, unsigned flat, int i,
                                               int j, int k) {
   if (i > G.dim[0] - 2 || j > G.dim[1] - 2 || k > G.dim[2] - 2) return 0u;
   const int64_t sy = 2 * (int64_t)G.dim[0], sz = sy * G.dim[1];
   const float* b = vol + 2 * (int64_t)flat;
-  unsigned m = 0;
-  bool active = true;
-#pragma unroll
-  for (int n = 0; n < 8; n++) {
-    const float2 v = *reinterpret_cast<const float2*>(b + 2 * (n & 1) + ((n >> 1) & 1) * sy + (n >> 2) * sz);
-    active = active && v.y >= wmin && __builtin_isfinite(v.x);
-    m |= (v.x <= 0.0f ? 1u : 0u) << n;
-  }
-  return active ? m : 0u;
+  return mc::cube_case([&](int n) { return *reinterpret_cast<const float2*>(b + 2 * (n & 1) + ((n >> 1) & 1) * sy + (n >> 2) * sz); }, wmin);
 }
 
 // one cube per lane, so that each of the 8 corner loads of a wave reads 512 contiguous bytes; `padded` = the chunks' voxels: the case
@@ -64,10 +55,8 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_classify_kernel(const float* 
 }
 
 // ---------------------------------------------------------------------------------------------- M2
-__device__ __forceinline__ unsigned crossed(unsigned c, int a, int b) { return ((c >> a) ^ (c >> b)) & 1u; }
-
-// the used-edge bits of voxel (i, j, k) = flat: bit a iff its edge along axis a is crossed in one of the active cubes containing it
-// (an inactive or missing cube has case 0 and crosses nothing).  cDDD = the case of the cube at (i - di, j - dj, k - dk).
+// the used-edge bits of voxel (i, j, k) = flat (mc::used_edges) from the case bytes of the cubes around it: cDDD = the case of the cube
+// at (i - di, j - dj, k - dk), 0 for a missing one
 __device__ __forceinline__ unsigned used_bits(const unsigned char* __restrict__ cs, const VolumeGeometry& G, unsigned flat, int i, int j,
                                               int k) {
   const unsigned d0 = (unsigned)G.dim[0], d01 = d0 * (unsigned)G.dim[1];
@@ -78,10 +67,7 @@ __device__ __forceinline__ unsigned used_bits(const unsigned char* __restrict__ 
   const unsigned c001 = k > 0 ? cs[flat - d01] : 0u;
   const unsigned c101 = i > 0 && k > 0 ? cs[flat - d01 - 1] : 0u;
   const unsigned c011 = j > 0 && k > 0 ? cs[flat - d01 - d0] : 0u;
-  const unsigned x = crossed(c000, 0, 1) | crossed(c010, 2, 3) | crossed(c001, 4, 5) | crossed(c011, 6, 7);
-  const unsigned y = crossed(c000, 0, 2) | crossed(c100, 1, 3) | crossed(c001, 4, 6) | crossed(c101, 5, 7);
-  const unsigned z = crossed(c000, 0, 4) | crossed(c100, 1, 5) | crossed(c010, 2, 6) | crossed(c110, 3, 7);
-  return x | (y << 1) | (z << 2);
+  return mc::used_edges(c000, c100, c010, c110, c001, c101, c011);
 }
 
 __global__ __launch_bounds__(kMeshBlock) void mesh_count_kernel(const unsigned char* __restrict__ cs, VolumeGeometry G, unsigned nvox,
@@ -133,8 +119,7 @@ __global__ __launch_bounds__(kScanBlock) void mesh_scan_kernel(const unsigned* _
 }
 
 // ---------------------------------------------------------------------------------------------- M4
-// vertex on the edge of voxel a = (i, j, k) along axis x (b = a + e_x), Fa, Fb its tsdf values: t = Fa / (Fa - Fb);
-// x = o + (((float)i + 0.5f) + t) * s, y and z the voxel centre's; likewise for y and z.  Normal: field_normal (NaN where unknown).
+// the vertex on a used edge of voxel (i, j, k): mc::edge_vertex (rpe_mc_rules.hpp).  Normal: field_normal (NaN where unknown).
 __global__ __launch_bounds__(kMeshBlock) void mesh_vertex_kernel(const float* __restrict__ vol, VolumeGeometry G, unsigned nvox,
                                                                  const unsigned char* __restrict__ used, const unsigned* __restrict__ chunk_v,
                                                                  const long long* __restrict__ off_v, int* __restrict__ first_id,
@@ -159,10 +144,8 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_vertex_kernel(const float* __
     for (int a = 0; a < 3; a++) {
       if (!((u >> a) & 1u)) continue;
       const float Fb = vol[2 * ((int64_t)v + stride[a])];
-      const float t = Fa / (Fa - Fb);
       float p[3];
-#pragma unroll
-      for (int q = 0; q < 3; q++) p[q] = q == a ? G.o[q] + (((float)ijk[q] + 0.5f) + t) * G.s : G.o[q] + ((float)ijk[q] + 0.5f) * G.s;
+      mc::edge_vertex(G, ijk, a, Fa, Fb, p);
       float nx = qnan(), ny = qnan(), nz = qnan();
       (void)field_normal(vol, G, p[0], p[1], p[2], nx, ny, nz);
       float* o = vout + 3 * (int64_t)id;
@@ -176,7 +159,7 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_vertex_kernel(const float* __
 
 // ---------------------------------------------------------------------------------------------- M5
 // triangles of the cube at voxel v in table order; the vertex of table edge e is on the edge its owner voxel v + kEdgeOwner[e] owns
-// along kEdgeAxis[e]: first_id[owner] + the owner's used edges of lower axis
+// along kEdgeAxis[e]: mc::corner_id of the owner's first id and used bits
 __global__ __launch_bounds__(kMeshBlock) void mesh_triangle_kernel(const unsigned char* __restrict__ cs, const unsigned char* __restrict__ used,
                                                                    const int* __restrict__ first_id, VolumeGeometry G, unsigned nvox,
                                                                    const unsigned* __restrict__ chunk_t, const long long* __restrict__ off_t,
@@ -197,7 +180,7 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_triangle_kernel(const unsigne
       const unsigned e = mc::kTriEdges[c][q];
       const unsigned o = mc::kEdgeOwner[e], axis = mc::kEdgeAxis[e];
       const unsigned owner = v + (o & 1u) + ((o >> 1) & 1u) * d0 + (o >> 2) * d01;
-      tout[3 * t0 + q] = first_id[owner] + __popc(used[owner] & ((1u << axis) - 1u));
+      tout[3 * t0 + q] = mc::corner_id(first_id[owner], used[owner], axis);
     }
   }
 }

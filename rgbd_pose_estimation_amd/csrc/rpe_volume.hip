@@ -24,10 +24,9 @@ namespace {
 constexpr int kVolBlock = 256;    // integrate: 4 voxels per lane
 constexpr int kRayTile = 16;      // raycast: 16 x 16 pixels per workgroup, 8 x 8 per wave
 
-__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
-
 // ---------------------------------------------------------------------------------------------- V1
-// The voxel's projection (voxel_sdf) and update (fuse): rpe_volume_field.hpp (shared with the colour integrate of rpe_color.hip).
+// The voxel's projection (voxel_sdf), its update (fuse) and the lane's pairs: rpe_volume_field.hpp (shared with the colour integrate
+// of rpe_color.hip).
 
 // nvox <= 2^30 (dims <= 1024): the flat voxel index fits 32 bits, byte offsets do not
 __global__ __launch_bounds__(kVolBlock) void volume_integrate_kernel(float* __restrict__ vol, VolumeGeometry G, int64_t nvox,
@@ -44,27 +43,16 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_kernel(float* __re
     up[q] = first + q < nvox && voxel_sdf(G, vmap, cam, T, i, j, k, f[q]);
     if (++i == G.dim[0]) { i = 0; if (++j == G.dim[1]) { j = 0; ++k; } }
   }
-  // the two 16-byte pairs of the lane: loaded if either voxel is updated, each updated voxel stored (a pair as one 16-byte store)
+  // the two 16-byte pairs of the lane (load_pair / store_pair): all loads before the first store
   float4 v[2];
 #pragma unroll
-  for (int p = 0; p < 2; p++) {
-    const int64_t a = first + 2 * p;
-    v[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (up[2 * p] || up[2 * p + 1]) {
-      if (a + 1 < nvox) v[p] = *reinterpret_cast<const float4*>(vol + 2 * a);
-      else { const float2 h = *reinterpret_cast<const float2*>(vol + 2 * a); v[p].x = h.x; v[p].y = h.y; }
-    }
-  }
+  for (int p = 0; p < 2; p++) v[p] = load_pair(vol, first + 2 * p, nvox, up[2 * p] || up[2 * p + 1]);
 #pragma unroll
   for (int p = 0; p < 2; p++) {
     const bool lo = up[2 * p], hi = up[2 * p + 1];
-    if (!lo && !hi) continue;
-    float* q = vol + 2 * (first + 2 * p);
     if (lo) fuse(v[p].x, v[p].y, f[2 * p], G.W);
     if (hi) fuse(v[p].z, v[p].w, f[2 * p + 1], G.W);
-    if (lo && hi) *reinterpret_cast<float4*>(q) = v[p];
-    else if (lo) *reinterpret_cast<float2*>(q) = make_float2(v[p].x, v[p].y);
-    else *reinterpret_cast<float2*>(q + 2) = make_float2(v[p].z, v[p].w);
+    store_pair(vol, first + 2 * p, v[p], lo, hi);
   }
 }
 

@@ -1,5 +1,5 @@
-// Device code shared by the volume's kernels: the voxel projection and update of the integrate (rpe_volume.hip V1, and the tsdf half of
-// rpe_color.hip C2) and the volume's field F(p) (the raycast V2 and the mesh normals of rpe_mesh.hip M4).
+// Device code shared by the volume's kernels, each rule stated once: voxel projection and update (V1, the tsdf half of C2, R2) and the
+// lane's {tsdf, w} pairs of V1 and C2; the field's cell, lerp chain and normal (F(p) of V2 and M4, C(p) of C3, both fields of rpe_mapmesh.hip).
 // Followed BIT-EXACTLY (include/rgbd_pose_hip.h Part 3, "TSDF volume"): FMA contraction is off from here to the end of the including unit.
 #pragma once
 #include "rpe_kernels.h"
@@ -61,22 +61,56 @@ __device__ __forceinline__ void blend(unsigned& rg, unsigned& bw, unsigned o, fl
   bw = f2h(b) | f2h(fminf(w + 1.0f, W)) << 16;
 }
 
+// V1, C2: the lane's pair of voxels a, a + 1 (16 bytes), loaded if either is updated (the volume's last voxel alone, as a float2)
+__device__ __forceinline__ float4 load_pair(const float* __restrict__ vol, int64_t a, int64_t nvox, bool either) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (either) {
+    if (a + 1 < nvox) v = *reinterpret_cast<const float4*>(vol + 2 * a);
+    else { const float2 h = *reinterpret_cast<const float2*>(vol + 2 * a); v.x = h.x; v.y = h.y; }
+  }
+  return v;
+}
+// ... and each updated voxel (lo: a, hi: a + 1) stored, a pair as one 16-byte store
+__device__ __forceinline__ void store_pair(float* __restrict__ vol, int64_t a, float4 v, bool lo, bool hi) {
+  if (!lo && !hi) return;
+  float* q = vol + 2 * a;
+  if (lo && hi) *reinterpret_cast<float4*>(q) = v;
+  else if (lo) *reinterpret_cast<float2*>(q) = make_float2(v.x, v.y);
+  else *reinterpret_cast<float2*>(q + 2) = make_float2(v.z, v.w);
+}
+
 // F(p): g = (p - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; known iff 0 <= i0 <= dim - 2 on every axis and all eight corner
 // weights are > 0; trilinear with lerp(x, y, t) = x + (y - x) * t along x for (j, k) = (0,0) (1,0) (0,1) (1,1), then y, then z.
 __device__ __forceinline__ float lerp(float x, float y, float t) { return x + (y - x) * t; }
-
-// the colour field's RGBA8 byte (rpe_color.hip C3, rpe_mapmesh.hip P3): q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f)
-__device__ __forceinline__ unsigned quantise(float x) { return (unsigned)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f); }
-
-__device__ __forceinline__ bool field(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz, float& F) {
+// the cell of p: i0 and a, false when i0 is out of range
+__device__ __forceinline__ bool cell(const VolumeGeometry& G, float px, float py, float pz, int i0[3], float a[3]) {
   const float gx = (px - G.o[0]) / G.s - 0.5f, gy = (py - G.o[1]) / G.s - 0.5f, gz = (pz - G.o[2]) / G.s - 0.5f;
   const float fx = floorf(gx), fy = floorf(gy), fz = floorf(gz);
   if (!(fx >= 0.0f && fx <= (float)(G.dim[0] - 2) && fy >= 0.0f && fy <= (float)(G.dim[1] - 2) && fz >= 0.0f &&
         fz <= (float)(G.dim[2] - 2)))
     return false;
-  const float ax = gx - fx, ay = gy - fy, az = gz - fz;
+  a[0] = gx - fx; a[1] = gy - fy; a[2] = gz - fz;
+  i0[0] = (int)fx; i0[1] = (int)fy; i0[2] = (int)fz;
+  return true;
+}
+// the chain's y and z steps on the four x lerps, and the whole chain on the eight corner values vIJK (I along x)
+__device__ __forceinline__ float bilerp(float c00, float c10, float c01, float c11, float ay, float az) {
+  return lerp(lerp(c00, c10, ay), lerp(c01, c11, ay), az);
+}
+__device__ __forceinline__ float trilerp(float v000, float v100, float v010, float v110, float v001, float v101, float v011, float v111,
+                                         float ax, float ay, float az) {
+  return bilerp(lerp(v000, v100, ax), lerp(v010, v110, ax), lerp(v001, v101, ax), lerp(v011, v111, ax), ay, az);
+}
+
+// the colour field's RGBA8 byte (rpe_color.hip C3, rpe_mapmesh.hip P3): q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f)
+__device__ __forceinline__ unsigned quantise(float x) { return (unsigned)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f); }
+
+__device__ __forceinline__ bool field(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz, float& F) {
+  int i0[3];
+  float a[3];
+  if (!cell(G, px, py, pz, i0, a)) return false;
   const int64_t sy = 2 * (int64_t)G.dim[0], sz = sy * G.dim[1];
-  const float* b = vol + (int64_t)(int)fz * sz + (int64_t)(int)fy * sy + 2 * (int64_t)(int)fx;
+  const float* b = vol + (int64_t)i0[2] * sz + (int64_t)i0[1] * sy + 2 * (int64_t)i0[0];
   const float2 v000 = *reinterpret_cast<const float2*>(b), v100 = *reinterpret_cast<const float2*>(b + 2);
   const float2 v010 = *reinterpret_cast<const float2*>(b + sy), v110 = *reinterpret_cast<const float2*>(b + sy + 2);
   const float2 v001 = *reinterpret_cast<const float2*>(b + sz), v101 = *reinterpret_cast<const float2*>(b + sz + 2);
@@ -84,26 +118,26 @@ __device__ __forceinline__ bool field(const float* __restrict__ vol, const Volum
   if (!(v000.y > 0.0f && v100.y > 0.0f && v010.y > 0.0f && v110.y > 0.0f && v001.y > 0.0f && v101.y > 0.0f && v011.y > 0.0f &&
         v111.y > 0.0f))
     return false;
-  const float c00 = lerp(v000.x, v100.x, ax), c10 = lerp(v010.x, v110.x, ax), c01 = lerp(v001.x, v101.x, ax), c11 = lerp(v011.x, v111.x, ax);
-  const float c0 = lerp(c00, c10, ay), c1 = lerp(c01, c11, ay);
-  F = lerp(c0, c1, az);
+  F = trilerp(v000.x, v100.x, v010.x, v110.x, v001.x, v101.x, v011.x, v111.x, a[0], a[1], a[2]);
   return true;
 }
 
-// the model normal at world point (px, py, pz): the central differences F(p + s e) - F(p - s e) per axis divided by
-// sqrtf(x*x + y*y + z*z); false (the caller leaves NaN) if any of the six samples is unknown or the length is 0
+// the normal from the central differences g = F(p + s e) - F(p - s e): g / sqrtf(x*x + y*y + z*z); false (NaN stays) if the length is 0
+__device__ __forceinline__ bool unit_normal(float gx, float gy, float gz, float& nx, float& ny, float& nz) {
+  const float len = sqrtf(gx * gx + gy * gy + gz * gz);
+  if (!(len > 0.0f)) return false;
+  nx = gx / len; ny = gy / len; nz = gz / len;
+  return true;
+}
+
+// the model normal at world point (px, py, pz); false also if any of the six samples is unknown
 __device__ __forceinline__ bool field_normal(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz,
                                              float& nx, float& ny, float& nz) {
   const float s = G.s;
   float a, b, c, d, e, f;
   const bool ok = field(vol, G, px + s, py, pz, a) && field(vol, G, px - s, py, pz, b) && field(vol, G, px, py + s, pz, c) &&
                   field(vol, G, px, py - s, pz, d) && field(vol, G, px, py, pz + s, e) && field(vol, G, px, py, pz - s, f);
-  if (!ok) return false;
-  const float gx = a - b, gy = c - d, gz = e - f;
-  const float len = sqrtf(gx * gx + gy * gy + gz * gz);
-  if (!(len > 0.0f)) return false;
-  nx = gx / len; ny = gy / len; nz = gz / len;
-  return true;
+  return ok && unit_normal(a - b, c - d, e - f, nx, ny, nz);
 }
 
 }  // namespace

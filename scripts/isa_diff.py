@@ -4,8 +4,9 @@
 
 OLD.o / NEW.o are `hipcc -c` objects of the same unit (for example rpe_volume.o of the parent commit and of this tree).  Every kernel
 whose mangled name contains one of the substrings (all kernels when none is given) is disassembled from both; each instruction is
-reduced to its text with v/s/a registers, register ranges and branch labels replaced by placeholders and addresses dropped.  Prints
-one line per kernel, "same" or the first differing instruction, and exits 1 if any kernel differs or is missing from either side."""
+reduced to its text with v/s/a registers, register ranges and branch labels replaced by placeholders and addresses dropped; so is the
+pc-relative literal of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 (the distance to a constant table, which moves when
+anything in the unit changes size).  Prints one line per kernel, "same" or the first differing instruction, and exits 1 if any kernel differs or is missing from either side."""
 import os
 import re
 import sys
@@ -15,10 +16,21 @@ import isa_tools as T  # noqa: E402
 
 REG = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
 LABEL = re.compile(r"\bL\d+\b")
+LITERAL = re.compile(r",\s*(0x[0-9a-f]+|-?\d+)$")
 
 
 def normalise(body):
-    return [LABEL.sub("L", REG.sub(lambda m: m.group(1) + "#", i.text)) for i in body]
+    out, pc = [], 0   # pc: how many of the two adds behind an s_getpc_b64 are still to come
+    for i in body:
+        t = i.text
+        if t.startswith("s_getpc_b64"):
+            pc = 2
+        elif pc and t.startswith(("s_add_u32", "s_addc_u32")):
+            t, pc = LITERAL.sub(", pcrel", t), pc - 1
+        else:
+            pc = 0   # only the pair directly behind the s_getpc_b64
+        out.append(LABEL.sub("L", REG.sub(lambda m: m.group(1) + "#", t)))
+    return out
 
 
 def main(argv):
