@@ -34,7 +34,7 @@ FILTER_MAX_RADIUS = 4
 GRAPH_RECORD = 92
 FUSE_CLEAR, FUSE_COLOR, FUSE_NO_CULL = 1, 2, 4
 
-# every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi.py)
+# every symbol include/rgbd_pose_hip.h declares (checked by tests/test_abi_and_host.py)
 SYMBOLS = [
     "ao", "ao_ransac", "py2c",
     "rpe_abi_version", "rpe_last_error", "rpe_device_count", "rpe_create", "rpe_destroy", "rpe_synchronize",

@@ -1,20 +1,15 @@
 """Compile the HIP backend for gfx950 in-tree: rgbd_pose_estimation_amd/lib/librgbdpose_hip.so.
 
-hipcc cross-compiles without a GPU.  Kernel units (shared device code in csrc/rpe_reduce.hpp and csrc/rpe_residuals.hpp; the front end's
-bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp):
-csrc/rpe_normal_eq.hip (K1-K3 Gauss-Newton normal equations + the resident form), csrc/rpe_icp.hip (fused ICP rounds),
-csrc/rpe_joint.hip (joint normal equations), csrc/rpe_score.hip (K4 scoring, K4b masks), csrc/rpe_nl.hip (K1' moments, K5, publish
-kernels), csrc/rpe_frontend.hip (depth-frame front end), csrc/rpe_filter.hip (the bilateral depth filter in front of it), csrc/rpe_volume.hip (TSDF volume: integrate, raycast), csrc/rpe_mesh.hip (marching cubes over the volume), csrc/rpe_color.hip (colour of the volume: frame
-colour, colour integrate, colour sampling), csrc/rpe_photo.hip (photometric term beside ICP: intensity maps, the RGB-D round), csrc/rpe_feature.hip (keypoints,
-descriptors and matches for relocalisation), csrc/rpe_feature_oriented.hip (the oriented descriptor: moments, angle bin, steered tests), csrc/rpe_feature_scale.hip (the scale levels: the detector and both descriptors over a ladder of resampled images in one index space), csrc/rpe_keyframe.hip (the keyframe store: snapshot, the batched match of a frame
-against every keyframe, count and rank, gather), csrc/rpe_graph.hip (the keyframe graph: pair lists of keyframe-to-keyframe matches,
-the joint Gauss-Newton round over every edge, the store rewritten at the corrected poses), csrc/rpe_rebuild.hip (the volume rebuilt from the keyframes: the
-depth packed beside a keyframe, a list of keyframes fused in one pass over the voxels), csrc/rpe_register.hip (colour registration: a separate colour
-camera reprojected onto the depth frame through a z-buffer), csrc/rpe_shift.hip (the moving volume: the TSDF and colour volume shifted by whole voxels into a spare), csrc/rpe_archive.hip (the volume archive: which leaving bricks are non-zero, bricks gathered into a pool of slots and scattered back), csrc/rpe_mapmesh.hip (the map mesh: marching cubes over the listed bricks of the window and the archive, a workgroup per brick), csrc/rpe_hypotheses.hip (batched hypothesis generation),
-csrc/rpe_prosac.hip (PROSAC order: top-k select + sort); the host units behind include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp
-lists them: rpe_context.hip, rpe_receive.hip, rpe_capi.hip = the thin C-ABI shim, rpe_refine.hip, rpe_session.hip, rpe_dist.hip,
-rpe_frontend_api.hip, rpe_volume_api.hip, rpe_mesh_api.hip, rpe_color_api.hip, rpe_photo_api.hip, rpe_feature_api.hip, rpe_keyframe_api.hip, rpe_graph_api.hip, rpe_rebuild_api.hip, rpe_register_api.hip, rpe_shift_api.hip, rpe_archive_api.hip, rpe_mapmesh_api.hip; csrc/rpe_devbuf.hpp owns their device memory, csrc/rpe_frontend_host.hpp holds what the Part 3 units share), csrc/library.cpp (reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines),
-csrc/rpe_hostex.cpp (host-side all-reduce between the rank processes of one node).  The units compile in parallel (RPE_BUILD_JOBS, default 6)."""
+hipcc cross-compiles without a GPU.  UNITS below is the manifest of the library: every compiled unit once, in link order, with its
+kind and what it holds.  Kernel units share device code in csrc/rpe_reduce.hpp and csrc/rpe_residuals.hpp and the front end's
+bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp; each names one of its kernels
+with RPE_PRELOAD (csrc/rpe_kernels.h), through which rpe_create loads its code object.  Host units are the C-ABI side behind
+include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp lists them; csrc/rpe_devbuf.hpp owns their device memory,
+csrc/rpe_frontend_host.hpp holds what the Part 3 units share).  What each unit must satisfy is the gate table of tests/unit_gates.py.
+
+{units}
+
+The units compile in parallel (RPE_BUILD_JOBS, default 6)."""
 from __future__ import annotations
 
 import os
@@ -26,7 +21,57 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "librgbdpose_hip.so")
-SOURCES = ["rpe_normal_eq.hip", "rpe_icp.hip", "rpe_joint.hip", "rpe_score.hip", "rpe_nl.hip", "rpe_frontend.hip", "rpe_filter.hip", "rpe_volume.hip", "rpe_mesh.hip", "rpe_color.hip", "rpe_photo.hip", "rpe_feature.hip", "rpe_feature_oriented.hip", "rpe_feature_scale.hip", "rpe_keyframe.hip", "rpe_graph.hip", "rpe_rebuild.hip", "rpe_register.hip", "rpe_shift.hip", "rpe_archive.hip", "rpe_mapmesh.hip", "rpe_hypotheses.hip", "rpe_prosac.hip", "rpe_context.hip", "rpe_receive.hip", "rpe_capi.hip", "rpe_refine.hip", "rpe_session.hip", "rpe_dist.hip", "rpe_frontend_api.hip", "rpe_volume_api.hip", "rpe_mesh_api.hip", "rpe_color_api.hip", "rpe_photo_api.hip", "rpe_feature_api.hip", "rpe_keyframe_api.hip", "rpe_graph_api.hip", "rpe_rebuild_api.hip", "rpe_register_api.hip", "rpe_shift_api.hip", "rpe_archive_api.hip", "rpe_mapmesh_api.hip", "library.cpp", "rpe_hostex.cpp"]
+# (source under csrc/, kind, what it holds).  kind: "kernel" = hipcc, must hold device code; "host" = hipcc, must hold none; "cpp" = g++
+UNITS = [
+    ("rpe_normal_eq.hip", "kernel", "K1-K3 Gauss-Newton normal equations + the resident form"),
+    ("rpe_icp.hip", "kernel", "fused ICP rounds"),
+    ("rpe_joint.hip", "kernel", "joint normal equations"),
+    ("rpe_score.hip", "kernel", "K4 scoring, K4b masks"),
+    ("rpe_nl.hip", "kernel", "K1' moments, K5, publish kernels"),
+    ("rpe_frontend.hip", "kernel", "depth-frame front end"),
+    ("rpe_filter.hip", "kernel", "the bilateral depth filter in front of it"),
+    ("rpe_volume.hip", "kernel", "TSDF volume: integrate, raycast"),
+    ("rpe_mesh.hip", "kernel", "marching cubes over the volume"),
+    ("rpe_color.hip", "kernel", "colour of the volume: frame colour, colour integrate, colour sampling"),
+    ("rpe_photo.hip", "kernel", "photometric term beside ICP: intensity maps, the RGB-D round"),
+    ("rpe_feature.hip", "kernel", "keypoints, descriptors and matches for relocalisation"),
+    ("rpe_feature_oriented.hip", "kernel", "the oriented descriptor: moments, angle bin, steered tests"),
+    ("rpe_feature_scale.hip", "kernel", "the scale levels: the detector and both descriptors over a ladder of resampled images in one index space"),
+    ("rpe_keyframe.hip", "kernel", "the keyframe store: snapshot, the batched match of a frame against every keyframe, count and rank, gather"),
+    ("rpe_graph.hip", "kernel", "the keyframe graph: pair lists of keyframe-to-keyframe matches, the joint Gauss-Newton round over every edge, "
+                                "the store rewritten at the corrected poses"),
+    ("rpe_rebuild.hip", "kernel", "the volume rebuilt from the keyframes: the depth packed beside a keyframe, a list of keyframes fused in one "
+                                  "pass over the voxels"),
+    ("rpe_register.hip", "kernel", "colour registration: a separate colour camera reprojected onto the depth frame through a z-buffer"),
+    ("rpe_shift.hip", "kernel", "the moving volume: the TSDF and colour volume shifted by whole voxels into a spare"),
+    ("rpe_archive.hip", "kernel", "the volume archive: which leaving bricks are non-zero, bricks gathered into a pool of slots and scattered back"),
+    ("rpe_mapmesh.hip", "kernel", "the map mesh: marching cubes over the listed bricks of the window and the archive, a workgroup per brick"),
+    ("rpe_hypotheses.hip", "kernel", "batched hypothesis generation"),
+    ("rpe_prosac.hip", "kernel", "PROSAC order: top-k select + sort"),
+    ("rpe_context.hip", "host", "context life cycle, resident arrays, the preload walk"),
+    ("rpe_receive.hip", "host", "where a launch leaves its result and how the host receives it"),
+    ("rpe_capi.hip", "host", "the thin C-ABI shim"),
+    ("rpe_refine.hip", "host", "the Gauss-Newton loops"),
+    ("rpe_session.hip", "host", "resident scoring sessions"),
+    ("rpe_dist.hip", "host", "sharded contexts"),
+    ("rpe_frontend_api.hip", "host", "Part 3: depth-frame front end and ICP"),
+    ("rpe_volume_api.hip", "host", "Part 3: TSDF volume"),
+    ("rpe_mesh_api.hip", "host", "Part 3: mesh extraction"),
+    ("rpe_color_api.hip", "host", "Part 3: colour of frame, volume, model and mesh"),
+    ("rpe_photo_api.hip", "host", "Part 3: photometric term beside ICP"),
+    ("rpe_feature_api.hip", "host", "Part 3: features and relocalisation"),
+    ("rpe_keyframe_api.hip", "host", "Part 3: keyframes"),
+    ("rpe_graph_api.hip", "host", "Part 3: the keyframe graph"),
+    ("rpe_rebuild_api.hip", "host", "Part 3: the volume rebuilt from the keyframes"),
+    ("rpe_register_api.hip", "host", "Part 3: colour registration"),
+    ("rpe_shift_api.hip", "host", "Part 3: the moving volume"),
+    ("rpe_archive_api.hip", "host", "Part 3: the volume archive"),
+    ("rpe_mapmesh_api.hip", "host", "Part 3: the map mesh"),
+    ("library.cpp", "cpp", "reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines"),
+    ("rpe_hostex.cpp", "cpp", "host-side all-reduce between the rank processes of one node"),
+]
+SOURCES = [src for src, _, _ in UNITS]
+__doc__ = (__doc__ or "{units}").format(units="\n".join(f"  csrc/{src} ({kind}): {what}" for src, kind, what in UNITS))
 ARCH = "gfx950"
 LINK_RT = "--rtlib=libgcc"
 

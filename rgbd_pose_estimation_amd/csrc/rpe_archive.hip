@@ -144,9 +144,6 @@ hipError_t launch_brick_copy(bool to_pool, float* vol, unsigned short* cvol, uns
   return hipGetLastError();
 }
 
-void preload_archive() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)brick_occupancy_kernel<false>) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(brick_occupancy_kernel<false>);
 
 }  // namespace rpe

@@ -157,9 +157,6 @@ hipError_t launch_color_sample(const unsigned short* cvol, const VolumeGeometry&
   return hipGetLastError();
 }
 
-void preload_color() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)volume_integrate_color_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(volume_integrate_color_kernel);
 
 }  // namespace rpe

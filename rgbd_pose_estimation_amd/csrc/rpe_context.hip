@@ -6,6 +6,9 @@
 #include "rpe_graph.h"
 using namespace rpeh;
 namespace { thread_local std::string g_err; }
+// the kernel units' RPE_PRELOAD nodes (rpe_kernels.h): a constant-initialised head, so it is null before the first node links itself in
+namespace { const rpe::PreloadNode* g_kernel_units = nullptr; }
+rpe::PreloadNode::PreloadNode(const void* k) : kernel(k), next(g_kernel_units) { g_kernel_units = this; }
 namespace rpeh {
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -154,10 +157,10 @@ int rpe_create(rpe_context** out, int device, void* stream) {
     static bool loaded[64];
     std::lock_guard<std::mutex> g(m);
     if (device < 64 && !loaded[device]) {
-      rpe::preload_normal_eq(); rpe::preload_icp(); rpe::preload_joint(); rpe::preload_score(); rpe::preload_nl();
-      rpe::preload_frontend(); rpe::preload_hypotheses(); rpe::preload_prosac(); rpe::preload_volume(); rpe::preload_mesh();
-      rpe::preload_color(); rpe::preload_photo(); rpe::preload_feature(); rpe::preload_feature_oriented(); rpe::preload_feature_scale(); rpe::preload_keyframe();
-      rpe::preload_filter(); rpe::preload_graph(); rpe::preload_rebuild(); rpe::preload_register(); rpe::preload_shift(); rpe::preload_archive(); rpe::preload_mapmesh();
+      for (const rpe::PreloadNode* n = g_kernel_units; n; n = n->next) {
+        hipFuncAttributes a;
+        if (hipFuncGetAttributes(&a, n->kernel) != hipSuccess) (void)hipGetLastError();
+      }
       loaded[device] = true;
     }
   }

@@ -311,9 +311,6 @@ hipError_t launch_feature_gather(const MatchLists& L, int matches, const int* fp
   return hipGetLastError();
 }
 
-void preload_feature() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)feat_best_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(feat_best_kernel);
 
 }  // namespace rpe

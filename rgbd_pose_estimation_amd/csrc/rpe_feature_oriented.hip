@@ -79,9 +79,6 @@ hipError_t launch_feature_describe_oriented(const unsigned int* rgba, const unsi
   return hipGetLastError();
 }
 
-void preload_feature_oriented() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)feat_describe_oriented_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(feat_describe_oriented_kernel);
 
 }  // namespace rpe

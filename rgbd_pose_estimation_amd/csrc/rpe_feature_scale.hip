@@ -240,9 +240,6 @@ hipError_t launch_feature_detect_levels(const unsigned int* rgba, const float* v
   return hipGetLastError();
 }
 
-void preload_feature_scale() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)feat_score_levels_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(feat_score_levels_kernel);
 
 }  // namespace rpe

@@ -111,9 +111,6 @@ hipError_t launch_depth_filter(const void* d_depth, int depth_type, int width, i
   return hipGetLastError();
 }
 
-void preload_filter() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)depth_filter_kernel<float>) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(depth_filter_kernel<float>);
 
 }  // namespace rpe

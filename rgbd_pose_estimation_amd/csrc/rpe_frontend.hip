@@ -408,9 +408,6 @@ hipError_t launch_associate(const float* vmap, const float* nmap, const float* b
   return hipGetLastError();
 }
 
-void preload_frontend() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)to_world_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(to_world_kernel);
 
 }  // namespace rpe

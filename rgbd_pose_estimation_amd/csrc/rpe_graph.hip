@@ -223,9 +223,6 @@ hipError_t launch_graph_apply(const KeyframeStore& S, int K, int used, const flo
   return hipGetLastError();
 }
 
-void preload_graph() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)graph_round_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(graph_round_kernel);
 
 }  // namespace rpe

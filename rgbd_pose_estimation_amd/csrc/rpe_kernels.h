@@ -107,8 +107,15 @@ constexpr unsigned long long kResidentLostMarker = 0x7ff8dead00c0ffeeull;
 int resident_cap_device();
 // Each kernel unit is a code object of its own that the runtime loads on the first launch out of it (a few milliseconds, once per
 // process and device).  rpe_create touches one kernel of every unit so that the first frame does not pay for it in the middle of a run.
-void preload_normal_eq(); void preload_icp(); void preload_joint(); void preload_score(); void preload_nl();
-void preload_frontend(); void preload_hypotheses(); void preload_prosac(); void preload_volume(); void preload_mesh(); void preload_color();
+// Every kernel unit ends with RPE_PRELOAD(<one of its kernels>): a node that links itself into a list when the library is loaded.  The
+// head is a plain pointer, zero before any constructor runs, so the order in which the units' nodes are built does not matter;
+// rpe_context.hip defines the constructor and walks the list (a unit without the line fails tests/test_isa_resources.py).
+struct PreloadNode {
+  const void* kernel;
+  const PreloadNode* next;
+  explicit PreloadNode(const void* kernel);
+};
+#define RPE_PRELOAD(...) static const ::rpe::PreloadNode unit_kernel((const void*)(__VA_ARGS__))
 void resident_geometry(const DeviceArrays& A, int kind, int max_blocks, int* grid, int* nacc, int* max_rows, int* rows_auto);
 // The solving workgroup of an autonomous resident loop (rpe_residuals.hpp solver_loop): ONE workgroup, launched on a stream of its own
 // BEFORE the workers' kernel (launch_normal_eq_resident / launch_normal_eq_joint_resident with rt.solver = 1, same rt otherwise); nacc =
@@ -241,7 +248,6 @@ struct FilterParams { int radius; float a, b; float ws[(2 * kFilterMaxRadius + 1
 // out := the filtered metric depth of the width x height image (NaN = invalid), what F1 / F1p then read as float32 with scale 1
 hipError_t launch_depth_filter(const void* d_depth, int depth_type, int width, int height, float scale, float dmin, float dmax,
                                const FilterParams& P, float* out, hipStream_t s);
-void preload_filter();
 // ---- TSDF volume (rpe_volume.hip): voxels are float2 {tsdf, weight} at (k * dim1 + j) * dim0 + i; geometry cast from the descriptor's
 // doubles once (include/rgbd_pose_hip.h Part 3)
 struct VolumeGeometry { int dim[3]; float o[3]; float s, tr, W; };
@@ -291,7 +297,6 @@ hipError_t launch_register_splat(const float* vmap, int64_t n, const RegisterRig
 constexpr int kRegCountWords = 64;
 hipError_t launch_register_gather(const float* vmap, int64_t n, const RegisterRig& G, const unsigned int* zbuf, const unsigned int* crgba,
                                   unsigned int* out, unsigned int* count, hipStream_t s);
-void preload_register();
 // ---- photometric term (rpe_photo.hip).  P1: the frame's intensity pyramid (one float per pixel, levels concatenated as G says) from
 // its level-0 RGBA8 colour.  P2: the model's photometric map (float4 {I, gx, gy, zm} per pixel, levels concatenated) from its level-0
 // RGBA8 colour and its world vertex / normal maps; M = world -> model camera
@@ -307,7 +312,6 @@ hipError_t launch_icp_photo(const float* vmap, const float* nmap, const float* f
 // P4: rows[k * n + i], k = 0 .. 6: {r, J[0..5]} (unscaled) of frame pixel i, NaN where it has no pair
 hipError_t launch_photo_rows(const float* vmap, const float* fint, int64_t n, const float* pmap4, const Camera& mcam, const PoseF& M,
                              float dist_thr, const double* pose12, float* rows, hipStream_t s);
-void preload_photo();
 // ---- features (rpe_feature.hip): keypoints, descriptors, matches.  All integer arithmetic; ids come from scans, never from atomics.
 constexpr int kMaxKeypoints = 4096;     // RPE_MAX_KEYPOINTS
 constexpr int kFeatScoreBins = 4096;    // a score is at most 16 * 255
@@ -328,7 +332,6 @@ hipError_t launch_feature_detect(const unsigned int* rgba, const float* vmap, co
 hipError_t launch_feature_describe_oriented(const unsigned int* rgba, const unsigned short* box, int w, int h, int max_keypoints,
                                             const int* ctl, const int* kp_pix, int* kp_xy, unsigned int* kp_desc, int* kp_bin,
                                             hipStream_t s);
-void preload_feature_oriented();
 // D3 / D5 on their own (rpe_feature.hip), for a detection whose other stages are not launch_feature_detect's: both work on a linear
 // index -- chunk counts of nchunks chunks and W.hist in, W.ctl and the kept survivors' indices (in W.spix's order) and scores out
 hipError_t launch_feature_scan(const FeatureWork& W, int nchunks, int max_keypoints, hipStream_t s);
@@ -357,7 +360,6 @@ inline FeatLevels feature_levels(int w, int h, int n) {
 hipError_t launch_feature_detect_levels(const unsigned int* rgba, const float* vmap, const float* nmap, const FeatLevels& L, int threshold,
                                         int max_keypoints, const FeatureWork& W, int kind, int* kp_pix, int* kp_score, int* kp_xy,
                                         unsigned int* kp_desc, int* kp_bin, int* kp_level, int* kp_lxy, hipStream_t s);
-void preload_feature_scale();
 // per keypoint of the list A: d1, index and d2 over the list B (ties to the lower index; d1 = d2 = 257, index -1 without any)
 struct MatchLists { int *d1, *idx, *d2, *back; int *mf, *mm, *md1, *md2; float* mw; };
 hipError_t launch_feature_best(const unsigned int* desc_a, int na, const unsigned int* desc_b, int nb, int* d1, int* idx, int* d2, hipStream_t s);
@@ -367,7 +369,6 @@ hipError_t launch_feature_accept(const MatchLists& L, int nf, int max_dist, int 
 hipError_t launch_feature_gather(const MatchLists& L, int matches, const int* fpix, const int* mpix, const float* fv, const float* fn,
                                  const float* fb, const float* mv, const float* mn, float* xw, float* xc, float* bv, float* nw, float* nc,
                                  hipStream_t s);
-void preload_feature();
 // ---- keyframes (rpe_keyframe.hip): the features of many model views in one packed store, CSR-style -- keyframe k owns the keypoints
 // off[k] .. off[k + 1] - 1 of desc (8 u32 each), xw / nw (3 floats each: the world vertex / normal at the keypoint) and xy (2 ints)
 constexpr int kMaxKeyframes = 256;      // RPE_MAX_KEYFRAMES
@@ -390,7 +391,6 @@ hipError_t launch_keyframe_rank(const int* counts, int K, int* order, hipStream_
 hipError_t launch_keyframe_gather(const int* mf, const int* mm, int matches, const int* fpix, const float* fv, const float* fn,
                                   const float* fb, const KeyframeStore& S, int base, float* xw, float* xc, float* bv, float* nw, float* nc,
                                   hipStream_t s);
-void preload_keyframe();
 // ---- keyframe graph (rpe_graph.hip): edges of keyframe-to-keyframe matches beside the store, and the joint Gauss-Newton round over
 // all of them.  An edge (j, i), j > i, owns `count` pairs from `off` of the pair arrays a / b (positions inside keyframe j / keyframe
 // i); `out` = the pairs of the edges before it in (j, i) order (where the row kernel writes).
@@ -411,7 +411,6 @@ hipError_t launch_graph_rows(const GraphEdgeDev* edges, int n_edges, const int* 
                              float gate2, float* rows, hipStream_t s);
 // G4: xw <- C_k xw + c_k, nw <- C_k nw for every keypoint of the K keyframes (`used` keypoints)
 hipError_t launch_graph_apply(const KeyframeStore& S, int K, int used, const float* corr, hipStream_t s);
-void preload_graph();
 // ---- rebuilding the volume from keyframes (rpe_rebuild.hip).  A keyframe's attachment is its level-0 depth as a packed plane (one fp32
 // per pixel, NaN = invalid) and, optionally, its RGBA8 colour; a list entry of the fuse is one attachment with the camera it was taken
 // with and the pose it is fused at.  The table of a call lives in device memory (count <= kMaxKeyframes entries)
@@ -422,13 +421,11 @@ hipError_t launch_attach_pack(const float* vmap, const unsigned int* fcolor, int
 // the volume (and cvol) is taken as all zero and every voxel is written; cull = false switches the per-workgroup cull off
 hipError_t launch_volume_fuse(float* vol, unsigned short* cvol, const VolumeGeometry& G, const FuseEntry* table, int count, bool clear,
                               bool color, bool cull, hipStream_t s);
-void preload_rebuild();
 // ---- moving the volume (rpe_shift.hip).  S1: out voxel (i, j, k) := voxel (i + shift[0], j + shift[1], k + shift[2]) of vol where that
 // lies inside dim, zero bits elsewhere; cvol != nullptr: the colour volume likewise into cvol_out, in the same launch.  Out of place:
 // vol_out / cvol_out must not overlap vol / cvol.  |shift[a]| <= dim[a] (the caller clears the volume itself for a larger one)
 hipError_t launch_volume_shift(const float* vol, float* vol_out, const unsigned short* cvol, unsigned short* cvol_out, const int dim[3],
                                const int shift[3], hipStream_t s);
-void preload_shift();
 // ---- the volume archive (rpe_archive.hip): bricks of 8 x 8 x 8 voxels kept in a pool of slots, kArchiveSlotBytes per slot and volume,
 // a brick's 64 rows of 8 voxels back to back in (z, y, x) order.  Every dim is a multiple of 8.
 constexpr int kArchiveSlotBytes = 4096;
@@ -443,7 +440,6 @@ hipError_t launch_brick_occupancy(const float* vol, const unsigned short* cvol, 
 // is not below capacity is skipped
 hipError_t launch_brick_copy(bool to_pool, float* vol, unsigned short* cvol, unsigned int* pool, unsigned int* cpool, const int dim[3],
                              const int* pairs, int n, int capacity, hipStream_t s);
-void preload_archive();
 // ---- the map mesh (rpe_mapmesh.hip): marching cubes over the LISTED bricks of the map -- the window's and the archive's that lie in a
 // box of world voxels -- one workgroup per brick.  The list is one upload of kMapListBytes per brick: key (ascending: the brick's
 // coordinates in the box, bz << 34 | by << 17 | bx), src (>= 0: the window brick bx + nb0 * (by + nb1 * bz); < 0: ~slot of the pool)
@@ -471,7 +467,6 @@ hipError_t launch_map_mesh_count(const MapMeshView& M, float wmin, const MapMesh
 // sampled) = one RGBA8 per vertex
 hipError_t launch_map_mesh_emit(const MapMeshView& M, const VolumeGeometry& G, const MapMeshWorkspace& W, float* vertices, float* normals,
                                 int* triangles, unsigned int* colours, hipStream_t s);
-void preload_mapmesh();
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

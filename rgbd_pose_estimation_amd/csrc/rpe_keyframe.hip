@@ -159,9 +159,6 @@ hipError_t launch_keyframe_gather(const int* mf, const int* mm, int matches, con
   return hipGetLastError();
 }
 
-void preload_keyframe() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)kf_best_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(kf_best_kernel);
 
 }  // namespace rpe

@@ -437,9 +437,6 @@ hipError_t launch_map_mesh_emit(const MapMeshView& M, const VolumeGeometry& G, c
   return hipGetLastError();
 }
 
-void preload_mapmesh() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)map_count_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(map_count_kernel);
 
 }  // namespace rpe

@@ -227,9 +227,6 @@ hipError_t launch_mesh_emit(const float* vol, const VolumeGeometry& G, const Mes
   return hipGetLastError();
 }
 
-void preload_mesh() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)mesh_classify_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(mesh_classify_kernel);
 
 }  // namespace rpe

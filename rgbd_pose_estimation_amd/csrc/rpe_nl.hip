@@ -556,9 +556,6 @@ hipError_t launch_nl_round(const DeviceArrays& A, const double* params24, const 
   return A.dtype ? nl_round_t<double>(A, params24, rt, s, e0, e1) : nl_round_t<float>(A, params24, rt, s, e0, e1);
 }
 
-void preload_nl() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)publish_votes_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(publish_votes_kernel);
 
 }  // namespace rpe

@@ -469,9 +469,6 @@ hipError_t launch_normal_eq_resident(const DeviceArrays& A, int kind, int flags,
                  : resident_t<float>(A, kind, flags, ctl, first_tag, max_iters, rt, s, ev0, ev1);
 }
 
-void preload_normal_eq() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)gn_update_probe_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(gn_update_probe_kernel);
 
 }  // namespace rpe

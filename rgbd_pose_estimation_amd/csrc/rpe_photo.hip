@@ -346,9 +346,6 @@ hipError_t launch_photo_rows(const float* vmap, const float* fint, int64_t n, co
   return hipGetLastError();
 }
 
-void preload_photo() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)icp_photo_kernel<KIND_P2PLANE, 256>) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(icp_photo_kernel<KIND_P2PLANE, 256>);
 
 }  // namespace rpe

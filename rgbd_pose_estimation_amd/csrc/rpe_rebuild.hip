@@ -220,9 +220,6 @@ hipError_t launch_volume_fuse(float* vol, unsigned short* cvol, const VolumeGeom
   return hipGetLastError();
 }
 
-void preload_rebuild() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)attach_pack_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(attach_pack_kernel);
 
 }  // namespace rpe

@@ -133,9 +133,6 @@ hipError_t launch_register_gather(const float* vmap, int64_t n, const RegisterRi
   return hipGetLastError();
 }
 
-void preload_register() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)register_gather_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(register_gather_kernel);
 
 }  // namespace rpe

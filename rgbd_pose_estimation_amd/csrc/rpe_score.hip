@@ -1042,9 +1042,6 @@ extern "C" int rpe_debug_read_score_stats(unsigned long long* out4) {   // diagn
 }
 namespace rpe {
 #endif
-void preload_score() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)mask_kernel<float, VOTE_33, true>) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(mask_kernel<float, VOTE_33, true>);
 
 }  // namespace rpe

@@ -103,9 +103,6 @@ hipError_t launch_volume_shift(const float* vol, float* vol_out, const unsigned 
   return hipGetLastError();
 }
 
-void preload_shift() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)volume_shift_kernel<false>) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(volume_shift_kernel<false>);
 
 }  // namespace rpe

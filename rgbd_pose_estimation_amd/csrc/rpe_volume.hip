@@ -112,9 +112,6 @@ hipError_t launch_volume_raycast(const float* vol, const VolumeGeometry& G, cons
   return hipGetLastError();
 }
 
-void preload_volume() {
-  hipFuncAttributes a;
-  if (hipFuncGetAttributes(&a, (const void*)volume_integrate_kernel) != hipSuccess) (void)hipGetLastError();
-}
+RPE_PRELOAD(volume_integrate_kernel);
 
 }  // namespace rpe

@@ -1,5 +1,6 @@
 """Disassembly helpers for the ISA-level guard (tests/test_isa_guard.py): extract the gfx950 code object of a compiled unit, split it
 into kernels, and answer questions about instruction order and loops.  CPU only: llvm-objdump ships with ROCm."""
+import collections
 import os
 import re
 import subprocess
@@ -81,9 +82,29 @@ def between(body, a, b):
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 
 
+def split_symbol(demangled):
+    """(readable name, base) of a demangled kernel symbol: the name is the symbol without `void` and the parameter list, namespaces and
+    template arguments kept; the base is the function's own name without either.  `(anonymous namespace)` is no parameter list, and
+    neither is a parenthesis inside template arguments."""
+    s = demangled.replace("(anonymous namespace)", "\0")
+    s = s[5:] if s.startswith("void ") else s
+    depth, end, start, targs = 0, len(s), 0, None
+    for i, ch in enumerate(s):
+        if ch == "<":
+            targs, depth = (i if depth == 0 and targs is None else targs), depth + 1
+        elif ch == ">":
+            depth -= 1
+        elif depth == 0 and ch == "(":
+            end = i
+            break
+        elif depth == 0 and ch == ":":
+            start, targs = i + 1, None
+    return s[:end].replace("\0", "(anonymous namespace)"), s[start:end if targs is None else targs]
+
+
 def kernel_resources(obj_path):
-    """[{name (demangled), vgpr, agpr, vgpr_spill, sgpr_spill, scratch}] of every kernel in the gfx950 code object of a hipcc -c object
-    (the metadata notes of the code object: what the loader goes by).  [] for a unit without device code."""
+    """[{mangled, name, base (split_symbol), vgpr, agpr, vgpr_spill, sgpr_spill, scratch, lds}] of every kernel in the gfx950 code object
+    of a hipcc -c object (the metadata notes of the code object: what the loader goes by).  [] for a unit without device code."""
     with tempfile.TemporaryDirectory() as tmp:
         co = code_object(obj_path, tmp)
         if co is None:
@@ -96,5 +117,10 @@ def kernel_resources(obj_path):
                          sgpr_spill=g("sgpr_spill_count"), scratch=g("private_segment_fixed_size"), lds=g("group_segment_fixed_size")))
     names = demangle([r["mangled"] for r in rows])
     for r in rows:
-        r["name"] = re.sub(r"\(.*", "", names[r["mangled"]]).replace("void ", "")
+        r["name"], r["base"] = split_symbol(names[r["mangled"]])
     return rows
+
+
+def kernel_bases(obj_path):
+    """{base name: how many kernels of the unit carry it} (the instances of a template count under one base)"""
+    return dict(collections.Counter(r["base"] for r in kernel_resources(obj_path)))

@@ -10,12 +10,10 @@ import pytest
 
 import archive_cases as AC
 import archive_oracle as AO
-import isa_tools as T
 import shift_oracle as SO
-from rgbd_pose_estimation_amd import _lib as L
+import unit_gates as UG
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 SYMS = {"rpe_volume_archive", "rpe_volume_archive_info", "rpe_volume_archive_download", "rpe_volume_archive_clear"}
 ENTRY_POINTS = SYMS | {"rpe_volume_shift"}
 DIMS = (24, 16, 8)
@@ -163,39 +161,13 @@ def test_the_conditions_on_the_case(walks):
 
 
 # ---------------------------------------------------------------------------------------------- build surface
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_archive_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert ENTRY_POINTS <= exported, sorted(ENTRY_POINTS - exported)
-    assert ENTRY_POINTS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in ENTRY_POINTS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(ENTRY_POINTS)
     assert "Volume archive" in hdr and hdr.index("Volume archive: what leaves") > hdr.index("Moving volume: the window")
 
 
-def test_the_archive_kernels_do_not_spill_and_the_host_unit_has_no_device_code():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_archive.o"))
-    names = sorted(r["mangled"] for r in rows)
-    assert len(rows) == 7 and sum("brick_occupancy_kernel" in n for n in names) == 2 and sum("brick_copy_kernel" in n for n in names) == 5, names
-    assert all(r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0 and r["lds"] == 0 for r in rows), rows
-    assert all(r["vgpr"] + r["agpr"] <= 64 for r in rows), rows       # 4 chunks x 2 volumes x 4 words, their indices, little else
-    assert T.kernel_resources(os.path.join(LIB, "rpe_archive_api.o")) == []
-    from rgbd_pose_estimation_amd import build as B
-    for unit in ("rpe_archive.hip", "rpe_archive_api.hip"):
-        assert unit in B.SOURCES and unit in B.__doc__
-    assert "rpe_archive_api.hip" in open(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_host.hpp")).read()
-
-
 def test_archive_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "volume_archive.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

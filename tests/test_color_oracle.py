@@ -10,6 +10,7 @@ import pytest
 import color_cases as CC
 import color_oracle as CO
 import isa_tools as T
+import unit_gates as UG
 import volume_oracle as VO
 from frontend_util import FO, SMALL_CAM, pose12, rot
 from rgbd_pose_estimation_amd import _lib as L
@@ -17,7 +18,6 @@ from rgbd_pose_estimation_amd import mesh as M
 from rgbd_pose_estimation_amd import simulator as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 f32, f16 = np.float32, np.float16
 I12 = pose12(np.eye(3), np.zeros(3))
 SYMS = {"rpe_frame_set_color", "rpe_volume_integrate_color", "rpe_model_sample_color", "rpe_color_download", "rpe_volume_mesh_colors",
@@ -324,51 +324,23 @@ def test_ply_round_trip_keeps_colours_and_read_ply_is_unchanged(tmp_path):
     assert v0.shape == (0, 3) and t0.shape == (0, 3) and n0 is None and M.read_ply_colors(str(tmp_path / "empty.ply")).shape == (0, 4)
 
 
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_colour_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     for e in ("RPE_COLOR_RGB8 = 0", "RPE_COLOR_BGR8 = 1", "RPE_COLOR_FRAME = 0", "RPE_COLOR_MODEL = 1"):
         assert e in hdr
     assert (L.COLOR_RGB8, L.COLOR_BGR8, L.COLOR_FRAME, L.COLOR_MODEL) == (0, 1, 0, 1)
 
 
-def test_colour_kernels_do_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_color.o"))
-    names = {r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows}
-    assert names == {"frame_color", "volume_integrate_color", "color_sample"}, rows
-    assert not [(r["name"], r["vgpr_spill"]) for r in rows if r["vgpr_spill"] > 0]
-    assert not [(r["name"], r["scratch"]) for r in rows if r["scratch"] > 16]
-    assert all(r["vgpr"] + r["agpr"] <= 512 for r in rows)
-
-
-def test_colour_host_unit_has_no_device_code():
-    _built()
-    assert T.kernel_resources(os.path.join(LIB, "rpe_color_api.o")) == []
-
-
 def test_volume_kernels_keep_their_instructions_beside_the_colour_integrate():
     """V1 and C2 share voxel_project / fuse (rpe_volume_field.hpp): the tsdf half of C2 is V1's code, and V1 still carries no colour"""
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_volume.o"))
-    assert {r["mangled"].split("volume_")[1].split("_kernel")[0] for r in rows} == {"integrate", "raycast"}
+    UG.built()
+    assert T.kernel_bases(UG.obj("rpe_volume.hip")) == {"volume_integrate_kernel": 1, "volume_raycast_kernel": 1}
     src = open(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_color.hip")).read()
     assert "voxel_project(" in src and "fuse(" in src
 
 
 def test_colour_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "volume_color.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

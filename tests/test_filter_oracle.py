@@ -1,7 +1,7 @@
 """CPU: the numpy statement of the depth filter (tests/filter_oracle.py) against itself -- constant images, NaN centres, steps, the
 window's bounds, the spatial table -- the figures of tests/filter_cases.py recomputed (what a depth sensor's noise does to the frame's
 normals and to the tracking loop, and what the filter makes of it), and the cross-compiled library: exports, header, argument errors,
-ISA resources of the new kernel, the C++ driver."""
+the unit the kernel lives in, the C++ driver."""
 import ctypes as C
 import math
 import os
@@ -14,11 +14,11 @@ import filter_cases as FC
 import filter_oracle as FLO
 import isa_tools as T
 import pyramid_oracle as PO
+import unit_gates as UG
 import volume_cases as VC
 from rgbd_pose_estimation_amd import _lib as L, simulator as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 SYMS = {"rpe_frame_set_filter", "rpe_frame_get_filter"}
 F = np.float32
 FILTERS = [(1, 0.8, 0.01, 0.02), (3, 2.0, 0.01, 0.02), (4, 2.5, 0.0072, 0.0114), (4, 3.0, 0.05, 0.0)]
@@ -183,20 +183,8 @@ def test_gpu_cases_have_what_they_claim():
 
 
 # ---------------------------------------------------------------------------------------------- the cross-compiled library
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_filter_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     assert "typedef struct { int radius; double sigma_space, depth_cut, depth_cut_z2; } rpe_depth_filter;" in hdr
     assert "RPE_FILTER_MAX_RADIUS = 4" in hdr and L.FILTER_MAX_RADIUS == FLO.MAX_RADIUS == 4
     assert "out of scope" in hdr.split("Depth filter")[1].split("TSDF volume")[0]       # raw fusion beside filtered tracking
@@ -206,29 +194,24 @@ def test_header_and_library_export_the_filter_entry_points():
 
 def test_filter_arguments_are_checked_before_anything_else():
     """the argument checks need no device: a null context and a null output are refused on any machine"""
-    _built()
+    UG.built()
     f = L.RpeDepthFilter(3, 2.0, 0.01, 0.02)
     assert L.lib().rpe_frame_set_filter(None, C.byref(f)) == L.RPE_ERR_ARG
     assert L.lib().rpe_frame_get_filter(None, C.byref(f)) == L.RPE_ERR_ARG
 
 
 def test_filter_unit_holds_the_filter_alone_and_does_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_filter.o"))
-    names = sorted(r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("EEv")[0] for r in rows)
-    assert names == ["depth_filter_kernelIf", "depth_filter_kernelIt"], rows      # one kernel, float and unsigned short raw depth
-    for r in rows:
-        assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0, r
-        # the build shows 6 560 B of LDS ((32 + 8) rows of 41 floats) and 38 VGPRs.  Two 256-thread workgroups on a CU need
-        # 2 waves per SIMD: <= 256 VGPRs each and <= 80 KiB of LDS each; the bounds below leave that far behind (8 waves per SIMD)
-        assert r["lds"] == 40 * 41 * 4 and r["lds"] <= 8 * 1024, r
-        assert r["vgpr"] + r["agpr"] <= 64, r
-    frontend = T.kernel_resources(os.path.join(LIB, "rpe_frontend.o"))
-    assert len(frontend) >= 7 and not any("filter" in r["mangled"] for r in frontend)
+    """the unit's design: the filter's two instances in a unit of their own, none in the front end's.  Its spills, scratch, LDS and registers
+    are its entry in tests/unit_gates.py"""
+    UG.built()
+    names = sorted(r["name"].rsplit("::", 1)[1] for r in T.kernel_resources(UG.obj("rpe_filter.hip")))
+    assert names == ["depth_filter_kernel<float>", "depth_filter_kernel<unsigned short>"], names      # one kernel, both raw depth types
+    frontend = T.kernel_bases(UG.obj("rpe_frontend.hip"))
+    assert sum(frontend.values()) >= 7 and not any("filter" in b for b in frontend), frontend
 
 
 def test_filter_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "depth_filter.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

@@ -155,18 +155,6 @@ def test_graph_solve_refuses_a_rank_deficient_edge():
     assert ei.value.code == L.RPE_ERR_DEGENERATE
 
 
-def test_the_graph_kernels_do_not_spill():
-    """the register gate of tests/test_isa_resources.py on the graph unit: no vector spills, no scratch"""
-    import os
-    import isa_tools as T
-    from rgbd_pose_estimation_amd import build as B
-    obj = os.path.join(os.path.dirname(B.LIB), "rpe_graph.o")
-    if not os.path.exists(obj):
-        B.build()
-    rows = T.kernel_resources(obj)
-    assert len(rows) == 4 and all(r["vgpr_spill"] == 0 and r["scratch"] == 0 for r in rows), rows
-
-
 def test_the_fp32_rows_are_not_fused():
     """the rows' operation order rounds every product and sum on its own (tests/graph_oracle.py rotate / transform): no kernel of the
     unit may hold an fp32 multiply-add -- the fp64 sums behind the rows may fuse, a product of two fp32 numbers is exact there"""

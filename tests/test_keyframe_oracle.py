@@ -1,6 +1,6 @@
 """CPU: the numpy statement of the keyframe store (tests/keyframe_oracle.py) against tests/feature_oracle.py and against itself -- the
 figures of tests/keyframe_cases.py recomputed, the rules of the ranking, relocalisation against eight keyframes end to end in the
-oracles -- and the cross-compiled library: exports, header, ISA resources of the new kernels, the C++ driver compiles."""
+oracles -- and the cross-compiled library: exports, header, the C++ driver compiles."""
 import os
 import subprocess
 from types import SimpleNamespace
@@ -10,15 +10,14 @@ import pytest
 
 import feature_cases as FC
 import feature_oracle as FE
-import isa_tools as T
 import keyframe_cases as KC
 import keyframe_oracle as KO
 import photo_cases as PC
+import unit_gates as UG
 import volume_cases as VC
 from rgbd_pose_estimation_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 SYMS = {"rpe_keyframe_add", "rpe_keyframe_add_host", "rpe_keyframe_info", "rpe_keyframe_download", "rpe_keyframes_count",
         "rpe_keyframes_clear", "rpe_keyframes_query", "rpe_keyframe_match", "rpe_relocalize_keyframes"}
 QUERIES = range(len(KC.KF_MOTIONS))
@@ -170,45 +169,15 @@ def test_flat_frame_is_degenerate(oracle):
 
 
 # ---------------------------------------------------------------------------------------------- the cross-compiled library
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_keyframe_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     assert "RPE_MAX_KEYFRAMES = 256" in hdr and L.MAX_KEYFRAMES == KO.MAX_KEYFRAMES == 256
     assert "no keyframe store yet" not in hdr and "Removing ONE keyframe is out of scope" in hdr
     assert L.lib().rpe_abi_version() == 1
 
 
-def test_keyframe_kernels_do_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_keyframe.o"))
-    names = sorted(r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows)
-    assert names == ["kf_best", "kf_gather", "kf_rank", "kf_snapshot"], rows
-    assert not [(r["mangled"], r["vgpr_spill"], r["sgpr_spill"]) for r in rows if r["vgpr_spill"] > 0 or r["sgpr_spill"] > 0]
-    assert not [(r["mangled"], r["scratch"]) for r in rows if r["scratch"] > 0]
-    assert all(r["vgpr"] + r["agpr"] <= 128 for r in rows)
-    assert max(r["lds"] for r in rows) <= 16 * 1024
-
-
-def test_keyframe_host_unit_has_no_device_code():
-    _built()
-    assert T.kernel_resources(os.path.join(LIB, "rpe_keyframe_api.o")) == []
-    assert os.path.getsize(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_keyframe_api.hip")) < 40 * 1024
-    assert os.path.getsize(os.path.join(LIB, "librgbdpose_hip.so")) < 10 * 1024 * 1024
-
-
 def test_keyframe_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "keyframe_reloc.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

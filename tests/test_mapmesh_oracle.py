@@ -1,23 +1,20 @@
 """CPU: the map mesh as tests/mapmesh_oracle.py states it.  The permutation into brick order is a bijection that keeps every triangle;
 the window's extent gives the window's own mesh; a map meshed as two boxes loses exactly the cubes across the cut; the bounds with
 negative world bricks; the figures of the use case of tests/mapmesh_cases.py recomputed; and the build surface: exported symbols, the
-header, registers and LDS of the new kernel unit, the C++ driver."""
+header, the C++ driver."""
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
-import isa_tools as T
 import mapmesh_cases as MC
 import mapmesh_oracle as MM
 import mesh_oracle as MO
 import shift_cases as SC
-from rgbd_pose_estimation_amd import _lib as L
+import unit_gates as UG
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 ENTRY_POINTS = {"rpe_volume_map_bounds", "rpe_volume_map_mesh"}
 
 
@@ -122,44 +119,14 @@ def test_the_condition_on_the_case(use_case):
 
 
 # ---------------------------------------------------------------------------------------------- build surface
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_map_mesh_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert ENTRY_POINTS <= exported, sorted(ENTRY_POINTS - exported)
-    assert ENTRY_POINTS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in ENTRY_POINTS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(ENTRY_POINTS)
     assert hdr.index("Map mesh: the window and the archived bricks") > hdr.index("Volume archive: what leaves")
     assert "meshing or raycasting the archive directly" not in hdr and "raycasting the archive directly" in hdr
 
 
-def test_the_map_mesh_kernels_do_not_spill_and_the_host_unit_has_no_device_code():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_mapmesh.o"))
-    names = sorted(re.search(r"map_\w+?_kernel", r["mangled"]).group(0) for r in rows)
-    assert names == ["map_colour_kernel", "map_count_kernel", "map_scan_kernel", "map_triangle_kernel", "map_vertex_kernel"], names
-    assert all(r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0 for r in rows), rows
-    lds = {re.search(r"map_\w+?_kernel", r["mangled"]).group(0): r["lds"] for r in rows}
-    # the staged region is 14 x 13 x 13 voxels of 8 bytes = 18 928 B; the count kernel adds its 729 case bytes
-    assert 18928 <= lds["map_vertex_kernel"] <= 18928 + 512 and 18928 + 729 <= lds["map_count_kernel"] <= 18928 + 729 + 1024, lds
-    assert all(v <= 65536 for v in lds.values()) and lds["map_triangle_kernel"] < 512 and lds["map_colour_kernel"] < 512
-    assert all(r["vgpr"] + r["agpr"] <= 128 for r in rows), rows
-    assert T.kernel_resources(os.path.join(LIB, "rpe_mapmesh_api.o")) == []
-    from rgbd_pose_estimation_amd import build as B
-    for unit in ("rpe_mapmesh.hip", "rpe_mapmesh_api.hip"):
-        assert unit in B.SOURCES and unit in B.__doc__
-    assert "rpe_mapmesh_api.hip" in open(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_host.hpp")).read()
-
-
 def test_map_mesh_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "volume_map_mesh.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

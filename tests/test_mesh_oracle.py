@@ -1,23 +1,19 @@
 """CPU: pins the numpy statement of the mesh extraction (tests/mesh_oracle.py) and the generated marching-cubes tables with analytic
 cases -- the tables against their rule, a plane, a sphere and a torus (closed, consistently oriented, Euler characteristic 2 and 0, on
 the surface), open boundaries at unknown voxels, min_weight, an empty volume -- and checks that the library exports the mesh entry
-points, that the mesh kernels neither spill nor carry scratch, that the mesh host unit has no device code, that write_ply round-trips
-and that the C++ driver compiles."""
+points, that write_ply round-trips and that the C++ driver compiles."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-import isa_tools as T
 import mesh_cases as MC
 import mesh_oracle as MO
-from rgbd_pose_estimation_amd import _lib as L
+import unit_gates as UG
 from rgbd_pose_estimation_amd import mesh as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
-CSRC = os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc")
 SYMS = {"rpe_volume_upload", "rpe_volume_mesh", "rpe_volume_mesh_download"}
 f32 = np.float32
 
@@ -188,41 +184,12 @@ def test_write_ply_round_trips(tmp_path):
     assert os.path.getsize(q) == len(open(q, "rb").read().split(b"end_header\n")[0]) + 11 + 12 * len(V) + 13 * len(Tri)
 
 
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_mesh_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
-
-
-def test_mesh_kernels_do_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_mesh.o"))
-    names = {r["mangled"].split("mesh_")[1].split("_kernel")[0] for r in rows}
-    assert names == {"classify", "count", "scan", "vertex", "triangle"}, rows
-    assert not [(r["name"], r["vgpr_spill"]) for r in rows if r["vgpr_spill"] > 0]
-    assert not [(r["name"], r["scratch"]) for r in rows if r["scratch"] > 16]
-    assert all(r["vgpr"] + r["agpr"] <= 512 for r in rows)
-
-
-def test_mesh_host_unit_has_no_device_code_and_stays_small():
-    _built()
-    assert T.kernel_resources(os.path.join(LIB, "rpe_mesh_api.o")) == []
-    for u in ("rpe_mesh_api.hip", "rpe_volume_api.hip", "rpe_host.hpp"):
-        assert os.path.getsize(os.path.join(CSRC, u)) < 40 * 1024, u
+    UG.check_entry_points(SYMS)
 
 
 def test_mesh_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "volume_mesh.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

@@ -1,7 +1,7 @@
 """CPU: the numpy statement of the oriented descriptor (tests/oriented_oracle.py) against itself -- the table, the tie rule, the
 quarter turns, the steered reach, bin 0 = the upright descriptor -- the figures of tests/oriented_cases.py recomputed (what a roll does
 to the upright descriptor and what the oriented one makes of it, matches and relocalisation end to end in the oracles), the case
-conditions the GPU tests rely on, and the cross-compiled library: exports, header, ISA resources of the new kernel, the C++ driver."""
+conditions the GPU tests rely on, and the cross-compiled library: exports, header, the C++ driver."""
 import os
 import subprocess
 
@@ -10,14 +10,13 @@ import pytest
 
 import feature_cases as FC
 import feature_oracle as FE
-import isa_tools as T
 import oriented_cases as OC
 import oriented_oracle as OO
+import unit_gates as UG
 import volume_cases as VC
 from rgbd_pose_estimation_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 SYMS = {"rpe_features_set_descriptor", "rpe_features_get_descriptor", "rpe_features_angles", "rpe_keyframes_descriptor"}
 
 
@@ -142,38 +141,16 @@ def test_upright_relocalisation_is_lost_under_a_roll(oracle, motion):
 
 
 # ---------------------------------------------------------------------------------------------- the cross-compiled library
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_descriptor_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     assert "RPE_DESC_UPRIGHT = 0, RPE_DESC_ORIENTED = 1" in hdr and (L.DESC_UPRIGHT, L.DESC_ORIENTED) == (0, 1)
     assert " ".join(str(c) for c in OO.COS) in " ".join(hdr.replace(" *", " ").split())        # the table as the header states it
     assert "typedef struct { int threshold; int max_keypoints; } rpe_feature_options;" in hdr       # the layout stays
     assert L.lib().rpe_abi_version() == 1
 
 
-def test_oriented_kernel_does_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_feature_oriented.o"))
-    names = [r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows]
-    assert names == ["feat_describe_oriented"], rows
-    r = rows[0]
-    assert r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0 and r["lds"] == 0
-    assert r["vgpr"] + r["agpr"] <= 64                                           # one wave per keypoint: full occupancy
-
-
 def test_oriented_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "oriented_reloc.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

@@ -1,6 +1,6 @@
 """CPU: the numpy statement of the photometric term (tests/photo_oracle.py) against itself -- its Jacobian row against central
 differences of its own residual, the NaN rules on small hand-made maps, the figures of tests/photo_cases.py recomputed -- and the
-cross-compiled library: exports, header, ISA resources of the new kernels, the C++ driver compiles."""
+cross-compiled library: exports, header, the C++ driver compiles."""
 import os
 import subprocess
 
@@ -10,12 +10,12 @@ import pytest
 import isa_tools as T
 import photo_cases as PC
 import photo_oracle as PH
+import unit_gates as UG
 import volume_cases as VC
 from frontend_util import SMALL_CAM, pose12
 from rgbd_pose_estimation_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 F = np.float32
 SYMS = {"rpe_model_color_upload", "rpe_model_color_from_frame", "rpe_photo_prepare", "rpe_photo_download", "rpe_photo_normal_eq",
         "rpe_photo_rows", "rpe_icp_rgbd", "rpe_icp_pyramid_rgbd"}
@@ -191,53 +191,23 @@ def test_wall_loop_figures(oracle):
 
 
 # ---------------------------------------------------------------------------------------------- the cross-compiled library
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_photometric_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     assert "RPE_PHOTO_FRAME = 0" in hdr and "RPE_PHOTO_MODEL = 1" in hdr and (L.PHOTO_FRAME, L.PHOTO_MODEL) == (0, 1)
     assert L.lib().rpe_abi_version() == 1
-
-
-def test_photometric_kernels_do_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_photo.o"))
-    names = sorted(r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows)
-    assert names == ["frame_intensity", "icp_photo", "icp_photo", "icp_photo", "icp_photo", "model_photo", "photo_rows"], rows
-    assert not [(r["mangled"], r["vgpr_spill"]) for r in rows if r["vgpr_spill"] > 0]
-    assert not [(r["mangled"], r["scratch"]) for r in rows if r["scratch"] > 16]
-    assert all(r["vgpr"] + r["agpr"] <= 512 for r in rows)
-
-
-def test_photometric_host_unit_has_no_device_code_and_keeps_its_size():
-    _built()
-    assert T.kernel_resources(os.path.join(LIB, "rpe_photo_api.o")) == []
-    assert os.path.getsize(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_photo_api.hip")) < 40 * 1024
-    assert os.path.getsize(os.path.join(LIB, "librgbdpose_hip.so")) < 10 * 1024 * 1024
 
 
 def test_icp_kernels_keep_their_unit():
     """the term is one new unit: the ICP unit still holds the fused and resident kernels only, and the new unit shares their
     per-pixel code (associate_pixel, pair_group) instead of restating it"""
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_icp.o"))
-    assert rows and all("icp_fused_kernel" in r["mangled"] or "icp_resident_kernel" in r["mangled"] for r in rows)
+    UG.built()
+    assert set(T.kernel_bases(UG.obj("rpe_icp.hip"))) == {"icp_fused_kernel", "icp_resident_kernel"}
     src = open(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_photo.hip")).read()
     assert "associate_pixel(" in src and "pair_group<" in src and "add_row2<" in src
 
 
 def test_photometric_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "photo_track.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

@@ -1,6 +1,6 @@
 """CPU: the volume rebuilt from keyframes, as tests/rebuild_oracle.py states it -- the figures of tests/rebuild_cases.py recomputed and
 the statement they carry (the map fused at the optimised poses is as good as the one fused at the true poses, the drifted one is
-not) --, the register gate on the new kernel unit, and the build surface: exported symbols, the header, the C++ driver."""
+not) --, and the build surface: exported symbols, the header, the C++ driver."""
 import os
 import subprocess
 
@@ -8,22 +8,16 @@ import numpy as np
 import pytest
 
 import color_oracle as CO
-import isa_tools as T
 import rebuild_cases as RC
 import rebuild_oracle as RO
+import unit_gates as UG
 import volume_cases as VC
 import volume_oracle as VO
 from rgbd_pose_estimation_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 SYMS = {"rpe_keyframe_attach_frame", "rpe_keyframe_attach_host", "rpe_keyframe_attachment_info", "rpe_keyframe_attachment_download",
         "rpe_volume_fuse_keyframes"}
-
-
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
 
 
 # ---------------------------------------------------------------------------------------------- the figures
@@ -85,39 +79,16 @@ def test_the_wide_volume_gives_the_cull_something_to_cull():
 
 
 # ---------------------------------------------------------------------------------------------- registers
-def test_the_rebuild_kernels_do_not_spill():
-    """the register gate of tests/test_isa_resources.py on the new unit: the pack kernel and the four flavours of the fuse kernel
-    (clear x colour), no vector or scalar spills, no scratch"""
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_rebuild.o"))
-    names = sorted(r["mangled"] for r in rows)
-    assert len(rows) == 5 and sum("volume_fuse_kernel" in n for n in names) == 4 and sum("attach_pack_kernel" in n for n in names) == 1, names
-    assert all(r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0 for r in rows), rows
-    assert all(r["vgpr"] + r["agpr"] <= 128 for r in rows), rows      # the registers of 4 voxels x 4 words plus one projection are few
-
-
 # ---------------------------------------------------------------------------------------------- build surface
 def test_header_and_library_export_the_rebuild_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     assert "enum { RPE_FUSE_CLEAR = 1, RPE_FUSE_COLOR = 2, RPE_FUSE_NO_CULL = 4 };" in hdr
     assert (L.FUSE_CLEAR, L.FUSE_COLOR, L.FUSE_NO_CULL) == (1, 2, 4)
     assert "the caller fuses its own" not in hdr                     # the graph section no longer sends the user away
 
 
-def test_rebuild_host_unit_has_no_device_code():
-    _built()
-    assert T.kernel_resources(os.path.join(LIB, "rpe_rebuild_api.o")) == []
-
-
 def test_rebuild_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "volume_rebuild.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

@@ -8,8 +8,7 @@ known without the device, and do not need the library: test_identity_rig_returns
 test_projection_is_the_written_expression_scalar_by_scalar, test_z_buffer_hides_the_far_one_of_two_points_on_one_ray,
 test_bilinear_sample_and_quantise_on_a_ramp, test_integrate_gate_is_color_integrate_where_alpha_is_set_and_nothing_where_it_is_not,
 test_registration_figures and test_accuracy_figures (the last three with the simulator's distorted camera).  Those that NEED THE
-FEATURE in the sources: test_render_rgb_with_distortion_inverts_the_forward_model (simulator), the export, kernel-resource,
-host-unit and C++ driver tests (library, header, ctypes, DepthFrontEnd.hpp).  Everything on the device is in
+FEATURE in the sources: test_render_rgb_with_distortion_inverts_the_forward_model (simulator), the export and C++ driver tests (library, header, ctypes, DepthFrontEnd.hpp).  Everything on the device is in
 tests/test_gpu_register.py."""
 import os
 import subprocess
@@ -18,9 +17,9 @@ import numpy as np
 
 import color_cases as CC
 import color_oracle as CO
-import isa_tools as T
 import register_cases as RC
 import register_oracle as RO
+import unit_gates as UG
 import volume_cases as VC
 import volume_oracle as VO
 from frontend_util import FO, SMALL_CAM, rot
@@ -28,7 +27,6 @@ from rgbd_pose_estimation_amd import _lib as L
 from rgbd_pose_estimation_amd import simulator as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 f32 = np.float32
 
 
@@ -222,40 +220,16 @@ def test_integrate_gate_is_color_integrate_where_alpha_is_set_and_nothing_where_
     assert np.all(RO.integrate(G.empty(), CO.empty(G), G, V, none, SMALL_CAM, p)[1] == 0)
 
 
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_entry_point():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert "rpe_frame_register_color" in exported and "rpe_frame_register_color" in L.SYMBOLS
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    assert "int rpe_frame_register_color(" in hdr and "} rpe_color_rig;" in hdr
+    hdr = UG.check_entry_points({"rpe_frame_register_color"})
+    assert "} rpe_color_rig;" in hdr
     import ctypes as C
     # the ctypes mirror has the C struct's layout: camera 40 bytes, 5 + 12 + 1 doubles, an int padded to 8, 2 doubles
     assert C.sizeof(L.ColorRig) == 40 + 8 * 18 + 8 + 16 and L.ColorRig.cell.offset == 40 + 8 * 18 and L.ColorRig.occl_tol.offset == 40 + 8 * 19
 
 
-def test_register_kernels_do_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_register.o"))
-    names = {r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows}
-    assert names == {"register_splat", "register_gather"}, rows
-    assert not [(r["name"], r["vgpr_spill"]) for r in rows if r["vgpr_spill"] > 0]
-    assert not [(r["name"], r["scratch"]) for r in rows if r["scratch"] > 0]
-    assert all(r["vgpr"] + r["agpr"] <= 512 for r in rows)
-
-
-def test_register_host_unit_has_no_device_code():
-    _built()
-    assert T.kernel_resources(os.path.join(LIB, "rpe_register_api.o")) == []
-
-
 def test_register_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "register_color.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

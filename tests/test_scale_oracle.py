@@ -1,7 +1,7 @@
 """CPU: the numpy statement of the scale levels (tests/scale_oracle.py) against itself -- sizes, weights, centres, one level = the
 stage as it was -- the figures of tests/scale_cases.py recomputed (what moving closer does to a one-level detection and what four levels
 make of it, matches and relocalisation end to end in the oracles), the case conditions the GPU tests rely on, and the cross-compiled
-library: exports, header, ISA resources of the new kernels, the C++ driver."""
+library: exports, header, the C++ driver."""
 import os
 import subprocess
 
@@ -11,17 +11,16 @@ import pytest
 import feature_cases as FC
 import feature_edge_cases as FEC
 import feature_oracle as FE
-import isa_tools as T
 import keyframe_cases as KC
 import oriented_oracle as OO
 import scale_cases as SC
 import scale_oracle as SO
+import unit_gates as UG
 import volume_cases as VC
 from frontend_util import SMALL_CAM
 from rgbd_pose_estimation_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 SYMS = {"rpe_features_set_levels", "rpe_features_get_levels", "rpe_features_scale"}
 
 
@@ -230,20 +229,8 @@ def test_mixed_cameras_match_across_levels():
 
 
 # ---------------------------------------------------------------------------------------------- the cross-compiled library
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_scale_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     flat = " ".join(hdr.replace(" *", " ").split())
     assert "Scale levels" in flat and "1 / 1, 2 / 3, 1 / 2, 1 / 3" in flat and "floor(((2 u + 1) q - p) / (2 p))" in flat
     assert "no suppression across levels" in flat and "no level above scale 1" in flat and "quantised to level-0 pixels" in flat
@@ -254,26 +241,14 @@ def test_header_and_library_export_the_scale_entry_points():
 
 def test_level_arguments_are_checked_before_anything_else():
     """the argument checks need no device: a null context and a null output are refused on any machine"""
-    _built()
+    UG.built()
     lib = L.lib()
     assert lib.rpe_features_set_levels(None, 2) == L.RPE_ERR_ARG and lib.rpe_features_get_levels(None, None) == L.RPE_ERR_ARG
     assert lib.rpe_features_scale(None, 0, None, None) == L.RPE_ERR_ARG
 
 
-def test_scale_kernels_do_not_spill():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_feature_scale.o"))
-    names = sorted(r["mangled"].split("_GLOBAL__N_1")[1].lstrip("0123456789").split("_kernel")[0] for r in rows)
-    assert names == ["feat_compact_levels", "feat_describe_levels", "feat_describe_oriented_levels", "feat_nms_levels", "feat_resample",
-                     "feat_score_levels"], rows
-    assert not [(r["mangled"], r["vgpr_spill"], r["sgpr_spill"]) for r in rows if r["vgpr_spill"] > 0 or r["sgpr_spill"] > 0]
-    assert not [(r["mangled"], r["scratch"]) for r in rows if r["scratch"] > 0]
-    assert all(r["vgpr"] + r["agpr"] <= 128 for r in rows)
-    assert max(r["lds"] for r in rows) <= 16 * 1024
-
-
 def test_scale_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "scale_reloc.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",

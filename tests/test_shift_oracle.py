@@ -9,16 +9,14 @@ from collections import Counter
 import numpy as np
 import pytest
 
-import isa_tools as T
 import mesh_oracle as MO
 import shift_cases as SC
 import shift_oracle as SO
+import unit_gates as UG
 import volume_cases as VC
 import volume_edge_cases as VE
-from rgbd_pose_estimation_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "rgbd_pose_estimation_amd", "lib")
 SYMS = {"rpe_volume_shift", "rpe_volume_geometry", "rpe_volume_follow", "rpe_volume_mesh_box"}
 DIMS = (23, 17, 19)                  # odd on every axis
 
@@ -159,37 +157,13 @@ def test_the_use_case_figures(oracle):
 
 
 # ---------------------------------------------------------------------------------------------- build surface
-def _built():
-    from rgbd_pose_estimation_amd import build as B
-    return B.build()
-
-
 def test_header_and_library_export_the_shift_entry_points():
-    lib = _built()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib]).decode()
-    exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert SYMS <= exported, sorted(SYMS - exported)
-    assert SYMS <= set(L.SYMBOLS)
-    hdr = open(os.path.join(ROOT, "include", "rgbd_pose_hip.h")).read()
-    for s in SYMS:
-        assert f"int {s}(" in hdr
+    hdr = UG.check_entry_points(SYMS)
     assert "Moving volume" in hdr
 
 
-def test_the_shift_kernels_do_not_spill_and_the_host_unit_has_no_device_code():
-    _built()
-    rows = T.kernel_resources(os.path.join(LIB, "rpe_shift.o"))
-    assert len(rows) == 2 and all("volume_shift_kernel" in r["mangled"] for r in rows), rows
-    assert all(r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["scratch"] == 0 and r["lds"] == 0 for r in rows), rows
-    assert all(r["vgpr"] + r["agpr"] <= 64 for r in rows), rows       # 4 pairs x 2 volumes x 4 words, their indices, little else
-    assert T.kernel_resources(os.path.join(LIB, "rpe_shift_api.o")) == []
-    from rgbd_pose_estimation_amd import build as B
-    assert "rpe_shift.hip" in B.SOURCES and "rpe_shift_api.hip" in B.SOURCES and "rpe_shift_api.hip" in B.__doc__
-    assert "rpe_shift_api.hip" in open(os.path.join(ROOT, "rgbd_pose_estimation_amd", "csrc", "rpe_host.hpp")).read()
-
-
 def test_shift_cpp_driver_compiles(tmp_path):
-    lib = _built()
+    lib = UG.built()
     inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
                            os.path.join(ROOT, "tests", "cpp", "volume_shift.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",
