@@ -1049,9 +1049,10 @@ int rpe_volume_mesh_box(rpe_context* ctx, double min_weight, const int32_t lo[3]
  * Lifetimes: rpe_volume_init drops the archive (pool and content).  rpe_volume_fuse_keyframes does not touch it: after a loop closure
  * has rebuilt the window at corrected poses, the archived bricks still hold the OLD poses' surface -- call rpe_volume_archive_clear.
  * rpe_volume_upload, rpe_volume_integrate and the colour calls write the window only.
- * The tracking loop: follow(granule = 8) -> if non-zero: shift -> raycast -> ICP -> integrate.
+ * The tracking loop: follow(granule = 8) -> if non-zero: shift -> map raycast ("Map raycast", below: raycasting the archive directly,
+ * beside the window) -> ICP -> integrate; with rpe_volume_raycast in its place the model shows the window only.
  * Out of scope: shifts or dims that are not multiples of 8 with the archive on; a device-side index (no host wait); spilling the pool
- * to host memory; raycasting the archive directly; moving the archived bricks under a loop-closure correction. */
+ * to host memory; moving the archived bricks under a loop-closure correction. */
 /* capacity_bricks > 0: switch the archive on with a pool of that many slots, or grow the pool to it (the content stays; a capacity
  * between the number of held bricks and the current capacity changes nothing: the pool does not shrink); 0: switch it off and free
  * everything.  RPE_ERR_ARG for a capacity below the number of held bricks, negative or above 2^24; RPE_ERR_STATE (nothing changed)
@@ -1089,8 +1090,8 @@ int rpe_volume_archive_clear(rpe_context* ctx);
  * colour volume or the pool a colour plane; rpe_volume_mesh_colors returns them for a map mesh, RPE_ERR_STATE if neither existed at
  * extraction time (for a window mesh it is unchanged).  Only the bricks of the map that lie in the box are visited, one workgroup per
  * brick; the workspace is 3 KB per such brick, nothing scales with the box.  The host waits once, for the two totals.
- * Out of scope: boxes that are not multiples of 8; raycasting or tracking against the archive; simplifying or welding the mesh; a
- * device-side brick index; dense order for the map mesh. */
+ * Out of scope: boxes that are not multiples of 8; simplifying or welding the mesh; a device-side brick index; dense order for the map
+ * mesh. */
 /* the world-voxel bounding box of the window and every held brick, in multiples of 8; RPE_ERR_STATE without a volume or when a dim or
  * a component of the total shift is not a multiple of 8 */
 int rpe_volume_map_bounds(rpe_context* ctx, int64_t lo[3], int64_t hi[3]);
@@ -1099,6 +1100,41 @@ int rpe_volume_map_bounds(rpe_context* ctx, int64_t lo[3], int64_t hi[3]);
  * on an axis, a bad min_weight, or 2^31 or more vertices */
 int rpe_volume_map_mesh(rpe_context* ctx, double min_weight, const int64_t lo[3], const int64_t hi[3], int64_t* n_vertices,
                         int64_t* n_triangles);
+
+/* ---- Map raycast: the window and the archived bricks as ONE model.  rpe_volume_raycast marches through the window's dense array, so a
+ * surface the map knows but the window no longer covers gives no model point; this call marches through the map.  The box lo <= w < hi
+ * of world voxels defines the VIRTUAL VOLUME that "Map mesh" defines (lo = hi = NULL: rpe_volume_map_bounds): dim = hi - lo,
+ * o = (float)(origin_init + (double)lo * voxel_size); voxel size, trunc and max weight are the init call's.  A map voxel holds the
+ * window's bits where the window covers it, the held brick's bits where the archive holds its world brick, {0, 0} elsewhere.
+ * THE CONTRACT: after the call the model -- vertex map, normal map, model pose and camera, one level -- is, bit for bit, what
+ * rpe_volume_raycast(pose12, cam, dmin, dmax) leaves on a fresh rpe_volume_init of that virtual volume with the map's content uploaded.
+ * The sample positions z_k = dmin + (float)k * s, the hit rule, z*, the six-sample normal and the NaN rules are the raycast's
+ * ("TSDF volume"); tests/mapray_oracle.py states the composition in numpy.  With the box equal to the window's extent o is the window's
+ * own o and the result is rpe_volume_raycast's.
+ * Colour: with RPE_MAPRAY_COLOR the model colour map is written too, and equals what rpe_model_sample_color would then leave: C(p) of
+ * the virtual colour volume -- the window's colour volume where it covers, the pool's colour plane for held bricks, zeros elsewhere.
+ * Without the flag the model colour is dropped, as after any raycast.  RPE_ERR_STATE if the flag is set and neither a colour volume
+ * nor a colour plane exists.
+ * Rules: nothing is written to the window, the archive, the geometry or the last mesh.  The archive need not be on.  Every dim and
+ * every component of the total shift must be a multiple of 8 (RPE_ERR_STATE, as rpe_volume_map_bounds); the box rules are the map
+ * mesh's (multiples of 8, 8 <= hi - lo <= 2^20), and the box may hold at most 2^24 bricks (RPE_ERR_ARG with the count in the
+ * message, decided before anything is reserved); dmin, dmax and the 2^22 samples per ray are rpe_volume_raycast's.
+ * How: the host writes a BRICK GRID, one int32 per brick of the box (x fastest; >= 0 a window brick, ~slot a held one, a sentinel for
+ * absent), from the window's extent and the archive's index, and uploads it in one copy per call: 4 B per brick of the BOX, 64 MB at
+ * the limit.  A sample whose cell starts in an absent brick is unknown without a voxel load.  An occupancy pre-pass first marks every
+ * window brick without a weight > 0 absent: exact, since F is known only where all eight corner weights are > 0, and it is the
+ * empty-space skip the window raycast does not have.  It reads the whole window once; RPE_MAPRAY_NO_SKIP switches it off and changes
+ * no bit of the result.  As measured the pre-pass does not pay in a fused room, where free space in front of a
+ * surface has a weight too: break-even at 256^3, 0.25 ms lost at 512^3; the Python and C++ wrappers pass RPE_MAPRAY_NO_SKIP unless
+ * asked.  The host does not wait.
+ * Out of scope: a device-side brick index; caching the grid between calls; boxes that are not multiples of 8; strides longer than one
+ * sample through absent space. */
+enum { RPE_MAPRAY_COLOR = 1, RPE_MAPRAY_NO_SKIP = 2 };
+/* the model := the map inside the box raycast from pose12 with camera cam over camera depths (dmin, dmax).  RPE_ERR_STATE without a
+ * volume, for unaligned dims or total shift, or for RPE_MAPRAY_COLOR without any colour; RPE_ERR_ARG for a NULL pose or camera, lo
+ * without hi, unknown flags, a bad box, more than 2^24 bricks, bad dmin / dmax: the model is as before */
+int rpe_volume_map_raycast(rpe_context* ctx, const double* pose12, const rpe_camera* cam, double dmin, double dmax,
+                           const int64_t lo[3], const int64_t hi[3], int flags);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

@@ -11,6 +11,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RPE_LIBRARY") or os.path.join(PKG, "lib", "librgbdpose_hip.so")
 
 RPE_OK, RPE_ERR_NO_DEVICE, RPE_ERR_HIP, RPE_ERR_ARG, RPE_ERR_STATE, RPE_ERR_DEGENERATE, RPE_ERR_ALIGN = 0, -1, -2, -3, -4, -5, -6
+RPE_MAPRAY_COLOR, RPE_MAPRAY_NO_SKIP = 1, 2          # flags of rpe_volume_map_raycast
 F32, F64 = 0, 1
 XW, XC, BV, NW, NC = 0, 1, 2, 3, 4
 MOD_23, MOD_33, MOD_NN = 0, 1, 2
@@ -61,7 +62,7 @@ SYMBOLS = [
     "rpe_volume_fuse_keyframes",
     "rpe_volume_shift", "rpe_volume_geometry", "rpe_volume_follow", "rpe_volume_mesh_box",
     "rpe_volume_archive", "rpe_volume_archive_info", "rpe_volume_archive_download", "rpe_volume_archive_clear",
-    "rpe_volume_map_bounds", "rpe_volume_map_mesh",
+    "rpe_volume_map_bounds", "rpe_volume_map_mesh", "rpe_volume_map_raycast",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
 ]
@@ -298,6 +299,7 @@ def lib():
         L.rpe_volume_archive_clear.argtypes = [C.c_void_p]
         L.rpe_volume_map_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_volume_map_mesh.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.rpe_volume_map_raycast.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RpeCamera), C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -441,6 +441,28 @@ class Context:
         L.check(L.lib().rpe_volume_map_bounds(self._h, _p(lo), _p(hi)))
         return lo, hi
 
+    def volume_map_raycast(self, pose12, cam, dmin: float, dmax: float, box=None, levels: int = 1, color: bool = False,
+                           skip_empty: bool = False):
+        """The model := the MAP -- the window plus the archived bricks -- raycast from pose12 with camera cam over camera depths
+        (dmin, dmax), inside box = (lo, hi) in world voxels (multiples of 8; None: volume_map_bounds): bit for bit volume_raycast of a
+        dense volume of the box holding the map's content (rpe_volume_map_raycast).  color: the model colour is sampled from the map
+        in the same pass (model_color_map() returns it; the photometric term and the features take it as any model colour).
+        skip_empty = True runs the occupancy pre-pass (flags without RPE_MAPRAY_NO_SKIP), which changes no bit; it is off here because
+        as measured it does not pay: it reads the whole window, break-even at 256^3 and 0.25 ms lost at 512^3.
+        levels > 1 also builds the model pyramid, as volume_raycast does."""
+        k = self._camera(cam)
+        p = np.array(pose12, np.float64).reshape(12)
+        flags = (L.RPE_MAPRAY_COLOR if color else 0) | (0 if skip_empty else L.RPE_MAPRAY_NO_SKIP)
+        if box is None:
+            L.check(L.lib().rpe_volume_map_raycast(self._h, _p(p), C.byref(k), float(dmin), float(dmax), None, None, flags))
+        else:
+            lo, hi = (np.ascontiguousarray(b, np.int64).reshape(3) for b in box)
+            L.check(L.lib().rpe_volume_map_raycast(self._h, _p(p), C.byref(k), float(dmin), float(dmax), _p(lo), _p(hi), flags))
+        self._model_pixels = k.width * k.height
+        if levels > 1:
+            self.model_build_pyramid(levels)
+        return self
+
     def volume_map_mesh(self, min_weight: float = 1.0, box=None):
         """Marching cubes over the MAP -- the window plus the archived bricks -- inside box = (lo, hi) in world voxels (multiples of 8;
         None: volume_map_bounds): (vertices, normals, triangles) as volume_mesh returns them, bit for bit the mesh of a dense volume
@@ -536,6 +558,14 @@ class Context:
         """Samples the colour field at the model's level-0 vertices (rpe_model_sample_color) and returns the map: (height, width, 4)
         uint8 RGBA of the model's view, A = 255 where the colour is known and (0, 0, 0, 0) where it is not."""
         L.check(L.lib().rpe_model_sample_color(self._h))
+        k = self.frame_camera(0, model=True)
+        out = np.empty((k[5], k[4], 4), np.uint8)
+        L.check(L.lib().rpe_color_download(self._h, L.COLOR_MODEL, _p(out)))
+        return out
+
+    def model_color_map(self) -> np.ndarray:
+        """The model colour map as the device holds it, nothing sampled: (height, width, 4) uint8 RGBA.  What
+        volume_map_raycast(color=True) left (model_color() would replace it with the WINDOW's colour field), or any other model colour."""
         k = self.frame_camera(0, model=True)
         out = np.empty((k[5], k[4], 4), np.uint8)
         L.check(L.lib().rpe_color_download(self._h, L.COLOR_MODEL, _p(out)))

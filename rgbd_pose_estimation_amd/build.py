@@ -28,7 +28,7 @@ UNITS = [
     ("rpe_joint.hip", "kernel", "joint normal equations"),
     ("rpe_score.hip", "kernel", "K4 scoring, K4b masks"),
     ("rpe_nl.hip", "kernel", "K1' moments, K5, publish kernels"),
-    ("rpe_frontend.hip", "kernel", "depth-frame front end"),
+    ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map"),
     ("rpe_filter.hip", "kernel", "the bilateral depth filter in front of it"),
     ("rpe_volume.hip", "kernel", "TSDF volume: integrate, raycast"),
     ("rpe_mesh.hip", "kernel", "marching cubes over the volume"),
@@ -66,7 +66,7 @@ UNITS = [
     ("rpe_register_api.hip", "host", "Part 3: colour registration"),
     ("rpe_shift_api.hip", "host", "Part 3: the moving volume"),
     ("rpe_archive_api.hip", "host", "Part 3: the volume archive"),
-    ("rpe_mapmesh_api.hip", "host", "Part 3: the map mesh"),
+    ("rpe_mapmesh_api.hip", "host", "Part 3: the map: mesh and raycast"),
     ("library.cpp", "cpp", "reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines"),
     ("rpe_hostex.cpp", "cpp", "host-side all-reduce between the rank processes of one node"),
 ]

@@ -99,7 +99,8 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_color_kernel(float
 // ---------------------------------------------------------------------------------------------- C3
 // C(p): F's cell (g, i0, a and the in-range rule: cell); known iff in range and all eight corner colour weights are > 0; each channel
 // with F's lerp chain (trilerp) on (float) of the binary16 values.  q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f)
-// (quantise).  All three: rpe_volume_field.hpp, shared with the map mesh of rpe_mapmesh.hip.
+// (quantise).  All three, and the chain from the eight corners to the byte quadruple (colour_rgba): rpe_volume_field.hpp, shared with the
+// map mesh of rpe_mapmesh.hip and the map raycast of rpe_frontend.hip.
 __global__ __launch_bounds__(kColorBlock) void color_sample_kernel(const unsigned short* __restrict__ cvol, VolumeGeometry G,
                                                                    const float* __restrict__ pts, int64_t n,
                                                                    unsigned int* __restrict__ rgba) {
@@ -115,20 +116,7 @@ __global__ __launch_bounds__(kColorBlock) void color_sample_kernel(const unsigne
     uint2 v[8];   // corner n = di + 2 dj + 4 dk
 #pragma unroll
     for (int m = 0; m < 8; m++) v[m] = *reinterpret_cast<const uint2*>(b + ((m & 4) ? sz : 0) + ((m & 2) ? sy : 0) + ((m & 1) ? 4 : 0));
-    bool known = true;
-#pragma unroll
-    for (int m = 0; m < 8; m++) known = known && h2f(v[m].y >> 16) > 0.0f;
-    if (known) {
-      float ch[3];
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        float x[8];
-#pragma unroll
-        for (int m = 0; m < 8; m++) x[m] = h2f(c == 0 ? v[m].x & 0xffffu : c == 1 ? v[m].x >> 16 : v[m].y & 0xffffu);
-        ch[c] = trilerp(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], a[0], a[1], a[2]);
-      }
-      out = quantise(ch[0]) | quantise(ch[1]) << 8 | quantise(ch[2]) << 16 | 0xff000000u;
-    }
+    out = colour_rgba(v, a);
   }
   rgba[e] = out;
 }

@@ -12,6 +12,12 @@
 //                               to_world_kernel launch over the concatenated levels
 //   F3  associate_kernel        projective data association of the frame against the model under a pose guess, with a
 //                               distance and a normal-angle gate; writes XW XC BV NW NC aligned per pixel
+//   R0  map_occupancy_kernel + R1 map_raycast_kernel: the model maps raycast from the MAP -- the window plus the archived bricks -- through
+//                               a grid of bricks (include/rgbd_pose_hip.h Part 3, "Map raycast"; host side in rpe_mapmesh_api.hip).  They
+//                               build model maps, as F2 / F2p do, contraction is off here as they need it, and every other volume unit
+//                               pins its exact set of kernels in the gate table of tests/unit_gates.py: that is why they live in this
+//                               unit.  A unit of their own comes with a gate entry of its own (0 spills, 0 scratch, no LDS; <= 128 and
+//                               <= 64 registers, which tests/test_mapray_oracle.py holds them to meanwhile).
 //
 // The reference has no such stage (its arrays come from Simulator.hpp or from the caller), so there is no reference text
 // to follow: parity is against the numpy statement of the same arithmetic that the tests hold, BIT-EXACT -- every expression below is
@@ -19,6 +25,7 @@
 // All three kernels are image-parallel and HBM/L2 streaming: one thread owns 4 consecutive pixels so that every
 // xyz-interleaved map is read and written as three 16-byte accesses per lane, like the solver kernels read them.
 #include "rpe_assoc.h"
+#include "rpe_volume_field.hpp"
 
 namespace rpe {
 
@@ -340,6 +347,125 @@ __global__ __launch_bounds__(kFeBlock) void associate_kernel(const float* __rest
   }
 }
 
+// ---------------------------------------------------------------------------------------------- R0, R1
+// The map raycast: V2 (rpe_volume.hip) on the VIRTUAL volume G of a box of world voxels, whose voxel at box index (ix, iy, iz) holds the
+// window's bits where the window covers it, the held brick's bits where the grid names a slot, {0, 0} elsewhere.  Bit for bit V2's
+// result on a dense copy of the box: the ray rule is V2's (ray_march / ray_normal), the field is F's cell, weight test and lerp chain
+// (cell / trilerp), the colour C3's (colour_rgba), all of rpe_volume_field.hpp; only where a corner's 8 bytes come from is stated here.
+constexpr int kRayTile = 16;      // as V2: 16 x 16 pixels per workgroup, 8 x 8 per wave
+
+__device__ __forceinline__ int grid_at(const MapRayView& M, int ix, int iy, int iz) {   // box index inside the box: <= 2^24 bricks
+  return M.grid[((iz >> 3) * M.nb[1] + (iy >> 3)) * M.nb[0] + (ix >> 3)];
+}
+
+// One voxel of the map at box index (ix, iy, iz), inside the box.  The window is the only holder of what it covers and is addressed by
+// the voxel's own index in it -- never through the grid, whose window entries R0 may have turned into kMapAbsent: that says "no weight
+// > 0 in here", not "all-zero bits", and the colour field reads colour weights.  Anything else is a held brick's slot or absent.  e0 =
+// the grid entry of the brick of (bx, by, bz), already read.  No address is formed outside the window's arrays or the pool's capacity
+template <bool COLOUR>
+__device__ __forceinline__ uint2 map_voxel(const MapRayView& M, int ix, int iy, int iz, int e0, int bx, int by, int bz) {
+  const int lx = ix - M.woff[0], ly = iy - M.woff[1], lz = iz - M.woff[2];
+  if ((unsigned)lx < (unsigned)M.wdim0 && (unsigned)ly < (unsigned)M.wdim1 && (unsigned)lz < (unsigned)M.wdim2) {
+    const unsigned int* p = COLOUR ? M.cvol : M.vol;
+    return p ? *reinterpret_cast<const uint2*>(p + 2 * (((int64_t)lz * M.wdim1 + ly) * M.wdim0 + lx)) : make_uint2(0u, 0u);
+  }
+  // a corner over a brick face, edge or corner: one more grid lookup
+  const int s = ((ix >> 3) == bx && (iy >> 3) == by && (iz >> 3) == bz) ? e0 : grid_at(M, ix, iy, iz);
+  int64_t w;
+  bool pooled;
+  const unsigned int* p = COLOUR ? M.cpool : M.pool;
+  if (s >= 0 || s == kMapAbsent || !p || !brick_word(M, s, ix & 7, iy & 7, iz & 7, w, pooled)) return make_uint2(0u, 0u);
+  return *reinterpret_cast<const uint2*>(p + w);
+}
+
+// the eight corners of the cell at i0 (corner n = di + 2 dj + 4 dk): where all eight lie in the window, the dense field's gathers
+template <bool COLOUR>
+__device__ __forceinline__ void map_corners(const MapRayView& M, const int i0[3], int e0, uint2 (&v)[8]) {
+  const int lx = i0[0] - M.woff[0], ly = i0[1] - M.woff[1], lz = i0[2] - M.woff[2];
+  const unsigned int* p = COLOUR ? M.cvol : M.vol;
+  if (p && (unsigned)lx < (unsigned)(M.wdim0 - 1) && (unsigned)ly < (unsigned)(M.wdim1 - 1) && (unsigned)lz < (unsigned)(M.wdim2 - 1)) {
+    const int64_t sy = 2 * (int64_t)M.wdim0, sz = sy * M.wdim1;
+    const unsigned int* b = p + (int64_t)lz * sz + (int64_t)ly * sy + 2 * (int64_t)lx;
+#pragma unroll
+    for (int n = 0; n < 8; n++) v[n] = *reinterpret_cast<const uint2*>(b + ((n & 4) ? sz : 0) + ((n & 2) ? sy : 0) + ((n & 1) ? 2 : 0));
+    return;
+  }
+  const int bx = i0[0] >> 3, by = i0[1] >> 3, bz = i0[2] >> 3;
+#pragma unroll
+  for (int n = 0; n < 8; n++) v[n] = map_voxel<COLOUR>(M, i0[0] + (n & 1), i0[1] + ((n >> 1) & 1), i0[2] + (n >> 2), e0, bx, by, bz);
+}
+
+// F(p) of the virtual volume.  The grid entry of corner 0's brick is read first: absent -- never held, or a window brick R0 found without
+// a weight > 0 -- makes corner 0's weight fail the test, so the sample is unknown without a voxel load.  That is the empty-space skip.
+__device__ __forceinline__ bool map_field(const MapRayView& M, const VolumeGeometry& G, float px, float py, float pz, float& F) {
+  int i0[3];
+  float a[3];
+  if (!cell(G, px, py, pz, i0, a)) return false;
+  const int e0 = grid_at(M, i0[0], i0[1], i0[2]);
+  if (e0 == kMapAbsent) return false;
+  uint2 v[8];
+  map_corners<false>(M, i0, e0, v);
+  bool known = true;
+#pragma unroll
+  for (int n = 0; n < 8; n++) known = known && __uint_as_float(v[n].y) > 0.0f;
+  if (!known) return false;
+  F = trilerp(__uint_as_float(v[0].x), __uint_as_float(v[1].x), __uint_as_float(v[2].x), __uint_as_float(v[3].x), __uint_as_float(v[4].x),
+              __uint_as_float(v[5].x), __uint_as_float(v[6].x), __uint_as_float(v[7].x), a[0], a[1], a[2]);
+  return true;
+}
+
+// C(p) of the virtual colour volume as RGBA8 (C3 of rpe_color.hip).  The grid is consulted for held bricks only (map_voxel), so R0's
+// verdicts on the window's bricks do not reach the colour
+__device__ __forceinline__ unsigned map_colour(const MapRayView& M, const VolumeGeometry& G, float px, float py, float pz) {
+  int i0[3];
+  float a[3];
+  if (!cell(G, px, py, pz, i0, a)) return 0u;
+  uint2 v[8];
+  map_corners<true>(M, i0, grid_at(M, i0[0], i0[1], i0[2]), v);
+  return colour_rgba(v, a);
+}
+
+__global__ __launch_bounds__(kRayTile * kRayTile) void map_raycast_kernel(MapRayView M, VolumeGeometry G, Camera cam, PoseF T, float dmin,
+                                                                          float dmax, float* __restrict__ mv, float* __restrict__ mn,
+                                                                          unsigned int* __restrict__ mc) {
+  const int tiles_x = (cam.width + kRayTile - 1) / kRayTile;
+  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const int u = (blockIdx.x % tiles_x) * kRayTile + (wave % 2) * 8 + lane % 8;
+  const int v = (blockIdx.x / tiles_x) * kRayTile + (wave / 2) * 8 + lane / 8;
+  if (u >= cam.width || v >= cam.height) return;
+  const float xn = ((float)u - cam.cx) / cam.fx, yn = ((float)v - cam.cy) / cam.fy;
+  const auto F = [&](float x, float y, float z, float& f) { return map_field(M, G, x, y, z, f); };
+  const float zh = ray_march(F, T, xn, yn, G.s, dmin, dmax);
+  float ox = qnan(), oy = qnan(), oz = qnan(), nx = qnan(), ny = qnan(), nz = qnan();
+  if (zh == zh) {
+    to_world(T, xn * zh, yn * zh, zh, ox, oy, oz);
+    (void)ray_normal(F, G.s, ox, oy, oz, nx, ny, nz);   // leaves the NaN normal where a sample is unknown
+  }
+  const int64_t pix = (int64_t)v * cam.width + u, o = 3 * pix;
+  mv[o] = ox; mv[o + 1] = oy; mv[o + 2] = oz;
+  mn[o] = nx; mn[o + 1] = ny; mn[o + 2] = nz;
+  if (mc != nullptr) mc[pix] = zh == zh ? map_colour(M, G, ox, oy, oz) : 0u;   // C of a NaN point: its cell is out of range, 0
+}
+
+// R0: one wave per brick of the window inside the box; a lane reads four 16-byte pairs of voxels of the brick's 64 rows of 8.  No weight
+// > 0 among the 512 (NaN fails the test) -> kMapAbsent.  The tsdf of such voxels is never read by anyone
+constexpr int kOccBlock = 256;
+__global__ __launch_bounds__(kOccBlock) void map_occupancy_kernel(MapRayView M) {
+  const int b = (int)blockIdx.x * (kOccBlock / 64) + (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+  if (b >= M.wbn[0] * M.wbn[1] * M.wbn[2]) return;   // the whole wave
+  const int bx = M.wb0[0] + b % M.wbn[0], by = M.wb0[1] + (b / M.wbn[0]) % M.wbn[1], bz = M.wb0[2] + b / (M.wbn[0] * M.wbn[1]);
+  bool some = false;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int c = q * 64 + lane, row = c >> 2, x = 2 * (c & 3);   // row = z * 8 + y
+    const int64_t vox = ((int64_t)(bz * 8 + (row >> 3)) * M.wdim1 + by * 8 + (row & 7)) * M.wdim0 + bx * 8 + x;
+    const uint4 p = *reinterpret_cast<const uint4*>(M.vol + 2 * vox);
+    some = some || __uint_as_float(p.y) > 0.0f || __uint_as_float(p.w) > 0.0f;
+  }
+  if (__ballot(some) == 0ull && lane == 0)
+    M.grid[((bz + (M.woff[2] >> 3)) * M.nb[1] + by + (M.woff[1] >> 3)) * M.nb[0] + bx + (M.woff[0] >> 3)] = kMapAbsent;
+}
+
 int fe_grid(int64_t n) { return (int)((n + 4 * kFeBlock - 1) / (4 * kFeBlock)); }
 
 }  // namespace
@@ -405,6 +531,20 @@ hipError_t launch_associate(const float* vmap, const float* nmap, const float* b
   hipLaunchKernelGGL(associate_kernel, dim3(fe_grid(n)), dim3(kFeBlock), 0, s, vmap, nmap, bmap, n, mv, mn, T, P, pose_dev, done, xw,
       xc, bv,
                      nw, nc, d_count);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_occupancy(const MapRayView& M, hipStream_t s) {
+  const int n = M.wbn[0] * M.wbn[1] * M.wbn[2];
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_occupancy_kernel, dim3((n + kOccBlock / 64 - 1) / (kOccBlock / 64)), dim3(kOccBlock), 0, s, M);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_raycast(const MapRayView& M, const VolumeGeometry& G, const Camera& cam, const PoseF& T, float dmin, float dmax,
+                              float* mv, float* mn, unsigned int* mc, hipStream_t s) {
+  const int tiles = ((cam.width + kRayTile - 1) / kRayTile) * ((cam.height + kRayTile - 1) / kRayTile);
+  hipLaunchKernelGGL(map_raycast_kernel, dim3(tiles), dim3(kRayTile * kRayTile), 0, s, M, G, cam, T, dmin, dmax, mv, mn, mc);
   return hipGetLastError();
 }
 

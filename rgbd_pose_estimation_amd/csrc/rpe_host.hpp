@@ -18,8 +18,9 @@
 //   rpe_shift_api.hip     Part 3: the moving volume (rpe_volume_shift / _geometry / _follow; kernel in rpe_shift.hip)
 //   rpe_archive_api.hip   Part 3: the volume archive (rpe_volume_archive / _info / _download / _clear and the two halves of a shift with the
 //                         archive on: the bricks that leave kept in a pool, the ones that return put back; kernels in rpe_archive.hip)
-//   rpe_mapmesh_api.hip   Part 3: the map mesh (rpe_volume_map_bounds / _map_mesh: the window and the archived bricks inside a box of world
-//                         voxels meshed in one extraction; the brick list and its neighbour table; kernels in rpe_mapmesh.hip)
+//   rpe_mapmesh_api.hip   Part 3: the map, mesh and raycast (rpe_volume_map_bounds / _map_mesh / _map_raycast: the window and the archived
+//                         bricks inside a box of world voxels; the mesh's brick list and neighbour table, kernels in rpe_mapmesh.hip;
+//                         the raycast's brick grid, kernels in rpe_frontend.hip)
 // Two headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
 // host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create) and rpe_frontend_host.hpp (what the
 // Part 3 units share: camera and pose casts, the solver slots, feature / match options, the relocalisers' common steps).
@@ -274,8 +275,8 @@ struct rpe_context {
       std::vector<unsigned int> h_flags;
       std::vector<int32_t> h_pairs;
     } arc;
-    // map mesh (rpe_mapmesh_api.hip): the brick list of the last rpe_volume_map_mesh on the device (keys | sources | neighbour table)
-    // and its host copy; mesh_is_map: the last mesh is a map mesh, whose colours were sampled into mc during the extraction if a colour
+    // the map (rpe_mapmesh_api.hip): the brick list of the last rpe_volume_map_mesh (keys | sources | neighbour table) or the brick grid
+    // of the last rpe_volume_map_raycast on the device, and its host copy: neither is read after its call; mesh_is_map: the last mesh is a map mesh, whose colours were sampled into mc during the extraction if a colour
     // source existed then (map_color).  The workspace is ws, shared with rpe_volume_mesh
     rpeh::DevBuf<void> map_list;
     std::vector<unsigned char> h_map_list;

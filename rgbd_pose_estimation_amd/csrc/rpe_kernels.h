@@ -467,6 +467,24 @@ hipError_t launch_map_mesh_count(const MapMeshView& M, float wmin, const MapMesh
 // sampled) = one RGBA8 per vertex
 hipError_t launch_map_mesh_emit(const MapMeshView& M, const VolumeGeometry& G, const MapMeshWorkspace& W, float* vertices, float* normals,
                                 int* triangles, unsigned int* colours, hipStream_t s);
+// ---- the map raycast (kernels in rpe_frontend.hip): V2's rays through the map inside a box of world voxels.  The BRICK GRID is one int32
+// per brick of the box, x fastest, in the codes of the map mesh's sources: >= 0 the window brick bx + nb0 * (by + nb1 * bz), < 0 the pool's
+// slot ~slot, kMapAbsent (no ~slot equals it: capacity <= 2^24) for a brick the map does not hold
+constexpr int kMapAbsent = -2147483647 - 1;
+struct MapRayView {
+  const unsigned int *vol, *cvol, *pool, *cpool;   // as MapMeshView
+  int wdim0, wdim1, wdim2, wnb[3], capacity;       // the window's dims, its bricks per axis, the pool's slots
+  int woff[3];                                     // the window's voxel (0, 0, 0) as an index of the box (clamped to +-2^21: far outside)
+  int nb[3];                                       // the box's bricks per axis
+  int wb0[3], wbn[3];                              // the window's bricks that lie in the box: the first, in window bricks, and how many
+  int* grid;
+};
+// R0: the window's bricks in the box that hold no weight > 0 become kMapAbsent in the grid (exact: F is known only with eight weights > 0)
+hipError_t launch_map_occupancy(const MapRayView& M, hipStream_t s);
+// R1: world vertex / normal maps as launch_volume_raycast leaves them on the dense virtual volume G of the box; mc (may be null) = the
+// RGBA8 colour field at each vertex, as launch_color_sample would leave it
+hipError_t launch_map_raycast(const MapRayView& M, const VolumeGeometry& G, const Camera& cam, const PoseF& T, float dmin, float dmax,
+                              float* mv, float* mn, unsigned int* mc, hipStream_t s);
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

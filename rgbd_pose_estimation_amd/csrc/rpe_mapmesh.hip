@@ -60,24 +60,7 @@ constexpr unsigned long long kKeyMask = (1ull << kMapKeyBits) - 1ull;
 __device__ __forceinline__ int stage_index(int lx, int ly, int lz) { return ((lz + 2) * kStY + (ly + 2)) * kStX + (lx + 2); }
 __device__ __forceinline__ int case_index(int lx, int ly, int lz) { return ((lz + 1) * 9 + (ly + 1)) * 9 + (lx + 1); }
 
-// the word index of voxel (x, y, z), each 0 .. 7, of the brick with source s, in the window's arrays (s >= 0; pooled = false) or in
-// the pool's planes (s < 0); false, and no address, for a brick index outside the window or a slot at or above the capacity.  A voxel
-// is two words in either volume ({tsdf, weight} / four binary16)
-__device__ __forceinline__ bool brick_word(const MapMeshView& M, int s, int x, int y, int z, int64_t& w, bool& pooled) {
-  pooled = s < 0;
-  if (pooled) {
-    const int slot = ~s;
-    if (slot >= M.capacity) return false;
-    w = (int64_t)slot * (kArchiveSlotBytes / 4) + 2 * ((z * 8 + y) * 8 + x);
-    return true;
-  }
-  const unsigned nb0 = (unsigned)M.wnb[0], nb1 = (unsigned)M.wnb[1];
-  if ((unsigned)s >= nb0 * nb1 * (unsigned)M.wnb[2]) return false;
-  const unsigned bx = (unsigned)s % nb0, t = (unsigned)s / nb0, by = t % nb1, bz = t / nb1;
-  const unsigned v = ((bz * 8u + (unsigned)z) * (unsigned)M.wdim1 + by * 8u + (unsigned)y) * (unsigned)M.wdim0 + bx * 8u + (unsigned)x;
-  w = 2 * (int64_t)v;   // the voxel index fits 32 bits (dims <= 1024), the word index is formed in 64
-  return true;
-}
+// where voxel (x, y, z) of the brick with source s lies: brick_word (rpe_volume_field.hpp, shared with the map raycast)
 
 // one voxel (8 bytes) of a listed brick's tsdf (COLOUR = false) or colour volume
 template <bool COLOUR>

@@ -59,10 +59,8 @@ __global__ __launch_bounds__(kVolBlock) void volume_integrate_kernel(float* __re
 // ---------------------------------------------------------------------------------------------- V2
 // F(p) and the model normal: rpe_volume_field.hpp (shared with the mesh normals of rpe_mesh.hip).
 
-// Ray of pixel (u, v): xn = ((float)u - cx) / fx, yn likewise; samples z_k = dmin + (float)k * s while z_k < dmax, each the camera
-// point (xn z, yn z, z) moved to the world (to_world).  Hit: the first k with F(z_k), F(z_k+1) known, F_k > 0 >= F_k+1:
-// z* = z_k + s * (F_k / (F_k - F_k+1)), vertex = to_world(xn z*, yn z*, z*); normal = the central differences F(pw +- s e_axis)
-// divided by sqrtf(x*x + y*y + z*z) (NaN if a sample is unknown or the length is 0).  No hit: NaN vertex and normal.
+// The ray rule -- sample positions, hit test, z*, the six-sample normal, NaN without a hit -- is ray_march / ray_normal of
+// rpe_volume_field.hpp over the dense field (shared with the map raycast of rpe_frontend.hip).
 __global__ __launch_bounds__(kRayTile * kRayTile) void volume_raycast_kernel(const float* __restrict__ vol, VolumeGeometry G, Camera cam,
                                                                              PoseF T, float dmin, float dmax, float* __restrict__ mv,
                                                                              float* __restrict__ mn) {
@@ -72,19 +70,7 @@ __global__ __launch_bounds__(kRayTile * kRayTile) void volume_raycast_kernel(con
   const int v = (blockIdx.x / tiles_x) * kRayTile + (wave / 2) * 8 + lane / 8;
   if (u >= cam.width || v >= cam.height) return;
   const float xn = ((float)u - cam.cx) / cam.fx, yn = ((float)v - cam.cy) / cam.fy;
-  const float s = G.s;
-  float zh = qnan();
-  bool prev = false;
-  float Fp = 0.0f, zp = 0.0f;
-  for (int k = 0;; k++) {
-    const float z = dmin + (float)k * s;
-    if (!(z < dmax)) break;
-    float wx, wy, wz, Fk;
-    to_world(T, xn * z, yn * z, z, wx, wy, wz);
-    const bool known = field(vol, G, wx, wy, wz, Fk);
-    if (known && prev && Fp > 0.0f && Fk <= 0.0f) { zh = zp + s * (Fp / (Fp - Fk)); break; }
-    prev = known; Fp = Fk; zp = z;
-  }
+  const float zh = ray_march([&](float x, float y, float z, float& F) { return field(vol, G, x, y, z, F); }, T, xn, yn, G.s, dmin, dmax);
   float ox = qnan(), oy = qnan(), oz = qnan(), nx = qnan(), ny = qnan(), nz = qnan();
   if (zh == zh) {
     to_world(T, xn * zh, yn * zh, zh, ox, oy, oz);

@@ -1,8 +1,10 @@
 // Device code shared by the volume's kernels, each rule stated once: voxel projection and update (V1, the tsdf half of C2, R2) and the
-// lane's {tsdf, w} pairs of V1 and C2; the field's cell, lerp chain and normal (F(p) of V2 and M4, C(p) of C3, both fields of rpe_mapmesh.hip).
+// lane's {tsdf, w} pairs of V1 and C2; the field's cell, lerp chain and normal (F(p) of V2 and M4, C(p) of C3, both fields of rpe_mapmesh.hip
+// and of the map raycast in rpe_frontend.hip); the ray rule of V2 and the map raycast (ray_march, ray_normal: templates over the field, so
+// neither kernel keeps the rule as its own text); where a voxel of a map brick lies (brick_word: the map mesh and the map raycast).
 // Followed BIT-EXACTLY (include/rgbd_pose_hip.h Part 3, "TSDF volume"): FMA contraction is off from here to the end of the including unit.
 #pragma once
-#include "rpe_kernels.h"
+#include "rpe_assoc.h"
 
 #pragma clang fp contract(off)
 
@@ -104,6 +106,26 @@ __device__ __forceinline__ float trilerp(float v000, float v100, float v010, flo
 
 // the colour field's RGBA8 byte (rpe_color.hip C3, rpe_mapmesh.hip P3): q(x) = (uint8)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f)
 __device__ __forceinline__ unsigned quantise(float x) { return (unsigned)floorf(fminf(fmaxf(x, 0.0f), 255.0f) + 0.5f); }
+// C(p) as RGBA8 from the cell's eight corner voxels v[di + 2 dj + 4 dk] (two words each, as blend's) and a: 0 unless all eight colour
+// weights are > 0; each channel with F's lerp chain on (float) of the binary16 values, quantised, A = 255 (C3, the map raycast)
+__device__ __forceinline__ unsigned colour_rgba(const uint2 (&v)[8], const float a[3]) {
+  unsigned out = 0u;
+  bool known = true;
+#pragma unroll
+  for (int m = 0; m < 8; m++) known = known && h2f(v[m].y >> 16) > 0.0f;
+  if (known) {
+    float ch[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      float x[8];
+#pragma unroll
+      for (int m = 0; m < 8; m++) x[m] = h2f(c == 0 ? v[m].x & 0xffffu : c == 1 ? v[m].x >> 16 : v[m].y & 0xffffu);
+      ch[c] = trilerp(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], a[0], a[1], a[2]);
+    }
+    out = quantise(ch[0]) | quantise(ch[1]) << 8 | quantise(ch[2]) << 16 | 0xff000000u;
+  }
+  return out;
+}
 
 __device__ __forceinline__ bool field(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz, float& F) {
   int i0[3];
@@ -130,14 +152,63 @@ __device__ __forceinline__ bool unit_normal(float gx, float gy, float gz, float&
   return true;
 }
 
-// the model normal at world point (px, py, pz); false also if any of the six samples is unknown
+// THE RAY RULE (V2 of rpe_volume.hip, the map raycast of rpe_frontend.hip), over any field F(x, y, z, value) -> known.  Ray of pixel
+// (u, v): xn = ((float)u - cx) / fx, yn likewise; samples z_k = dmin + (float)k * s while z_k < dmax, each the camera point (xn z, yn z, z)
+// moved to the world (to_world).  Hit: the first k with F(z_k), F(z_k+1) known, F_k > 0 >= F_k+1: z* = z_k + s * (F_k / (F_k - F_k+1));
+// NaN without a hit.  The vertex is to_world(xn z*, yn z*, z*).
+template <class Field>
+__device__ __forceinline__ float ray_march(Field F, const PoseF& T, float xn, float yn, float s, float dmin, float dmax) {
+  float zh = qnan();
+  bool prev = false;
+  float Fp = 0.0f, zp = 0.0f;
+  for (int k = 0;; k++) {
+    const float z = dmin + (float)k * s;
+    if (!(z < dmax)) break;
+    float wx, wy, wz, Fk;
+    to_world(T, xn * z, yn * z, z, wx, wy, wz);
+    const bool known = F(wx, wy, wz, Fk);
+    if (known && prev && Fp > 0.0f && Fk <= 0.0f) { zh = zp + s * (Fp / (Fp - Fk)); break; }
+    prev = known; Fp = Fk; zp = z;
+  }
+  return zh;
+}
+
+// the normal at world point (px, py, pz) from the six samples F(p +- s e_axis): unit_normal of their differences; false (NaN stays) also
+// if any sample is unknown
+template <class Field>
+__device__ __forceinline__ bool ray_normal(Field F, float s, float px, float py, float pz, float& nx, float& ny, float& nz) {
+  float a, b, c, d, e, f;
+  const bool ok = F(px + s, py, pz, a) && F(px - s, py, pz, b) && F(px, py + s, pz, c) && F(px, py - s, pz, d) && F(px, py, pz + s, e) &&
+                  F(px, py, pz - s, f);
+  return ok && unit_normal(a - b, c - d, e - f, nx, ny, nz);
+}
+
+// the model normal of a dense volume at world point (px, py, pz)
 __device__ __forceinline__ bool field_normal(const float* __restrict__ vol, const VolumeGeometry& G, float px, float py, float pz,
                                              float& nx, float& ny, float& nz) {
-  const float s = G.s;
-  float a, b, c, d, e, f;
-  const bool ok = field(vol, G, px + s, py, pz, a) && field(vol, G, px - s, py, pz, b) && field(vol, G, px, py + s, pz, c) &&
-                  field(vol, G, px, py - s, pz, d) && field(vol, G, px, py, pz + s, e) && field(vol, G, px, py, pz - s, f);
-  return ok && unit_normal(a - b, c - d, e - f, nx, ny, nz);
+  return ray_normal([&](float x, float y, float z, float& F) { return field(vol, G, x, y, z, F); }, G.s, px, py, pz, nx, ny, nz);
+}
+
+// A MAP BRICK'S VOXEL (the map mesh of rpe_mapmesh.hip, the map raycast of rpe_frontend.hip).  The word index of voxel (x, y, z), each
+// 0 .. 7, of the brick with source s, in the window's arrays (s >= 0: the window brick bx + nb0 * (by + nb1 * bz); pooled = false) or in the
+// pool's planes (s < 0: slot ~s, 8 x 8 x 8 voxels in (z, y, x) order); false, and no address, for a brick index outside the window or a
+// slot at or above the capacity.  A voxel is two words in either volume ({tsdf, weight} / four binary16).  View: wnb[3], wdim0, wdim1,
+// capacity (MapMeshView, MapRayView)
+template <class View>
+__device__ __forceinline__ bool brick_word(const View& M, int s, int x, int y, int z, int64_t& w, bool& pooled) {
+  pooled = s < 0;
+  if (pooled) {
+    const int slot = ~s;
+    if (slot >= M.capacity) return false;
+    w = (int64_t)slot * (kArchiveSlotBytes / 4) + 2 * ((z * 8 + y) * 8 + x);
+    return true;
+  }
+  const unsigned nb0 = (unsigned)M.wnb[0], nb1 = (unsigned)M.wnb[1];
+  if ((unsigned)s >= nb0 * nb1 * (unsigned)M.wnb[2]) return false;
+  const unsigned bx = (unsigned)s % nb0, t = (unsigned)s / nb0, by = t % nb1, bz = t / nb1;
+  const unsigned v = ((bz * 8u + (unsigned)z) * (unsigned)M.wdim1 + by * 8u + (unsigned)y) * (unsigned)M.wdim0 + bx * 8u + (unsigned)x;
+  w = 2 * (int64_t)v;   // the voxel index fits 32 bits (dims <= 1024), the word index is formed in 64
+  return true;
 }
 
 }  // namespace

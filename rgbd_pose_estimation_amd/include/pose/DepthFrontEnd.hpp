@@ -338,6 +338,18 @@ class DepthFrontEnd {
     check(rpe_volume_mesh_download(_ctx, M.vertices.data(), M.normals.data(), M.triangles.data()), "rpe_volume_mesh_download");
     return M;
   }
+  // the model := the map -- the window plus the archived bricks -- raycast from T_cw with camera cam over camera depths (r.dmin, r.dmax)
+  // inside the box lo <= w < hi of world voxels (multiples of 8; both null: the bounds), plus its pyramid of `levels`: bit for bit
+  // raycast() of a dense volume of the box (rpe_volume_map_raycast).  flags: RPE_MAPRAY_COLOR samples the model colour in the same pass
+  // (modelColorMap() returns it); RPE_MAPRAY_NO_SKIP, the default here, leaves the occupancy pre-pass out: it changes no bit and, as
+  // measured, does not pay for reading the whole window (pass 0 to run it)
+  void raycastMap(const Pose& T_cw, const PinholeCamera& cam, const DepthRange& r, int levels = 1, const int64_t* lo = nullptr,
+                  const int64_t* hi = nullptr, int flags = RPE_MAPRAY_NO_SKIP) {
+    double p[12]; pose12(T_cw, p);
+    const rpe_camera k = cam_of(cam);
+    check(rpe_volume_map_raycast(_ctx, p, &k, r.dmin, r.dmax, lo, hi, flags), "rpe_volume_map_raycast");
+    if (levels > 1) buildModelPyramid(levels);
+  }
   // where the window is now: the descriptor of initVolume with its origin moved by the total shift (total, if given, receives it)
   VolumeDesc volumeGeometry(int64_t total[3] = nullptr) const {
     rpe_volume_desc v;
@@ -379,6 +391,15 @@ class DepthFrontEnd {
   std::vector<uint8_t> modelColor() const {
     rpe_camera k;
     check(rpe_model_sample_color(_ctx), "rpe_model_sample_color");
+    check(rpe_frame_level_camera(_ctx, 0, 1, &k), "rpe_frame_level_camera");
+    std::vector<uint8_t> out((size_t)k.width * k.height * 4);
+    check(rpe_color_download(_ctx, RPE_COLOR_MODEL, out.data()), "rpe_color_download");
+    return out;
+  }
+  // the model colour map as the device holds it, nothing sampled: what raycastMap with RPE_MAPRAY_COLOR left (modelColor() would replace
+  // it with the WINDOW's colour field), or any other model colour
+  std::vector<uint8_t> modelColorMap() const {
+    rpe_camera k;
     check(rpe_frame_level_camera(_ctx, 0, 1, &k), "rpe_frame_level_camera");
     std::vector<uint8_t> out((size_t)k.width * k.height * 4);
     check(rpe_color_download(_ctx, RPE_COLOR_MODEL, out.data()), "rpe_color_download");
