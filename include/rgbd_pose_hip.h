@@ -708,6 +708,57 @@ int rpe_icp_pyramid_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double ph
                          const double* dist_thr_per_level, double* pose12, int* iters_out, double* last_step, double* final_cost,
                          int64_t* matched, double* photo_cost, int64_t* photo_matched);
 
+/* ---- Volume term: a frame tracked against the TSDF volume ITSELF (Bylow et al., RSS 2013; Canelhas' SDF tracker).  No raycast, no
+ * model view, no model pyramid and no projective association: each frame vertex is moved to the world under the current pose, the
+ * trilinear TSDF there is the residual and the gradient of the same eight corners is the row.  A round reads the frame's pixels and
+ * one 8-corner gather per pixel; a tracked frame needs rpe_volume_raycast only when someone wants to look at the model.
+ * Conventions, followed bit for bit for everything per pixel (fp32, the written order, no FMA contraction; tests/sdf_oracle.py
+ * states them in numpy); the sums are held to a rounding bound.  Casts are made once: (R, t) as every pose12 (Xc = R Xw + t); the
+ * volume's o, s, tr as rpe_volume_init cast them; gate = (float)dist_thr, c = (float)cos_thr, k = tr / s.
+ * The term, per frame pixel of level l with vertex Xc and normal Nc (frame camera coordinates):
+ *  1. Xc has three finite components.  Xw = R^T (Xc - t) exactly as rpe_associate forms it.
+ *  2. The field's cell of Xw: g = (Xw - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; needs 0 <= i0 <= dim - 2 on every axis.
+ *  3. The eight corner voxels v[di][dj][dk] = voxel (i0 + (di, dj, dk)): all eight weights > 0 (the field's "known"), and all eight
+ *     tsdf values with fabsf(v) < 1.0f -- no corner saturated, so the point is inside the truncation band on every side (a NaN tsdf
+ *     fails this test).
+ *  4. D = the field's trilinear value (lerp(x, y, t) = x + (y - x) * t along x, then y, then z); r = D * tr [m]; needs fabsf(r) <= gate.
+ *  5. The gradient of the same interpolant, in tsdf per voxel, from corner differences through the same lerp:
+ *       gx = lerp(lerp(v100 - v000, v110 - v010, ay), lerp(v101 - v001, v111 - v011, ay), az)
+ *       gy = lerp(lerp(v010 - v000, v110 - v100, ax), lerp(v011 - v001, v111 - v101, ax), az)
+ *       gz = lerp(lerp(v001 - v000, v101 - v100, ax), lerp(v011 - v010, v111 - v110, ax), ay)
+ *     len = sqrtf((gx * gx + gy * gy) + gz * gz), needs len > 0;  n = (gx * k, gy * k, gz * k), metres per metre, about unit length
+ *     on a clean surface.
+ *  6. a[i] = -((R[3i] * n.x + R[3i+1] * n.y) + R[3i+2] * n.z): the gradient turned into the camera frame and negated.
+ *  7. With use_normals: Nc finite and (-((a[0] * Nc.x + a[1] * Nc.y) + a[2] * Nc.z)) / (len * k) >= c -- the frame normal agrees with
+ *     the field's gradient, as ICP's cos_thr demands of the model normal.
+ *  8. Residual r, J = [a | Xc x a] with (Xc x a)[0] = Xc.y * a[2] - Xc.z * a[1] and cyclic, in the tangent order (upsilon, omega) of
+ *     rpe_normal_eq, update T <- exp(delta) T (dXw = -R^T (upsilon + omega x Xc)).
+ *  9. Accumulated the way every Gauss-Newton row here is: fp32 fused multiply-adds on pairs of pixels into partial sums of one group
+ *     of 4 consecutive pixels, widened to fp64 once per group, then the fixed order of every reduction here.  Steps 1-8 are bit for
+ *     bit the oracle's; every sum is within 8 * 2^-24 of the sum of the magnitudes of its products.
+ * What the term is NOT.  Its basin is the truncation band: a point further than trunc from the fused surface gives no row, so a
+ * start more than a few voxels off wants a coarse level or rpe_icp first.  Rows are not weighted by voxel weight.  It reads the
+ * dense window only: voxels in the archive's bricks give no row (the map form over the brick grid of rpe_volume_map_raycast is the
+ * follow-up).
+ * The calls need a frame (with the levels asked) and a volume, RPE_ERR_STATE otherwise; they need NO model, and neither read nor
+ * replace the model, the solver slots or the prepared photometric maps. */
+/* {r, J[0..5]} of every frame pixel of the level, as 7 planes of w_l*h_l floats (rows[k * w_l*h_l + pixel]), NaN where the pixel has
+ * no row.  Plane 0 is the residual image in metres.  level >= 0, dist_thr >= 0 */
+int rpe_sdf_rows(rpe_context* ctx, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals, float* rows);
+/* the normal equations of one level: the 32 doubles of rpe_normal_eq -- H upper triangle (21) | g (6) | [27] sum r^2 | [28] rows |
+ * [29] pivot floor (the rows' products are fp32) */
+int rpe_sdf_normal_eq(rpe_context* ctx, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals, double* out32);
+/* rpe_icp / rpe_icp_pyramid on the volume term: per round ONE launch, one host wait, the host solve and left update of rpe_icp;
+ * opt->tol ends a level early.  Of opt, max_iter (>= 1; the pyramid form takes iters_per_level), tol, dist_thr, cos_thr and
+ * use_normals are read; kind and fused are not consulted; host-driven only: device_resident = 1 is RPE_ERR_ARG.  final_cost is the
+ * sum of r^2 and matched the rows of the last round; the pyramid form reports level 0's.  A round whose normal equations are not
+ * positive definite returns RPE_ERR_DEGENERATE with iters_out the rounds completed, as rpe_icp does. */
+int rpe_icp_sdf(rpe_context* ctx, const rpe_icp_options* opt, double* pose12, int* iters_out, double* last_step, double* final_cost,
+                int64_t* matched);
+int rpe_icp_pyramid_sdf(rpe_context* ctx, const rpe_icp_options* opt, int levels, const int* iters_per_level,
+                        const double* dist_thr_per_level, double* pose12, int* iters_out, double* last_step, double* final_cost,
+                        int64_t* matched);
+
 /* ---- Features and relocalisation: correspondences WITHOUT a pose guess.  rpe_associate pairs under a guess, so every entry above
  * that produces a pose from images needs a start inside ICP's basin; a lost tracker has none.  Here keypoints of the frame's colour
  * and of the model view's colour are described and matched by appearance, the matched pixels' vertices, normals and bearings go into

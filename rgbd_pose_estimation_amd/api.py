@@ -644,6 +644,49 @@ class Context:
         self.n, self.dtype = self._pixels, L.F32
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
 
+    # ---- volume term (Part 3): a frame tracked against the TSDF volume itself -- no raycast, no model
+    def sdf_rows(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True) -> np.ndarray:
+        """(7, pixels) float32: the residual in metres (row 0: the residual image) and Jacobian row of every frame pixel of the level in
+        the volume's field under pose12, NaN where the pixel has no row."""
+        p = np.array(pose12, np.float64).reshape(12)
+        h, w = getattr(self, "_frame_hw", (0, 0))      # (the library checks the level: a level's size is the frame's halved per level)
+        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
+        L.check(L.lib().rpe_sdf_rows(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(out)))
+        return out
+
+    def sdf_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True) -> np.ndarray:
+        """The volume term's normal equations of one level: H upper triangle (21) | g (6) | sum r^2 | rows | pivot floor | pad, 32 float64."""
+        p = np.array(pose12, np.float64).reshape(12)
+        out = np.zeros(32, np.float64)
+        L.check(L.lib().rpe_sdf_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(out)))
+        return out
+
+    def icp_sdf(self, pose12, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True):
+        """Gauss-Newton on the volume term, one launch per round; needs a frame and a volume, no model.  Returns (pose12, iterations,
+        last |delta|, sum r^2, rows of the last round)."""
+        p = np.array(pose12, np.float64).reshape(12).copy()
+        o = L.RpeIcpOptions(L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, int(use_normals), 0, 1)
+        it, step, cost, m = C.c_int(0), C.c_double(0), C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_sdf(self._h, C.byref(o), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m)))
+        return p, it.value, step.value, cost.value, m.value
+
+    def icp_pyramid_sdf(self, pose12, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9, use_normals: bool = True):
+        """icp_sdf coarse to fine over len(iters) levels of the frame; dist_thr as icp_pyramid's.  Returns (pose12, rounds per level,
+        last |delta|, sum r^2, rows of the last round), the last three of level 0."""
+        p = np.array(pose12, np.float64).reshape(12).copy()
+        levels = len(iters)
+        it_in = np.ascontiguousarray(iters, np.int32)
+        one = 0.1 if dist_thr is None else dist_thr
+        thr = None if np.ndim(one) == 0 else np.ascontiguousarray(one, np.float64)
+        if thr is not None and len(thr) != levels:
+            raise ValueError("dist_thr needs one gate per level")
+        o = L.RpeIcpOptions(L.RES_P2PLANE, 1, tol, float(one) if thr is None else 0.0, cos_thr, int(use_normals), 0, 1)
+        it_out = np.zeros(levels, np.int32)
+        step, cost, m = C.c_double(0), C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_pyramid_sdf(self._h, C.byref(o), levels, _p(it_in), None if thr is None else _p(thr), _p(p), _p(it_out),
+                                            C.byref(step), C.byref(cost), C.byref(m)))
+        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
+
     # ---- features and relocalisation (Part 3): correspondences without a pose guess
     def features_detect(self, which: int = L.FEAT_FRAME, threshold: int = 12, max_keypoints: int = L.MAX_KEYPOINTS) -> int:
         """Detect and describe the keypoints of the frame's colour (FEAT_FRAME) or the model colour (FEAT_MODEL); returns their number."""

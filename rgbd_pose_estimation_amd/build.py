@@ -2,7 +2,7 @@
 
 hipcc cross-compiles without a GPU.  UNITS below is the manifest of the library: every compiled unit once, in link order, with its
 kind and what it holds.  Kernel units share device code in csrc/rpe_reduce.hpp and csrc/rpe_residuals.hpp and the front end's
-bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp; each names one of its kernels
+bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_sdf_rule.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp; each names one of its kernels
 with RPE_PRELOAD (csrc/rpe_kernels.h), through which rpe_create loads its code object.  Host units are the C-ABI side behind
 include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp lists them; csrc/rpe_devbuf.hpp owns their device memory,
 csrc/rpe_frontend_host.hpp holds what the Part 3 units share).  What each unit must satisfy is the gate table of tests/unit_gates.py.
@@ -28,7 +28,7 @@ UNITS = [
     ("rpe_joint.hip", "kernel", "joint normal equations"),
     ("rpe_score.hip", "kernel", "K4 scoring, K4b masks"),
     ("rpe_nl.hip", "kernel", "K1' moments, K5, publish kernels"),
-    ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map"),
+    ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map; the volume term's rows and round"),
     ("rpe_filter.hip", "kernel", "the bilateral depth filter in front of it"),
     ("rpe_volume.hip", "kernel", "TSDF volume: integrate, raycast"),
     ("rpe_mesh.hip", "kernel", "marching cubes over the volume"),
@@ -59,6 +59,7 @@ UNITS = [
     ("rpe_mesh_api.hip", "host", "Part 3: mesh extraction"),
     ("rpe_color_api.hip", "host", "Part 3: colour of frame, volume, model and mesh"),
     ("rpe_photo_api.hip", "host", "Part 3: photometric term beside ICP"),
+    ("rpe_sdf_api.hip", "host", "Part 3: the volume term, a frame tracked against the TSDF volume itself"),
     ("rpe_feature_api.hip", "host", "Part 3: features and relocalisation"),
     ("rpe_keyframe_api.hip", "host", "Part 3: keyframes"),
     ("rpe_graph_api.hip", "host", "Part 3: the keyframe graph"),

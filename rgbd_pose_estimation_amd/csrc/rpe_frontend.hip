@@ -551,3 +551,169 @@ hipError_t launch_map_raycast(const MapRayView& M, const VolumeGeometry& G, cons
 RPE_PRELOAD(to_world_kernel);
 
 }  // namespace rpe
+
+// ================================================================================================
+// THE VOLUME TERM (include/rgbd_pose_hip.h Part 3, "Volume term"): a frame tracked against the TSDF volume itself.  The per-pixel rule
+// is sdf_pixel of rpe_sdf_rule.hpp, bit-exact; the sums are those of every Gauss-Newton kernel (rpe_residuals.hpp add_row2,
+// rpe_reduce.hpp reduce_and_finish), included here so that the kernels above compile as they did without them.
+//   sdf_rows_kernel      {r, J[0..5]} of every frame pixel (NaN where there is no row): the residual image and the tests' hook.
+//   icp_sdf_kernel<BLK>  one Gauss-Newton round in one pass over the level's frame pixels: per pixel 12 B of vertex (24 B with the
+//                        normal gate) streamed and eight 8-byte corner voxels gathered; add_row2 on pairs of pixels into fp32 partial
+//                        sums of one group of 4 pixels, widened to fp64 per group; the 29 sums of every normal-equation record.
+// ================================================================================================
+#include "rpe_residuals.hpp"
+#include "rpe_sdf_rule.hpp"
+
+namespace rpe {
+
+namespace {
+
+constexpr int kSdfRowsBlock = 256;   // one pixel per lane
+
+// One group of 4 pixels into the accumulators (a pixel that is not there has a NaN vertex: no row).  The order is chosen for the
+// registers (tests/test_sdf_oracle.py holds the kernel to 128): the four rows first, from the vertices alone; then the normals are
+// fetched (normals(N): only with use_normals) and gate them; then the sums.
+template <class Normals>
+__device__ __forceinline__ void sdf_group(const float* __restrict__ vol, const VolumeGeometry& G, const PoseF& T, const SdfParams& Q,
+                                          const float (&V)[12], Normals normals, double (&acc)[28], float& rows) {
+  typedef float V2 __attribute__((ext_vector_type(2)));
+  const dense_corners corners(vol, G);
+  float r[4], J[4][6], len[4];
+  bool ok[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) ok[i] = sdf_pixel_row(corners, G, T, Q, V[3 * i], V[3 * i + 1], V[3 * i + 2], r[i], J[i], len[i]);
+  if (Q.use_normals) {
+    float N[12];
+    normals(N);
+#pragma unroll
+    for (int i = 0; i < 4; i++) ok[i] = ok[i] && sdf_normal_gate(Q, N[3 * i], N[3 * i + 1], N[3 * i + 2], len[i], r[i], J[i]);
+  }
+  // add_row2 (rpe_residuals.hpp) on the pair of pixels 0, 1 and then on the pair 2, 3, and the group's sums widened to fp64 once --
+  // written sum by sum, so that the 28 fp32 pair sums need not all be held at once: for every sum the two fused multiply-adds of
+  // add_row2 on a zero start, the addition of the pair's lanes and the widening are the operations add_row2 twice and
+  // (double)(s.x + s.y) perform, in their order
+  const V2 wa = V2{ok[0] ? 1.f : 0.f, ok[1] ? 1.f : 0.f}, wb = V2{ok[2] ? 1.f : 0.f, ok[3] ? 1.f : 0.f};
+  const V2 ra = V2{r[0], r[1]}, rb = V2{r[2], r[3]}, zero = V2{0.f, 0.f};
+  V2 Ja[6], Jb[6];
+#pragma unroll
+  for (int a = 0; a < 6; a++) { Ja[a] = V2{J[0][a], J[1][a]}; Jb[a] = V2{J[2][a], J[3][a]}; }
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+    const V2 xa = wa * Ja[a], xb = wb * Jb[a];
+#pragma unroll
+    for (int b = a; b < 6; b++) {
+      const V2 t = __builtin_elementwise_fma(xb, Jb[b], __builtin_elementwise_fma(xa, Ja[b], zero));
+      acc[k] += (double)(t.x + t.y); k++;
+    }
+    const V2 t = __builtin_elementwise_fma(xb, rb, __builtin_elementwise_fma(xa, ra, zero));
+    acc[21 + a] += (double)(t.x + t.y);
+  }
+  const V2 t = __builtin_elementwise_fma(wb * rb, rb, __builtin_elementwise_fma(wa * ra, ra, zero));
+  acc[27] += (double)(t.x + t.y);
+  rows += (wa.x + wa.y) + (wb.x + wb.y);   // (a thread sees fewer than 2^24 pixels: exact)
+}
+
+// The kernel's arguments as the kernarg segment lays them out (every argument at its natural alignment, in order), for late_finish
+struct SdfRoundArgs { const float* vmap; const float* nmap; int64_t n; const float* vol; VolumeGeometry G; SdfParams Q; PoseF T; Finish fin; };
+// (tests/test_sdf_oracle.py reads the same offset and size from the code object's metadata)
+static_assert(offsetof(SdfRoundArgs, fin) == 136 && sizeof(Finish) == 136, "late_finish: where the kernarg segment holds the reduction's argument");
+// The reduction's argument read from the kernarg segment where it is needed, behind the pixel loop: as a plain argument the compiler
+// loads all of it in the kernel's first block and keeps its scalar registers through the loop, beside pose, geometry and gates, which
+// is more than the 102 there are.  (The offset goes through an empty asm so that the loads stay below it.)
+__device__ __forceinline__ Finish late_finish() {
+  unsigned off = (unsigned)offsetof(SdfRoundArgs, fin);
+  asm volatile("" : "+s"(off));
+  Finish f;
+  __builtin_memcpy(&f, (const char*)__builtin_amdgcn_kernarg_segment_ptr() + off, sizeof(Finish));
+  return f;
+}
+
+// four waves per SIMD's worth of registers: 128
+template <int BLK>
+__global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(4))) void icp_sdf_kernel(
+    const float* __restrict__ vmap, const float* __restrict__ nmap, int64_t n, const float* __restrict__ vol, VolumeGeometry G, SdfParams Q,
+    PoseF T, Finish /* read by late_finish */) {
+  double acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; k++) acc[k] = 0.0;
+  float rows = 0.f;
+  const int full = (int)(n / 4);                  // (n <= 2^28 pixels: rpe_frame_set_depth)
+  const int stride = (int)gridDim.x * BLK;
+  const float4* __restrict__ v4 = reinterpret_cast<const float4*>(vmap);
+  const float4* __restrict__ n4 = reinterpret_cast<const float4*>(nmap);
+  for (int g = (int)blockIdx.x * BLK + (int)threadIdx.x; g < full; g += stride) {
+    const int64_t q = 3 * (int64_t)g;
+    float V[12];
+    unpack3(v4[q], v4[q + 1], v4[q + 2], V);
+    sdf_group(vol, G, T, Q, V, [&](float (&N)[12]) { unpack3(n4[q], n4[q + 1], n4[q + 2], N); }, acc, rows);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (int64_t)full * 4 < n) {  // leftover pixels
+    const int left = (int)(n - (int64_t)full * 4);
+    float V[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) V[i] = i < 3 * left ? vmap[12 * (int64_t)full + i] : qnan();
+    sdf_group(vol, G, T, Q, V, [&](float (&N)[12]) {
+#pragma unroll
+      for (int i = 0; i < 12; i++) N[i] = i < 3 * left ? nmap[12 * (int64_t)full + i] : qnan();
+    }, acc, rows);
+  }
+  double sums[29];
+#pragma unroll
+  for (int k = 0; k < 28; k++) sums[k] = acc[k];
+  sums[28] = (double)rows;
+  reduce_and_finish<29, kNeLd, 0, BLK, false>(sums, late_finish());   // host-driven only: no device-side solve in this kernel
+}
+
+__global__ __launch_bounds__(kSdfRowsBlock) void sdf_rows_kernel(const float* __restrict__ vmap, const float* __restrict__ nmap, int64_t n,
+                                                                 const float* __restrict__ vol, VolumeGeometry G, SdfParams Q, PoseF T,
+                                                                 float* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * kSdfRowsBlock + threadIdx.x;
+  if (i >= n) return;
+  float r, J[6], nx = 0.f, ny = 0.f, nz = 0.f;
+  if (Q.use_normals) { nx = nmap[3 * i]; ny = nmap[3 * i + 1]; nz = nmap[3 * i + 2]; }
+  const bool ok = sdf_pixel(dense_corners(vol, G), G, T, Q, vmap[3 * i], vmap[3 * i + 1], vmap[3 * i + 2], nx, ny, nz, r, J);
+  rows[i] = ok ? r : qnan();
+#pragma unroll
+  for (int k = 0; k < 6; k++) rows[(int64_t)(k + 1) * n + i] = ok ? J[k] : qnan();
+}
+
+SdfParams sdf_params(const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals) {
+  SdfParams Q;
+  Q.gate = dist_thr; Q.c = cos_thr; Q.k = G.tr / G.s; Q.use_normals = use_normals;
+  return Q;
+}
+PoseF sdf_pose(const double* p12) {
+  PoseF T;
+  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
+  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
+  return T;
+}
+
+}  // namespace
+
+hipError_t launch_icp_sdf(const float* vmap, const float* nmap, int64_t n, const float* vol, const VolumeGeometry& G, float dist_thr,
+                          float cos_thr, int use_normals, const double* pose12, const ReduceTarget& rt, hipStream_t s) {
+  const SdfParams Q = sdf_params(G, dist_thr, cos_thr, use_normals);
+  const PoseF T = sdf_pose(pose12);
+  const Finish fin = make_finish(rt);
+  // geometry as the fused ICP round's: one pixel group per thread while the grid allows it
+  const int blk = pick_block(rt);
+  const int64_t groups = (n + 3) / 4;
+  int grid = rt.max_blocks;
+  if ((int64_t)grid > (groups + blk - 1) / blk) grid = (int)((groups + blk - 1) / blk);
+  if (grid < 1) grid = 1;
+  if (blk == 512) hipLaunchKernelGGL((icp_sdf_kernel<512>), dim3(grid), dim3(512), 0, s, vmap, nmap, n, vol, G, Q, T, fin);
+  else hipLaunchKernelGGL((icp_sdf_kernel<256>), dim3(grid), dim3(256), 0, s, vmap, nmap, n, vol, G, Q, T, fin);
+  return hipGetLastError();
+}
+
+hipError_t launch_sdf_rows(const float* vmap, const float* nmap, int64_t n, const float* vol, const VolumeGeometry& G, float dist_thr,
+                           float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s) {
+  const int64_t blocks = (n + kSdfRowsBlock - 1) / kSdfRowsBlock;
+  hipLaunchKernelGGL(sdf_rows_kernel, dim3((unsigned)blocks), dim3(kSdfRowsBlock), 0, s, vmap, nmap, n, vol, G,
+                     sdf_params(G, dist_thr, cos_thr, use_normals), sdf_pose(pose12), rows);
+  return hipGetLastError();
+}
+
+}  // namespace rpe

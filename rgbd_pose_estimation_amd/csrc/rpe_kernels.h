@@ -497,4 +497,12 @@ hipError_t launch_icp_resident(const float* vmap, const float* nmap, int64_t n, 
                                float dist_sq, float cos_thr, int use_normals, int kind, const unsigned long long* ctl, unsigned long long first_tag,
                                int max_iters, const ReduceTarget& rt, hipStream_t s);
 
+// ---- the volume term (rpe_frontend.hip; rule in rpe_sdf_rule.hpp): the frame level's vertices (and, with use_normals, normals) in the
+// field of the dense volume `vol` under pose12.  One round in one kernel, record as launch_normal_eq's (H (21) | g (6) | sum r^2 | rows)
+hipError_t launch_icp_sdf(const float* vmap, const float* nmap, int64_t n, const float* vol, const VolumeGeometry& G, float dist_thr,
+                          float cos_thr, int use_normals, const double* pose12, const ReduceTarget& rt, hipStream_t s);
+// rows[k * n + i], k = 0 .. 6: {r, J[0..5]} of frame pixel i, NaN where it has no row
+hipError_t launch_sdf_rows(const float* vmap, const float* nmap, int64_t n, const float* vol, const VolumeGeometry& G, float dist_thr,
+                           float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s);
+
 }  // namespace rpe

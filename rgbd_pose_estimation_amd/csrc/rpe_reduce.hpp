@@ -802,7 +802,8 @@ __device__ __forceinline__ void collect_and_send(const double (*red)[NACC], cons
   RPE_STAMP(9);
 }
 
-template <int NACC, int LD, int MODE, int BLK>
+// GN = false: a kernel whose rounds are host-driven only leaves the device-side solve (fin.gn) out, and with it the solve's call frame
+template <int NACC, int LD, int MODE, int BLK, bool GN = true>
 __device__ __forceinline__ void reduce_and_finish(double (&acc)[NACC], const Finish& fin) {
   constexpr int NW = BLK / 64;
   constexpr int RG = BLK / LD;
@@ -911,13 +912,13 @@ __device__ __forceinline__ void reduce_and_finish(double (&acc)[NACC], const Fin
     if (failed && threadIdx.x == 31) val = 1e300;   // error marker in the last (padding) entry of the record: the host checks it
   }
   if (threadIdx.x < LD) {
-    if (fin.gn == nullptr) {
+    if (!GN || fin.gn == nullptr) {
       if (fin.out_dev) fin.out_dev[threadIdx.x] = val;
       // pinned, coherent host memory: system-scope stores go straight out over PCIe (posted, ordered)
       if (fin.out_host) __hip_atomic_store(fin.out_host + threadIdx.x, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
-  if (fin.gn != nullptr) {
+  if (GN && fin.gn != nullptr) {
     // device-resident Gauss-Newton: this workgroup solves the 6x6 system, updates the pose in HBM and decides whether
     // the loop is finished; only a finished loop is published to the host (pose 12 | step | cost | iters | status | weight sum)
     __shared__ double gn_rec[LD];

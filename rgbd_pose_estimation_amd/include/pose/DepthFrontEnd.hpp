@@ -15,6 +15,7 @@
 //   fe.initVolume(desc);  fe.setDepthPyramid(d0, cam, 3);  fe.integrate(T0);
 //   for each frame: fe.setDepthPyramid(d, cam, 3);  fe.raycast(T, cam, range, 3);  fe.icpPyramid(T, {6, 4, 3});  fe.integrate(T);
 //   rpe::Mesh m = fe.mesh();                                             // the surface: marching cubes on the GPU
+// ... or without the raycast, against the volume's field itself:  fe.setDepthPyramid(d, cam, 3);  fe.icpPyramidVolume(T, {6, 4, 3});  fe.integrate(T);
 // A real sensor's depth is noisy (centimetres at room distances): fe.setDepthFilter(rpe::DepthFilter()) once, before the first frame
 // With a registered RGB image per frame (pixel (u, v) of colour and depth see the same ray), the volume also fuses colour:
 //   fe.setDepth(d, cam);  fe.setColor(rgb);  fe.integrateColor(T);  ...  fe.modelColor();  fe.meshColors();   // RGBA8, 4 bytes each
@@ -456,6 +457,46 @@ class DepthFrontEnd {
     const size_t n = (size_t)k.width * k.height;
     std::vector<float> rows(7 * n);
     check(rpe_photo_rows(_ctx, level, p, dist_thr, rows.data()), "rpe_photo_rows");
+    rows.resize(n);
+    return rows;
+  }
+  // ---- the volume term: the frame tracked against the TSDF volume ITSELF -- no raycast, no model (rpe_icp_sdf).  Of o: max_iter, tol,
+  // dist_thr, cos_thr and use_normals are read; o.device_resident must be false.  The basin is the truncation band: start within a few
+  // voxels of the truth (the previous frame's pose does), or let a coarse level or icp bring the pose there first
+  IcpResult icpVolume(Pose& pose, const IcpOptions& o = IcpOptions()) {
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    IcpResult r;
+    int64_t m = 0;
+    check(rpe_icp_sdf(_ctx, &opt, p, &r.iterations, &r.last_step, &r.cost, &m), "rpe_icp_sdf");
+    r.pairs = (long long)m;
+    pose = pose_of(p);
+    return r;
+  }
+  // ... coarse to fine over the frame's levels, as icpPyramid: iters[l] rounds and gate dist_thr[l] at level l
+  PyramidIcpResult icpPyramidVolume(Pose& pose, const std::vector<int>& iters, const std::vector<double>& dist_thr = std::vector<double>(),
+                                    const IcpOptions& o = IcpOptions()) {
+    if (!dist_thr.empty() && dist_thr.size() != iters.size()) throw DeviceError(RPE_ERR_ARG, "icpPyramidVolume: one gate per level");
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    PyramidIcpResult r;
+    int64_t m = 0;
+    check(rpe_icp_pyramid_sdf(_ctx, &opt, (int)iters.size(), iters.data(), dist_thr.empty() ? nullptr : dist_thr.data(), p, r.level_iterations,
+                              &r.last_step, &r.cost, &m), "rpe_icp_pyramid_sdf");
+    for (size_t l = 0; l < iters.size(); l++) r.iterations += r.level_iterations[l];
+    r.pairs = (long long)m;
+    pose = pose_of(p);
+    return r;
+  }
+  // the residual image of a level under `pose`: the signed distance [m] of every frame vertex to the fused surface, NaN where the
+  // pixel has no row (row 0 of rpe_sdf_rows)
+  std::vector<float> volumeResiduals(const Pose& pose, int level = 0, const IcpOptions& o = IcpOptions()) const {
+    double p[12]; pose12(pose, p);
+    rpe_camera k;
+    check(rpe_frame_level_camera(_ctx, level, 0, &k), "rpe_frame_level_camera");
+    const size_t n = (size_t)k.width * k.height;
+    std::vector<float> rows(7 * n);
+    check(rpe_sdf_rows(_ctx, level, p, o.dist_thr, o.cos_thr, o.use_normals ? 1 : 0, rows.data()), "rpe_sdf_rows");
     rows.resize(n);
     return rows;
   }
