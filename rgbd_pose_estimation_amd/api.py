@@ -289,19 +289,24 @@ class Context:
     def icp(self, pose12, kind: int = L.RES_P2PLANE, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9,
             use_normals: bool = True, device_resident: bool = False, fused: bool = False):
         """Projective-association ICP; returns (pose12, iterations, last |delta|, cost, pairs of the last round)."""
-        p = np.array(pose12, np.float64).reshape(12).copy()
-        o = L.RpeIcpOptions(kind, max_iter, tol, dist_thr, cos_thr, int(use_normals), int(device_resident), int(fused))
-        it, step, cost, m = C.c_int(0), C.c_double(0), C.c_double(0), C.c_int64(0)
+        p, o, it, step, cost, m = self._icp_args(pose12, kind, max_iter, tol, dist_thr, cos_thr, use_normals, device_resident, fused)
         L.check(L.lib().rpe_icp(self._h, C.byref(o), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m)))
         self.n, self.dtype = self._pixels, L.F32
         return p, it.value, step.value, cost.value, m.value
 
+    @staticmethod
+    def _icp_args(pose12, kind, max_iter, tol, dist_thr, cos_thr, use_normals, device_resident, fused):
+        """What the single-level loops (icp, icp_rgbd, icp_sdf) hand the library: a copy of the pose, the options, and the words the
+        iterations, the last |delta|, the cost and the pairs come back in."""
+        p = np.array(pose12, np.float64).reshape(12).copy()
+        o = L.RpeIcpOptions(kind, max_iter, tol, dist_thr, cos_thr, int(use_normals), int(device_resident), int(fused))
+        return p, o, C.c_int(0), C.c_double(0), C.c_double(0), C.c_int64(0)
 
-    def icp_pyramid(self, pose12, iters=(10, 5, 4), dist_thr=None, kind: int = L.RES_P2PLANE, tol: float = 1e-6, cos_thr: float = 0.9,
-                    use_normals: bool = True, device_resident: bool = False, fused: bool = False):
-        """Coarse-to-fine ICP over len(iters) levels; iters[l] rounds at level l (0 = finest).  dist_thr: one gate per level, one gate
-        for every level, or None (0.1 m, icp's default).  Returns (pose12, rounds per level, last |delta|, cost, pairs of the last round),
-        the last three of level 0."""
+    @staticmethod
+    def _pyramid_args(pose12, iters, dist_thr, kind, tol, cos_thr, use_normals, device_resident, fused):
+        """What the coarse-to-fine loops (icp_pyramid, icp_pyramid_rgbd, icp_pyramid_sdf) hand the library: a copy of the pose, the
+        number of levels, the rounds per level, the gates per level (None: the one gate is in the options), the options, the rounds run
+        per level, and the words the last |delta|, the cost and the pairs of level 0 come back in."""
         p = np.array(pose12, np.float64).reshape(12).copy()
         levels = len(iters)
         it_in = np.ascontiguousarray(iters, np.int32)
@@ -310,10 +315,16 @@ class Context:
         if thr is not None and len(thr) != levels:
             raise ValueError("dist_thr needs one gate per level")
         o = L.RpeIcpOptions(kind, 1, tol, float(one) if thr is None else 0.0, cos_thr, int(use_normals), int(device_resident), int(fused))
-        it_out = np.zeros(levels, np.int32)
-        step, cost, m = C.c_double(0), C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_pyramid(self._h, C.byref(o), levels, _p(it_in), None if thr is None else _p(thr), _p(p), _p(it_out), C.byref(step),
-                                        C.byref(cost), C.byref(m)))
+        return p, levels, it_in, thr, o, np.zeros(levels, np.int32), C.c_double(0), C.c_double(0), C.c_int64(0)
+
+    def icp_pyramid(self, pose12, iters=(10, 5, 4), dist_thr=None, kind: int = L.RES_P2PLANE, tol: float = 1e-6, cos_thr: float = 0.9,
+                    use_normals: bool = True, device_resident: bool = False, fused: bool = False):
+        """Coarse-to-fine ICP over len(iters) levels; iters[l] rounds at level l (0 = finest).  dist_thr: one gate per level, one gate
+        for every level, or None (0.1 m, icp's default).  Returns (pose12, rounds per level, last |delta|, cost, pairs of the last round),
+        the last three of level 0."""
+        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, kind, tol, cos_thr, use_normals,
+                                                                             device_resident, fused)
+        L.check(L.lib().rpe_icp_pyramid(self._h, C.byref(o), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step), C.byref(cost), C.byref(m)))
         self.n, self.dtype = self._pixels, L.F32
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
 
@@ -618,9 +629,8 @@ class Context:
     def icp_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9):
         """icp with the photometric term (weight in metres per intensity level) beside point-to-plane, one launch per round; returns
         (pose12, iterations, last |delta|, geometric cost, geometric pairs, photometric cost, photometric pairs) of the last round."""
-        p = np.array(pose12, np.float64).reshape(12).copy()
-        o = L.RpeIcpOptions(L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, 1, 0, 1)
-        it, step, cost, m, pc, pm = C.c_int(0), C.c_double(0), C.c_double(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
+        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, 1, 0, 1)
+        pc, pm = C.c_double(0), C.c_int64(0)
         L.check(L.lib().rpe_icp_rgbd(self._h, C.byref(o), float(weight), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m),
                                      C.byref(pc), C.byref(pm)))
         self.n, self.dtype = self._pixels, L.F32
@@ -629,18 +639,10 @@ class Context:
     def icp_pyramid_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9):
         """icp_pyramid with the photometric term; returns (pose12, rounds per level, last |delta|, geometric cost, geometric pairs,
         photometric cost, photometric pairs), the last five of level 0."""
-        p = np.array(pose12, np.float64).reshape(12).copy()
-        levels = len(iters)
-        it_in = np.ascontiguousarray(iters, np.int32)
-        one = 0.1 if dist_thr is None else dist_thr
-        thr = None if np.ndim(one) == 0 else np.ascontiguousarray(one, np.float64)
-        if thr is not None and len(thr) != levels:
-            raise ValueError("dist_thr needs one gate per level")
-        o = L.RpeIcpOptions(L.RES_P2PLANE, 1, tol, float(one) if thr is None else 0.0, cos_thr, 1, 0, 1)
-        it_out = np.zeros(levels, np.int32)
-        step, cost, m, pc, pm = C.c_double(0), C.c_double(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_pyramid_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), None if thr is None else _p(thr), _p(p),
-                                             _p(it_out), C.byref(step), C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
+        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, 1, 0, 1)
+        pc, pm = C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_pyramid_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step),
+                                             C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
         self.n, self.dtype = self._pixels, L.F32
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
 
@@ -664,27 +666,15 @@ class Context:
     def icp_sdf(self, pose12, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True):
         """Gauss-Newton on the volume term, one launch per round; needs a frame and a volume, no model.  Returns (pose12, iterations,
         last |delta|, sum r^2, rows of the last round)."""
-        p = np.array(pose12, np.float64).reshape(12).copy()
-        o = L.RpeIcpOptions(L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, int(use_normals), 0, 1)
-        it, step, cost, m = C.c_int(0), C.c_double(0), C.c_double(0), C.c_int64(0)
+        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
         L.check(L.lib().rpe_icp_sdf(self._h, C.byref(o), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m)))
         return p, it.value, step.value, cost.value, m.value
 
     def icp_pyramid_sdf(self, pose12, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9, use_normals: bool = True):
         """icp_sdf coarse to fine over len(iters) levels of the frame; dist_thr as icp_pyramid's.  Returns (pose12, rounds per level,
         last |delta|, sum r^2, rows of the last round), the last three of level 0."""
-        p = np.array(pose12, np.float64).reshape(12).copy()
-        levels = len(iters)
-        it_in = np.ascontiguousarray(iters, np.int32)
-        one = 0.1 if dist_thr is None else dist_thr
-        thr = None if np.ndim(one) == 0 else np.ascontiguousarray(one, np.float64)
-        if thr is not None and len(thr) != levels:
-            raise ValueError("dist_thr needs one gate per level")
-        o = L.RpeIcpOptions(L.RES_P2PLANE, 1, tol, float(one) if thr is None else 0.0, cos_thr, int(use_normals), 0, 1)
-        it_out = np.zeros(levels, np.int32)
-        step, cost, m = C.c_double(0), C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_pyramid_sdf(self._h, C.byref(o), levels, _p(it_in), None if thr is None else _p(thr), _p(p), _p(it_out),
-                                            C.byref(step), C.byref(cost), C.byref(m)))
+        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
+        L.check(L.lib().rpe_icp_pyramid_sdf(self._h, C.byref(o), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step), C.byref(cost), C.byref(m)))
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
 
     # ---- features and relocalisation (Part 3): correspondences without a pose guess

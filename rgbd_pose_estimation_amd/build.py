@@ -5,7 +5,8 @@ kind and what it holds.  Kernel units share device code in csrc/rpe_reduce.hpp a
 bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_sdf_rule.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp; each names one of its kernels
 with RPE_PRELOAD (csrc/rpe_kernels.h), through which rpe_create loads its code object.  Host units are the C-ABI side behind
 include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp lists them; csrc/rpe_devbuf.hpp owns their device memory,
-csrc/rpe_frontend_host.hpp holds what the Part 3 units share).  What each unit must satisfy is the gate table of tests/unit_gates.py.
+csrc/rpe_gn_host.hpp holds the Gauss-Newton step, round loop and coarse-to-fine walk of their host loops,
+csrc/rpe_frontend_host.hpp what the Part 3 units share).  What each unit must satisfy is the gate table of tests/unit_gates.py.
 
 {units}
 

@@ -189,14 +189,13 @@ int rpe_normal_eq_device(rpe_context* c, int kind, int flags, const double* pose
 // One Gauss-Newton step on one GPU: normal equations (device) -> solve -> pose <- exp(delta) * pose (host).
 int rpe_gn_step(rpe_context* c, int kind, int flags, double* pose12, double* ne32_out, double* step_norm) {
   session_end(c);
-  double ne[32], d[6];
+  double ne[32], step;
   int rc = rpe_normal_eq(c, kind, flags, pose12, ne);
   if (rc) return rc;
-  if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(c->dtype == RPE_F64))) return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite (weight sum %g)",
-      ne[28]);
-  rpe::se3_left_update(d, pose12);
+  if (!gn_update(ne, rpe::pivot_floor(c->dtype == RPE_F64), pose12, &step))
+    return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite (weight sum %g)", ne[28]);
   if (ne32_out) std::memcpy(ne32_out, ne, sizeof(ne));
-  if (step_norm) *step_norm = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
+  if (step_norm) *step_norm = step;
   return RPE_OK;
 }
 

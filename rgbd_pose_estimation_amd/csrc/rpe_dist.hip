@@ -189,20 +189,25 @@ int rpe_hostex_destroy(rpe_context* c) {
   return RPE_OK;
 }
 
+// what every route of the sharded step ends with, identically on every rank: the summed record takes the floor word rpe_gn_solve reads
+// (as rpe_normal_eq's does), then the step
+static int sharded_update(rpe_context* c, double* ne, double* pose12, double* ne32_out, double* step_norm) {
+  double step;
+  ne[29] = rpe::pivot_floor(c->dtype == RPE_F64);
+  if (!gn_update(ne, ne[29], pose12, &step)) return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite (weight sum %g)", ne[28]);
+  if (ne32_out) std::memcpy(ne32_out, ne, 32 * sizeof(double));
+  if (step_norm) *step_norm = step;
+  return RPE_OK;
+}
+
 int rpe_gn_step_dist(rpe_context* c, int kind, int flags, double* pose12, double* ne32_out, double* step_norm) {
   session_end(c);
   if (c && c->hostex) {   // ONE launch with the single-GPU collecting stage; the shards' records meet on the hosts
-    double ne[32], d[6];
+    double ne[32];
     int rc = rpe_normal_eq(c, kind, flags, pose12, ne);
     if (rc) return rc;
     if ((rc = rpe_host_exchange_allreduce_f64(c->hostex, ne, 32))) return rc;
-    ne[29] = rpe::pivot_floor(c->dtype == RPE_F64);   // slot 29 is not a sum: after the exchange it held world x floor
-    if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(c->dtype == RPE_F64))) return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite (weight sum %g)",
-        ne[28]);
-    rpe::se3_left_update(d, pose12);
-    if (ne32_out) std::memcpy(ne32_out, ne, sizeof(ne));
-    if (step_norm) *step_norm = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-    return RPE_OK;
+    return sharded_update(c, ne, pose12, ne32_out, step_norm);   // (word 29 is not a sum: after the exchange it held world x floor)
   }
   if (!c || (!c->comm && c->p2p_world < 1)) return fail(RPE_ERR_STATE, "neither rpe_p2p_init nor rpe_comm_init was called");
   int rc;
@@ -246,17 +251,11 @@ int rpe_gn_step_dist(rpe_context* c, int kind, int flags, double* pose12, double
     else { for (int i = 0; i < 32; i++) c->h_out[i] = i < 29 ? tot[i] : 0.0; }
   }
   if (c->p2p_world >= 1 && (rc = wait_host(c, rpe::kNeLd))) return rc;
-  double ne[32], d[6];
+  double ne[32];
   for (int i = 0; i < 32; i++) ne[i] = c->h_out[i];
   if (c->p2p_world >= 1 && ne[31] != 0.0) return fail(RPE_ERR_HIP,
       "peer-to-peer exchange timed out at step %llu (a peer did not deliver its record)", c->p2p_step - 1);
-  ne[29] = rpe::pivot_floor(c->dtype == RPE_F64);   // the record handed out carries the floor rpe_gn_solve reads, as rpe_normal_eq's does
-  if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(c->dtype == RPE_F64))) return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite (weight sum %g)",
-      ne[28]);
-  rpe::se3_left_update(d, pose12);
-  if (ne32_out) std::memcpy(ne32_out, ne, sizeof(ne));
-  if (step_norm) *step_norm = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-  return RPE_OK;
+  return sharded_update(c, ne, pose12, ne32_out, step_norm);
 }
 
 // `steps` sharded steps in one call (the host loop stays inside the library, as rpe_gn_refine keeps it for one GPU)

@@ -26,17 +26,6 @@ int model_room(rpe_context* c, int64_t n) {
 extern "C" {
 // ---------------------------------------------------------------------------------------------- Part 3: front end
 namespace {
-// one pyramid level of frame and model: maps, pixels, model camera (level 0 = the single-level front end)
-struct Level { const float* f[3]; const float* m[2]; int64_t n; rpe::Camera mcam; };
-Level level_of(rpe_context* c, int l) {
-  auto& F = c->fe;
-  Level L;
-  for (int k = 0; k < 3; k++) L.f[k] = F.fmap[k] + 3 * F.fgeo.off[l];
-  for (int k = 0; k < 2; k++) L.m[k] = F.mmap[k] + 3 * F.mgeo.off[l];
-  L.n = (int64_t)F.fgeo.cam[l].width * F.fgeo.cam[l].height;
-  L.mcam = F.mgeo.cam[l];
-  return L;
-}
 int associate_launch(rpe_context* c, const Level& lv, const double* pose12, double dist_thr, double cos_thr, int use_normals,
     bool pose_on_device, bool count) {
   auto& F = c->fe;
@@ -311,8 +300,7 @@ namespace {
 int icp_level(rpe_context* c, const rpe_icp_options* o, const Level& lv, bool leave_pairs, double* pose12, int* iters_out,
               double* last_step, double* final_cost, int64_t* matched) {
   int rc = RPE_OK;
-  int it = 0;
-  double step = 0, cost = 0, pairs = 0;
+  GnRun run;   // run.weight: the pairs of the last round (the record's weight sum)
   bool host_rounds = false;
   const int64_t n = lv.n;
   const float dgate = (float)o->dist_thr;
@@ -369,11 +357,11 @@ int icp_level(rpe_context* c, const rpe_icp_options* o, const Level& lv, bool le
       if ((rc = wait_host(c, rpe::kNeLd))) return rc;
     }
     for (int i = 0; i < 12; i++) pose12[i] = c->h_out[i];
-    step = c->h_out[12]; cost = c->h_out[13]; it = (int)c->h_out[14]; pairs = c->h_out[16];
-    if (c->h_out[15] == 2.0) { if (iters_out) *iters_out = it; return fail(RPE_ERR_HIP,
-        "ICP device loop: a workgroup's sums never arrived at iteration %d", it); }
-    if (c->h_out[15] != 0.0) { if (iters_out) *iters_out = it; return fail(RPE_ERR_DEGENERATE,
-        "ICP: normal equations are not positive definite at iteration %d", it - 1); }
+    run.step = c->h_out[12]; run.cost = c->h_out[13]; run.it = (int)c->h_out[14]; run.weight = c->h_out[16];
+    if (c->h_out[15] == 2.0) { if (iters_out) *iters_out = run.it; return fail(RPE_ERR_HIP,
+        "ICP device loop: a workgroup's sums never arrived at iteration %d", run.it); }
+    if (c->h_out[15] != 0.0) { if (iters_out) *iters_out = run.it; return fail(RPE_ERR_DEGENERATE,
+        "ICP: normal equations are not positive definite at iteration %d", run.it - 1); }
   } else if (o->fused && c->resident && c->host_resident && o->max_iter >= 2 && !c->hostex && !c->comm && c->p2p_world_saved < 1) {
     // host-driven ICP in ONE launch: the frame's pixels stay in registers, every iteration the host hands the pose over, the grid pairs
     // its pixels with the model under that pose and sends the run records back (rpe_icp.hip icp_resident_kernel)
@@ -386,33 +374,27 @@ int icp_level(rpe_context* c, const rpe_icp_options* o, const Level& lv, bool le
     };
     { SlotHold one_resident_grid(resident_mutex(c->device));
       if (!one_resident_grid) rc = kResidentBusy;   // (a session holds the slot: every round a launch)
-      else rc = resident_host_loop(c, launch, grid, nacc, max_rows, rows_auto, 1.0, pose12, o->max_iter, o->tol, &it, &step, &cost, &pairs,
-          "ICP: normal equations"); }
-    if (rc != RPE_OK && rc != kResidentLost && rc != kResidentBusy) { if (iters_out) *iters_out = it; return rc; }
+      else rc = resident_host_loop(c, launch, grid, nacc, max_rows, rows_auto, 1.0, pose12, o->max_iter, o->tol, &run.it, &run.step, &run.cost,
+          &run.weight, "ICP: normal equations"); }
+    if (rc != RPE_OK && rc != kResidentLost && rc != kResidentBusy) { if (iters_out) *iters_out = run.it; return rc; }
     host_rounds = rc == kResidentLost || rc == kResidentBusy;   // the grid was lost after `it` whole rounds (or never launched): the rest one launch per round
   } else host_rounds = true;
   if (host_rounds) {
-    for (; it < o->max_iter; it++) {
-      if ((rc = round(pose12, collect_target(c), false))) return rc;
-      if ((rc = wait_host(c, rpe::kNeLd))) return rc;
-      double ne[32], d[6];
+    rc = gn_host_rounds([&](const double* pose, double* ne) -> int {
+      int r = round(pose, collect_target(c), false);
+      if (r || (r = wait_host(c, rpe::kNeLd))) return r;
       for (int i = 0; i < 32; i++) ne[i] = c->h_out[i];
-      cost = ne[27]; pairs = ne[28];
-      if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(c->dtype == RPE_F64))) {
-        if (iters_out) *iters_out = it;
-        return fail(RPE_ERR_DEGENERATE, "ICP: normal equations are not positive definite at iteration %d (%g pairs)", it, pairs);
-      }
-      rpe::se3_left_update(d, pose12);
-      step = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-      if (step < o->tol) { it++; break; }
+      return RPE_OK;
+    }, rpe::pivot_floor(c->dtype == RPE_F64), 1.0, o->max_iter, o->tol, pose12, &run);
+    if (rc == kGnRefused) {
+      if (iters_out) *iters_out = run.it;
+      return fail(RPE_ERR_DEGENERATE, "ICP: normal equations are not positive definite at iteration %d (%g pairs)", run.it, run.weight);
     }
+    if (rc) return rc;
   }
   // leave the pairs in the slots
   if (leave_pairs && o->fused && (rc = associate_launch(c, lv, pose12, o->dist_thr, o->cos_thr, o->use_normals, false, false))) return rc;
-  if (iters_out) *iters_out = it;
-  if (last_step) *last_step = step;
-  if (final_cost) *final_cost = cost;
-  if (matched) *matched = (int64_t)pairs;   // pairs of the last round (the record's weight sum)
+  run.report(iters_out, last_step, final_cost, matched);
   return RPE_OK;
 }
 
@@ -441,35 +423,21 @@ int rpe_icp_pyramid(rpe_context* c, const rpe_icp_options* o, int levels, const 
     return fail(RPE_ERR_ARG, "rpe_icp_pyramid: bad options (kind must be RPE_RES_P2P or RPE_RES_P2PLANE)");
   if (o->kind == RPE_RES_P2PLANE && !o->use_normals)
     return fail(RPE_ERR_ARG, "rpe_icp_pyramid: point-to-plane needs use_normals = 1");
-  if (levels < 1 || levels > RPE_MAX_LEVELS) return fail(RPE_ERR_ARG, "rpe_icp_pyramid: levels must be 1 .. %d (got %d)", RPE_MAX_LEVELS,
-      levels);
-  for (int l = 0; l < levels; l++) {
-    if (iters_per_level[l] < (l == 0 ? 1 : 0))
-      return fail(RPE_ERR_ARG, "rpe_icp_pyramid: level %d needs %s rounds (got %d)", l, l == 0 ? ">= 1" : ">= 0", iters_per_level[l]);
-    if (dist_thr_per_level && !(dist_thr_per_level[l] >= 0))
-      return fail(RPE_ERR_ARG, "rpe_icp_pyramid: bad distance gate at level %d", l);
-  }
+  if ((rc = pyramid_complaint("rpe_icp_pyramid", levels, iters_per_level, dist_thr_per_level))) return rc;
   auto& F = c->fe;
   if (F.fgeo.levels < levels) return fail(RPE_ERR_STATE, "rpe_icp_pyramid: the frame has %d level(s), %d asked (rpe_frame_set_depth_pyramid)",
       F.fgeo.levels, levels);
   if (F.mgeo.levels < levels) return fail(RPE_ERR_STATE, "rpe_icp_pyramid: the model has %d level(s), %d asked (rpe_model_from_frame of a "
       "pyramid frame, or rpe_model_build_pyramid)", F.mgeo.levels, levels);
   HIP_TRY(hipSetDevice(c->device));
-  for (int l = levels - 1; l >= 0; l--) {
-    int it = 0;
-    if (iters_per_level[l] > 0) {
-      rpe_icp_options lo = *o;
-      lo.max_iter = iters_per_level[l];
-      if (dist_thr_per_level) lo.dist_thr = dist_thr_per_level[l];
-      const Level lv = level_of(c, l);
-      if ((rc = claim_slots(c, lv.n))) return rc;
-      rc = icp_level(c, &lo, lv, l == 0, pose12, &it, l == 0 ? last_step : nullptr, l == 0 ? final_cost : nullptr,
-                     l == 0 ? matched : nullptr);
-    }
-    if (iters_out) iters_out[l] = it;
-    if (rc) return rc;
-  }
-  return RPE_OK;
+  return coarse_to_fine(levels, iters_per_level, dist_thr_per_level, o->dist_thr, iters_out,
+                        [&](int l, int rounds, double gate, bool fine, int* it) -> int {
+    rpe_icp_options lo = *o;
+    lo.max_iter = rounds; lo.dist_thr = gate;
+    const Level lv = level_of(c, l);
+    if (int r = claim_slots(c, lv.n)) return r;
+    return icp_level(c, &lo, lv, fine, pose12, it, fine ? last_step : nullptr, fine ? final_cost : nullptr, fine ? matched : nullptr);
+  });
 }
 
 }  // extern "C"

@@ -32,6 +32,29 @@ inline void one_level(const rpe_camera& k, const rpe::Camera& f, rpe_camera* kc,
   g->levels = 1; g->cam[0] = f; kc[0] = k;
   for (int l = 1; l <= RPE_MAX_LEVELS; l++) g->off[l] = (int64_t)f.width * f.height;
 }
+// one pyramid level of frame and model: maps (frame vertex, normal, bearing; model vertex, normal), pixels, model camera (level 0 = the
+// single-level front end).  A side that is not there yields pointers nobody reads
+struct Level { const float* f[3]; const float* m[2]; int64_t n; rpe::Camera mcam; };
+inline Level level_of(rpe_context* c, int l) {
+  auto& F = c->fe;
+  Level L;
+  for (int k = 0; k < 3; k++) L.f[k] = F.fmap[k] + 3 * F.fgeo.off[l];
+  for (int k = 0; k < 2; k++) L.m[k] = F.mmap[k] + 3 * F.mgeo.off[l];
+  L.n = (int64_t)F.fgeo.cam[l].width * F.fgeo.cam[l].height;
+  L.mcam = F.mgeo.cam[l];
+  return L;
+}
+// pyramid_args (rpe_gn_host.hpp) worded for the coarse-to-fine entry point `who`: RPE_ERR_ARG, or RPE_OK
+inline int pyramid_complaint(const char* who, int levels, const int* iters_per_level, const double* dist_thr_per_level) {
+  int l = 0;
+  switch (pyramid_args(levels, iters_per_level, dist_thr_per_level, &l)) {
+    case kPyramidLevels: return fail(RPE_ERR_ARG, "%s: levels must be 1 .. %d (got %d)", who, RPE_MAX_LEVELS, levels);
+    case kPyramidRounds: return fail(RPE_ERR_ARG, "%s: level %d needs %s rounds (got %d)", who, l, l == 0 ? ">= 1" : ">= 0", iters_per_level[l]);
+    case kPyramidGate: return fail(RPE_ERR_ARG, "%s: bad distance gate at level %d", who, l);
+    case kPyramidOk: break;
+  }
+  return RPE_OK;
+}
 
 // ---- rpe_color_api.hip
 // the colour volume of the current volume: allocated on first use after rpe_volume_init, cleared to 0 unless `clear` is false (the

@@ -22,15 +22,16 @@
 //   rpe_mapmesh_api.hip   Part 3: the map, mesh and raycast (rpe_volume_map_bounds / _map_mesh / _map_raycast: the window and the archived
 //                         bricks inside a box of world voxels; the mesh's brick list and neighbour table, kernels in rpe_mapmesh.hip;
 //                         the raycast's brick grid, kernels in rpe_frontend.hip)
-// Two headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
-// host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create) and rpe_frontend_host.hpp (what the
-// Part 3 units share: camera and pose casts, the solver slots, feature / match options, the relocalisers' common steps).
+// Three headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
+// host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create), rpe_gn_host.hpp (the Gauss-Newton
+// step, round loop and coarse-to-fine walk of every host loop) and rpe_frontend_host.hpp (what the Part 3 units share: camera and pose
+// casts, the pyramid-level view, the solver slots, feature / match options, the relocalisers' common steps).
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
 #include "rpe_kernels.h"
 #include "rpe_devbuf.hpp"
-#include "../include/rpe/linalg.hpp"
+#include "rpe_gn_host.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types only: the RCCL entry points are resolved with dlopen/dlsym (no DT_NEEDED on librccl)
@@ -454,7 +455,7 @@ bool session_matches(const rpe_context* c, int kind, int mode, double thre_3d, d
 
 // Host side of a RESIDENT loop (rpe_gn_refine, rpe_icp): ONE launch (`launch(rt, base)`) whose grid stays resident; the host hands
 // every pose to it through the control block in device memory (two stores' worth of PCIe latency instead of a kernel launch per
-// iteration), receives the run records of every iteration, adds them, solves the 6x6 system and applies the SE(3) update, as the
+// iteration), receives the run records of every iteration, adds them and takes the step (gn_update), as the
 // one-launch-per-iteration loop does.  Pose i carries tag base + i, the records of iteration i carry sequence base + i.
 // Cross-workgroup stage: runs of `rows` workgroups are added by the first workgroup of the run (granule hand-off, one hop), the run
 // records come to the host, which adds them in run order.  A handful of small records (grid x sums <= 1024 pairs, i.e. a few thousand
@@ -494,8 +495,7 @@ inline int resident_host_loop(rpe_context* c, Launch launch, int grid, int nacc,
   double tp = c->loop_prof ? clock_us() : 0;
   for (;;) {
     c->seq = base + (unsigned long long)received + 1;
-    double ne[32], d[6];
-    double tot[32];
+    double ne[32], tot[32];
     if ((rc = wait_host_partials(c, runs, nacc, tot, 0, true))) { status = rc; break; }
     if (nacc == 17) expand_p2p17(tot, ne); else { for (int i = 0; i < 32; i++) ne[i] = i < nacc ? tot[i] : 0.0; }
     // CLEAN flavour: a NaN or an infinity anywhere in the arrays shows in the very first record (before any pose update could
@@ -506,10 +506,8 @@ inline int resident_host_loop(rpe_context* c, Launch launch, int grid, int nacc,
     received++;
     if (c->loop_prof) { const double t = clock_us(); if (received > 1) { c->prof_wait_us += t - tp; c->prof_steps++; } tp = t; }
     cost = cost_scale * ne[27]; weight = ne[28];
-    if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(c->dtype == RPE_F64))) { status = fail(RPE_ERR_DEGENERATE,
+    if (!gn_update(ne, rpe::pivot_floor(c->dtype == RPE_F64), pose12, &step)) { status = fail(RPE_ERR_DEGENERATE,
         "%s are not positive definite at iteration %d (weight sum %g)", what, it, ne[28]); break; }
-    rpe::se3_left_update(d, pose12);
-    step = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
     it = received;
     if (step < tol || received == max_iter) break;
     hand_over(pose12, base + (unsigned long long)received + 1);

@@ -5,16 +5,12 @@
 using namespace rpeh;
 
 namespace {
-// one level of what a round reads: frame vertex / normal / intensity, model vertex / normal / photometric map, pixels, model camera
-struct PhotoLevel { const float *fv, *fn, *fi, *mv, *mn, *pm; int64_t n; rpe::Camera mcam; };
+// one level of what a round reads: the front end's level (frame vertex / normal, model vertex / normal, pixels, model camera) and
+// the photometric maps beside it: the frame's intensity, the model's {I, gx, gy, zm}
+struct PhotoLevel : Level { const float *fi, *pm; };
 PhotoLevel photo_level(rpe_context* c, int l) {
   auto& F = c->fe;
-  PhotoLevel L;
-  L.fv = F.fmap[0] + 3 * F.fgeo.off[l]; L.fn = F.fmap[1] + 3 * F.fgeo.off[l]; L.fi = F.pint + F.fgeo.off[l];
-  L.mv = F.mmap[0] + 3 * F.mgeo.off[l]; L.mn = F.mmap[1] + 3 * F.mgeo.off[l]; L.pm = F.pmap + 4 * F.mgeo.off[l];
-  L.n = (int64_t)F.fgeo.cam[l].width * F.fgeo.cam[l].height;
-  L.mcam = F.mgeo.cam[l];
-  return L;
+  return {level_of(c, l), F.pint + F.fgeo.off[l], F.pmap + 4 * F.mgeo.off[l]};
 }
 int photo_ready(rpe_context* c, int levels, const char* who) {
   if (!c) return fail(RPE_ERR_ARG, "null context");
@@ -29,7 +25,7 @@ int photo_ready(rpe_context* c, int levels, const char* who) {
 // one round: launch, wait, the 32-double record of both terms in ne (cost and pairs the geometric ones), the photometric cost / pairs
 int rgbd_round(rpe_context* c, const PhotoLevel& lv, const rpe_icp_options* o, double dist_thr, float lam, int geometric,
                const double* pose12, double* ne, double* pcost, double* ppairs) {
-  HIP_TRY(rpe::launch_icp_photo(lv.fv, lv.fn, lv.fi, lv.n, lv.mv, lv.mn, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr,
+  HIP_TRY(rpe::launch_icp_photo(lv.f[0], lv.f[1], lv.fi, lv.n, lv.m[0], lv.m[1], lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr,
                                 o ? (float)o->cos_thr : 0.f, lam, geometric, pose12, collect_target(c), c->stream));
   int rc = wait_host(c, rpe::kNlLd);
   if (rc) return rc;
@@ -41,25 +37,17 @@ int rgbd_round(rpe_context* c, const PhotoLevel& lv, const rpe_icp_options* o, d
 int rgbd_level(rpe_context* c, const rpe_icp_options* o, int l, int max_iter, double dist_thr, float lam, double* pose12, int* iters_out,
                double* last_step, double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched) {
   const PhotoLevel lv = photo_level(c, l);
-  int it = 0, rc;
-  double step = 0, cost = 0, pairs = 0, pcost = 0, ppairs = 0;
-  for (; it < max_iter; it++) {
-    double ne[32], d[6];
-    if ((rc = rgbd_round(c, lv, o, dist_thr, lam, 1, pose12, ne, &pcost, &ppairs))) return rc;
-    cost = ne[27]; pairs = ne[28];
-    if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(false))) {
-      if (iters_out) *iters_out = it;
-      return fail(RPE_ERR_DEGENERATE, "RGB-D ICP: normal equations are not positive definite at iteration %d (%g + %g pairs)", it, pairs,
-                  ppairs);
-    }
-    rpe::se3_left_update(d, pose12);
-    step = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-    if (step < o->tol) { it++; break; }
+  GnRun run;   // run.weight: the geometric pairs
+  double pcost = 0, ppairs = 0;
+  const int rc = gn_host_rounds([&](const double* pose, double* ne) { return rgbd_round(c, lv, o, dist_thr, lam, 1, pose, ne, &pcost, &ppairs); },
+                                rpe::pivot_floor(false), 1.0, max_iter, o->tol, pose12, &run);
+  if (rc == kGnRefused) {
+    if (iters_out) *iters_out = run.it;
+    return fail(RPE_ERR_DEGENERATE, "RGB-D ICP: normal equations are not positive definite at iteration %d (%g + %g pairs)", run.it, run.weight,
+                ppairs);
   }
-  if (iters_out) *iters_out = it;
-  if (last_step) *last_step = step;
-  if (final_cost) *final_cost = cost;
-  if (matched) *matched = (int64_t)pairs;
+  if (rc) return rc;
+  run.report(iters_out, last_step, final_cost, matched);
   if (photo_cost) *photo_cost = pcost;
   if (photo_matched) *photo_matched = (int64_t)ppairs;
   return RPE_OK;
@@ -179,7 +167,7 @@ int rpe_photo_rows(rpe_context* c, int level, const double* pose12, double dist_
   const PhotoLevel lv = photo_level(c, level);
   DevBuf<float> d_rows;
   if ((rc = d_rows.once(c, (size_t)lv.n * 7 * sizeof(float)))) return rc;
-  hipError_t e = rpe::launch_photo_rows(lv.fv, lv.fi, lv.n, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr, pose12, d_rows, c->stream);
+  hipError_t e = rpe::launch_photo_rows(lv.f[0], lv.fi, lv.n, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr, pose12, d_rows, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, (size_t)lv.n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(RPE_ERR_HIP, "rpe_photo_rows: %s", hipGetErrorString(e));
@@ -208,26 +196,15 @@ int rpe_icp_pyramid_rgbd(rpe_context* c, const rpe_icp_options* o, double photo_
   if (!c) return fail(RPE_ERR_ARG, "null context");
   int rc = rgbd_options(o, photo_weight, pose12, "rpe_icp_pyramid_rgbd");
   if (rc) return rc;
-  if (!iters_per_level || levels < 1 || levels > RPE_MAX_LEVELS)
-    return fail(RPE_ERR_ARG, "rpe_icp_pyramid_rgbd: levels must be 1 .. %d (got %d)", RPE_MAX_LEVELS, levels);
-  for (int l = 0; l < levels; l++) {
-    if (iters_per_level[l] < (l == 0 ? 1 : 0))
-      return fail(RPE_ERR_ARG, "rpe_icp_pyramid_rgbd: level %d needs %s rounds (got %d)", l, l == 0 ? ">= 1" : ">= 0", iters_per_level[l]);
-    if (dist_thr_per_level && !(dist_thr_per_level[l] >= 0))
-      return fail(RPE_ERR_ARG, "rpe_icp_pyramid_rgbd: bad distance gate at level %d", l);
-  }
+  if ((rc = pyramid_complaint("rpe_icp_pyramid_rgbd", levels, iters_per_level, dist_thr_per_level))) return rc;
   if ((rc = photo_ready(c, levels, "rpe_icp_pyramid_rgbd"))) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  for (int l = levels - 1; l >= 0; l--) {
-    int it = 0;
-    const bool fine = l == 0;
-    if (iters_per_level[l] > 0)
-      rc = rgbd_level(c, o, l, iters_per_level[l], dist_thr_per_level ? dist_thr_per_level[l] : o->dist_thr, (float)photo_weight, pose12, &it,
-                      fine ? last_step : nullptr, fine ? final_cost : nullptr, fine ? matched : nullptr, fine ? photo_cost : nullptr,
-                      fine ? photo_matched : nullptr);
-    if (iters_out) iters_out[l] = it;
-    if (rc) return rc;
-  }
+  rc = coarse_to_fine(levels, iters_per_level, dist_thr_per_level, o->dist_thr, iters_out,
+                      [&](int l, int rounds, double gate, bool fine, int* it) {
+    return rgbd_level(c, o, l, rounds, gate, (float)photo_weight, pose12, it, fine ? last_step : nullptr, fine ? final_cost : nullptr,
+                      fine ? matched : nullptr, fine ? photo_cost : nullptr, fine ? photo_matched : nullptr);
+  });
+  if (rc) return rc;
   return rpe_associate(c, pose12, dist_thr_per_level ? dist_thr_per_level[0] : o->dist_thr, o->cos_thr, o->use_normals, nullptr);
 }
 

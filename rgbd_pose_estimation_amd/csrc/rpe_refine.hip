@@ -64,13 +64,22 @@ bool pin_calling_thread(int cpu) {
   CPU_SET(cpu, &set);
   return sched_setaffinity(0, sizeof set, &set) == 0;   // pid 0: the calling thread
 }
+// how the one-launch-per-iteration rounds of both refinements end (gn_host_rounds): a round's own error as it is, a refused system
+// worded, else the loop's figures
+int refine_result(int rc, const GnRun& run, int* iters_out, double* last_step, double* final_cost) {
+  if (rc != RPE_OK && rc != kGnRefused) return rc;
+  if (iters_out) *iters_out = run.it;
+  if (rc == kGnRefused)
+    return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite at iteration %d (weight sum %g)", run.it, run.weight);
+  run.report(nullptr, last_step, final_cost);
+  return RPE_OK;
+}
 }  // namespace
 extern "C" {
 int rpe_gn_refine_joint(rpe_context* c, int nterms, const rpe_term* terms, int flags, double* pose12, int max_iter, double tol,
                         int* iters_out, double* last_step, double* final_cost) {
   session_end(c);
-  int it = 0;
-  double step = 0, cost = 0;
+  GnRun run;
   if (c && c->resident && c->host_resident && max_iter >= 2 && !c->hostex && !c->comm && c->p2p_world_saved < 1) {
     // ONE launch for the whole refinement, as rpe_gn_refine: the grid of the joint kernel stays resident, the host hands every pose
     // over through the control block, adds the run records, solves and updates.  Frame-sized problems only (one group per thread,
@@ -83,51 +92,34 @@ int rpe_gn_refine_joint(rpe_context* c, int nterms, const rpe_term* terms, int f
     std::memcpy(start, pose12, sizeof(start));
     for (int attempt = 0; attempt < 2; attempt++) {
       const bool clean = take_clean_terms(c, sp.bits, true);   // CLEAN flavour first; its first record is checked
-      if (!rpe::joint_resident_fits(c->arrays(), sp.bits, flags, c->max_blocks, false, clean)) { rc = kResidentLost; it = 0; break; }
+      if (!rpe::joint_resident_fits(c->arrays(), sp.bits, flags, c->max_blocks, false, clean)) { rc = kResidentLost; run.it = 0; break; }
       int grid = 0, nacc = 0, max_rows = 1, rows_auto = 1;
       rpe::resident_geometry(c->arrays(), RPE_RES_P2PLANE, c->max_blocks, &grid, &nacc, &max_rows, &rows_auto);   // the 29-sum geometry
-      double weight = 0;
       bool verified = false;
       auto launch = [&](const rpe::ReduceTarget& rt, unsigned long long base) -> hipError_t {
         return rpe::launch_normal_eq_joint_resident(c->arrays(), sp.bits, flags, sp.scale, sp.robust, sp.rk,
                                                     (const unsigned long long*)c->ctl, base, max_iter, rt, c->stream);
       };
       { SlotHold one_resident_grid(resident_mutex(c->device));
-        if (!one_resident_grid) { rc = kResidentBusy; it = 0; break; }   // (a session holds the slot: one launch per iteration below)
-        rc = resident_host_loop(c, launch, grid, nacc, max_rows, rows_auto, 1.0, pose12, max_iter, tol, &it, &step, &cost, &weight,
-            "normal equations", clean, &verified); }
+        if (!one_resident_grid) { rc = kResidentBusy; run.it = 0; break; }   // (a session holds the slot: one launch per iteration below)
+        rc = resident_host_loop(c, launch, grid, nacc, max_rows, rows_auto, 1.0, pose12, max_iter, tol, &run.it, &run.step, &run.cost,
+            &run.weight, "normal equations", clean, &verified); }
       if (clean && rc == kResidentDirty) note_clean_terms(c, sp.bits, false);
       else if (clean && verified) note_clean_terms(c, sp.bits, true);
       if (rc != kResidentDirty) break;   // else: NaN-marked arrays -- once more, guarded, from the untouched start pose
       std::memcpy(pose12, start, sizeof(start));
-      it = 0;
+      run.it = 0;
     }
     if (rc != kResidentLost && rc != kResidentBusy) {
-      if (iters_out) *iters_out = it;
-      if (rc != RPE_OK) return rc;
-      if (last_step) *last_step = step;
-      if (final_cost) *final_cost = cost;
-      return RPE_OK;
+      if (iters_out) *iters_out = run.it;
+      if (rc == RPE_OK) run.report(nullptr, last_step, final_cost);
+      return rc;
     }
     // the resident grid was lost after `it` whole iterations (or never launched): carry on below, one launch per iteration
   }
-  for (; it < max_iter; it++) {
-    double ne[32], d[6];
-    int rc = rpe_normal_eq_joint(c, nterms, terms, flags, pose12, ne);
-    if (rc) return rc;
-    cost = ne[27];
-    if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(c->dtype == RPE_F64))) {
-      if (iters_out) *iters_out = it;
-      return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite at iteration %d (weight sum %g)", it, ne[28]);
-    }
-    rpe::se3_left_update(d, pose12);
-    step = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-    if (step < tol) { it++; break; }
-  }
-  if (iters_out) *iters_out = it;
-  if (last_step) *last_step = step;
-  if (final_cost) *final_cost = cost;
-  return RPE_OK;
+  const int rc = gn_host_rounds([&](const double* pose, double* ne) { return rpe_normal_eq_joint(c, nterms, terms, flags, pose, ne); },
+                                rpe::pivot_floor(c && c->dtype == RPE_F64), 1.0, max_iter, tol, pose12, &run);   // (no context: the round says so)
+  return refine_result(rc, run, iters_out, last_step, final_cost);
 }
 
 // Device-resident Gauss-Newton: the pose and the loop state live in HBM; every iteration is ONE launch whose last workgroup
@@ -313,8 +305,7 @@ int rpe_gn_refine(rpe_context* c, int nterms, const int* kinds, const double* sc
         terms[t].robust_k = 1.0; }
     return rpe_gn_refine_joint(c, nterms, terms, flags, pose12, max_iter, tol, iters_out, last_step, final_cost);
   }
-  int it = 0;
-  double step = 0, cost = 0;
+  GnRun run;
   const double sc = scales ? scales[0] : 1.0;
   // sharded contexts: only with the host-side exchange (every rank's host thread adds the peers' records to its own each iteration);
   // RCCL / in-kernel peer-to-peer contexts take rpe_gn_steps_dist
@@ -337,7 +328,6 @@ int rpe_gn_refine(rpe_context* c, int nterms, const int* kinds, const double* sc
     int grid = 0, nacc = 0, max_rows = 1, rows_auto = 1;
     rpe::resident_geometry(c->arrays(), kinds[0], c->max_blocks, &grid, &nacc, &max_rows, &rows_auto);
     const int kind = kinds[0];
-    double weight = 0;
     auto launch = [&](const rpe::ReduceTarget& rt, unsigned long long base) -> hipError_t {
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (c->timing && c->ev_used < c->ev0.size() && (c->timing_calls++ % c->timing_stride) == 0) { e0 = c->ev0[c->ev_used];
@@ -349,43 +339,28 @@ int rpe_gn_refine(rpe_context* c, int nterms, const int* kinds, const double* sc
       const bool clean = take_clean(c, kind, true);   // CLEAN flavour first; its first record is checked
       bool verified = false;
       { SlotHold one_resident_grid(resident_mutex(c->device));
-        if (!one_resident_grid) { rc = kResidentBusy; it = 0; break; }   // (a session holds the slot: one launch per iteration below)
-        rc = resident_host_loop(c, launch, grid, nacc, max_rows, rows_auto, sc, pose12, max_iter, tol, &it, &step, &cost, &weight,
-            "normal equations", clean, &verified); }
+        if (!one_resident_grid) { rc = kResidentBusy; run.it = 0; break; }   // (a session holds the slot: one launch per iteration below)
+        rc = resident_host_loop(c, launch, grid, nacc, max_rows, rows_auto, sc, pose12, max_iter, tol, &run.it, &run.step, &run.cost,
+            &run.weight, "normal equations", clean, &verified); }
       // promoted to "verified finite" only by a first record that was received and finite: a launch error, a wait that timed out or a
       // grid lost before the first record say nothing about the arrays (their state stays as it was)
       if (clean && rc == kResidentDirty) note_clean_launch(c, kind, false);
       else if (clean && verified) note_clean_launch(c, kind, true);
       if (rc != kResidentDirty) break;   // else: NaN-marked arrays -- once more, guarded, from the untouched start pose
-      it = 0;
+      run.it = 0;
     }
     if (rc != kResidentLost && rc != kResidentBusy) {
-      if (iters_out) *iters_out = it;
-      if (rc != RPE_OK) return rc;
-      if (last_step) *last_step = step;
-      if (final_cost) *final_cost = cost;
-      return RPE_OK;
+      if (iters_out) *iters_out = run.it;
+      if (rc == RPE_OK) run.report(nullptr, last_step, final_cost);
+      return rc;
     }
     // the resident grid was lost after `it` whole iterations (or never launched): carry on from pose12 below, one launch per iteration
   }
-  for (; it < max_iter; it++) {
-    double ne[32], d[6];
-    int rc = rpe_normal_eq(c, kinds[0], flags, pose12, ne);
-    if (rc) return rc;
-    if (c->hostex && (rc = rpe_host_exchange_allreduce_f64(c->hostex, ne, 32))) return rc;
-    cost = sc * ne[27];
-    if (!rpe::solve_normal_eq6(ne, d, rpe::pivot_floor(c->dtype == RPE_F64))) {
-      if (iters_out) *iters_out = it;
-      return fail(RPE_ERR_DEGENERATE, "normal equations are not positive definite at iteration %d (weight sum %g)", it, ne[28]);
-    }
-    rpe::se3_left_update(d, pose12);
-    step = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-    if (step < tol) { it++; break; }
-  }
-  if (iters_out) *iters_out = it;
-  if (last_step) *last_step = step;
-  if (final_cost) *final_cost = cost;
-  return RPE_OK;
+  const int rc = gn_host_rounds([&](const double* pose, double* ne) -> int {
+    const int r = rpe_normal_eq(c, kinds[0], flags, pose, ne);
+    return r || !c->hostex ? r : rpe_host_exchange_allreduce_f64(c->hostex, ne, 32);
+  }, rpe::pivot_floor(c->dtype == RPE_F64), sc, max_iter, tol, pose12, &run);
+  return refine_result(rc, run, iters_out, last_step, final_cost);
 }
 
 // ---------------------------------------------------------------------------------------------- host thread of the resident loops

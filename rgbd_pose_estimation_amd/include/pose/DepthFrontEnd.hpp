@@ -208,9 +208,7 @@ class DepthFrontEnd {
   // dense ICP from `pose` (in/out)
   IcpResult icp(Pose& pose, const IcpOptions& o = IcpOptions()) {
     double p[12]; pose12(pose, p);
-    rpe_icp_options opt;
-    opt.kind = o.kind; opt.max_iter = o.max_iter; opt.tol = o.tol; opt.dist_thr = o.dist_thr; opt.cos_thr = o.cos_thr;
-    opt.use_normals = o.use_normals; opt.device_resident = o.device_resident; opt.fused = o.fused;
+    const rpe_icp_options opt = options_of(o);
     IcpResult r;
     int64_t m = 0;
     check(rpe_icp(_ctx, &opt, p, &r.iterations, &r.last_step, &r.cost, &m), "rpe_icp");
@@ -221,19 +219,9 @@ class DepthFrontEnd {
   // coarse-to-fine ICP from `pose` (in/out): iters[l] rounds and gate dist_thr[l] at level l (0 = finest; dist_thr empty: o.dist_thr)
   PyramidIcpResult icpPyramid(Pose& pose, const std::vector<int>& iters, const std::vector<double>& dist_thr = std::vector<double>(),
                               const IcpOptions& o = IcpOptions()) {
-    if (!dist_thr.empty() && dist_thr.size() != iters.size()) throw DeviceError(RPE_ERR_ARG, "icpPyramid: one gate per level");
-    double p[12]; pose12(pose, p);
-    rpe_icp_options opt;
-    opt.kind = o.kind; opt.max_iter = o.max_iter; opt.tol = o.tol; opt.dist_thr = o.dist_thr; opt.cos_thr = o.cos_thr;
-    opt.use_normals = o.use_normals; opt.device_resident = o.device_resident; opt.fused = o.fused;
-    PyramidIcpResult r;
-    int64_t m = 0;
-    check(rpe_icp_pyramid(_ctx, &opt, (int)iters.size(), iters.data(), dist_thr.empty() ? nullptr : dist_thr.data(), p, r.level_iterations,
-                          &r.last_step, &r.cost, &m), "rpe_icp_pyramid");
-    for (size_t l = 0; l < iters.size(); l++) r.iterations += r.level_iterations[l];
-    r.pairs = (long long)m;
-    pose = pose_of(p);
-    return r;
+    return pyramidIcp<PyramidIcpResult>("icpPyramid", "rpe_icp_pyramid", pose, iters, dist_thr, o,
+        [&](const rpe_icp_options* opt, int levels, const double* gates, double* p, PyramidIcpResult& r, int64_t* m) {
+          return rpe_icp_pyramid(_ctx, opt, levels, iters.data(), gates, p, r.level_iterations, &r.last_step, &r.cost, m); });
   }
   // (re)allocate and clear the TSDF volume
   void initVolume(const VolumeDesc& d) {
@@ -436,16 +424,12 @@ class DepthFrontEnd {
   // icpPyramid with the photometric term
   RgbdIcpResult icpPyramidRgbd(Pose& pose, double weight, const std::vector<int>& iters,
                                const std::vector<double>& dist_thr = std::vector<double>(), const IcpOptions& o = IcpOptions()) {
-    if (!dist_thr.empty() && dist_thr.size() != iters.size()) throw DeviceError(RPE_ERR_ARG, "icpPyramidRgbd: one gate per level");
-    double p[12]; pose12(pose, p);
-    const rpe_icp_options opt = options_of(o);
-    RgbdIcpResult r;
-    int64_t m = 0, pm = 0;
-    check(rpe_icp_pyramid_rgbd(_ctx, &opt, weight, (int)iters.size(), iters.data(), dist_thr.empty() ? nullptr : dist_thr.data(), p,
-                               r.level_iterations, &r.last_step, &r.cost, &m, &r.photo_cost, &pm), "rpe_icp_pyramid_rgbd");
-    for (size_t l = 0; l < iters.size(); l++) r.iterations += r.level_iterations[l];
-    r.pairs = (long long)m; r.photo_pairs = (long long)pm;
-    pose = pose_of(p);
+    int64_t pm = 0;
+    RgbdIcpResult r = pyramidIcp<RgbdIcpResult>("icpPyramidRgbd", "rpe_icp_pyramid_rgbd", pose, iters, dist_thr, o,
+        [&](const rpe_icp_options* opt, int levels, const double* gates, double* p, RgbdIcpResult& res, int64_t* m) {
+          return rpe_icp_pyramid_rgbd(_ctx, opt, weight, levels, iters.data(), gates, p, res.level_iterations, &res.last_step, &res.cost, m,
+                                      &res.photo_cost, &pm); });
+    r.photo_pairs = (long long)pm;
     return r;
   }
   // the residual image of a level under `pose`: model intensity at the pixel's projection minus the frame's (intensity levels), NaN
@@ -476,17 +460,9 @@ class DepthFrontEnd {
   // ... coarse to fine over the frame's levels, as icpPyramid: iters[l] rounds and gate dist_thr[l] at level l
   PyramidIcpResult icpPyramidVolume(Pose& pose, const std::vector<int>& iters, const std::vector<double>& dist_thr = std::vector<double>(),
                                     const IcpOptions& o = IcpOptions()) {
-    if (!dist_thr.empty() && dist_thr.size() != iters.size()) throw DeviceError(RPE_ERR_ARG, "icpPyramidVolume: one gate per level");
-    double p[12]; pose12(pose, p);
-    const rpe_icp_options opt = options_of(o);
-    PyramidIcpResult r;
-    int64_t m = 0;
-    check(rpe_icp_pyramid_sdf(_ctx, &opt, (int)iters.size(), iters.data(), dist_thr.empty() ? nullptr : dist_thr.data(), p, r.level_iterations,
-                              &r.last_step, &r.cost, &m), "rpe_icp_pyramid_sdf");
-    for (size_t l = 0; l < iters.size(); l++) r.iterations += r.level_iterations[l];
-    r.pairs = (long long)m;
-    pose = pose_of(p);
-    return r;
+    return pyramidIcp<PyramidIcpResult>("icpPyramidVolume", "rpe_icp_pyramid_sdf", pose, iters, dist_thr, o,
+        [&](const rpe_icp_options* opt, int levels, const double* gates, double* p, PyramidIcpResult& r, int64_t* m) {
+          return rpe_icp_pyramid_sdf(_ctx, opt, levels, iters.data(), gates, p, r.level_iterations, &r.last_step, &r.cost, m); });
   }
   // the residual image of a level under `pose`: the signed distance [m] of every frame vertex to the fused surface, NaN where the
   // pixel has no row (row 0 of rpe_sdf_rows)
@@ -716,6 +692,22 @@ class DepthFrontEnd {
   }
 
  private:
+  // what the three icpPyramid* members share: one gate per level or none, the options, the pose in and out, the rounds of all levels
+  // and the pairs; call(options, levels, gates or null, pose12, result, &pairs) is the entry point `entry`
+  template <class Result, class Call>
+  Result pyramidIcp(const char* member, const char* entry, Pose& pose, const std::vector<int>& iters, const std::vector<double>& dist_thr,
+                    const IcpOptions& o, Call call) {
+    if (!dist_thr.empty() && dist_thr.size() != iters.size()) throw DeviceError(RPE_ERR_ARG, std::string(member) + ": one gate per level");
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    Result r;
+    int64_t m = 0;
+    check(call(&opt, (int)iters.size(), dist_thr.empty() ? nullptr : dist_thr.data(), p, r, &m), entry);
+    for (size_t l = 0; l < iters.size(); l++) r.iterations += r.level_iterations[l];
+    r.pairs = (long long)m;
+    pose = pose_of(p);
+    return r;
+  }
   static rpe_icp_options options_of(const IcpOptions& o) {
     rpe_icp_options opt;
     opt.kind = o.kind; opt.max_iter = o.max_iter; opt.tol = o.tol; opt.dist_thr = o.dist_thr; opt.cos_thr = o.cos_thr;

@@ -353,3 +353,29 @@ def test_icp_pyramid_cpp(tmp_path):
                            "-Wl,-rpath," + os.path.dirname(lib), "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, RPE_QUIET="1"))
     assert r.returncode == 0 and "pyramid_icp: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("entry", ["icp_pyramid", "icp_pyramid_rgbd", "icp_pyramid_sdf"])
+def test_pyramid_entries_refuse_in_their_own_order(gpu_ctx_factory, entry):
+    """Which error a doubly wrong call gets is each entry point's own order of checks: rpe_icp_pyramid asks for frame and model (STATE)
+    before it looks at the levels (ARG); the RGB-D and the volume form look at options and levels (ARG) before what is prepared
+    (STATE).  No call here gets as far as a launch."""
+    P0 = pose12(np.eye(3), np.zeros(3))
+
+    def refused(ctx, **kw):
+        with pytest.raises(L.RpeError) as e:
+            getattr(ctx, entry)(P0, **kw)
+        return e.value
+
+    fresh = gpu_ctx_factory()                                  # no frame AND bad levels
+    first = L.RPE_ERR_STATE if entry == "icp_pyramid" else L.RPE_ERR_ARG
+    assert refused(fresh, iters=(0, 3)).code == first          # a finest level without rounds
+    assert refused(fresh, iters=()).code == first              # no level at all
+    cam = (20.0, 20.0, 7.5, 5.5, 16, 12)
+    ctx = gpu_ctx_factory().frame_set_depth(np.full((12, 16), 1.0, np.float32), cam)
+    ctx.model_from_frame(P0)
+    if entry == "icp_pyramid_sdf":
+        ctx.volume_init((8, 8, 8), 0.25, (-1.0, -1.0, 0.0), 0.5)
+    assert refused(ctx, iters=(3,), dist_thr=(-0.1,)).code == L.RPE_ERR_ARG
+    e = refused(ctx, iters=(3, 3))                             # one level is there (the RGB-D form: none prepared), two are asked
+    assert e.code == L.RPE_ERR_STATE and "2 asked" in str(e)

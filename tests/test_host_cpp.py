@@ -54,3 +54,15 @@ def test_device_buffer_cpp(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "devbuf_host.cpp"), "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0 and "devbuf_host: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_gn_host_cpp(tmp_path):
+    """The Gauss-Newton step, the round loop and the coarse-to-fine walk every host loop of the library runs (csrc/rpe_gn_host.hpp) on
+    scripted rounds and levels: round counts under tol and at max_iter, a loop taken up part way, a refused system, a round's own error,
+    the cost scale, level order, gates, the fine level, an error at a level, the argument complaints.  g++ with AddressSanitizer and
+    UBSan; a stand-alone program that links neither the library nor the HIP runtime."""
+    exe = str(tmp_path / "gn_host")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "cpp", "gn_host.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0 and "gn_host: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

@@ -70,7 +70,7 @@ MAX_KERNELS = {"rpe_normal_eq.hip": 320, "rpe_joint.hip": 160}
 MAX_LIBRARY_BYTES = 10 * 1024 * 1024
 # the C-ABI side is split by job (rpe_host.hpp lists the units); neither a host unit nor a header they share may grow back into a catch-all file
 MAX_HOST_SOURCE_BYTES = 40 * 1024
-SHARED_HOST_HEADERS = ("rpe_host.hpp", "rpe_devbuf.hpp", "rpe_frontend_host.hpp")
+SHARED_HOST_HEADERS = ("rpe_host.hpp", "rpe_devbuf.hpp", "rpe_gn_host.hpp", "rpe_frontend_host.hpp")
 
 
 def built():
