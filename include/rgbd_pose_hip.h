@@ -1187,6 +1187,45 @@ enum { RPE_MAPRAY_COLOR = 1, RPE_MAPRAY_NO_SKIP = 2 };
 int rpe_volume_map_raycast(rpe_context* ctx, const double* pose12, const rpe_camera* cam, double dmin, double dmax,
                            const int64_t lo[3], const int64_t hi[3], int flags);
 
+/* ---- Map volume term: a frame tracked against the TSDF of the whole MAP -- the window and the archived bricks.  "Volume term" reads the
+ * window's dense array, so a surface the map knows but the window no longer covers gives no row; these calls read the map.  No new
+ * arithmetic: the box lo <= w < hi of world voxels defines the VIRTUAL VOLUME that "Map mesh" and "Map raycast" define (lo = hi = NULL:
+ * rpe_volume_map_bounds): dim = hi - lo, o = (float)(origin_init + (double)lo * voxel_size), one rounding; voxel size, trunc and max
+ * weight are the init call's.  A map voxel holds the window's bits where the window covers it, the held brick's bits where the archive
+ * holds its world brick, {0, 0} elsewhere.
+ * THE CONTRACT: rpe_map_sdf_rows returns, bit for bit, what rpe_sdf_rows returns in a second context whose volume is a fresh
+ * rpe_volume_init of that virtual volume with the map's content uploaded: steps 1-8 of "Volume term" on the virtual volume
+ * (tests/mapsdf_oracle.py states the composition in numpy).  With the box equal to the window's extent o is the window's own o and the
+ * rows are rpe_sdf_rows' of the same context.  The record of rpe_map_sdf_normal_eq is the one rpe_sdf_normal_eq returns -- the same 32
+ * doubles, the row count exact, every sum within 8 * 2^-24 of the sum of the magnitudes of its products; it need not equal
+ * rpe_sdf_normal_eq's to the bit, because the sums are formed otherwise: a pixel's fp32 row is widened to fp64 and its products are
+ * accumulated in fp64 (a product of two floats is exact there), one pixel per thread and loop trip, then the fixed order of every
+ * reduction here.  The loops are rpe_icp_sdf's and rpe_icp_pyramid_sdf's, round for round, with that record.
+ * Rules: a frame (with the levels asked) and a volume, as "Volume term"; every dim and every component of the total shift a multiple of
+ * 8 (RPE_ERR_STATE, as rpe_volume_map_bounds); the box rules are the map mesh's (multiples of 8, 8 <= hi - lo <= 2^20), lo and hi both
+ * given or both NULL, and the box may hold at most 2^24 bricks (RPE_ERR_ARG with the count in the message).  The archive need not be on:
+ * the map is then the window.  The calls read the frame's maps, the window, the pool and the archive's index, and write nothing but the
+ * uploaded grid and the reduction's scratch: the model, the model colour, the prepared photometric maps, the solver slots, the last
+ * mesh, both volumes and the archive stay as they were.
+ * How: the BRICK GRID of "Map raycast" (one int32 per brick of the box) is built on the host and uploaded ONCE per call -- the map cannot
+ * change inside a call, so every round of a loop reads the same grid.  A pixel whose cell starts in an absent brick has no row without a
+ * voxel load; a cell inside the window is gathered as the window term gathers it; a cell across a brick face costs one grid lookup per
+ * corner beyond it.
+ * What it is NOT: rows are still not weighted by voxel weight; the grid is rebuilt and uploaded on every call (4 B per brick of the
+ * box), not kept between calls; the occupancy pre-pass of the raycast is not run. */
+/* rpe_sdf_rows / rpe_sdf_normal_eq / rpe_icp_sdf / rpe_icp_pyramid_sdf on the map inside the box; every other argument as theirs.
+ * RPE_ERR_STATE without a frame, a volume or the levels asked, or for unaligned dims or total shift; RPE_ERR_ARG for what the window
+ * forms refuse, lo without hi, a bad box, or more than 2^24 bricks */
+int rpe_map_sdf_rows(rpe_context* ctx, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals,
+                     const int64_t lo[3], const int64_t hi[3], float* rows);
+int rpe_map_sdf_normal_eq(rpe_context* ctx, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals,
+                          const int64_t lo[3], const int64_t hi[3], double* out32);
+int rpe_icp_map_sdf(rpe_context* ctx, const rpe_icp_options* opt, const int64_t lo[3], const int64_t hi[3], double* pose12,
+                    int* iters_out, double* last_step, double* final_cost, int64_t* matched);
+int rpe_icp_pyramid_map_sdf(rpe_context* ctx, const rpe_icp_options* opt, int levels, const int* iters_per_level,
+                            const double* dist_thr_per_level, const int64_t lo[3], const int64_t hi[3], double* pose12, int* iters_out,
+                            double* last_step, double* final_cost, int64_t* matched);
+
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.
  * 3 x K inputs are column-major doubles whose values are rounded to dtype before use. */

@@ -677,6 +677,50 @@ class Context:
         L.check(L.lib().rpe_icp_pyramid_sdf(self._h, C.byref(o), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step), C.byref(cost), C.byref(m)))
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
 
+    # ---- map volume term (Part 3): the volume term on the whole map -- the window plus the archived bricks -- inside a box
+    @staticmethod
+    def _box(box):
+        """(lo, hi) of a box of world voxels as the library takes them: two int64 triples, or two NULLs for the map's bounds"""
+        if box is None:
+            return None, None
+        return tuple(np.ascontiguousarray(b, np.int64).reshape(3) for b in box)
+
+    def map_sdf_rows(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True, box=None) -> np.ndarray:
+        """sdf_rows in the field of the MAP inside box = (lo, hi) in world voxels (multiples of 8; None: volume_map_bounds): bit for bit
+        sdf_rows of a dense volume of the box holding the map's content (rpe_map_sdf_rows)."""
+        p = np.array(pose12, np.float64).reshape(12)
+        lo, hi = self._box(box)
+        h, w = getattr(self, "_frame_hw", (0, 0))
+        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
+        L.check(L.lib().rpe_map_sdf_rows(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(lo), _p(hi), _p(out)))
+        return out
+
+    def map_sdf_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True, box=None) -> np.ndarray:
+        """sdf_normal_eq on the map inside the box: the same 32 float64."""
+        p = np.array(pose12, np.float64).reshape(12)
+        lo, hi = self._box(box)
+        out = np.zeros(32, np.float64)
+        L.check(L.lib().rpe_map_sdf_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(lo), _p(hi), _p(out)))
+        return out
+
+    def icp_map_sdf(self, pose12, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True,
+                    box=None):
+        """icp_sdf on the map inside the box; the brick grid is built and uploaded once for all rounds.  Returns what icp_sdf returns."""
+        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
+        lo, hi = self._box(box)
+        L.check(L.lib().rpe_icp_map_sdf(self._h, C.byref(o), _p(lo), _p(hi), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m)))
+        return p, it.value, step.value, cost.value, m.value
+
+    def icp_pyramid_map_sdf(self, pose12, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9, use_normals: bool = True,
+                            box=None):
+        """icp_pyramid_sdf on the map inside the box: the tracker of a moving window with the archive on (volume_follow -> volume_shift ->
+        icp_pyramid_map_sdf -> volume_integrate).  Returns what icp_pyramid_sdf returns."""
+        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
+        lo, hi = self._box(box)
+        L.check(L.lib().rpe_icp_pyramid_map_sdf(self._h, C.byref(o), levels, _p(it_in), _p(thr), _p(lo), _p(hi), _p(p), _p(it_out), C.byref(step),
+                                                C.byref(cost), C.byref(m)))
+        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
+
     # ---- features and relocalisation (Part 3): correspondences without a pose guess
     def features_detect(self, which: int = L.FEAT_FRAME, threshold: int = 12, max_keypoints: int = L.MAX_KEYPOINTS) -> int:
         """Detect and describe the keypoints of the frame's colour (FEAT_FRAME) or the model colour (FEAT_MODEL); returns their number."""

@@ -621,13 +621,13 @@ static_assert(offsetof(SdfRoundArgs, fin) == 136 && sizeof(Finish) == 136, "late
 // The reduction's argument read from the kernarg segment where it is needed, behind the pixel loop: as a plain argument the compiler
 // loads all of it in the kernel's first block and keeps its scalar registers through the loop, beside pose, geometry and gates, which
 // is more than the 102 there are.  (The offset goes through an empty asm so that the loads stay below it.)
-__device__ __forceinline__ Finish late_finish() {
-  unsigned off = (unsigned)offsetof(SdfRoundArgs, fin);
+__device__ __forceinline__ Finish late_finish_at(unsigned off) {
   asm volatile("" : "+s"(off));
   Finish f;
   __builtin_memcpy(&f, (const char*)__builtin_amdgcn_kernarg_segment_ptr() + off, sizeof(Finish));
   return f;
 }
+__device__ __forceinline__ Finish late_finish() { return late_finish_at((unsigned)offsetof(SdfRoundArgs, fin)); }
 
 // four waves per SIMD's worth of registers: 128
 template <int BLK>
@@ -712,6 +712,175 @@ hipError_t launch_sdf_rows(const float* vmap, const float* nmap, int64_t n, cons
                            float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s) {
   const int64_t blocks = (n + kSdfRowsBlock - 1) / kSdfRowsBlock;
   hipLaunchKernelGGL(sdf_rows_kernel, dim3((unsigned)blocks), dim3(kSdfRowsBlock), 0, s, vmap, nmap, n, vol, G,
+                     sdf_params(G, dist_thr, cos_thr, use_normals), sdf_pose(pose12), rows);
+  return hipGetLastError();
+}
+
+// ================================================================================================
+// THE MAP VOLUME TERM (include/rgbd_pose_hip.h Part 3, "Map volume term"): the volume term on the virtual volume of a box of the map --
+// the window plus the archived bricks.  No new arithmetic: the rule is sdf_pixel with a corner fetch over the brick grid of the map
+// raycast (grid_at / map_corners above), so the rows are bit for bit sdf_rows_kernel's on a dense copy of the box.
+//   map_sdf_rows_kernel      sdf_rows_kernel with that fetch.
+//   icp_map_sdf_kernel<BLK>  one Gauss-Newton round.  ONE pixel per loop trip: the fetch's branches (window, held brick, a grid lookup per
+//                            corner over a brick face) cost the registers that sdf_group's four pixels in flight need (462 vector spills
+//                            when reused as it is).  A pixel's fp32 row is widened to fp64 and its 28 products are fp64 fused
+//                            multiply-adds: a product of two floats is exact in fp64, so a sum carries fp64 accumulation error only.
+// ================================================================================================
+namespace {
+
+// what the fetch reads of a MapRayView: the kernel argument (16 scalars for the round kernel's loop to keep, not 29)
+struct MapSdfView {
+  const unsigned int *vol, *pool;
+  const int* grid;
+  int wdim0, wdim1, wdim2, woff[3], nb0, nb1, capacity;
+};
+__device__ __forceinline__ MapRayView ray_view(const MapSdfView& S) {
+  MapRayView M{};   // no colour; wnb, nb[2], wb0, wbn are not read by grid_at / map_corners<false>
+  M.vol = S.vol; M.pool = S.pool; M.grid = const_cast<int*>(S.grid);
+  M.wdim0 = S.wdim0; M.wdim1 = S.wdim1; M.wdim2 = S.wdim2; M.capacity = S.capacity;
+#pragma unroll
+  for (int a = 0; a < 3; a++) M.woff[a] = S.woff[a];
+  M.nb[0] = S.nb0; M.nb[1] = S.nb1;
+  return M;
+}
+
+// The eight corner voxels of the cell i0 of the virtual volume (i0 inside the box, i0 + 1 too: sdf_cell).  The grid entry of corner 0's
+// brick is read first: absent -> "no voxels" without a voxel load, which is exact, since corner 0 is then {0, 0} and fails the weight
+// test.  Otherwise map_corners: dense gathers when all eight lie in the window, a grid lookup per corner over a brick face.  No address
+// is formed outside the window's arrays or the pool's capacity (map_voxel)
+struct map_sdf_corners {
+  const MapRayView& M;
+  __device__ __forceinline__ bool operator()(const int (&i0)[3], float2 (&v)[8]) const {
+    const int e0 = grid_at(M, i0[0], i0[1], i0[2]);
+    uint2 u[8];
+#pragma unroll
+    for (int n = 0; n < 8; n++) u[n] = make_uint2(0u, 0u);
+    if (e0 != kMapAbsent) map_corners<false>(M, i0, e0, u);
+#pragma unroll
+    for (int n = 0; n < 8; n++) v[n] = make_float2(__uint_as_float(u[n].x), __uint_as_float(u[n].y));
+    return e0 != kMapAbsent;
+  }
+};
+
+struct MapSdfRoundArgs { const float* vmap; const float* nmap; int64_t n; MapSdfView S; VolumeGeometry G; SdfParams Q; PoseF T; Finish fin; };
+// (tests/test_mapsdf_oracle.py reads the same offset and size from the code object's metadata)
+static_assert(offsetof(MapSdfRoundArgs, fin) == 192 && sizeof(Finish) == 136, "late_finish_at: where the kernarg segment holds the reduction's argument");
+static_assert(offsetof(MapSdfRoundArgs, T) == 140 && sizeof(PoseF) == 48, "late_pose: where the kernarg segment holds the pose");
+
+// The pose read from the kernarg segment with scalar loads (the segment is constant memory), where a loop trip needs it.  As a plain
+// argument its twelve scalars are live through the whole loop beside view, geometry, gates and the exec masks of the fetch's nested
+// branches, which is more than the 102 there are (4 - 7 scalar spills, however the rest is arranged).  The offset goes through an empty
+// asm, as late_finish's does, so that the loads stay where they are written and the two of a trip are not merged
+__device__ __forceinline__ PoseF late_pose() {
+  typedef const __attribute__((address_space(4))) float* KernargFloats;
+  unsigned off = (unsigned)offsetof(MapSdfRoundArgs, T);
+  asm volatile("" : "+s"(off));
+  KernargFloats p = (KernargFloats)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+  PoseF T;
+#pragma unroll
+  for (int k = 0; k < 9; k++) T.R[k] = p[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) T.t[k] = p[9 + k];
+  return T;
+}
+
+template <int BLK>
+__global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(4))) void icp_map_sdf_kernel(
+    const float* __restrict__ vmap, const float* __restrict__ nmap, int64_t n, MapSdfView S, VolumeGeometry G, SdfParams Q,
+    PoseF /* read by late_pose */, Finish /* read by late_finish_at */) {
+  const MapRayView M = ray_view(S);
+  double acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; k++) acc[k] = 0.0;
+  float rows = 0.f;
+  const int stride = (int)gridDim.x * BLK;
+  for (int i = (int)blockIdx.x * BLK + (int)threadIdx.x; i < (int)n; i += stride) {   // (n <= 2^28 pixels: rpe_frame_set_depth)
+    const int64_t q = 3 * (int64_t)i;
+    // sdf_pixel in its parts (sdf_pixel_row's composition, then the normal gate), so that the pose is read once for the cell and once
+    // more, behind the fetch, for the row; the normal is fetched behind the corners too (as sdf_group does, for the registers)
+    const float x = vmap[q], y = vmap[q + 1], z = vmap[q + 2];
+    int i0[3];
+    float a[3], r, J[6], len;
+    float2 v[8];
+    const bool in = sdf_cell(G, late_pose(), x, y, z, i0, a);
+    const bool have = map_sdf_corners{M}(i0, v);
+    bool ok = sdf_row(v, a, G, late_pose(), Q, x, y, z, r, J, len) && in && have;
+    if (ok && Q.use_normals) ok = sdf_normal_gate(Q, nmap[q], nmap[q + 1], nmap[q + 2], len, r, J);
+    if (!ok) {
+      r = 0.f;
+#pragma unroll
+      for (int k = 0; k < 6; k++) J[k] = 0.f;
+    }
+    // a pixel without a row has r = 0 and J = 0: its products add exact zeros
+    double Jd[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) Jd[a] = (double)J[a];
+    const double rd = (double)r;
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+      for (int b = a; b < 6; b++) { acc[k] = __builtin_fma(Jd[a], Jd[b], acc[k]); k++; }
+      acc[21 + a] = __builtin_fma(Jd[a], rd, acc[21 + a]);
+    }
+    acc[27] = __builtin_fma(rd, rd, acc[27]);
+    rows += ok ? 1.f : 0.f;   // (a thread sees fewer than 2^24 pixels: exact)
+  }
+  double sums[29];
+#pragma unroll
+  for (int k = 0; k < 28; k++) sums[k] = acc[k];
+  sums[28] = (double)rows;
+  reduce_and_finish<29, kNeLd, 0, BLK, false>(sums, late_finish_at((unsigned)offsetof(MapSdfRoundArgs, fin)));   // host-driven only
+}
+
+__global__ __launch_bounds__(kSdfRowsBlock) void map_sdf_rows_kernel(const float* __restrict__ vmap, const float* __restrict__ nmap,
+                                                                     int64_t n, MapSdfView S, VolumeGeometry G, SdfParams Q, PoseF T,
+                                                                     float* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * kSdfRowsBlock + threadIdx.x;
+  if (i >= n) return;
+  const MapRayView M = ray_view(S);
+  float r, J[6], nx = 0.f, ny = 0.f, nz = 0.f;
+  if (Q.use_normals) { nx = nmap[3 * i]; ny = nmap[3 * i + 1]; nz = nmap[3 * i + 2]; }
+  const bool ok = sdf_pixel(map_sdf_corners{M}, G, T, Q, vmap[3 * i], vmap[3 * i + 1], vmap[3 * i + 2], nx, ny, nz, r, J);
+  rows[i] = ok ? r : qnan();
+#pragma unroll
+  for (int k = 0; k < 6; k++) rows[(int64_t)(k + 1) * n + i] = ok ? J[k] : qnan();
+}
+
+MapSdfView sdf_view(const MapRayView& M) {
+  MapSdfView S;
+  S.vol = M.vol; S.pool = M.pool; S.grid = M.grid;
+  S.wdim0 = M.wdim0; S.wdim1 = M.wdim1; S.wdim2 = M.wdim2; S.capacity = M.capacity;
+  for (int a = 0; a < 3; a++) S.woff[a] = M.woff[a];
+  S.nb0 = M.nb[0]; S.nb1 = M.nb[1];
+  return S;
+}
+
+// a node per new kernel, beside the unit's own (one code object: whichever is touched first loads all of it)
+namespace rows_node { RPE_PRELOAD(map_sdf_rows_kernel); }
+namespace round_node { RPE_PRELOAD(icp_map_sdf_kernel<256>); }
+
+}  // namespace
+
+hipError_t launch_icp_map_sdf(const float* vmap, const float* nmap, int64_t n, const MapRayView& M, const VolumeGeometry& G, float dist_thr,
+                              float cos_thr, int use_normals, const double* pose12, const ReduceTarget& rt, hipStream_t s) {
+  const SdfParams Q = sdf_params(G, dist_thr, cos_thr, use_normals);
+  const PoseF T = sdf_pose(pose12);
+  const Finish fin = make_finish(rt);
+  const MapSdfView S = sdf_view(M);
+  const int blk = pick_block(rt);   // one pixel per thread while the grid allows it
+  int grid = rt.max_blocks;
+  if ((int64_t)grid > (n + blk - 1) / blk) grid = (int)((n + blk - 1) / blk);
+  if (grid < 1) grid = 1;
+  if (blk == 512) hipLaunchKernelGGL((icp_map_sdf_kernel<512>), dim3(grid), dim3(512), 0, s, vmap, nmap, n, S, G, Q, T, fin);
+  else hipLaunchKernelGGL((icp_map_sdf_kernel<256>), dim3(grid), dim3(256), 0, s, vmap, nmap, n, S, G, Q, T, fin);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_sdf_rows(const float* vmap, const float* nmap, int64_t n, const MapRayView& M, const VolumeGeometry& G, float dist_thr,
+                               float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s) {
+  const int64_t blocks = (n + kSdfRowsBlock - 1) / kSdfRowsBlock;
+  hipLaunchKernelGGL(map_sdf_rows_kernel, dim3((unsigned)blocks), dim3(kSdfRowsBlock), 0, s, vmap, nmap, n, sdf_view(M), G,
                      sdf_params(G, dist_thr, cos_thr, use_normals), sdf_pose(pose12), rows);
   return hipGetLastError();
 }

@@ -76,4 +76,16 @@ int detect_if_stale(rpe_context* c, int which, const rpe_feature_options& fo);
 int run_on_slots(rpe_context* c, int m, int method, double thre_3d, double thre_2d, double thre_nl, int* iter_io, double confidence,
                  uint64_t seed, int ls, double* pose12, int* max_votes, short* mask_out);
 
+// ---- rpe_mapmesh_api.hip: the map -- the window plus the archived bricks -- for the calls that read a box of it
+// what every such call asks of the context (`who` names the caller in the messages): a volume whose dims and total shift are multiples
+// of 8 (RPE_ERR_STATE)
+int map_state(const char* who, const rpe_context::Volume& V);
+// the box's rules (RPE_ERR_ARG).  lo = NULL: the map's bounds.  On success G is the virtual volume's geometry and b0 / nb the box in bricks
+int map_box(const char* who, const rpe_context::Volume& V, const int64_t* lo, const int64_t* hi, rpe::VolumeGeometry& G, int64_t b0[3],
+            int64_t nb[3]);
+// the brick grid (rpe_kernels.h MapRayView) of the box into h, one int32 per brick, and M's description of window and box; the caller
+// refuses a box of more than kMaxGrid bricks first
+constexpr int64_t kMaxGrid = (int64_t)1 << 24;
+void build_grid(const rpe_context::Volume& V, const int64_t b0[3], const int64_t nb[3], std::vector<unsigned char>& h, rpe::MapRayView& M);
+
 }  // namespace rpeh

@@ -504,5 +504,11 @@ hipError_t launch_icp_sdf(const float* vmap, const float* nmap, int64_t n, const
 // rows[k * n + i], k = 0 .. 6: {r, J[0..5]} of frame pixel i, NaN where it has no row
 hipError_t launch_sdf_rows(const float* vmap, const float* nmap, int64_t n, const float* vol, const VolumeGeometry& G, float dist_thr,
                            float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s);
+// ---- the map volume term (rpe_frontend.hip): the same two on the virtual volume G of a box of the map, through the brick grid of M
+// (as launch_map_raycast takes them; the colour planes, wnb, wb0, wbn are not read).  Rows bit for bit launch_sdf_rows' on a dense copy
+hipError_t launch_icp_map_sdf(const float* vmap, const float* nmap, int64_t n, const MapRayView& M, const VolumeGeometry& G, float dist_thr,
+                              float cos_thr, int use_normals, const double* pose12, const ReduceTarget& rt, hipStream_t s);
+hipError_t launch_map_sdf_rows(const float* vmap, const float* nmap, int64_t n, const MapRayView& M, const VolumeGeometry& G, float dist_thr,
+                               float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s);
 
 }  // namespace rpe

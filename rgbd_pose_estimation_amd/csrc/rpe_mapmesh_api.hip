@@ -36,8 +36,10 @@ void map_bounds(const rpe_context::Volume& V, int64_t lo[3], int64_t hi[3]) {
     }
 }
 
+}  // namespace
+
 // what every entry point asks of the context (`who` names the caller in the messages) ...
-int map_state(const char* who, const rpe_context::Volume& V) {
+int rpeh::map_state(const char* who, const rpe_context::Volume& V) {
   if (!V.have) return fail(RPE_ERR_STATE, "no volume: call rpe_volume_init first");
   if (!multiples_of_brick(V))
     return fail(RPE_ERR_STATE, "%s: every dim (%d %d %d) and every component of the total shift (%lld %lld %lld) must be a "
@@ -46,8 +48,8 @@ int map_state(const char* who, const rpe_context::Volume& V) {
 }
 // ... and the mesh and the raycast of the box.  lo = NULL: the map's bounds.  On success G is the virtual volume's geometry and b0 / nb
 // the box in bricks
-int map_box(const char* who, const rpe_context::Volume& V, const int64_t* lo, const int64_t* hi, rpe::VolumeGeometry& G, int64_t b0[3],
-            int64_t nb[3]) {
+int rpeh::map_box(const char* who, const rpe_context::Volume& V, const int64_t* lo, const int64_t* hi, rpe::VolumeGeometry& G, int64_t b0[3],
+                  int64_t nb[3]) {
   int64_t blo[3], bhi[3];
   if (lo) for (int a = 0; a < 3; a++) { blo[a] = lo[a]; bhi[a] = hi[a]; }
   else map_bounds(V, blo, bhi);
@@ -63,6 +65,8 @@ int map_box(const char* who, const rpe_context::Volume& V, const int64_t* lo, co
   }
   return RPE_OK;
 }
+
+namespace {
 
 inline unsigned long long pack(int64_t bx, int64_t by, int64_t bz) {
   return (unsigned long long)bz << (2 * rpe::kMapKeyBits) | (unsigned long long)by << rpe::kMapKeyBits | (unsigned long long)bx;
@@ -124,8 +128,10 @@ int64_t build_list(const rpe_context::Volume& V, const int64_t b0[3], const int6
 // The brick grid of the box [b0, b0 + nb) of world bricks into h, x fastest, every entry written: kMapAbsent, then the window's bricks
 // by their linear index, then the held ones as ~slot (the window is the only holder of what it covers: they do not meet).  Also M's
 // description of window and box
-constexpr int64_t kMaxGrid = (int64_t)1 << 24;
-void build_grid(const rpe_context::Volume& V, const int64_t b0[3], const int64_t nb[3], std::vector<unsigned char>& h, rpe::MapRayView& M) {
+// (rpe_frontend_host.hpp: kMaxGrid, the most bricks a caller lets a box have)
+}  // namespace
+
+void rpeh::build_grid(const rpe_context::Volume& V, const int64_t b0[3], const int64_t nb[3], std::vector<unsigned char>& h, rpe::MapRayView& M) {
   const int64_t n = nb[0] * nb[1] * nb[2];
   h.resize((size_t)n * sizeof(int32_t));
   int32_t* g = reinterpret_cast<int32_t*>(h.data());
@@ -150,8 +156,6 @@ void build_grid(const rpe_context::Volume& V, const int64_t b0[3], const int64_t
     if (x >= 0 && x < nb[0] && y >= 0 && y < nb[1] && z >= 0 && z < nb[2]) g[x + nb[0] * (y + nb[1] * z)] = ~kv.second;
   }
 }
-
-}  // namespace
 
 extern "C" {
 

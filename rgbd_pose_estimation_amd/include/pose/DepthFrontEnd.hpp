@@ -476,6 +476,37 @@ class DepthFrontEnd {
     rows.resize(n);
     return rows;
   }
+  // ---- the map volume term: icpVolume / icpPyramidVolume / volumeResiduals against the whole MAP -- the window plus the archived
+  // bricks -- inside the box lo <= w < hi of world voxels (multiples of 8; both null: the bounds): a surface the window has left still
+  // gives rows (rpe_icp_map_sdf).  The tracked frame of a moving window with the archive on: followVolume -> shiftVolume ->
+  // icpPyramidMap -> integrate
+  IcpResult icpMap(Pose& pose, const IcpOptions& o = IcpOptions(), const int64_t* lo = nullptr, const int64_t* hi = nullptr) {
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    IcpResult r;
+    int64_t m = 0;
+    check(rpe_icp_map_sdf(_ctx, &opt, lo, hi, p, &r.iterations, &r.last_step, &r.cost, &m), "rpe_icp_map_sdf");
+    r.pairs = (long long)m;
+    pose = pose_of(p);
+    return r;
+  }
+  PyramidIcpResult icpPyramidMap(Pose& pose, const std::vector<int>& iters, const std::vector<double>& dist_thr = std::vector<double>(),
+                                 const IcpOptions& o = IcpOptions(), const int64_t* lo = nullptr, const int64_t* hi = nullptr) {
+    return pyramidIcp<PyramidIcpResult>("icpPyramidMap", "rpe_icp_pyramid_map_sdf", pose, iters, dist_thr, o,
+        [&](const rpe_icp_options* opt, int levels, const double* gates, double* p, PyramidIcpResult& r, int64_t* m) {
+          return rpe_icp_pyramid_map_sdf(_ctx, opt, levels, iters.data(), gates, lo, hi, p, r.level_iterations, &r.last_step, &r.cost, m); });
+  }
+  std::vector<float> mapResiduals(const Pose& pose, int level = 0, const IcpOptions& o = IcpOptions(), const int64_t* lo = nullptr,
+                                  const int64_t* hi = nullptr) const {
+    double p[12]; pose12(pose, p);
+    rpe_camera k;
+    check(rpe_frame_level_camera(_ctx, level, 0, &k), "rpe_frame_level_camera");
+    const size_t n = (size_t)k.width * k.height;
+    std::vector<float> rows(7 * n);
+    check(rpe_map_sdf_rows(_ctx, level, p, o.dist_thr, o.cos_thr, o.use_normals ? 1 : 0, lo, hi, rows.data()), "rpe_map_sdf_rows");
+    rows.resize(n);
+    return rows;
+  }
   // keypoints and descriptors of the frame's colour (which = RPE_FEAT_FRAME) or of the model colour (RPE_FEAT_MODEL); returns their
   // number.  A new depth, colour, model or model colour drops the side's features
   int detectFeatures(int which, const FeatureOptions& o = FeatureOptions()) {
