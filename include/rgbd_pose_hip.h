@@ -1098,12 +1098,13 @@ int rpe_volume_mesh_box(rpe_context* ctx, double min_weight, const int32_t lo[3]
  * for the flags that say which leaving bricks are non-zero.  With the archive off rpe_volume_shift is what it was, call for call, and
  * does not wait.
  * Lifetimes: rpe_volume_init drops the archive (pool and content).  rpe_volume_fuse_keyframes does not touch it: after a loop closure
- * has rebuilt the window at corrected poses, the archived bricks still hold the OLD poses' surface -- call rpe_volume_archive_clear.
+ * has rebuilt the window at corrected poses, the archived bricks still hold the OLD poses' surface -- rebuild window and archive
+ * together with rpe_volume_map_fuse_keyframes ("Map fuse", below) instead, or forget the bricks with rpe_volume_archive_clear.
  * rpe_volume_upload, rpe_volume_integrate and the colour calls write the window only.
  * The tracking loop: follow(granule = 8) -> if non-zero: shift -> map raycast ("Map raycast", below: raycasting the archive directly,
  * beside the window) -> ICP -> integrate; with rpe_volume_raycast in its place the model shows the window only.
  * Out of scope: shifts or dims that are not multiples of 8 with the archive on; a device-side index (no host wait); spilling the pool
- * to host memory; moving the archived bricks under a loop-closure correction. */
+ * to host memory; moving the archived bricks under a loop-closure correction (they are rebuilt instead: "Map fuse"). */
 /* capacity_bricks > 0: switch the archive on with a pool of that many slots, or grow the pool to it (the content stays; a capacity
  * between the number of held bricks and the current capacity changes nothing: the pool does not shrink); 0: switch it off and free
  * everything.  RPE_ERR_ARG for a capacity below the number of held bricks, negative or above 2^24; RPE_ERR_STATE (nothing changed)
@@ -1115,7 +1116,8 @@ int rpe_volume_archive_info(rpe_context* ctx, int64_t* held, int64_t* capacity);
  * as rpe_volume_download lays a window out; colour (may be NULL) = held x 8 x 8 x 8 x 4 binary16, zeros where none was kept.  Slot
  * numbers are not part of the contract.  With nothing held nothing is written */
 int rpe_volume_archive_download(rpe_context* ctx, int64_t* coords, float* tsdf, uint16_t* colour);
-/* forget every brick, keep the pool: for use after rpe_volume_fuse_keyframes has rebuilt the map at corrected poses */
+/* forget every brick, keep the pool.  (To CORRECT the archived bricks after a loop closure, rather than lose them, rebuild the map
+ * with rpe_volume_map_fuse_keyframes.) */
 int rpe_volume_archive_clear(rpe_context* ctx);
 
 /* ---- Map mesh: the window and the archived bricks meshed in one extraction.  The MAP is a sparse grid of world voxels (world voxel =
@@ -1225,6 +1227,44 @@ int rpe_icp_map_sdf(rpe_context* ctx, const rpe_icp_options* opt, const int64_t 
 int rpe_icp_pyramid_map_sdf(rpe_context* ctx, const rpe_icp_options* opt, int levels, const int* iters_per_level,
                             const double* dist_thr_per_level, const int64_t lo[3], const int64_t hi[3], double* pose12, int* iters_out,
                             double* last_step, double* final_cost, int64_t* matched);
+
+/* ---- Map fuse: the whole MAP rebuilt from the keyframes -- the window and the archived bricks.  rpe_volume_fuse_keyframes writes the
+ * dense window only: after a loop closure the archived bricks, most of a walked map, would keep the surface fused at the drifted poses.
+ * This call fuses a list of keyframes into every brick of a box of world voxels, in the window or not, takes archive slots for the
+ * bricks that become non-empty and releases the slots of bricks that become empty.  No new arithmetic: the box lo <= w < hi defines the
+ * VIRTUAL VOLUME that "Map mesh" defines (lo = hi = NULL: rpe_volume_map_bounds): dim = hi - lo, o = (float)(origin_init + (double)lo *
+ * voxel_size), one rounding; voxel size, trunc and max weight are the init call's; its content is the map's (the window's bits where
+ * the window covers, the held brick's where the archive holds one, zeros elsewhere; colour likewise).
+ * THE CONTRACT: after the call the map holds inside the box, bit for bit, what rpe_volume_fuse_keyframes(ids, count, poses12, flags)
+ * leaves in a second context whose volume is a fresh rpe_volume_init of that virtual volume with the map's content uploaded: voxel
+ * centre o + ((float)i + 0.5f) * s with i the index inside the box, projection, update, colour blend and list order are those of
+ * "Keyframe depth and rebuilding the volume" (tests/mapfuse_oracle.py states the composition in numpy).  A brick of the box that the
+ * window covers holds its part of the result in the window.  A brick of the box outside the window is held by the archive afterwards
+ * if and only if any 32-bit word of its tsdf or colour brick is non-zero -- the archive's own rule for a leaving brick.  Nothing outside
+ * the box changes: window voxels outside it keep their bits, held bricks outside it keep their slots.  With the box equal to the
+ * window's extent o is the window's own o and the window holds what rpe_volume_fuse_keyframes would leave in it.
+ * Flags are rpe_volume_fuse_keyframes' (RPE_FUSE_CLEAR | RPE_FUSE_COLOR | RPE_FUSE_NO_CULL).  RPE_FUSE_CLEAR: the box starts from zeros
+ * in both volumes; where a colour volume or a colour plane of the pool exists it is zeroed inside the box even without RPE_FUSE_COLOR;
+ * a held brick of the box that ends all zero is released (its slot returns to the free list, no device work); whether a colour volume
+ * exists does not change.  Without it window and held bricks are loaded, updated and stored, and an absent brick starts from zeros.
+ * RPE_FUSE_COLOR creates the colour volume, zero-filled, if there is none, and the pool's colour plane, zeroed, when a brick of the
+ * pool is written and there is none.  The last mesh is treated as rpe_volume_fuse_keyframes treats it (dropped with RPE_FUSE_CLEAR);
+ * the model, the solver slots and the photometric maps stay.
+ * Refusals, all before anything is written: the list's are rpe_volume_fuse_keyframes', code for code; the box rules are the map
+ * mesh's, and the box may hold at most 2^24 bricks (RPE_ERR_ARG); unaligned dims or total shift are RPE_ERR_STATE, as
+ * rpe_volume_map_bounds; a box that reaches outside the window while the archive is off is RPE_ERR_STATE; and CAPACITY: if the absent
+ * bricks that become non-zero need more slots than are free (counting those RPE_FUSE_CLEAR releases) the call returns RPE_ERR_STATE
+ * with both numbers in the message and window, pool, index and free list are exactly as before.
+ * How: two passes of one kernel, a workgroup per brick.  Pass 1 runs the fuse from zeros on every brick of the box without touching a
+ * voxel and leaves one flag word per brick (non-zero after the fuse; some voxel updated); the host waits ONCE, for the flags, checks
+ * the capacity, hands slots out and lists the bricks to write; pass 2 loads, fuses and stores the listed bricks only.  The projection
+ * is computed twice: the price of refusing before writing without a staging pool of the box's size.
+ * stats (may be NULL) = {bricks in the box, bricks written, slots newly taken, slots released}.
+ * Out of scope: the default box is the current map's bounds -- surfaces the corrected poses see beyond it are fused only if the caller
+ * widens the box; only keyframes are fused, not the frames between them; the index stays on the host; no per-frame integrate into
+ * archived bricks. */
+int rpe_volume_map_fuse_keyframes(rpe_context* ctx, const int32_t* ids, int count, const double* poses12, int flags,
+                                  const int64_t lo[3], const int64_t hi[3], int64_t stats[4]);
 
 /* ---- host-side pieces of the solvers (no GPU needed): sampling, minimal solvers, small algebra.  They exist so that
  * hosts in other languages do not have to re-implement them, and so that the host logic can be tested on a CPU box.

@@ -440,7 +440,8 @@ class Context:
         return coords, tsdf, colour if colour.view(np.uint16).any() else None
 
     def volume_archive_clear(self):
-        """Forget every archived brick and keep the pool (after volume_fuse_keyframes rebuilt the map at corrected poses)."""
+        """Forget every archived brick and keep the pool.  (To correct the archived bricks after a loop closure instead of losing them,
+        rebuild the map with volume_map_fuse_keyframes.)"""
         L.check(L.lib().rpe_volume_archive_clear(self._h))
         return self
 
@@ -1008,6 +1009,26 @@ class Context:
         if clear:
             self._mesh_nv = None
         return self
+
+    def volume_map_fuse_keyframes(self, ids=None, poses=None, clear: bool = True, color: bool = False, cull: bool = True, box=None) -> dict:
+        """Rebuild the MAP -- the window plus the archived bricks -- from the keyframes: the list (as volume_fuse_keyframes takes it) fused
+        into every brick of box = (lo, hi) in world voxels (multiples of 8; None: volume_map_bounds), in the window or not, bit for bit
+        what volume_fuse_keyframes leaves in a dense volume of the box that held the map's content (rpe_volume_map_fuse_keyframes).
+        Bricks outside the window that become non-empty take archive slots -- RPE_ERR_STATE, and nothing written, if the pool is too
+        small --, held bricks that end empty under clear give theirs back.  Returns dict(bricks in the box, written, archived = slots
+        newly taken, released).  After a loop closure: keyframes_optimize -> volume_map_fuse_keyframes(clear=True) -> volume_map_mesh."""
+        flags = (L.FUSE_CLEAR if clear else 0) | (L.FUSE_COLOR if color else 0) | (0 if cull else L.FUSE_NO_CULL)
+        i = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1)
+        p = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        if p is not None and (i is None or len(p) != len(i)):
+            raise ValueError("volume_map_fuse_keyframes: poses need ids, and one pose per list entry")
+        lo, hi = self._box(box)
+        st = np.zeros(4, np.int64)
+        L.check(L.lib().rpe_volume_map_fuse_keyframes(self._h, None if i is None else _p(i), 0 if i is None else len(i),
+                                                      None if p is None else _p(p), flags, _p(lo), _p(hi), _p(st)))
+        if clear:
+            self._mesh_nv = None
+        return dict(zip(("bricks", "written", "archived", "released"), (int(x) for x in st)))
 
     def volume_mesh_colors(self) -> np.ndarray:
         """(V, 4) uint8 RGBA of the last mesh's vertices (volume_mesh, volume_map_mesh): the colour field there, as model_color samples

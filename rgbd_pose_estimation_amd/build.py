@@ -29,7 +29,8 @@ UNITS = [
     ("rpe_joint.hip", "kernel", "joint normal equations"),
     ("rpe_score.hip", "kernel", "K4 scoring, K4b masks"),
     ("rpe_nl.hip", "kernel", "K1' moments, K5, publish kernels"),
-    ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map; the volume term's rows and round, on the window and on the map"),
+    ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map; the volume term's rows and round, on the window and on the map; "
+                                   "the keyframe list fused into the map's bricks (csrc/rpe_mapfuse.hpp)"),
     ("rpe_filter.hip", "kernel", "the bilateral depth filter in front of it"),
     ("rpe_volume.hip", "kernel", "TSDF volume: integrate, raycast"),
     ("rpe_mesh.hip", "kernel", "marching cubes over the volume"),
@@ -69,6 +70,7 @@ UNITS = [
     ("rpe_shift_api.hip", "host", "Part 3: the moving volume"),
     ("rpe_archive_api.hip", "host", "Part 3: the volume archive"),
     ("rpe_mapmesh_api.hip", "host", "Part 3: the map: mesh and raycast"),
+    ("rpe_mapfuse_api.hip", "host", "Part 3: the map rebuilt from the keyframes"),
     ("library.cpp", "cpp", "reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines"),
     ("rpe_hostex.cpp", "cpp", "host-side all-reduce between the rank processes of one node"),
 ]

@@ -886,3 +886,9 @@ hipError_t launch_map_sdf_rows(const float* vmap, const float* nmap, int64_t n, 
 }
 
 }  // namespace rpe
+
+// ================================================================================================
+// THE MAP FUSE (include/rgbd_pose_hip.h Part 3, "Map fuse"): the keyframe list of rpe_rebuild.hip's R2 fused into every brick of a box of the
+// map.  The kernel's text is rpe_mapfuse.hpp; it is compiled here, with the map raycast and the map volume term, whose view of a brick
+// (brick_word) it shares.
+#include "rpe_mapfuse.hpp"

@@ -56,6 +56,39 @@ inline int pyramid_complaint(const char* who, int levels, const int* iters_per_l
   return RPE_OK;
 }
 
+// ---- the keyframe list of a fuse (rpe_volume_fuse_keyframes, rpe_volume_map_fuse_keyframes; `who` names the caller in the messages):
+// ids = NULL lists every keyframe that carries depth, by id.  An id outside the store or a count outside 1 .. RPE_MAX_KEYFRAMES is
+// RPE_ERR_ARG; a listed keyframe without depth -- or, with `color`, without colour -- and an empty store are RPE_ERR_STATE.  On success
+// table holds one entry per list entry: the attachment, its camera and the pose it is fused at (poses12, or the store's)
+inline int fuse_list(rpe_context* c, const char* who, const int32_t* ids, int count, const double* poses12, bool color,
+                     std::vector<rpe::FuseEntry>& table) {
+  auto& K = c->kf;
+  const int stored = (int)K.meta.size();
+  auto has_depth = [&](int id) { return id < (int)K.att.size() && K.att[id].have_depth; };
+  int32_t all[RPE_MAX_KEYFRAMES];
+  if (!ids) {
+    count = 0;
+    for (int id = 0; id < stored; id++) if (has_depth(id)) all[count++] = id;
+    if (count == 0) return fail(RPE_ERR_STATE, "%s: no keyframe has depth attached (rpe_keyframe_attach_frame)", who);
+    ids = all;
+  } else {
+    if (count < 1 || count > RPE_MAX_KEYFRAMES) return fail(RPE_ERR_ARG, "%s: count 1 .. %d (got %d)", who, RPE_MAX_KEYFRAMES, count);
+    for (int e = 0; e < count; e++)
+      if (ids[e] < 0 || ids[e] >= stored) return fail(RPE_ERR_ARG, "%s: no keyframe %d (%d in the store)", who, ids[e], stored);
+  }
+  for (int e = 0; e < count; e++) {
+    if (!has_depth(ids[e])) return fail(RPE_ERR_STATE, "%s: keyframe %d has no depth attached (rpe_keyframe_attach_frame)", who, ids[e]);
+    if (color && !K.att[ids[e]].have_color) return fail(RPE_ERR_STATE, "%s: keyframe %d has no colour attached", who, ids[e]);
+  }
+  table.resize((size_t)count);
+  for (int e = 0; e < count; e++) {
+    const auto& A = K.att[ids[e]];
+    table[e].z = A.z; table[e].rgba = color ? A.rgba.get() : nullptr; table[e].cam = A.cam;
+    table[e].T = pose_f(poses12 ? poses12 + 12 * (size_t)e : K.meta[ids[e]].pose);
+  }
+  return RPE_OK;
+}
+
 // ---- rpe_color_api.hip
 // the colour volume of the current volume: allocated on first use after rpe_volume_init, cleared to 0 unless `clear` is false (the
 // caller overwrites every voxel)

@@ -23,6 +23,8 @@
 //   rpe_mapmesh_api.hip   Part 3: the map, mesh and raycast (rpe_volume_map_bounds / _map_mesh / _map_raycast: the window and the archived
 //                         bricks inside a box of world voxels; the mesh's brick list and neighbour table, kernels in rpe_mapmesh.hip;
 //                         the raycast's brick grid, kernels in rpe_frontend.hip)
+//   rpe_mapfuse_api.hip   Part 3: the map rebuilt from the keyframes (rpe_volume_map_fuse_keyframes: a list of keyframes fused into every
+//                         brick of a box, window or archive; slots taken and released; kernel in rpe_mapfuse.hpp, compiled into rpe_frontend.hip)
 // Three headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
 // host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create), rpe_gn_host.hpp (the Gauss-Newton
 // step, round loop and coarse-to-fine walk of every host loop) and rpe_frontend_host.hpp (what the Part 3 units share: camera and pose

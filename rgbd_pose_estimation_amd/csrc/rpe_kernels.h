@@ -485,6 +485,21 @@ hipError_t launch_map_occupancy(const MapRayView& M, hipStream_t s);
 // RGBA8 colour field at each vertex, as launch_color_sample would leave it
 hipError_t launch_map_raycast(const MapRayView& M, const VolumeGeometry& G, const Camera& cam, const PoseF& T, float dmin, float dmax,
                               float* mv, float* mn, unsigned int* mc, hipStream_t s);
+// ---- the map fuse (kernel in rpe_mapfuse.hpp, compiled into rpe_frontend.hip): R2's list of keyframes fused into the bricks of a box of
+// the map, wherever they lie.  Sources as in the brick grid: >= 0 the window brick, < 0 the pool's slot ~slot
+struct MapFuseView {
+  unsigned int *vol, *cvol, *pool, *cpool;         // the window's two volumes and the pool's two planes as words; null = none
+  int wdim0, wdim1, wnb[3], capacity;              // as MapMeshView
+  int nb[3];                                       // the box's bricks per axis
+  const FuseEntry* table; int count, cull;         // R2's table
+  int n;                                           // workgroups: every brick of the box (pass 1) or the list's entries (pass 2)
+  const int* list;                                 // pass 2: {box brick (x fastest), source, fresh} per entry
+  unsigned int* flags;                             // pass 1: per box brick, 1 = non-zero after the fuse from zeros | 2 = some voxel updated
+};
+// pass 1 over every brick of the box (G = the box's virtual volume), no volume access; M.list is not read
+hipError_t launch_map_fuse_mark(const MapFuseView& M, const VolumeGeometry& G, bool color, hipStream_t s);
+// pass 2 over M.list; clear: every entry is fresh.  M.flags is not read
+hipError_t launch_map_fuse(const MapFuseView& M, const VolumeGeometry& G, bool clear, bool color, hipStream_t s);
 // one ICP round in one kernel: association + normal equations of kind 0 (p2p) / 1 (p2plane, frame normals); record as launch_normal_eq
 hipError_t launch_icp_fused(const float* vmap, const float* nmap, int64_t n, const float* mv, const float* mn, const Camera& mcam,
                             const PoseF& M, float dist_sq, float cos_thr, int use_normals, int kind, const double* pose12, const ReduceTarget& rt,

@@ -14,31 +14,10 @@ int rpe_volume_fuse_keyframes(rpe_context* c, const int32_t* ids, int count, con
   auto& V = c->vol;
   auto& K = c->kf;
   if (!V.have) return fail(RPE_ERR_STATE, "no volume: call rpe_volume_init first");
-  const int stored = (int)K.meta.size();
-  auto has_depth = [&](int id) { return id < (int)K.att.size() && K.att[id].have_depth; };
-  // the list
-  int32_t all[RPE_MAX_KEYFRAMES];
-  if (!ids) {
-    count = 0;
-    for (int id = 0; id < stored; id++) if (has_depth(id)) all[count++] = id;
-    if (count == 0) return fail(RPE_ERR_STATE, "rpe_volume_fuse_keyframes: no keyframe has depth attached (rpe_keyframe_attach_frame)");
-    ids = all;
-  } else {
-    if (count < 1 || count > RPE_MAX_KEYFRAMES) return fail(RPE_ERR_ARG, "rpe_volume_fuse_keyframes: count 1 .. %d (got %d)", RPE_MAX_KEYFRAMES, count);
-    for (int e = 0; e < count; e++)
-      if (ids[e] < 0 || ids[e] >= stored) return fail(RPE_ERR_ARG, "rpe_volume_fuse_keyframes: no keyframe %d (%d in the store)", ids[e], stored);
-  }
-  for (int e = 0; e < count; e++) {
-    if (!has_depth(ids[e])) return fail(RPE_ERR_STATE, "rpe_volume_fuse_keyframes: keyframe %d has no depth attached (rpe_keyframe_attach_frame)", ids[e]);
-    if (color && !K.att[ids[e]].have_color) return fail(RPE_ERR_STATE, "rpe_volume_fuse_keyframes: keyframe %d has no colour attached", ids[e]);
-  }
+  std::vector<rpe::FuseEntry> table;
+  if (int rc = fuse_list(c, "rpe_volume_fuse_keyframes", ids, count, poses12, color, table)) return rc;
+  count = (int)table.size();
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<rpe::FuseEntry> table((size_t)count);
-  for (int e = 0; e < count; e++) {
-    const auto& A = K.att[ids[e]];
-    table[e].z = A.z; table[e].rgba = color ? A.rgba : nullptr; table[e].cam = A.cam;
-    table[e].T = pose_f(poses12 ? poses12 + 12 * (size_t)e : K.meta[ids[e]].pose);
-  }
   if (int rc = K.d_table.once(c, RPE_MAX_KEYFRAMES * sizeof(rpe::FuseEntry))) return rc;
   // the call's one host wait: the table is the host's again (and an earlier fuse has read the table it was given)
   HIP_TRY(hipMemcpyAsync(K.d_table, table.data(), table.size() * sizeof(rpe::FuseEntry), hipMemcpyHostToDevice, c->stream));

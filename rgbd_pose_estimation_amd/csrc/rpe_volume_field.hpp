@@ -47,6 +47,47 @@ __device__ __forceinline__ void fuse(float& tsdf, float& w, float f, float W) {
   w = fminf(w + 1.0f, W);
 }
 
+// THE FUSE'S CULL (R2 of rpe_rebuild.hip, the map fuse of rpe_mapfuse.hpp): can a list entry update any voxel of a brick?
+// the cull's margin on a camera coordinate, relative to the sum of the magnitudes that enter it (64 ulp: see box_can_update)
+constexpr float kCullEps = 1.0f / 262144.0f;
+// Can entry E update ANY voxel whose centre lies in the box [lo, hi] (per axis the centres of the brick's first and last voxel, formed
+// with voxel_project's own expression: fp32 rounding is monotonic, so every centre of the brick lies inside)?  false only when every
+// centre fails voxel_project: all behind the camera, or all outside the same image edge.
+// The box in the camera frame is its centre R c + t with the half extents |R| h.  Exactly, every centre's camera coordinate lies in
+// that interval; in fp32 the kernel's own coordinate (three products, three sums) and the interval's ends (c and h: one and two
+// roundings; the centre six, the extent five) are each off by a few ulp of M = |R| max(|lo|, |hi|) + |t|, the sum of the magnitudes
+// that enter them: fewer than 32 roundings of at most 2^-24 M in all.  The interval is widened by 2^-18 M = 64 ulp on either side.
+// The pixel of the interval's extreme ratio is then formed with voxel_project's expression, fx * (x / z) + cx + 0.5f: division,
+// product and sums are correctly rounded and so monotonic in x and z, hence no voxel's pixel coordinate passes the extreme one; one
+// whole pixel (and 2^-18 of the coordinate) is left on top.  Every comparison is written so that a NaN keeps the entry.
+__device__ __forceinline__ bool edge_outside(float xlo, float xhi, float zl, float zh, float f, float c, int size) {
+  const float inf = __int_as_float(0x7f800000);
+  // the largest and the smallest x / z over the part of the box in front of the camera (0 < z, zl <= z <= zh)
+  const float rmax = xhi >= 0.0f ? (zl > 0.0f ? xhi / zl : inf) : xhi / zh;
+  const float rmin = xlo <= 0.0f ? (zl > 0.0f ? xlo / zl : -inf) : xlo / zh;
+  const float umax = f * rmax + c + 0.5f, umin = f * rmin + c + 0.5f;
+  return umax + (1.0f + kCullEps * fabsf(umax)) < 0.0f || umin - (1.0f + kCullEps * fabsf(umin)) > (float)size;
+}
+
+__device__ __forceinline__ bool box_can_update(const float* lo, const float* hi, const Camera& cam, const PoseF& T) {
+  float c[3], h[3], a[3];
+#pragma unroll
+  for (int d = 0; d < 3; d++) { c[d] = 0.5f * (lo[d] + hi[d]); h[d] = 0.5f * (hi[d] - lo[d]); a[d] = fmaxf(fabsf(lo[d]), fabsf(hi[d])); }
+  float l[3], u[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const float R0 = T.R[3 * r], R1 = T.R[3 * r + 1], R2 = T.R[3 * r + 2];
+    const float q = R0 * c[0] + R1 * c[1] + R2 * c[2] + T.t[r];
+    const float e = fabsf(R0) * h[0] + fabsf(R1) * h[1] + fabsf(R2) * h[2];
+    const float m = kCullEps * (fabsf(R0) * a[0] + fabsf(R1) * a[1] + fabsf(R2) * a[2] + fabsf(T.t[r]));
+    l[r] = q - e - m; u[r] = q + e + m;
+  }
+  if (u[2] <= 0.0f) return false;                                                        // every centre behind the camera
+  if (edge_outside(l[0], u[0], l[2], u[2], cam.fx, cam.cx, cam.width)) return false;    // all left of column 0 or right of the last
+  if (edge_outside(l[1], u[1], l[2], u[2], cam.fy, cam.cy, cam.height)) return false;   // all above row 0 or below the last
+  return true;
+}
+
 // binary16 <-> fp32.  h(x): round to nearest even, subnormals kept, every NaN to the quiet NaN 0x7e00.
 __device__ __forceinline__ float h2f(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
 __device__ __forceinline__ unsigned f2h(float x) { return x == x ? (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x) : 0x7e00u; }

@@ -308,7 +308,7 @@ class DepthFrontEnd {
     check(rpe_volume_archive_download(_ctx, coords.data(), tsdf.data(), colour ? colour->data() : nullptr), "rpe_volume_archive_download");
     return n;
   }
-  // forget every archived brick, keep the pool (after fuseKeyframes rebuilt the map at corrected poses)
+  // forget every archived brick, keep the pool (to correct them after a loop closure instead, rebuild the map with fuseKeyframesMap)
   void archiveClear() { check(rpe_volume_archive_clear(_ctx), "rpe_volume_archive_clear"); }
   // the world-voxel bounding box of the window and every archived brick, in multiples of 8 (rpe_volume_map_bounds)
   void mapBounds(int64_t lo[3], int64_t hi[3]) const { check(rpe_volume_map_bounds(_ctx, lo, hi), "rpe_volume_map_bounds"); }
@@ -693,6 +693,30 @@ class DepthFrontEnd {
     check(rpe_volume_fuse_keyframes(_ctx, list.empty() ? nullptr : list.data(), (int)list.size(), poses.empty() ? nullptr : p.data(), flags),
           "rpe_volume_fuse_keyframes");
     if (clear) _mesh_vertices = -1;
+  }
+  // what fuseKeyframesMap did: bricks in the box, bricks written, archive slots newly taken, slots released
+  struct MapFuseStats { int64_t bricks = 0, written = 0, archived = 0, released = 0; };
+  // the whole MAP rebuilt from the keyframes: the list fused into every brick of the box lo <= w < hi of world voxels (multiples of 8;
+  // both null: the map's bounds), in the window or in the archive, bit for bit what fuseKeyframes leaves in a dense volume of the box
+  // that held the map's content (rpe_volume_map_fuse_keyframes).  Bricks outside the window that become non-empty take archive slots
+  // (RPE_ERR_STATE, nothing written, if the pool is too small), held bricks that end empty under `clear` give theirs back.  The
+  // loop-closure recipe: optimizeKeyframes -> fuseKeyframesMap(clear = true) -> meshMap
+  MapFuseStats fuseKeyframesMap(const std::vector<int>& ids = std::vector<int>(), const std::vector<Pose>& poses = std::vector<Pose>(),
+                                bool clear = true, bool color = false, bool cull = true, const int64_t* lo = nullptr,
+                                const int64_t* hi = nullptr) {
+    if (!poses.empty() && poses.size() != ids.size()) throw DeviceError(RPE_ERR_ARG, "fuseKeyframesMap: one pose per list entry");
+    std::vector<int32_t> list(ids.begin(), ids.end());
+    std::vector<double> p((size_t)12 * poses.size());
+    for (size_t e = 0; e < poses.size(); e++) pose12(poses[e], p.data() + 12 * e);
+    const int flags = (clear ? RPE_FUSE_CLEAR : 0) | (color ? RPE_FUSE_COLOR : 0) | (cull ? 0 : RPE_FUSE_NO_CULL);
+    int64_t st[4] = {0, 0, 0, 0};
+    check(rpe_volume_map_fuse_keyframes(_ctx, list.empty() ? nullptr : list.data(), (int)list.size(), poses.empty() ? nullptr : p.data(), flags,
+                                        lo, hi, st),
+          "rpe_volume_map_fuse_keyframes");
+    if (clear) _mesh_vertices = -1;
+    MapFuseStats out;
+    out.bricks = st[0]; out.written = st[1]; out.archived = st[2]; out.released = st[3];
+    return out;
   }
   // associate under `guess` and bring the five arrays to the host (the adapters' getters and the minimal solvers read them)
   Pairs pairs(const Pose& guess, double dist_thr = 0.1, double cos_thr = 0.9, bool use_normals = true) {
