@@ -78,6 +78,9 @@ SOURCES = [src for src, _, _ in UNITS]
 __doc__ = (__doc__ or "{units}").format(units="\n".join(f"  csrc/{src} ({kind}): {what}" for src, kind, what in UNITS))
 ARCH = "gfx950"
 LINK_RT = "--rtlib=libgcc"
+# what every kernel unit (and anything that must see the device rules as the kernels do: tests/test_gpu_volume_rules.py) is compiled
+# with; FMA contraction is switched off in the sources themselves (#pragma clang fp contract(off)), not here
+HIP_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "--offload-compress"]
 
 
 def _deps():
@@ -138,7 +141,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         else:
             # --offload-compress: the gfx950 code objects are stored compressed in the fat binary (a third of the size; the runtime
             # unpacks a unit once, when its first kernel is looked up -- rpe_create touches every unit)
-            cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "--offload-compress",
+            cmd = [hipcc, *HIP_FLAGS,
                    "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
         if not force and os.path.exists(obj) and all(os.path.getmtime(p) <= os.path.getmtime(obj) for p in _deps()):
             objs.append(obj)   # this unit is newer than every source and header: keep it
@@ -166,7 +169,7 @@ def build_stamps(level: int = 1, verbose: bool = False) -> str:
     obj = os.path.join(LIBDIR, f"rpe_normal_eq_stamps{level}.o")
     if os.path.exists(out) and all(os.path.getmtime(p) <= os.path.getmtime(out) for p in _deps()):
         return out
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "--offload-compress", f"-DRPE_STAMPS={level}",
+    cmd = [hipcc, *HIP_FLAGS, f"-DRPE_STAMPS={level}",
            "-x", "hip", "-c", os.path.join(CSRC, "rpe_normal_eq.hip"), "-o", obj]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
@@ -182,7 +185,7 @@ def build_score_stats(verbose: bool = False) -> str:
     build()
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     out, obj = os.path.join(LIBDIR, "librgbdpose_hip_scorestats.so"), os.path.join(LIBDIR, "rpe_score_stats.o")
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "--offload-compress", "-DRPE_SCORE_STATS",
+    cmd = [hipcc, *HIP_FLAGS, "-DRPE_SCORE_STATS",
            "-x", "hip", "-c", os.path.join(CSRC, "rpe_score.hip"), "-o", obj]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

@@ -39,6 +39,15 @@ def frame_rgba(rgb, order="rgb"):
     return np.concatenate([a, np.full((len(a), 1), 255, np.uint8)], 1)
 
 
+def blend(c, wc, o, W):
+    """one observation o (n, 3) fp32 blended into the colours c (n, 3) of weight wc (n,), all fp32: the new (colour, weight) as
+    binary16 bits"""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nc = h((c * wc[:, None] + o) / (wc[:, None] + F(1.0)))
+        nw = h(np.fmin(wc + F(1.0), W))                          # fminf: a NaN weight becomes W
+    return nc, nw
+
+
 def integrate(vol, cvol, G, V, rgba, cam, pose12, k0=0, with_band=False):
     """C2: (tsdf volume, colour volume) with the frame (level-0 vertex map V (h*w, 3), colour rgba (h*w, 4)) fused in under pose12.
     The tsdf half is volume_oracle.integrate's; the colour half recomputes sdf and the pixel of each updated voxel and blends the band
@@ -59,8 +68,7 @@ def integrate(vol, cvol, G, V, rgba, cam, pose12, k0=0, with_band=False):
         o = rgba[j[band], :3].astype(F)
         c = f32(cvol[band][:, :3])
         wc = f32(cvol[band][:, 3])
-        nc = h((c * wc[:, None] + o) / (wc[:, None] + F(1.0)))
-        nw = h(np.fmin(wc + F(1.0), G.W))                        # fminf: a NaN weight becomes W
+        nc, nw = blend(c, wc, o, G.W)
     cout = cvol.copy()
     sel = cout[band]
     sel[:, :3] = nc

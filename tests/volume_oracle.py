@@ -63,19 +63,26 @@ def _lerp(x, y, t):
     return x + (y - x) * t
 
 
-def field(vol, G, X, k0=0):
-    """F at world points X (n, 3): (value (n,), known (n,)).  vol may be the z-slab window [k0, k0 + len(vol)) of the volume, every
-    voxel outside it unobserved (weight 0): a point whose cell reaches outside the window is unknown."""
-    d0, d1, d2 = G.dim
+def cell(G, X):
+    """the cell of world points X (n, 3) fp32: g = (p - o) / s - 0.5f, i0 = floorf(g), a = g - i0 per axis; (in range (n,), [i0 per axis]
+    as fp32, [a per axis]) -- in range iff 0 <= i0 <= dim - 2 on every axis"""
     with np.errstate(invalid="ignore", over="ignore"):
         g = [(X[:, a] - G.o[a]) / G.s - F(0.5) for a in range(3)]
         i0 = [np.floor(x) for x in g]
         ok = np.ones(len(X), bool)
         for a in range(3):
             ok &= (i0[a] >= F(0)) & (i0[a] <= F(G.dim[a] - 2))
+        return ok, i0, [g[a] - i0[a] for a in range(3)]
+
+
+def field(vol, G, X, k0=0):
+    """F at world points X (n, 3): (value (n,), known (n,)).  vol may be the z-slab window [k0, k0 + len(vol)) of the volume, every
+    voxel outside it unobserved (weight 0): a point whose cell reaches outside the window is unknown."""
+    d0, d1, d2 = G.dim
+    ok, i0, (ax, ay, az) = cell(G, X)
+    with np.errstate(invalid="ignore"):
         ok &= (i0[2] >= F(k0)) & (i0[2] <= F(k0 + vol.shape[0] - 2))
-        ax, ay, az = [g[a] - i0[a] for a in range(3)]
-    i, j, k = [np.where(ok, i0[a], F(0)).astype(np.int64) for a in range(3)]
+    i, j, k =[np.where(ok, i0[a], F(0)).astype(np.int64) for a in range(3)]
     k = np.where(ok, k - k0, 0)
     flat = vol.reshape(-1, 2)
     base = (k * d1 + j) * d0 + i
