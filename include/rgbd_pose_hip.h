@@ -759,6 +759,56 @@ int rpe_icp_pyramid_sdf(rpe_context* ctx, const rpe_icp_options* opt, int levels
                         const double* dist_thr_per_level, double* pose12, int* iters_out, double* last_step, double* final_cost,
                         int64_t* matched);
 
+/* ---- Volume colour term: a photometric term beside the volume term, against the COLOUR VOLUME itself.  The volume term is geometry
+ * only: where geometry does not hold all six degrees of freedom -- a wall, a floor, a corridor -- it has nothing to hold the in-plane
+ * motion with.  The colour that does is already in the volume, beside the TSDF (rpe_volume_integrate_color): in the cell a frame vertex
+ * lands in, the trilinear luma of the eight colour voxels against the frame's intensity is the residual, and the gradient of the same
+ * eight lumas is the row.  No raycast, no model, no model colour, no rpe_photo_prepare; a round is ONE launch that forms both rows.
+ * Conventions, followed bit for bit for everything per pixel (fp32, the written order, no FMA contraction; tests/sdf_photo_oracle.py
+ * states them in numpy); the sums are held to a rounding bound.  (R, t) as every pose12 (Xc = R Xw + t); the frame's level-l vertex Xc
+ * and level-l intensity If (the photometric term's intensity pyramid of the frame's colour: NaN where A = 0); the volume's o, s, tr as
+ * rpe_volume_init cast them; gate = (float)dist_thr; lam = (float)weight, in metres per intensity level.
+ * The term, per frame pixel of level l:
+ *  1. Xc has three finite components and If is finite.  Xw and the field's cell (i0, a) are steps 1-2 of the volume term.
+ *  2. The eight TSDF corners are known and unsaturated and fabsf(D * tr) <= gate: the volume term's steps 3-4.  Its slope and normal
+ *     gates are NOT asked: a photometric row stands wherever the point lies on the fused surface within the gate.
+ *  3. The eight colour-volume corners of the same cell all have colour weight > 0 (the colour field's "known").  Each corner's luma
+ *     y = ((0.299f * r + 0.587f * g) + 0.114f * b), on its binary16 channels widened exactly to fp32: the photometric term's
+ *     intensity, on the 0 .. 255 scale.  A channel that is NaN or Inf under a weight > 0 is NOT gated: it goes through steps 4-6 as
+ *     any value does, into the row and into the sums.
+ *  4. Iv = the trilinear value of the eight y through the field's lerp chain (x, then y, then z).  The gradient (gx, gy, gz) of the
+ *     same eight y by exactly the three corner-difference expressions of the volume term's step 5, in levels per voxel;
+ *     m = (gx / s, gy / s, gz / s).
+ *  5. a[i] = -((R[3i] * m.x + R[3i+1] * m.y) + R[3i+2] * m.z); r = Iv - If; J = [a | Xc x a], the cross product as in the volume
+ *     term's step 8; tangent order and update are those of rpe_normal_eq.
+ *  6. r' = lam * r and J' = lam * J (fp32), accumulated beside the geometric row of the same pixel -- the volume term's, unchanged,
+ *     normal gate included, weight 1.  Both fp32 rows are widened to fp64 and their products added with fp64 fused multiply-adds
+ *     (a product of two floats is exact in fp64), then the fixed order of every reduction here: every sum is within 8 * 2^-24 of the
+ *     sum of the magnitudes of its products.
+ * What the term is NOT.  The colour is the volume's voxel-size blend: a coarser, noisier measurement than a frame's own pixels.  It
+ * reads the dense window only: voxels in the archive's bricks give no row (the rule is written over the colour-corner fetch, so the
+ * map form can follow).  Rows are not weighted by voxel weight.  Its basin is still the truncation band: a point further than trunc
+ * from the fused surface gives neither row.
+ * The calls need a frame (with the levels asked), a frame colour, a volume and a colour volume, RPE_ERR_STATE otherwise; they need NO
+ * model and NO rpe_photo_prepare.  They build the frame's intensity pyramid themselves (one launch, into a buffer of their own, kept
+ * until the frame's depth or colour is replaced) and neither read nor replace the model, the model colour, the prepared photometric
+ * maps, the solver slots, the volumes or the archive. */
+/* {r, J[0..5]} of the photometric row of every frame pixel of the level, UNSCALED as rpe_photo_rows gives them, as 7 planes of
+ * w_l*h_l floats, NaN where the pixel has no row.  level >= 0, dist_thr >= 0 */
+int rpe_sdf_photo_rows(rpe_context* ctx, int level, const double* pose12, double dist_thr, float* rows);
+/* the photometric normal equations ALONE, laid out as rpe_photo_normal_eq: H upper triangle (21) | g (6) of the rows scaled by
+ * weight | [27] sum r'^2 | [28] rows | [29] pivot floor.  weight finite and > 0 */
+int rpe_sdf_photo_normal_eq(rpe_context* ctx, int level, const double* pose12, double dist_thr, double weight, double* out32);
+/* rpe_icp_sdf / rpe_icp_pyramid_sdf with the photometric rows beside the geometric ones: the same conventions (of opt, max_iter, tol,
+ * dist_thr, cos_thr and use_normals are read; host-driven only: device_resident = 1 is RPE_ERR_ARG; RPE_ERR_DEGENERATE as rpe_icp_sdf)
+ * and photo_weight, finite and > 0 (RPE_ERR_ARG otherwise).  final_cost / matched are the geometric sum of r^2 and rows of the last
+ * round, photo_cost / photo_matched the photometric sum of r'^2 and rows; the pyramid form reports level 0's. */
+int rpe_icp_sdf_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double photo_weight, double* pose12, int* iters_out, double* last_step,
+                     double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched);
+int rpe_icp_pyramid_sdf_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double photo_weight, int levels, const int* iters_per_level,
+                             const double* dist_thr_per_level, double* pose12, int* iters_out, double* last_step, double* final_cost,
+                             int64_t* matched, double* photo_cost, int64_t* photo_matched);
+
 /* ---- Features and relocalisation: correspondences WITHOUT a pose guess.  rpe_associate pairs under a guess, so every entry above
  * that produces a pose from images needs a start inside ICP's basin; a lost tracker has none.  Here keypoints of the frame's colour
  * and of the model view's colour are described and matched by appearance, the matched pixels' vertices, normals and bearings go into

@@ -51,6 +51,7 @@ SYMBOLS = [
     "rpe_model_color_upload", "rpe_model_color_from_frame", "rpe_photo_prepare", "rpe_photo_download", "rpe_photo_normal_eq", "rpe_photo_rows",
     "rpe_icp_rgbd", "rpe_icp_pyramid_rgbd",
     "rpe_sdf_rows", "rpe_sdf_normal_eq", "rpe_icp_sdf", "rpe_icp_pyramid_sdf",
+    "rpe_sdf_photo_rows", "rpe_sdf_photo_normal_eq", "rpe_icp_sdf_rgbd", "rpe_icp_pyramid_sdf_rgbd",
     "rpe_features_detect", "rpe_features_download", "rpe_features_match", "rpe_matches_download", "rpe_relocalize",
     "rpe_keyframe_add", "rpe_keyframe_add_host", "rpe_keyframe_info", "rpe_keyframe_download", "rpe_keyframes_count", "rpe_keyframes_clear",
     "rpe_keyframes_query", "rpe_keyframe_match", "rpe_relocalize_keyframes",
@@ -257,6 +258,12 @@ def lib():
         L.rpe_icp_sdf.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_icp_pyramid_sdf.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_sdf_photo_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p]
+        L.rpe_sdf_photo_normal_eq.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+        L.rpe_icp_sdf_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
+        L.rpe_icp_pyramid_sdf_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_features_detect.argtypes = [C.c_void_p, C.c_int, C.POINTER(RpeFeatureOptions), C.c_void_p]
         L.rpe_features_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rpe_features_match.argtypes = [C.c_void_p, C.POINTER(RpeMatchOptions), C.c_void_p]

@@ -678,6 +678,44 @@ class Context:
         L.check(L.lib().rpe_icp_pyramid_sdf(self._h, C.byref(o), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step), C.byref(cost), C.byref(m)))
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
 
+    # ---- volume colour term (Part 3): a photometric term against the colour volume beside the volume term -- no model, no photo_prepare
+    def sdf_photo_rows(self, pose12, level: int = 0, dist_thr: float = 0.1) -> np.ndarray:
+        """(7, pixels) float32: the unscaled photometric residual in intensity levels (row 0: the residual image) and Jacobian row of
+        every frame pixel of the level against the colour volume under pose12, NaN where the pixel has no row."""
+        p = np.array(pose12, np.float64).reshape(12)
+        h, w = getattr(self, "_frame_hw", None) or (0, 0)      # (no frame yet: the library says so; it checks the level too)
+        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
+        L.check(L.lib().rpe_sdf_photo_rows(self._h, int(level), _p(p), float(dist_thr), _p(out)))
+        return out
+
+    def sdf_photo_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, weight: float = 0.01) -> np.ndarray:
+        """The volume colour term's normal equations alone: H upper triangle (21) | g (6) | cost | rows | pivot floor | pad, 32 float64."""
+        p = np.array(pose12, np.float64).reshape(12)
+        out = np.zeros(32, np.float64)
+        L.check(L.lib().rpe_sdf_photo_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(weight), _p(out)))
+        return out
+
+    def icp_sdf_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9,
+                     use_normals: bool = True):
+        """icp_sdf with the photometric rows against the colour volume (weight in metres per intensity level) beside the geometric ones,
+        one launch per round; needs a frame with colour, a volume and a colour volume.  Returns (pose12, iterations, last |delta|,
+        geometric sum r^2, geometric rows, photometric cost, photometric rows) of the last round."""
+        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
+        pc, pm = C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_sdf_rgbd(self._h, C.byref(o), float(weight), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m),
+                                         C.byref(pc), C.byref(pm)))
+        return p, it.value, step.value, cost.value, m.value, pc.value, pm.value
+
+    def icp_pyramid_sdf_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9,
+                             use_normals: bool = True):
+        """icp_sdf_rgbd coarse to fine over len(iters) levels of the frame; dist_thr as icp_pyramid's.  Returns (pose12, rounds per level,
+        last |delta|, geometric sum r^2, geometric rows, photometric cost, photometric rows), the last five of level 0."""
+        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
+        pc, pm = C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_pyramid_sdf_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step),
+                                                 C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
+        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
+
     # ---- map volume term (Part 3): the volume term on the whole map -- the window plus the archived bricks -- inside a box
     @staticmethod
     def _box(box):

@@ -30,7 +30,7 @@ UNITS = [
     ("rpe_score.hip", "kernel", "K4 scoring, K4b masks"),
     ("rpe_nl.hip", "kernel", "K1' moments, K5, publish kernels"),
     ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map; the volume term's rows and round, on the window and on the map; "
-                                   "the keyframe list fused into the map's bricks (csrc/rpe_mapfuse.hpp)"),
+                                   "the keyframe list fused into the map's bricks (csrc/rpe_mapfuse.hpp); the volume colour term's rows and round (csrc/rpe_sdf_photo.hpp)"),
     ("rpe_filter.hip", "kernel", "the bilateral depth filter in front of it"),
     ("rpe_volume.hip", "kernel", "TSDF volume: integrate, raycast"),
     ("rpe_mesh.hip", "kernel", "marching cubes over the volume"),
@@ -62,6 +62,7 @@ UNITS = [
     ("rpe_color_api.hip", "host", "Part 3: colour of frame, volume, model and mesh"),
     ("rpe_photo_api.hip", "host", "Part 3: photometric term beside ICP"),
     ("rpe_sdf_api.hip", "host", "Part 3: the volume term, a frame tracked against the TSDF volume itself or against the whole map's"),
+    ("rpe_sdf_photo_api.hip", "host", "Part 3: the volume colour term, a photometric term against the colour volume beside the volume term"),
     ("rpe_feature_api.hip", "host", "Part 3: features and relocalisation"),
     ("rpe_keyframe_api.hip", "host", "Part 3: keyframes"),
     ("rpe_graph_api.hip", "host", "Part 3: the keyframe graph"),

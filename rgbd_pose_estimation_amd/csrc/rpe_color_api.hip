@@ -27,7 +27,7 @@ int rpe_frame_set_color(rpe_context* c, const uint8_t* pixels, int format) {
   const int64_t n = (int64_t)F.cam.width * F.cam.height;
   int rc;
   if ((rc = F.d_rgb.reserve(c, (size_t)n * 3)) || (rc = F.fcolor.reserve(c, (size_t)n * 4))) return rc;
-  F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
+  F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0; F.sint_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_rgb, pixels, (size_t)n * 3, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_color(F.d_rgb, n, format == RPE_COLOR_BGR8 ? 1 : 0, F.fcolor, c->stream));
   F.have_fcolor = true;

@@ -892,3 +892,9 @@ hipError_t launch_map_sdf_rows(const float* vmap, const float* nmap, int64_t n, 
 // map.  The kernel's text is rpe_mapfuse.hpp; it is compiled here, with the map raycast and the map volume term, whose view of a brick
 // (brick_word) it shares.
 #include "rpe_mapfuse.hpp"
+
+// ================================================================================================
+// THE VOLUME COLOUR TERM (include/rgbd_pose_hip.h Part 3, "Volume colour term"): a photometric term against the colour volume, beside the
+// volume term and in one launch with it.  The kernels' text is rpe_sdf_photo.hpp; it is compiled here, with the volume term whose cell,
+// corner fetch, row and late_finish_at it shares.
+#include "rpe_sdf_photo.hpp"

@@ -129,7 +129,7 @@ int rpe_frame_set_depth(rpe_context* c, const void* depth, int depth_type, const
   auto& F = c->fe;
   const int64_t n = (int64_t)k.width * k.height;
   if ((rc = stage_depth(c, depth_type, n, n))) return rc;
-  F.have_frame = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
+  F.have_frame = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0; F.sint_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   DepthSource src;
   if ((rc = depth_source(c, depth_type, k, (float)depth_scale, (float)dmin, (float)dmax, &src))) return rc;
@@ -155,7 +155,7 @@ int rpe_frame_set_depth_pyramid(rpe_context* c, const void* depth, int depth_typ
   auto& F = c->fe;
   const int64_t n = (int64_t)g.cam[0].width * g.cam[0].height, total = g.off[levels];
   if ((rc = stage_depth(c, depth_type, n, total)) || (rc = F.fdepth.reserve(c, (size_t)total * sizeof(float)))) return rc;
-  F.have_frame = false; F.have_depth = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
+  F.have_frame = false; F.have_depth = false; F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0; F.sint_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.d_depth, depth, (size_t)n * (depth_type == RPE_DEPTH_U16 ? 2 : 4), hipMemcpyHostToDevice, c->stream));
   DepthSource src;
   if ((rc = depth_source(c, depth_type, g.cam[0], (float)depth_scale, (float)dmin, (float)dmax, &src))) return rc;

@@ -13,6 +13,7 @@
 //   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
 //   rpe_sdf_api.hip       Part 3: the volume term (a frame tracked against the TSDF volume itself, or against the whole map's through the
 //                         brick grid of rpe_mapmesh_api.hip; kernels in rpe_frontend.hip)
+//   rpe_sdf_photo_api.hip Part 3: the volume colour term (a photometric term against the colour volume beside the volume term; kernels in rpe_sdf_photo.hpp)
 //   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
 //   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)
@@ -194,6 +195,10 @@ struct rpe_context {
     // (0 = not prepared: whatever replaces the frame's depth or colour, the model or the model colour resets it)
     rpeh::DevBuf<float> pint, pmap;
     int photo_levels = 0;
+    // volume colour term (rpe_sdf_photo_api.hip): its own intensity pyramid of the frame, all sint_levels levels of it (0 = not built:
+    // whatever replaces the frame's depth or colour resets it, nothing else does)
+    rpeh::DevBuf<float> sint;
+    int sint_levels = 0;
     // features (rpe_feature_api.hip): per side (RPE_FEAT_FRAME / RPE_FEAT_MODEL) the keypoints of the last detection -- pixel index,
     // score, xy and 8 descriptor words each, RPE_MAX_KEYPOINTS slots, allocated on first use -- valid while `have` (whatever replaces
     // the side's depth, model or colour resets it); gen counts the side's detections so that a match list knows what it was made of

@@ -526,4 +526,13 @@ hipError_t launch_icp_map_sdf(const float* vmap, const float* nmap, int64_t n, c
 hipError_t launch_map_sdf_rows(const float* vmap, const float* nmap, int64_t n, const MapRayView& M, const VolumeGeometry& G, float dist_thr,
                                float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s);
 
+// ---- the volume colour term (rpe_sdf_photo.hpp, compiled into rpe_frontend.hip): the photometric rows of a frame against the colour
+// volume cvol (4 binary16 per voxel at the tsdf's index) beside the volume term's, one round in one kernel.  fint: the level's frame
+// intensity.  geometric != 0: the volume term's rows (weight 1) as well.  Record of kNlLd doubles laid out as launch_icp_photo's
+hipError_t launch_icp_sdf_photo(const float* vmap, const float* nmap, const float* fint, int64_t n, const float* vol, const unsigned short* cvol,
+                                const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals, float lam, int geometric,
+                                const double* pose12, const ReduceTarget& rt, hipStream_t s);
+// rows[k * n + i], k = 0 .. 6: {r, J[0..5]} (unscaled) of the photometric row of frame pixel i, NaN where it has no row
+hipError_t launch_sdf_photo_rows(const float* vmap, const float* fint, int64_t n, const float* vol, const unsigned short* cvol,
+                                 const VolumeGeometry& G, float dist_thr, const double* pose12, float* rows, hipStream_t s);
 }  // namespace rpe

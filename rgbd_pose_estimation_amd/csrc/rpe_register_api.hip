@@ -51,7 +51,7 @@ int rpe_frame_register_color(rpe_context* c, const uint8_t* pixels, int format, 
   if ((rc = F.rg_rgb.reserve(c, (size_t)nc * 3)) || (rc = F.rg_rgba.reserve(c, (size_t)nc * 4)) ||
       (rc = F.rg_zbuf.reserve(c, (zwords + rpe::kRegCountWords) * 4)) || (rc = F.fcolor.reserve(c, (size_t)n * 4)))
     return rc;
-  F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0;
+  F.have_fcolor = false; F.feat[0].have = false; F.photo_levels = 0; F.sint_levels = 0;
   HIP_TRY(hipMemcpyAsync(F.rg_rgb, pixels, (size_t)nc * 3, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(rpe::launch_frame_color(F.rg_rgb, nc, format == RPE_COLOR_BGR8 ? 1 : 0, F.rg_rgba, c->stream));
   unsigned int* count = known ? F.rg_zbuf + zwords : nullptr;

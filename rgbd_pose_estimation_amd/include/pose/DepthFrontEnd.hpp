@@ -476,6 +476,42 @@ class DepthFrontEnd {
     rows.resize(n);
     return rows;
   }
+  // ---- the volume colour term: icpVolume / icpPyramidVolume with a photometric term against the COLOUR VOLUME beside the geometric one
+  // (weight in metres per intensity level): where geometry leaves the pose open -- a wall, a floor -- the colour holds it, still without
+  // raycast, model or preparePhoto (rpe_icp_sdf_rgbd).  Needs setColor on the frame and a volume fused with integrateColor
+  RgbdIcpResult icpVolumeColor(Pose& pose, double weight = 0.01, const IcpOptions& o = IcpOptions()) {
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    RgbdIcpResult r;
+    int64_t m = 0, pm = 0;
+    check(rpe_icp_sdf_rgbd(_ctx, &opt, weight, p, &r.iterations, &r.last_step, &r.cost, &m, &r.photo_cost, &pm), "rpe_icp_sdf_rgbd");
+    r.level_iterations[0] = r.iterations;
+    r.pairs = (long long)m; r.photo_pairs = (long long)pm;
+    pose = pose_of(p);
+    return r;
+  }
+  RgbdIcpResult icpPyramidVolumeColor(Pose& pose, double weight, const std::vector<int>& iters,
+                                      const std::vector<double>& dist_thr = std::vector<double>(), const IcpOptions& o = IcpOptions()) {
+    int64_t pm = 0;
+    RgbdIcpResult r = pyramidIcp<RgbdIcpResult>("icpPyramidVolumeColor", "rpe_icp_pyramid_sdf_rgbd", pose, iters, dist_thr, o,
+        [&](const rpe_icp_options* opt, int levels, const double* gates, double* p, RgbdIcpResult& res, int64_t* m) {
+          return rpe_icp_pyramid_sdf_rgbd(_ctx, opt, weight, levels, iters.data(), gates, p, res.level_iterations, &res.last_step, &res.cost, m,
+                                          &res.photo_cost, &pm); });
+    r.photo_pairs = (long long)pm;
+    return r;
+  }
+  // the residual image of a level under `pose`: the colour volume's luma at every frame vertex minus the frame's intensity (intensity
+  // levels), NaN where the pixel has no photometric row (row 0 of rpe_sdf_photo_rows)
+  std::vector<float> volumeColorResiduals(const Pose& pose, int level = 0, double dist_thr = 0.1) const {
+    double p[12]; pose12(pose, p);
+    rpe_camera k;
+    check(rpe_frame_level_camera(_ctx, level, 0, &k), "rpe_frame_level_camera");
+    const size_t n = (size_t)k.width * k.height;
+    std::vector<float> rows(7 * n);
+    check(rpe_sdf_photo_rows(_ctx, level, p, dist_thr, rows.data()), "rpe_sdf_photo_rows");
+    rows.resize(n);
+    return rows;
+  }
   // ---- the map volume term: icpVolume / icpPyramidVolume / volumeResiduals against the whole MAP -- the window plus the archived
   // bricks -- inside the box lo <= w < hi of world voxels (multiples of 8; both null: the bounds): a surface the window has left still
   // gives rows (rpe_icp_map_sdf).  The tracked frame of a moving window with the archive on: followVolume -> shiftVolume ->
