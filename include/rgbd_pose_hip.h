@@ -786,8 +786,8 @@ int rpe_icp_pyramid_sdf(rpe_context* ctx, const rpe_icp_options* opt, int levels
  *     (a product of two floats is exact in fp64), then the fixed order of every reduction here: every sum is within 8 * 2^-24 of the
  *     sum of the magnitudes of its products.
  * What the term is NOT.  The colour is the volume's voxel-size blend: a coarser, noisier measurement than a frame's own pixels.  It
- * reads the dense window only: voxels in the archive's bricks give no row (the rule is written over the colour-corner fetch, so the
- * map form can follow).  Rows are not weighted by voxel weight.  Its basin is still the truncation band: a point further than trunc
+ * reads the dense window only: voxels in the archive's bricks give no row here -- "Map volume colour term" below is the same term over
+ * the window AND the archived bricks (rpe_map_sdf_photo_rows ... rpe_icp_pyramid_map_sdf_rgbd).  Rows are not weighted by voxel weight.  Its basin is still the truncation band: a point further than trunc
  * from the fused surface gives neither row.
  * The calls need a frame (with the levels asked), a frame colour, a volume and a colour volume, RPE_ERR_STATE otherwise; they need NO
  * model and NO rpe_photo_prepare.  They build the frame's intensity pyramid themselves (one launch, into a buffer of their own, kept
@@ -1277,6 +1277,45 @@ int rpe_icp_map_sdf(rpe_context* ctx, const rpe_icp_options* opt, const int64_t 
 int rpe_icp_pyramid_map_sdf(rpe_context* ctx, const rpe_icp_options* opt, int levels, const int* iters_per_level,
                             const double* dist_thr_per_level, const int64_t lo[3], const int64_t hi[3], double* pose12, int* iters_out,
                             double* last_step, double* final_cost, int64_t* matched);
+
+/* ---- Map volume colour term: a frame tracked with colour against the whole MAP -- the TSDF AND the colour of the window and the
+ * archived bricks.  "Volume colour term" reads the window's two dense arrays, so a textured surface the map knows but the window no longer
+ * covers gives no photometric row, and "Map volume term" is geometry only; these calls read both of the map.  No new arithmetic: the box
+ * lo <= w < hi of world voxels (lo = hi = NULL: rpe_volume_map_bounds) defines the VIRTUAL VOLUME of "Map volume term" and, beside it,
+ * the VIRTUAL COLOUR VOLUME that "Map raycast" and "Map mesh" sample: a voxel holds the window's colour bits where the window covers
+ * it, the held brick's colour plane where the archive holds its world brick, {0, 0} elsewhere -- also for a brick archived before the
+ * colour volume existed (held without a colour plane: the archive restores zeros for those) and while the pool has no colour plane at
+ * all.  Zeros have no colour weight > 0: such a cell gives a geometric row and no photometric one.
+ * THE CONTRACT: rpe_map_sdf_photo_rows returns, bit for bit, what rpe_sdf_photo_rows returns in a second context whose volume is a
+ * fresh rpe_volume_init of the virtual volume with the map's TSDF and colour uploaded (rpe_volume_upload, rpe_volume_color_upload) and
+ * the same frame: steps 1-5 of "Volume colour term" on the two virtual volumes (tests/mapsdf_photo_oracle.py states the composition in
+ * numpy).  With the box equal to the window's extent the rows are rpe_sdf_photo_rows' of the same context.  The records are laid out as
+ * the window calls', the row counts exact, every sum within 8 * 2^-24 of the sum of the magnitudes of its products (both rows widened
+ * to fp64, fp64 fused multiply-adds, one pixel per thread and loop trip, in the combined round the geometric row before the photometric
+ * one); the loops are rpe_icp_sdf_rgbd's and rpe_icp_pyramid_sdf_rgbd's, round for round, with that record.
+ * Rules: the union of the two terms'.  A frame (with the levels asked), a frame colour, a volume and a colour volume, and every dim and
+ * every component of the total shift a multiple of 8 (RPE_ERR_STATE); weight / photo_weight finite and > 0, the box rules of "Map
+ * volume term" (multiples of 8, 8 <= hi - lo <= 2^20, lo and hi both given or both NULL, at most 2^24 bricks), host-driven only
+ * (RPE_ERR_ARG).  The archive need not be on: the map is then the window.  The calls write nothing but the uploaded grid, their own
+ * intensity pyramid and the reduction's scratch: the model, the model colour, the prepared photometric maps, the solver slots, the last
+ * mesh, both volumes and the archive stay as they were.
+ * How: the brick grid is built and uploaded ONCE per call and serves both fetches and every round.  The colour corners are fetched
+ * behind the TSDF corners' gates (a pixel whose TSDF corners give no row needs no colour; the result is the same bits); a cell whose
+ * corner-0 brick is absent costs no voxel load.
+ * What it is NOT: as "Map volume term" -- rows not weighted by voxel weight, the grid rebuilt on every call, no device-side brick index,
+ * no device-resident loop. */
+/* rpe_sdf_photo_rows / rpe_sdf_photo_normal_eq / rpe_icp_sdf_rgbd / rpe_icp_pyramid_sdf_rgbd on the map inside the box; every other
+ * argument as theirs */
+int rpe_map_sdf_photo_rows(rpe_context* ctx, int level, const double* pose12, double dist_thr, const int64_t lo[3], const int64_t hi[3],
+                           float* rows);
+int rpe_map_sdf_photo_normal_eq(rpe_context* ctx, int level, const double* pose12, double dist_thr, double weight, const int64_t lo[3],
+                                const int64_t hi[3], double* out32);
+int rpe_icp_map_sdf_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double photo_weight, const int64_t lo[3], const int64_t hi[3],
+                         double* pose12, int* iters_out, double* last_step, double* final_cost, int64_t* matched, double* photo_cost,
+                         int64_t* photo_matched);
+int rpe_icp_pyramid_map_sdf_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double photo_weight, int levels, const int* iters_per_level,
+                                 const double* dist_thr_per_level, const int64_t lo[3], const int64_t hi[3], double* pose12, int* iters_out,
+                                 double* last_step, double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched);
 
 /* ---- Map fuse: the whole MAP rebuilt from the keyframes -- the window and the archived bricks.  rpe_volume_fuse_keyframes writes the
  * dense window only: after a loop closure the archived bricks, most of a walked map, would keep the surface fused at the drifted poses.

@@ -66,6 +66,7 @@ SYMBOLS = [
     "rpe_volume_archive", "rpe_volume_archive_info", "rpe_volume_archive_download", "rpe_volume_archive_clear",
     "rpe_volume_map_bounds", "rpe_volume_map_mesh", "rpe_volume_map_raycast",
     "rpe_map_sdf_rows", "rpe_map_sdf_normal_eq", "rpe_icp_map_sdf", "rpe_icp_pyramid_map_sdf",
+    "rpe_map_sdf_photo_rows", "rpe_map_sdf_photo_normal_eq", "rpe_icp_map_sdf_rgbd", "rpe_icp_pyramid_map_sdf_rgbd",
     "rpe_volume_map_fuse_keyframes",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
@@ -322,6 +323,13 @@ def lib():
                                       C.c_void_p]
         L.rpe_icp_pyramid_map_sdf.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_map_sdf_photo_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_map_sdf_photo_normal_eq.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_icp_map_sdf_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_icp_pyramid_map_sdf_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

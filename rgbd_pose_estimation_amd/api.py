@@ -760,6 +760,47 @@ class Context:
                                                 C.byref(cost), C.byref(m)))
         return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
 
+    # ---- map volume colour term (Part 3): the volume colour term on the whole map -- TSDF and colour of the window plus the archived bricks
+    def map_sdf_photo_rows(self, pose12, level: int = 0, dist_thr: float = 0.1, box=None) -> np.ndarray:
+        """sdf_photo_rows against the MAP inside box = (lo, hi) in world voxels (multiples of 8; None: volume_map_bounds): bit for bit
+        sdf_photo_rows of a dense volume and colour volume of the box holding the map's content (rpe_map_sdf_photo_rows)."""
+        p = np.array(pose12, np.float64).reshape(12)
+        lo, hi = self._box(box)
+        h, w = getattr(self, "_frame_hw", None) or (0, 0)
+        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
+        L.check(L.lib().rpe_map_sdf_photo_rows(self._h, int(level), _p(p), float(dist_thr), _p(lo), _p(hi), _p(out)))
+        return out
+
+    def map_sdf_photo_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, weight: float = 0.01, box=None) -> np.ndarray:
+        """sdf_photo_normal_eq on the map inside the box: the same 32 float64."""
+        p = np.array(pose12, np.float64).reshape(12)
+        lo, hi = self._box(box)
+        out = np.zeros(32, np.float64)
+        L.check(L.lib().rpe_map_sdf_photo_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(weight), _p(lo), _p(hi), _p(out)))
+        return out
+
+    def icp_map_sdf_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9,
+                         use_normals: bool = True, box=None):
+        """icp_sdf_rgbd on the map inside the box; the brick grid is built and uploaded once for both fetches and all rounds.  Returns
+        what icp_sdf_rgbd returns."""
+        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
+        lo, hi = self._box(box)
+        pc, pm = C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_map_sdf_rgbd(self._h, C.byref(o), float(weight), _p(lo), _p(hi), _p(p), C.byref(it), C.byref(step), C.byref(cost),
+                                             C.byref(m), C.byref(pc), C.byref(pm)))
+        return p, it.value, step.value, cost.value, m.value, pc.value, pm.value
+
+    def icp_pyramid_map_sdf_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9,
+                                 use_normals: bool = True, box=None):
+        """icp_pyramid_sdf_rgbd on the map inside the box: the colour tracker of a moving window with the archive on (volume_follow ->
+        volume_shift -> icp_pyramid_map_sdf_rgbd -> volume_integrate_color).  Returns what icp_pyramid_sdf_rgbd returns."""
+        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
+        lo, hi = self._box(box)
+        pc, pm = C.c_double(0), C.c_int64(0)
+        L.check(L.lib().rpe_icp_pyramid_map_sdf_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), _p(thr), _p(lo), _p(hi), _p(p),
+                                                     _p(it_out), C.byref(step), C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
+        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
+
     # ---- features and relocalisation (Part 3): correspondences without a pose guess
     def features_detect(self, which: int = L.FEAT_FRAME, threshold: int = 12, max_keypoints: int = L.MAX_KEYPOINTS) -> int:
         """Detect and describe the keypoints of the frame's colour (FEAT_FRAME) or the model colour (FEAT_MODEL); returns their number."""

@@ -30,7 +30,8 @@ UNITS = [
     ("rpe_score.hip", "kernel", "K4 scoring, K4b masks"),
     ("rpe_nl.hip", "kernel", "K1' moments, K5, publish kernels"),
     ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map; the volume term's rows and round, on the window and on the map; "
-                                   "the keyframe list fused into the map's bricks (csrc/rpe_mapfuse.hpp); the volume colour term's rows and round (csrc/rpe_sdf_photo.hpp)"),
+                                   "the keyframe list fused into the map's bricks (csrc/rpe_mapfuse.hpp); the volume colour term's rows and round (csrc/rpe_sdf_photo.hpp), "
+                                   "on the window and on the map (csrc/rpe_map_sdf_photo.hpp)"),
     ("rpe_filter.hip", "kernel", "the bilateral depth filter in front of it"),
     ("rpe_volume.hip", "kernel", "TSDF volume: integrate, raycast"),
     ("rpe_mesh.hip", "kernel", "marching cubes over the volume"),
@@ -62,7 +63,8 @@ UNITS = [
     ("rpe_color_api.hip", "host", "Part 3: colour of frame, volume, model and mesh"),
     ("rpe_photo_api.hip", "host", "Part 3: photometric term beside ICP"),
     ("rpe_sdf_api.hip", "host", "Part 3: the volume term, a frame tracked against the TSDF volume itself or against the whole map's"),
-    ("rpe_sdf_photo_api.hip", "host", "Part 3: the volume colour term, a photometric term against the colour volume beside the volume term"),
+    ("rpe_sdf_photo_api.hip", "host", "Part 3: the volume colour term, a photometric term against the colour volume beside the volume term, on the window or "
+                                      "on the whole map's two volumes"),
     ("rpe_feature_api.hip", "host", "Part 3: features and relocalisation"),
     ("rpe_keyframe_api.hip", "host", "Part 3: keyframes"),
     ("rpe_graph_api.hip", "host", "Part 3: the keyframe graph"),
@@ -70,7 +72,7 @@ UNITS = [
     ("rpe_register_api.hip", "host", "Part 3: colour registration"),
     ("rpe_shift_api.hip", "host", "Part 3: the moving volume"),
     ("rpe_archive_api.hip", "host", "Part 3: the volume archive"),
-    ("rpe_mapmesh_api.hip", "host", "Part 3: the map: mesh and raycast"),
+    ("rpe_mapmesh_api.hip", "host", "Part 3: the map: mesh and raycast; the brick grid and the map's field for the calls that track against it"),
     ("rpe_mapfuse_api.hip", "host", "Part 3: the map rebuilt from the keyframes"),
     ("library.cpp", "cpp", "reference-compatible ao / ao_ransac / py2c and the adapter-level pipelines"),
     ("rpe_hostex.cpp", "cpp", "host-side all-reduce between the rank processes of one node"),

@@ -120,5 +120,10 @@ int map_box(const char* who, const rpe_context::Volume& V, const int64_t* lo, co
 // refuses a box of more than kMaxGrid bricks first
 constexpr int64_t kMaxGrid = (int64_t)1 << 24;
 void build_grid(const rpe_context::Volume& V, const int64_t b0[3], const int64_t nb[3], std::vector<unsigned char>& h, rpe::MapRayView& M);
+// the map's field inside the box (lo = NULL: the map's bounds), for the calls that track a frame against it (rpe_sdf_api.hip,
+// rpe_sdf_photo_api.hip): the state and box rules of rpe_volume_map_raycast, then the brick grid built and uploaded ONCE, for every fetch
+// and round of the call.  On success G is the virtual volume's geometry and M the view, both volumes and both planes of the pool
+// included (null where there is none).  Nothing but the volume's map list is written
+int map_field(rpe_context* c, const char* who, const int64_t* lo, const int64_t* hi, rpe::VolumeGeometry& G, rpe::MapRayView& M);
 
 }  // namespace rpeh

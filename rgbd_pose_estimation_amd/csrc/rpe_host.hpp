@@ -13,7 +13,8 @@
 //   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
 //   rpe_sdf_api.hip       Part 3: the volume term (a frame tracked against the TSDF volume itself, or against the whole map's through the
 //                         brick grid of rpe_mapmesh_api.hip; kernels in rpe_frontend.hip)
-//   rpe_sdf_photo_api.hip Part 3: the volume colour term (a photometric term against the colour volume beside the volume term; kernels in rpe_sdf_photo.hpp)
+//   rpe_sdf_photo_api.hip Part 3: the volume colour term (a photometric term against the colour volume beside the volume term,
+//                         on the window or on the whole map; kernels in rpe_sdf_photo.hpp and rpe_map_sdf_photo.hpp)
 //   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
 //   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)

@@ -535,4 +535,12 @@ hipError_t launch_icp_sdf_photo(const float* vmap, const float* nmap, const floa
 // rows[k * n + i], k = 0 .. 6: {r, J[0..5]} (unscaled) of the photometric row of frame pixel i, NaN where it has no row
 hipError_t launch_sdf_photo_rows(const float* vmap, const float* fint, int64_t n, const float* vol, const unsigned short* cvol,
                                  const VolumeGeometry& G, float dist_thr, const double* pose12, float* rows, hipStream_t s);
+// ---- the map volume colour term (rpe_map_sdf_photo.hpp, compiled into rpe_frontend.hip): the same two on the virtual volume G of a box
+// of the map and its virtual colour volume, through the brick grid of M (as launch_map_raycast takes them, the colour sources M.cvol /
+// M.cpool included, either may be null; wnb, wb0, wbn are not read).  Rows bit for bit launch_sdf_photo_rows' on dense copies
+hipError_t launch_icp_map_sdf_photo(const float* vmap, const float* nmap, const float* fint, int64_t n, const MapRayView& M,
+                                    const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals, float lam, int geometric,
+                                    const double* pose12, const ReduceTarget& rt, hipStream_t s);
+hipError_t launch_map_sdf_photo_rows(const float* vmap, const float* fint, int64_t n, const MapRayView& M, const VolumeGeometry& G,
+                                     float dist_thr, const double* pose12, float* rows, hipStream_t s);
 }  // namespace rpe

@@ -157,6 +157,24 @@ void rpeh::build_grid(const rpe_context::Volume& V, const int64_t b0[3], const i
   }
 }
 
+int rpeh::map_field(rpe_context* c, const char* who, const int64_t* lo, const int64_t* hi, rpe::VolumeGeometry& G, rpe::MapRayView& M) {
+  auto& V = c->vol;
+  int64_t b0[3], nb[3];
+  int rc;
+  if ((rc = map_state(who, V)) || (rc = map_box(who, V, lo, hi, G, b0, nb))) return rc;
+  const int64_t n = nb[0] * nb[1] * nb[2];   // <= 2^51
+  if (n > kMaxGrid) return fail(RPE_ERR_ARG, "%s: %lld bricks in the box; the brick grid holds at most 2^24", who, (long long)n);
+  if ((rc = V.map_list.reserve(c, (size_t)n * sizeof(int32_t)))) return rc;
+  build_grid(V, b0, nb, V.h_map_list, M);
+  HIP_TRY(hipMemcpyAsync(V.map_list, V.h_map_list.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  M.vol = reinterpret_cast<const unsigned int*>(V.d.get());
+  M.cvol = V.have_color ? reinterpret_cast<const unsigned int*>(V.cd.get()) : nullptr;
+  M.pool = V.arc.pool; M.cpool = V.arc.cpool;
+  M.capacity = (int)V.arc.capacity;
+  M.grid = static_cast<int*>(V.map_list.get());
+  return RPE_OK;
+}
+
 extern "C" {
 
 int rpe_volume_map_bounds(rpe_context* c, int64_t lo[3], int64_t hi[3]) {

@@ -24,24 +24,11 @@ Field window_field(rpe_context* c) {
   f.g = c->vol.g;
   return f;
 }
-// the map's field inside the box (lo = NULL: the map's bounds): the state and box rules of rpe_volume_map_raycast, then the brick grid
-// built and uploaded.  Nothing but the volume's map list is written
+// the map's field inside the box (rpe_frontend_host.hpp map_field, in rpe_mapmesh_api.hip: rules, grid, upload)
 int map_field(rpe_context* c, const char* who, const int64_t* lo, const int64_t* hi, Field& f) {
-  auto& V = c->vol;
-  int64_t b0[3], nb[3];
-  int rc;
-  if ((rc = map_state(who, V)) || (rc = map_box(who, V, lo, hi, f.g, b0, nb))) return rc;
-  const int64_t n = nb[0] * nb[1] * nb[2];   // <= 2^51
-  if (n > kMaxGrid) return fail(RPE_ERR_ARG, "%s: %lld bricks in the box; the brick grid holds at most 2^24", who, (long long)n);
-  if ((rc = V.map_list.reserve(c, (size_t)n * sizeof(int32_t)))) return rc;
-  build_grid(V, b0, nb, V.h_map_list, f.M);
-  HIP_TRY(hipMemcpyAsync(V.map_list, V.h_map_list.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  f.M.vol = reinterpret_cast<const unsigned int*>(V.d.get());
-  f.M.pool = V.arc.pool;
-  f.M.capacity = (int)V.arc.capacity;
-  f.M.grid = static_cast<int*>(V.map_list.get());
-  f.map = true;
-  return RPE_OK;
+  const int rc = rpeh::map_field(c, who, lo, hi, f.g, f.M);
+  f.map = rc == RPE_OK;
+  return rc;
 }
 // one round: launch, wait, the 32-double record (H | g | sum r^2 | rows | pivot floor)
 int sdf_round(rpe_context* c, const Field& f, const Level& lv, double dist_thr, double cos_thr, int use_normals, const double* pose12,

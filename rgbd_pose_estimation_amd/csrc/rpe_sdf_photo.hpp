@@ -56,16 +56,21 @@ __device__ __forceinline__ bool colour_lumas(const uint2 (&c)[8], float (&l)[8])
 // a: the UNSCALED r [levels] and J = [a | Xc x a], 0 when the pixel has no row.  The slope and normal gates of the volume term are not
 // asked: a photometric row stands wherever the point lies on the fused surface within the gate and the cell has colour.  A colour channel
 // that is NaN or Inf under a weight > 0 is not gated either: it goes into r and J as any value does
-__device__ __forceinline__ bool sdf_photo_row(const float2 (&v)[8], const float (&l)[8], bool known, const float (&a)[3], const VolumeGeometry& G,
-                                              const PoseF& T, float gate, float x, float y, float z, float If, float& r, float (&J)[6]) {
-  r = 0.f;
-#pragma unroll
-  for (int k = 0; k < 6; k++) J[k] = 0.f;
-  bool ok = known && __builtin_isfinite(If);
+//
+// In two parts, so that a caller whose colour fetch is dear may ask the TSDF corners first and fetch colour only past them.  Step 2,
+// what the TSDF corners alone decide, on top of the earlier answers `ok`:
+__device__ __forceinline__ bool sdf_photo_gate(const float2 (&v)[8], const float (&a)[3], const VolumeGeometry& G, float gate, bool ok) {
 #pragma unroll
   for (int m = 0; m < 8; m++) ok = ok && v[m].y > 0.0f && fabsf(v[m].x) < 1.0f;
   const float D = trilerp(v[0].x, v[1].x, v[2].x, v[3].x, v[4].x, v[5].x, v[6].x, v[7].x, a[0], a[1], a[2]);
-  ok = ok && fabsf(D * G.tr) <= gate;
+  return ok && fabsf(D * G.tr) <= gate;
+}
+// ... and steps 4 and 5 for a pixel that every gate has let through (ok)
+__device__ __forceinline__ bool sdf_photo_value(bool ok, const float (&l)[8], const float (&a)[3], const VolumeGeometry& G, const PoseF& T, float x,
+                                                float y, float z, float If, float& r, float (&J)[6]) {
+  r = 0.f;
+#pragma unroll
+  for (int k = 0; k < 6; k++) J[k] = 0.f;
   if (!ok) return false;
   const float Iv = trilerp(l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7], a[0], a[1], a[2]);
   const float gx = bilerp(l[1] - l[0], l[3] - l[2], l[5] - l[4], l[7] - l[6], a[1], a[2]);
@@ -79,6 +84,10 @@ __device__ __forceinline__ bool sdf_photo_row(const float2 (&v)[8], const float 
   J[0] = a0; J[1] = a1; J[2] = a2;
   J[3] = y * a2 - z * a1; J[4] = z * a0 - x * a2; J[5] = x * a1 - y * a0;
   return true;
+}
+__device__ __forceinline__ bool sdf_photo_row(const float2 (&v)[8], const float (&l)[8], bool known, const float (&a)[3], const VolumeGeometry& G,
+                                              const PoseF& T, float gate, float x, float y, float z, float If, float& r, float (&J)[6]) {
+  return sdf_photo_value(sdf_photo_gate(v, a, G, gate, known && __builtin_isfinite(If)), l, a, G, T, x, y, z, If, r, J);
 }
 
 // The whole rule for one pixel.  Corners / Colours: (i0, corner[8]) -> false when the cell has no voxels.
@@ -249,3 +258,6 @@ hipError_t launch_sdf_photo_rows(const float* vmap, const float* fint, int64_t n
 }
 
 }  // namespace rpe
+
+// the same term on the whole map -- the window plus the archived bricks: the fetch over the brick grid's colour planes and its two kernels
+#include "rpe_map_sdf_photo.hpp"

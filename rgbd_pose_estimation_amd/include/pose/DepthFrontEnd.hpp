@@ -543,6 +543,44 @@ class DepthFrontEnd {
     rows.resize(n);
     return rows;
   }
+  // ---- the map volume colour term: icpVolumeColor / icpPyramidVolumeColor / volumeColorResiduals against the whole MAP -- the TSDF and
+  // the colour of the window plus the archived bricks -- inside the box (as icpMap's): a textured surface the window has left still
+  // holds the in-plane motion (rpe_icp_map_sdf_rgbd).  The colour-tracked frame of a moving window with the archive on: followVolume ->
+  // shiftVolume -> icpPyramidMapColor -> integrateColor
+  RgbdIcpResult icpMapColor(Pose& pose, double weight = 0.01, const IcpOptions& o = IcpOptions(), const int64_t* lo = nullptr,
+                            const int64_t* hi = nullptr) {
+    double p[12]; pose12(pose, p);
+    const rpe_icp_options opt = options_of(o);
+    RgbdIcpResult r;
+    int64_t m = 0, pm = 0;
+    check(rpe_icp_map_sdf_rgbd(_ctx, &opt, weight, lo, hi, p, &r.iterations, &r.last_step, &r.cost, &m, &r.photo_cost, &pm), "rpe_icp_map_sdf_rgbd");
+    r.level_iterations[0] = r.iterations;
+    r.pairs = (long long)m; r.photo_pairs = (long long)pm;
+    pose = pose_of(p);
+    return r;
+  }
+  RgbdIcpResult icpPyramidMapColor(Pose& pose, double weight, const std::vector<int>& iters,
+                                   const std::vector<double>& dist_thr = std::vector<double>(), const IcpOptions& o = IcpOptions(),
+                                   const int64_t* lo = nullptr, const int64_t* hi = nullptr) {
+    int64_t pm = 0;
+    RgbdIcpResult r = pyramidIcp<RgbdIcpResult>("icpPyramidMapColor", "rpe_icp_pyramid_map_sdf_rgbd", pose, iters, dist_thr, o,
+        [&](const rpe_icp_options* opt, int levels, const double* gates, double* p, RgbdIcpResult& res, int64_t* m) {
+          return rpe_icp_pyramid_map_sdf_rgbd(_ctx, opt, weight, levels, iters.data(), gates, lo, hi, p, res.level_iterations, &res.last_step,
+                                              &res.cost, m, &res.photo_cost, &pm); });
+    r.photo_pairs = (long long)pm;
+    return r;
+  }
+  std::vector<float> mapColorResiduals(const Pose& pose, int level = 0, double dist_thr = 0.1, const int64_t* lo = nullptr,
+                                       const int64_t* hi = nullptr) const {
+    double p[12]; pose12(pose, p);
+    rpe_camera k;
+    check(rpe_frame_level_camera(_ctx, level, 0, &k), "rpe_frame_level_camera");
+    const size_t n = (size_t)k.width * k.height;
+    std::vector<float> rows(7 * n);
+    check(rpe_map_sdf_photo_rows(_ctx, level, p, dist_thr, lo, hi, rows.data()), "rpe_map_sdf_photo_rows");
+    rows.resize(n);
+    return rows;
+  }
   // keypoints and descriptors of the frame's colour (which = RPE_FEAT_FRAME) or of the model colour (RPE_FEAT_MODEL); returns their
   // number.  A new depth, colour, model or model colour drops the side's features
   int detectFeatures(int which, const FeatureOptions& o = FeatureOptions()) {

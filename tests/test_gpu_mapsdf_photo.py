@@ -1,0 +1,427 @@
+"""GPU: the map volume colour term (map_sdf_photo_rows_kernel / icp_map_sdf_photo_kernel of csrc/rpe_map_sdf_photo.hpp,
+rpe_sdf_photo_api.hip).  The rows are held BIT FOR BIT -- NaN for NaN -- to tests/mapsdf_photo_oracle.py and, independent of the oracle,
+to the window's kernel: rpe_sdf_photo_rows of a second context that holds the dense virtual volume and colour volume of the box.  The
+record is held to its rounding bound, the combined round and the loops to the oracle's and the second context's, the wall walk of
+tests/mapsdf_photo_cases.py to its recorded figures, and the state rules to the union of the two terms'.  The maps are assembled on the
+device by volume_upload, volume_color_upload and volume_shift with the archive on."""
+import ctypes as C_
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import mapmesh_cases as MC
+import mapsdf_cases as MSC
+import mapsdf_photo_cases as C
+import mapsdf_photo_oracle as MP
+import sdf_oracle as SO
+import volume_cases as VC
+from rgbd_pose_estimation_amd import _lib as L, api
+from test_gpu_mapmesh import snapshot, unchanged
+from test_gpu_photo import close, raises, same
+from test_gpu_sdf_photo import BOUND, check_record
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def set_frame(ctxs, depth, cam, seed=0, rng=C.RANGE, rgb=None):
+    """the frame, its pyramid and its colour on every context given; returns the oracle's [(V, N, If)] per level, its pyramid and its
+    intensity pyramid, from the RGBA the device holds"""
+    rgb = C.frame_rgba(cam, seed)[:, :3].reshape(cam[5], cam[4], 3) if rgb is None else rgb
+    for ctx in ctxs:
+        ctx.frame_set_depth(depth, cam, 1.0, *rng, levels=C.LEVELS)
+        ctx.frame_set_color(np.ascontiguousarray(rgb))
+    return C.frame_levels(cam, depth, ctxs[0].frame_color().reshape(-1, 4), rng)
+
+
+def check_rows(ctx, ref, m, box, lv, pose, gate, what=""):
+    """map_sdf_photo_rows against the oracle and against sdf_photo_rows of the reference context (which holds the box's dense volumes and
+    the same frame), at every level; returns the rows of level 0"""
+    first = None
+    for l, (V, N, If) in enumerate(lv):
+        r, J, ok = C.oracle_rows(m, m.bounds() if box is None else box, V, If, pose, gate)
+        got = ctx.map_sdf_photo_rows(pose, l, gate, box=box)
+        assert got.shape == (7, len(V))
+        assert same(got[0], r) and same(got[1:].T, J), (what, l, int(np.isnan(got[0]).sum()), int((~ok).sum()))
+        if ref is not None:
+            assert same(ref.sdf_photo_rows(pose, l, gate), got), (what, l)
+        first = int(ok.sum()) if first is None else first
+    return first
+
+
+def cut_box(m):
+    """a box that cuts the window: the bounds without the window's last brick layer along x and its first along z"""
+    lo, hi = m.bounds()
+    wlo, whi = m.extent()
+    return np.array([lo[0], lo[1], wlo[2] + 8]), np.array([whi[0] - 8, hi[1], hi[2]])
+
+
+# ---------------------------------------------------------------------------------------------- 1. rows, bit for bit
+@pytest.fixture(scope="module")
+def sphere(gpu_ctx_factory):
+    ctx = gpu_ctx_factory()
+    return ctx, C.sphere_map(ctx)
+
+
+@pytest.mark.parametrize("which", ("bounds", "grown", "cut"))
+def test_a_sphere_over_window_held_and_absent_bricks(sphere, gpu_ctx_factory, which):
+    """the bounds, a grown box with absent bricks around the map and another fp32 origin, and a box that cuts the window; the sphere's own
+    frames at both cameras and, on the bounds, class_depth's frames, which reach the corner of eight held bricks and the window's last z
+    layer with a row"""
+    ctx, m = sphere
+    assert tuple(ctx.volume_geometry()["total_shift"]) == (0, 0, -16) and ctx.volume_archive_info()["held"] == len(m.store) == 32
+    before = snapshot(ctx, m)
+    ref = gpu_ctx_factory()
+    box = dict(bounds=None, grown=MSC.GROWN_BOX, cut=cut_box(m))[which]
+    b = m.bounds() if box is None else box
+    C.reference_context(ref, m, b)
+    rows, with_row = 0, np.zeros(len(C.CLASSES), np.int64)
+    frames = [(cam, f) for cam in C.CAMS.values() for f in MSC.sphere_frames(m, cam)]
+    if which == "bounds":
+        frames += [(C.CAM_A, f) for f in C.sphere_class_frames(m, b, C.CAM_A)]
+    for cam, (name, pose, depth) in frames:
+        lv, _, _ = set_frame((ctx, ref), depth, cam)
+        rows += check_rows(ctx, ref, m, box, lv, pose, 0.1, what=f"sphere, {name}")
+        with_row += C.rows_per_class(m, b, lv[0][0], pose, 0.1)
+    print("rows", rows, dict(zip(C.CLASSES, with_row)))
+    need = C.SPHERE_ROW_CLASSES if which == "bounds" else ("window", "held/held face")
+    assert rows > 200 and all(with_row[C.CLASSES.index(k)] > 0 for k in need), with_row
+    assert unchanged(before, snapshot(ctx, m))
+
+
+def test_random_content_reaches_every_path_of_the_fetch(gpu_ctx_factory):
+    """random tsdf and colour: colour weights 0, negative, NaN and Inf, channels NaN / Inf under a weight > 0 (they propagate); gate =
+    trunc.  Every frame has a pixel in each class of cell, and over the frames a pixel whose TSDF corners let a row through in each of
+    RANDOM_ROW_CLASSES (class_depth chose the depths so, from the oracle alone)"""
+    ctx, ref = gpu_ctx_factory(), gpu_ctx_factory()
+    m = C.random_map(ctx)
+    lo, hi = m.bounds()
+    assert all(np.array_equal(a, b) for a, b in zip(ctx.volume_map_bounds(), (lo, hi))) and (hi - lo <= 40).all()
+    before = snapshot(ctx, m)
+    rows = not_finite = 0
+    with_row = np.zeros(len(C.CLASSES), np.int64)
+    for box in (None, (lo - 8, hi + 8), cut_box(m)):
+        b = m.bounds() if box is None else box
+        cut = box is not None and not np.array_equal(box[0], lo - 8)
+        C.reference_context(ref, m, b)
+        for n, pose in enumerate(MSC.random_views(m, b)):
+            lv, _, _ = set_frame((ctx, ref), C.class_depth(m, b, C.CAM_A, pose, MSC.RANDOM_GATE, every=not cut), C.CAM_A, n)
+            seen = MSC.classes(m, b, lv[0][0], pose).sum(0)
+            assert cut or (seen > 0).all(), dict(zip(C.CLASSES, seen))         # (the cut box has no last x layer of the window)
+            with_row += C.rows_per_class(m, b, lv[0][0], pose, MSC.RANDOM_GATE)
+            rows += check_rows(ctx, ref, m, box, lv, pose, MSC.RANDOM_GATE, what=f"random, view {n}")
+            r = ctx.map_sdf_photo_rows(pose, 0, MSC.RANDOM_GATE, box=box)[0]
+            not_finite += int(np.isinf(r).sum())
+    print("rows", rows, "of them not finite (Inf)", not_finite, dict(zip(C.CLASSES, with_row)))
+    assert all(with_row[C.CLASSES.index(k)] > 0 for k in C.RANDOM_ROW_CLASSES), with_row
+    assert rows > 60 and unchanged(before, snapshot(ctx, m))
+
+
+def test_a_map_archived_in_two_stages(gpu_ctx_factory):
+    """bricks archived before the first colour upload are held without a colour plane: a TSDF row there, no photometric row; bricks
+    archived after it are held with theirs.  The frames see both kinds"""
+    ctx, ref = gpu_ctx_factory(), gpu_ctx_factory()
+    m = C.two_stage_map(ctx)
+    assert ctx.volume_archive_info()["held"] == len(m.store) == 32
+    C.reference_context(ref, m, m.bounds())
+    rows_plane = tsdf_bare = rows = 0
+    for name, pose, depth in C.two_stage_frames(m, C.CAM_A):
+        lv, _, _ = set_frame((ctx, ref), depth, C.CAM_A)
+        rows += check_rows(ctx, ref, m, None, lv, pose, 0.1, what="two stages, " + name)
+        V, N, If = lv[0]
+        plane, bare = C.held_kinds(m, m.bounds(), V, pose)
+        got = ~np.isnan(ctx.map_sdf_photo_rows(pose, 0, 0.1)[0])
+        geo = ~np.isnan(ctx.map_sdf_rows(pose, 0, 0.1, C.COS_THR, False)[0])
+        assert not (got & bare).any()
+        rows_plane += int((got & plane).sum())
+        tsdf_bare += int((geo & bare).sum())
+    print("rows", rows, "in held bricks with a colour plane", rows_plane, "geometric rows in held bricks without one", tsdf_bare)
+    assert rows > 300 and rows_plane > 50 and tsdf_bare > 50
+
+
+def test_a_far_origin(gpu_ctx_factory):
+    """|o| / s = 2^22: an ulp of a world point is a quarter of a voxel"""
+    ctx, ref = gpu_ctx_factory(), gpu_ctx_factory()
+    m = C.far_map(ctx)
+    C.reference_context(ref, m, m.bounds())
+    rows = 0
+    for name, pose, depth in MSC.far_frames(m, C.CAM_A):
+        lv, _, _ = set_frame((ctx, ref), depth, C.CAM_A, rng=MSC.FAR_RANGE)
+        rows += check_rows(ctx, ref, m, None, lv, pose, 0.1, what="a far origin, " + name)
+    assert rows > 100
+
+
+# ---------------------------------------------------------------------------------------------- 2. box = the window's extent
+@pytest.mark.parametrize("archive", (True, False), ids=("archive on", "archive off"))
+def test_the_windows_extent_is_the_window_term(gpu_ctx_factory, archive):
+    ctx = gpu_ctx_factory()
+    m = C.scene_map(ctx, archive)
+    assert (ctx.volume_archive_info()["held"] > 0) == archive
+    pose, rows = MSC.scene_pose(), 0
+    for n, cam in enumerate(C.CAMS.values()):
+        lv, _, _ = set_frame((ctx,), MSC.scene_depth(cam), cam, n)
+        for l in range(C.LEVELS):
+            want = ctx.sdf_photo_rows(pose, l, 0.1)
+            assert same(ctx.map_sdf_photo_rows(pose, l, 0.1, box=m.extent()), want), l
+            if not archive:                                           # the map is the window: its bounds are the extent
+                assert same(ctx.map_sdf_photo_rows(pose, l, 0.1), want), l
+            rows += int((~np.isnan(want[0])).sum())
+        check_rows(ctx, None, m, None, lv, pose, 0.1, what="the scene")
+    assert rows > 150
+
+
+# ---------------------------------------------------------------------------------------------- 3. the record
+@pytest.fixture(scope="module")
+def scene(gpu_ctx_factory):
+    ctx = gpu_ctx_factory()
+    return ctx, C.scene_map(ctx)
+
+
+@pytest.mark.parametrize("cam", list(C.CAMS), ids=list(C.CAMS))
+def test_normal_eq_within_the_rounding_bound(scene, cam):
+    """row counts equal; every entry within 8 * 2^-24 * S of the fp64 sum of the exact products of the fp32 rows, S the sum of the
+    products' magnitudes: the project's bound (tests/test_gpu_sdf_photo.py BOUND).  The kernel widens each fp32 row and adds its products
+    with fp64 fused multiply-adds, so what a sum carries is fp64 accumulation error, orders below the bound; the worst ratio is printed"""
+    ctx, m = scene
+    cam = C.CAMS[cam]
+    lv, _, _ = set_frame((ctx,), MSC.scene_depth(cam), cam)
+    worst = 0.0
+    for pose in (MSC.scene_pose(), MSC.scene_start()):
+        for l, (V, N, If) in enumerate(lv):
+            for box in (None, MSC.grown(m)):
+                b = m.bounds() if box is None else box
+                pho = C.oracle_rows(m, b, V, If, pose, 0.1)
+                rec, S = MP.record(*pho, C.WEIGHT)
+                got = ctx.map_sdf_photo_normal_eq(pose, l, 0.1, C.WEIGHT, box=box)
+                assert got[28] == rec[28]
+                ratio = check_record(got, rec, S, slice(0, 28), ("photo", l))
+                print("level", l, "rows", int(rec[28]), "worst error / (2^-24 S):", ratio)
+                worst = max(worst, ratio)
+                assert got[29] == 16 * 2.0 ** -24 and got[30] == 0 and got[31] == 0
+    print("worst ratio", worst, "of the bound's", BOUND / 2.0 ** -24)
+    assert ctx.map_sdf_photo_normal_eq(MSC.scene_pose(), 0, 0.1, C.WEIGHT)[28] > 0.2 * cam[4] * cam[5]
+
+
+# ---------------------------------------------------------------------------------------------- 4. the combined round
+@pytest.mark.parametrize("cam", list(C.CAMS), ids=list(C.CAMS))
+def test_one_round_is_the_oracles_step_and_the_dense_contexts(scene, gpu_ctx_factory, oracle, cam):
+    """no entry point exposes the combined H and g: the round is held through its costs, counts and step, against the oracle's one-round
+    step and against icp_sdf_rgbd(max_iter = 1) of the second context, with tests/test_gpu_sdf_photo.py's agreement for its steps (poses
+    and |delta| within 1e-6, counts equal, costs within the record's bound)"""
+    ctx, m = scene
+    cam = C.CAMS[cam]
+    ref = gpu_ctx_factory()
+    start = MSC.scene_start()
+    worst = 0.0
+    for box in (None, MSC.grown(m)):
+        b = m.bounds() if box is None else box
+        C.reference_context(ref, m, b)
+        lv, _, _ = set_frame((ctx, ref), MSC.scene_depth(cam), cam)
+        V, N, If = lv[0]
+        for use_normals in (True, False):
+            po, hist = MP.icp_map_sdf_rgbd(oracle, m.window, m.cwindow, m.total, m.store, m.kw, b, V, N, If, start, 1, 0.1, 0.8, C.WEIGHT, use_normals)
+            p, it, step, cost, rows, pcost, prows = ctx.icp_map_sdf_rgbd(start, C.WEIGHT, 1, 0.0, 0.1, 0.8, use_normals, box=box)
+            assert it == 1 and close(p, po, 1e-6), (p, po)
+            assert (rows, prows) == hist[-1][:2] and abs(step - hist[-1][2]) < 1e-6 and step > 1e-3 and cost > 0 and pcost > 0 and rows > 100
+            q, it2, step2, cost2, rows2, pcost2, prows2 = ref.icp_sdf_rgbd(start, C.WEIGHT, 1, 0.0, 0.1, 0.8, use_normals)
+            assert close(p, q, 1e-6) and (rows, prows) == (rows2, prows2) and abs(step - step2) < 1e-6
+            vol, _, G, _ = MP.virtual(m.window, m.cwindow, m.total, m.store, m.kw, b)
+            geo = SO.rows(vol, G, V, N, start, 0.1, 0.8, use_normals)
+            crec, cS = MP.combined(geo, C.oracle_rows(m, b, V, If, start, 0.1), C.WEIGHT)
+            assert (rows, prows) == (int(crec[28]), int(crec[30]))
+            worst = max(worst, check_record(np.array([cost, pcost]), crec[[27, 29]], cS[[27, 29]], slice(0, 2), ("costs", use_normals)))
+            # ... and the step put together from the two terms' own records
+            ne = ctx.map_sdf_normal_eq(start, 0, 0.1, 0.8, use_normals, box=box)
+            pe = ctx.map_sdf_photo_normal_eq(start, 0, 0.1, C.WEIGHT, box=box)
+            ne[:27] += pe[:27]
+            assert close(p, api.gn_apply(api.gn_solve(ne), start), 1e-6) and rows == int(ne[28]) and prows == int(pe[28])
+    print("costs: worst error / (2^-24 S):", worst)
+
+
+# ---------------------------------------------------------------------------------------------- 5. the loops
+@pytest.mark.parametrize("cam,iters", [("40x30", (6, 4, 3)), ("21x13", (6, 4))], ids=list(C.CAMS))
+def test_loops_match_the_oracle_loops(scene, oracle, cam, iters):
+    """tests/test_gpu_sdf_photo.py's digits: poses within 1e-5 after several rounds, rows within 2 + 1e-4 * rows"""
+    ctx, m = scene
+    cam = C.CAMS[cam]
+    lv, pyr, fint = set_frame((ctx,), MSC.scene_depth(cam), cam)
+    start, (V, N, If) = MSC.scene_start(), lv[0]
+    map_of = (m.window, m.cwindow, m.total, m.store, m.kw)
+    po, hist = MP.icp_map_sdf_rgbd(oracle, *map_of, m.bounds(), V, N, If, start, 6, 0.1, 0.8, C.WEIGHT)
+    p, it, step, cost, rows, pcost, prows = ctx.icp_map_sdf_rgbd(start, C.WEIGHT, 6, 0.0, 0.1, 0.8)
+    assert it == 6 and close(p, po, 1e-5), (p, po)
+    assert abs(rows - hist[-1][0]) <= 2 + 1e-4 * hist[-1][0] and abs(prows - hist[-1][1]) <= 2 + 1e-4 * hist[-1][1]
+    assert rows > 0.2 * len(V) and prows > 0.1 * len(V)                        # (no passing on an empty answer)
+    # coarse to fine without the normal gate (as tests/test_gpu_mapsdf.py: the coarse levels of this small frame keep too few rows with it)
+    gates = (0.1, 0.15, 0.2)[:len(iters)]
+    for box in (None, MSC.grown(m)):
+        b = m.bounds() if box is None else box
+        po, hist = MP.icp_pyramid_map_sdf_rgbd(oracle, *map_of, b, pyr, fint, start, iters, gates, 0.8, C.WEIGHT, False)
+        p, its, step, cost, rows, pcost, prows = ctx.icp_pyramid_map_sdf_rgbd(start, C.WEIGHT, iters, gates, 0.0, 0.8, False, box=box)
+        assert its == iters and close(p, po, 1e-5), (p, po)
+        assert abs(rows - hist[-1][0]) <= 2 + 1e-4 * hist[-1][0] and abs(prows - hist[-1][1]) <= 2 + 1e-4 * hist[-1][1] and cost > 0 and pcost > 0
+
+
+def test_the_wall_seen_from_a_moving_window(gpu_ctx_factory):
+    """tests/mapsdf_photo_cases.py's walk through the API: fused with colour at the true poses, the window a brick further with every
+    frame, the archive on.  At the evaluated positions the photometric rows of window and map are the oracle's (within the loops'
+    tolerance), the map has more, and the new loop ends within the recorded errors (x2, as volume_cases gives such loops); the map's
+    geometry alone and the window's colour end where the oracle's loops end, to the same margin"""
+    ctx = gpu_ctx_factory()
+    ctx.volume_init(C.WALK_DIMS, **C.WALK_KW)
+    ctx.volume_archive(1024)
+    for n in range(C.WALK_FRAMES):
+        if n:
+            ctx.volume_shift((C.WALK_STEP, 0, 0))
+        d, rgb = C.walk_frame(C.walk_pose(n), n)
+        ctx.frame_set_depth(d, C.WALK_CAM, 1.0, *VC.RANGE, levels=1)
+        ctx.frame_set_color(rgb)
+        ctx.volume_integrate_color(C.walk_pose(n))
+    assert tuple(ctx.volume_geometry()["total_shift"]) == C.WALK_TOTAL and ctx.volume_archive_info()["held"] == C.WALK_HELD
+    for k in range(len(C.WALK_BACK)):
+        p = C.walk_eval_pose(k)
+        d, rgb = C.walk_frame(p, 50 + k)
+        ctx.frame_set_depth(d, C.WALK_CAM, 1.0, *VC.RANGE, levels=C.LEVELS)
+        ctx.frame_set_color(rgb)
+        rw = int(ctx.sdf_photo_normal_eq(p, 0, C.WALK_GATES[0], C.WEIGHT)[28])
+        rm = int(ctx.map_sdf_photo_normal_eq(p, 0, C.WALK_GATES[0], C.WEIGHT)[28])
+        assert rm == int((~np.isnan(ctx.map_sdf_photo_rows(p, 0, C.WALK_GATES[0])[0])).sum())
+        q = ctx.icp_pyramid_map_sdf_rgbd(C.walk_start(k), C.WEIGHT, C.WALK_ITERS, C.WALK_GATES, 0.0, C.COS_THR)
+        e = VC.pose_error(q[0], p)
+        eg = VC.pose_error(ctx.icp_pyramid_map_sdf(C.walk_start(k), C.WALK_ITERS, C.WALK_GATES, 0.0, C.COS_THR)[0], p)
+        ew = VC.pose_error(ctx.icp_pyramid_sdf_rgbd(C.walk_start(k), C.WEIGHT, C.WALK_ITERS, C.WALK_GATES, 0.0, C.COS_THR)[0], p)
+        print("back", C.WALK_BACK[k], "rows window", rw, "map", rm, "ends: map with colour", e, "map geometry", eg, "window colour", ew)
+        assert abs(rw - C.ROWS_WINDOW[k]) <= 2 + 1e-4 * C.ROWS_WINDOW[k] and abs(rm - C.ROWS_MAP[k]) <= 2 + 1e-4 * C.ROWS_MAP[k] and rm > rw
+        lim = C.walk_limit(k)
+        assert e[0] <= lim[0] and e[1] <= lim[1], (e, lim)
+        assert e[1] <= 0.5 * min(eg[1], ew[1]), (e, eg, ew)
+        assert abs(q[6] - rm) <= 0.02 * rm and q[4] > 0                           # the loop ends near the true pose: its rows are those
+
+
+# ---------------------------------------------------------------------------------------------- 6. state
+def raw(ctx, name, pose, weight=C.WEIGHT, device_resident=0, max_iter=2, lo=None, hi=None):
+    p = np.array(pose, np.float64).copy()
+    o = L.RpeIcpOptions(L.RES_P2PLANE, max_iter, 0.0, 0.1, 0.8, 1, device_resident, 1)
+    lo64, hi64 = (None if b is None else np.ascontiguousarray(b, np.int64) for b in (lo, hi))       # (kept alive over the call)
+    lo, hi = (None if b is None else b.ctypes.data for b in (lo64, hi64))
+    if name == "icp":
+        return L.lib().rpe_icp_map_sdf_rgbd(ctx._h, C_.byref(o), weight, lo, hi, p.ctypes.data, None, None, None, None, None, None)
+    its, out = np.array([2, 2], np.int32), np.zeros(2, np.int32)
+    return L.lib().rpe_icp_pyramid_map_sdf_rgbd(ctx._h, C_.byref(o), weight, 2, its.ctypes.data, None, lo, hi, p.ctypes.data, out.ctypes.data,
+                                                None, None, None, None, None)
+
+
+def test_every_refusal_returns_its_code_before_anything_is_written(gpu_ctx_factory):
+    ctx, cam, pose = gpu_ctx_factory(), C.CAM_A, MSC.scene_pose()
+    calls = (lambda **kw: ctx.map_sdf_photo_rows(pose, **kw), lambda **kw: ctx.map_sdf_photo_normal_eq(pose, **kw),
+             lambda **kw: ctx.icp_map_sdf_rgbd(pose, **kw), lambda **kw: ctx.icp_pyramid_map_sdf_rgbd(pose, C.WEIGHT, (2, 2), **kw))
+    for call in calls:
+        raises(L.RPE_ERR_STATE, call)                                        # nothing there
+    m = C.scene_map(ctx)
+    for call in calls:
+        raises(L.RPE_ERR_STATE, call)                                        # both volumes, no frame
+    ctx.frame_set_depth(MSC.scene_depth(cam), cam, 1.0, *C.RANGE, levels=2)
+    before = snapshot(ctx, m)
+    for call in calls:
+        raises(L.RPE_ERR_STATE, call)                                        # no frame colour
+    ctx.frame_set_color(C.frame_rgba(cam)[:, :3].reshape(cam[5], cam[4], 3).copy())
+    for call in calls:
+        call()
+    raises(L.RPE_ERR_STATE, ctx.map_sdf_photo_rows, pose, 2)                 # the frame has 2 levels
+    raises(L.RPE_ERR_STATE, ctx.map_sdf_photo_normal_eq, pose, 2)
+    raises(L.RPE_ERR_STATE, ctx.icp_pyramid_map_sdf_rgbd, pose, C.WEIGHT, (2, 2, 2))
+    for bad in (0.0, -0.01, float("nan"), float("inf")):                     # the weight
+        raises(L.RPE_ERR_ARG, ctx.map_sdf_photo_normal_eq, pose, 0, 0.1, bad)
+        raises(L.RPE_ERR_ARG, ctx.icp_map_sdf_rgbd, pose, bad)
+        raises(L.RPE_ERR_ARG, ctx.icp_pyramid_map_sdf_rgbd, pose, bad, (2, 2))
+    lo, hi = ctx.volume_map_bounds()
+    bad_boxes = [(lo + [4, 0, 0], hi), (lo, hi - [0, 1, 0]), (lo, lo), (hi, lo), (lo, lo + [8, 8, (1 << 20) + 8]),
+                 (lo, lo + [1 << 20, 1 << 20, 8])]                            # the last: 2^34 bricks for a grid of 2^24
+    for box in bad_boxes:
+        for call in calls:
+            raises(L.RPE_ERR_ARG, call, box=box)
+    with pytest.raises(L.RpeError) as e:
+        ctx.map_sdf_photo_rows(pose, box=bad_boxes[-1])
+    assert "17179869184 bricks" in str(e.value)
+    p, lo64 = np.array(pose, np.float64), np.ascontiguousarray(lo, np.int64)
+    out = np.zeros(7 * 1200, np.float32)
+    lib = L.lib()
+    assert lib.rpe_map_sdf_photo_rows(ctx._h, 0, p.ctypes.data, 0.1, lo64.ctypes.data, None, out.ctypes.data) == L.RPE_ERR_ARG     # lo without hi
+    assert lib.rpe_map_sdf_photo_normal_eq(ctx._h, 0, p.ctypes.data, 0.1, C.WEIGHT, None, lo64.ctypes.data, out.ctypes.data) == L.RPE_ERR_ARG
+    for name in ("icp", "pyramid"):
+        assert raw(ctx, name, pose, lo=lo) == L.RPE_ERR_ARG and raw(ctx, name, pose, hi=hi) == L.RPE_ERR_ARG
+        assert raw(ctx, name, pose, device_resident=1) == L.RPE_ERR_ARG
+        assert raw(ctx, name, pose) == L.RPE_OK
+    assert raw(ctx, "icp", pose, max_iter=0) == L.RPE_ERR_ARG
+    raises(L.RPE_ERR_ARG, ctx.map_sdf_photo_rows, pose, 0, float("nan"))
+    raises(L.RPE_ERR_ARG, ctx.map_sdf_photo_rows, pose, -1)
+    raises(L.RPE_ERR_ARG, ctx.icp_pyramid_map_sdf_rgbd, pose, C.WEIGHT, (0, 2))
+    assert unchanged(before, snapshot(ctx, m))
+    # a volume without a colour volume; dims or a total shift that are no multiples of 8
+    ctx.volume_init((24, 24, 24), **MC.KW)
+    for call in calls:
+        raises(L.RPE_ERR_STATE, call)
+    for dims, shift in (((20, 16, 8), None), ((16, 16, 8), (4, 0, 0))):
+        ctx.volume_init(dims, **MC.KW)
+        ctx.volume_color_upload(np.zeros((dims[2], dims[1], dims[0], 4), np.float16))
+        if shift:
+            ctx.volume_shift(shift)
+        for call in calls:
+            raises(L.RPE_ERR_STATE, call)
+    ctx.volume_shift((4, 0, 0))
+    # an empty map: no rows, and the loop's answer for a round without a solution
+    assert ctx.map_sdf_photo_normal_eq(pose)[28] == 0 and np.isnan(ctx.map_sdf_photo_rows(pose)).all()
+    raises(L.RPE_ERR_DEGENERATE, ctx.icp_map_sdf_rgbd, pose)
+
+
+def test_nothing_else_is_touched(gpu_ctx_factory):
+    """after each of the four calls: the model maps, the model colour, the prepared photometric maps, the solver slots, the last mesh,
+    the volume's and the colour volume's bits, the geometry and the archive are what they were; a prepared photometric term survives"""
+    ctx, cam, pose = gpu_ctx_factory(), C.CAM_A, MSC.scene_pose()
+    m = C.scene_map(ctx)
+    rgb = np.random.default_rng(4).integers(0, 256, (cam[5], cam[4], 3)).astype(np.uint8)
+    ctx.frame_set_depth(MSC.scene_depth(cam), cam, 1.0, *C.RANGE, levels=C.LEVELS)
+    ctx.frame_set_color(rgb)
+    ctx.model_from_frame(pose)
+    ctx.model_color_from_frame()
+    ctx.photo_prepare(C.LEVELS)
+    pairs = ctx.associate(pose, 0.1, 0.8, True)
+    V, N, T = ctx.volume_map_mesh(1.0)
+    colours = ctx.volume_mesh_colors()
+    photo_rows = ctx.photo_rows(pose, 2)
+
+    def state():
+        maps = [ctx.frame_download(w, l) for w in (L.MAP_MODEL_VERTEX, L.MAP_MODEL_NORMAL) for l in range(C.LEVELS)]
+        photo = [ctx.photo_download(w, l) for w in (L.PHOTO_FRAME, L.PHOTO_MODEL) for l in range(C.LEVELS)]
+        slots = [ctx.download(k) for k in (L.XW, L.XC, L.NC)]
+        V2, N2, T2 = (np.empty_like(a) for a in (V, N, T))
+        assert L.lib().rpe_volume_mesh_download(ctx._h, V2.ctypes.data, N2.ctypes.data, T2.ctypes.data) == L.RPE_OK      # the last mesh is valid
+        return maps + photo + slots + [V2, N2, ctx.model_color_map().astype(np.float32), ctx.volume_mesh_colors().astype(np.float32),
+                                       T2.astype(np.float32)], snapshot(ctx, m)
+    before = state()
+    assert pairs > 300 and len(T) > 500 and len(colours) == len(V)
+    calls = (lambda: ctx.map_sdf_photo_rows(pose, 1), lambda: ctx.map_sdf_photo_normal_eq(pose, 2), lambda: ctx.icp_map_sdf_rgbd(MSC.scene_start(), C.WEIGHT, 3),
+             lambda: ctx.icp_pyramid_map_sdf_rgbd(MSC.scene_start(), C.WEIGHT, (2, 2, 2), use_normals=False),
+             lambda: ctx.map_sdf_photo_rows(pose, 0, box=MSC.grown(m)))
+    for n, call in enumerate(calls):
+        call()
+        after = state()
+        assert all(same(x, y) for x, y in zip(before[0], after[0])) and unchanged(before[1], after[1]), n
+    assert ctx.associate(pose, 0.1, 0.8, True) == pairs and same(ctx.photo_rows(pose, 2), photo_rows)
+
+
+# ---------------------------------------------------------------------------------------------- 7. the C++ front end
+def test_volume_map_sdf_color_track_cpp_runs(tmp_path):
+    """DepthFrontEnd::icpMapColor / icpPyramidMapColor / mapColorResiduals from plain C++ (tests/cpp/volume_map_sdf_color_track.cpp)"""
+    from rgbd_pose_estimation_amd import build
+    lib = build.build()
+    exe = str(tmp_path / "volume_map_sdf_color_track")
+    inc = os.path.join(ROOT, "rgbd_pose_estimation_amd", "include")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wno-unused-function", "-I", os.path.join(inc, "pose"), "-I", inc,
+                           os.path.join(ROOT, "tests", "cpp", "volume_map_sdf_color_track.cpp"), "-L", os.path.dirname(lib), "-lrgbdpose_hip",
+                           "-Wl,-rpath," + os.path.dirname(lib), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, RPE_QUIET="1"))
+    print(r.stdout)
+    assert r.returncode == 0 and "volume_map_sdf_color_track: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
