@@ -613,10 +613,7 @@ class Context:
 
     def photo_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, weight: float = 0.01) -> np.ndarray:
         """The photometric normal equations alone: H upper triangle (21) | g (6) | cost | pairs | pivot floor | pad, 32 float64."""
-        p = np.array(pose12, np.float64).reshape(12)
-        out = np.zeros(32, np.float64)
-        L.check(L.lib().rpe_photo_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(weight), _p(out)))
-        return out
+        return self._level_call("rpe_photo_normal_eq", False, pose12, level, float(dist_thr), float(weight))
 
     def photo_rows(self, pose12, level: int = 0, dist_thr: float = 0.1) -> np.ndarray:
         """(7, pixels) float32: the unscaled residual (row 0: the residual image) and Jacobian row of every frame pixel of the level,
@@ -630,93 +627,34 @@ class Context:
     def icp_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9):
         """icp with the photometric term (weight in metres per intensity level) beside point-to-plane, one launch per round; returns
         (pose12, iterations, last |delta|, geometric cost, geometric pairs, photometric cost, photometric pairs) of the last round."""
-        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, 1, 0, 1)
-        pc, pm = C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_rgbd(self._h, C.byref(o), float(weight), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m),
-                                     C.byref(pc), C.byref(pm)))
+        out = self._loop("rpe_icp_rgbd", pose12, max_iter, tol, dist_thr, cos_thr, 1, weight)
         self.n, self.dtype = self._pixels, L.F32
-        return p, it.value, step.value, cost.value, m.value, pc.value, pm.value
+        return out
 
     def icp_pyramid_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9):
         """icp_pyramid with the photometric term; returns (pose12, rounds per level, last |delta|, geometric cost, geometric pairs,
         photometric cost, photometric pairs), the last five of level 0."""
-        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, 1, 0, 1)
-        pc, pm = C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_pyramid_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step),
-                                             C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
+        out = self._pyramid_loop("rpe_icp_pyramid_rgbd", pose12, iters, dist_thr, tol, cos_thr, 1, weight)
         self.n, self.dtype = self._pixels, L.F32
-        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
-
-    # ---- volume term (Part 3): a frame tracked against the TSDF volume itself -- no raycast, no model
-    def sdf_rows(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True) -> np.ndarray:
-        """(7, pixels) float32: the residual in metres (row 0: the residual image) and Jacobian row of every frame pixel of the level in
-        the volume's field under pose12, NaN where the pixel has no row."""
-        p = np.array(pose12, np.float64).reshape(12)
-        h, w = getattr(self, "_frame_hw", (0, 0))      # (the library checks the level: a level's size is the frame's halved per level)
-        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
-        L.check(L.lib().rpe_sdf_rows(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(out)))
         return out
 
-    def sdf_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True) -> np.ndarray:
-        """The volume term's normal equations of one level: H upper triangle (21) | g (6) | sum r^2 | rows | pivot floor | pad, 32 float64."""
-        p = np.array(pose12, np.float64).reshape(12)
-        out = np.zeros(32, np.float64)
-        L.check(L.lib().rpe_sdf_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(out)))
+    # ---- what the calls of the volume terms (and the RGB-D loops above) share, each stated once
+    def _level_call(self, name, rows, pose12, level, *scalars, box=()):
+        """The rows call (rows: a (7, pixels) float32 buffer sized for the level) or the normal-equations call (a record of 32 float64)
+        `name` of the library: level, pose, the call's own scalars, a map call's box (what _box made of it), the buffer, which it returns."""
+        if rows:    # a level's size is the frame's halved per level (no frame yet, no such level: the library says so)
+            h, w = self._frame_hw or (0, 0)
+            out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
+        else:
+            out = np.zeros(32, np.float64)
+        L.check(getattr(L.lib(), name)(self._h, int(level), _p(np.array(pose12, np.float64).reshape(12)), *scalars, *map(_p, box), _p(out)))
         return out
 
-    def icp_sdf(self, pose12, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True):
-        """Gauss-Newton on the volume term, one launch per round; needs a frame and a volume, no model.  Returns (pose12, iterations,
-        last |delta|, sum r^2, rows of the last round)."""
-        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
-        L.check(L.lib().rpe_icp_sdf(self._h, C.byref(o), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m)))
-        return p, it.value, step.value, cost.value, m.value
+    @staticmethod
+    def _colour(weight):
+        """what a loop with colour adds to its call: the photometric weight in front, the words its cost and rows come back in behind"""
+        return ((), ()) if weight is None else ((float(weight),), (C.c_double(0), C.c_int64(0)))
 
-    def icp_pyramid_sdf(self, pose12, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9, use_normals: bool = True):
-        """icp_sdf coarse to fine over len(iters) levels of the frame; dist_thr as icp_pyramid's.  Returns (pose12, rounds per level,
-        last |delta|, sum r^2, rows of the last round), the last three of level 0."""
-        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
-        L.check(L.lib().rpe_icp_pyramid_sdf(self._h, C.byref(o), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step), C.byref(cost), C.byref(m)))
-        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
-
-    # ---- volume colour term (Part 3): a photometric term against the colour volume beside the volume term -- no model, no photo_prepare
-    def sdf_photo_rows(self, pose12, level: int = 0, dist_thr: float = 0.1) -> np.ndarray:
-        """(7, pixels) float32: the unscaled photometric residual in intensity levels (row 0: the residual image) and Jacobian row of
-        every frame pixel of the level against the colour volume under pose12, NaN where the pixel has no row."""
-        p = np.array(pose12, np.float64).reshape(12)
-        h, w = getattr(self, "_frame_hw", None) or (0, 0)      # (no frame yet: the library says so; it checks the level too)
-        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
-        L.check(L.lib().rpe_sdf_photo_rows(self._h, int(level), _p(p), float(dist_thr), _p(out)))
-        return out
-
-    def sdf_photo_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, weight: float = 0.01) -> np.ndarray:
-        """The volume colour term's normal equations alone: H upper triangle (21) | g (6) | cost | rows | pivot floor | pad, 32 float64."""
-        p = np.array(pose12, np.float64).reshape(12)
-        out = np.zeros(32, np.float64)
-        L.check(L.lib().rpe_sdf_photo_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(weight), _p(out)))
-        return out
-
-    def icp_sdf_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9,
-                     use_normals: bool = True):
-        """icp_sdf with the photometric rows against the colour volume (weight in metres per intensity level) beside the geometric ones,
-        one launch per round; needs a frame with colour, a volume and a colour volume.  Returns (pose12, iterations, last |delta|,
-        geometric sum r^2, geometric rows, photometric cost, photometric rows) of the last round."""
-        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
-        pc, pm = C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_sdf_rgbd(self._h, C.byref(o), float(weight), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m),
-                                         C.byref(pc), C.byref(pm)))
-        return p, it.value, step.value, cost.value, m.value, pc.value, pm.value
-
-    def icp_pyramid_sdf_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9,
-                             use_normals: bool = True):
-        """icp_sdf_rgbd coarse to fine over len(iters) levels of the frame; dist_thr as icp_pyramid's.  Returns (pose12, rounds per level,
-        last |delta|, geometric sum r^2, geometric rows, photometric cost, photometric rows), the last five of level 0."""
-        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
-        pc, pm = C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_pyramid_sdf_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), _p(thr), _p(p), _p(it_out), C.byref(step),
-                                                 C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
-        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
-
-    # ---- map volume term (Part 3): the volume term on the whole map -- the window plus the archived bricks -- inside a box
     @staticmethod
     def _box(box):
         """(lo, hi) of a box of world voxels as the library takes them: two int64 triples, or two NULLs for the map's bounds"""
@@ -724,82 +662,108 @@ class Context:
             return None, None
         return tuple(np.ascontiguousarray(b, np.int64).reshape(3) for b in box)
 
+    def _loop(self, name, pose12, max_iter, tol, dist_thr, cos_thr, use_normals, weight=None, box=()):
+        """The single-level loop `name` of the library.  weight: the photometric weight of a loop with colour (None: a loop without,
+        which returns no photometric figures); box: what _box made of a map call's box (() for a call on the window)."""
+        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
+        lam, photo = self._colour(weight)
+        L.check(getattr(L.lib(), name)(self._h, C.byref(o), *lam, *map(_p, box), _p(p), *map(C.byref, (it, step, cost, m) + photo)))
+        return (p, it.value, step.value, cost.value, m.value) + tuple(w.value for w in photo)
+
+    def _pyramid_loop(self, name, pose12, iters, dist_thr, tol, cos_thr, use_normals, weight=None, box=()):
+        """The coarse-to-fine loop `name` of the library; weight and box as _loop's."""
+        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
+        lam, photo = self._colour(weight)
+        L.check(getattr(L.lib(), name)(self._h, C.byref(o), *lam, levels, _p(it_in), _p(thr), *map(_p, box), _p(p), _p(it_out),
+                                       *map(C.byref, (step, cost, m) + photo)))
+        return (p, tuple(int(i) for i in it_out), step.value, cost.value, m.value) + tuple(w.value for w in photo)
+
+    # ---- volume term (Part 3): a frame tracked against the TSDF volume itself -- no raycast, no model
+    def sdf_rows(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True) -> np.ndarray:
+        """(7, pixels) float32: the residual in metres (row 0: the residual image) and Jacobian row of every frame pixel of the level in
+        the volume's field under pose12, NaN where the pixel has no row."""
+        return self._level_call("rpe_sdf_rows", True, pose12, level, float(dist_thr), float(cos_thr), int(use_normals))
+
+    def sdf_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True) -> np.ndarray:
+        """The volume term's normal equations of one level: H upper triangle (21) | g (6) | sum r^2 | rows | pivot floor | pad, 32 float64."""
+        return self._level_call("rpe_sdf_normal_eq", False, pose12, level, float(dist_thr), float(cos_thr), int(use_normals))
+
+    def icp_sdf(self, pose12, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True):
+        """Gauss-Newton on the volume term, one launch per round; needs a frame and a volume, no model.  Returns (pose12, iterations,
+        last |delta|, sum r^2, rows of the last round)."""
+        return self._loop("rpe_icp_sdf", pose12, max_iter, tol, dist_thr, cos_thr, use_normals)
+
+    def icp_pyramid_sdf(self, pose12, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9, use_normals: bool = True):
+        """icp_sdf coarse to fine over len(iters) levels of the frame; dist_thr as icp_pyramid's.  Returns (pose12, rounds per level,
+        last |delta|, sum r^2, rows of the last round), the last three of level 0."""
+        return self._pyramid_loop("rpe_icp_pyramid_sdf", pose12, iters, dist_thr, tol, cos_thr, use_normals)
+
+    # ---- volume colour term (Part 3): a photometric term against the colour volume beside the volume term -- no model, no photo_prepare
+    def sdf_photo_rows(self, pose12, level: int = 0, dist_thr: float = 0.1) -> np.ndarray:
+        """(7, pixels) float32: the unscaled photometric residual in intensity levels (row 0: the residual image) and Jacobian row of
+        every frame pixel of the level against the colour volume under pose12, NaN where the pixel has no row."""
+        return self._level_call("rpe_sdf_photo_rows", True, pose12, level, float(dist_thr))
+
+    def sdf_photo_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, weight: float = 0.01) -> np.ndarray:
+        """The volume colour term's normal equations alone: H upper triangle (21) | g (6) | cost | rows | pivot floor | pad, 32 float64."""
+        return self._level_call("rpe_sdf_photo_normal_eq", False, pose12, level, float(dist_thr), float(weight))
+
+    def icp_sdf_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9,
+                     use_normals: bool = True):
+        """icp_sdf with the photometric rows against the colour volume (weight in metres per intensity level) beside the geometric ones,
+        one launch per round; needs a frame with colour, a volume and a colour volume.  Returns (pose12, iterations, last |delta|,
+        geometric sum r^2, geometric rows, photometric cost, photometric rows) of the last round."""
+        return self._loop("rpe_icp_sdf_rgbd", pose12, max_iter, tol, dist_thr, cos_thr, use_normals, weight)
+
+    def icp_pyramid_sdf_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9,
+                             use_normals: bool = True):
+        """icp_sdf_rgbd coarse to fine over len(iters) levels of the frame; dist_thr as icp_pyramid's.  Returns (pose12, rounds per level,
+        last |delta|, geometric sum r^2, geometric rows, photometric cost, photometric rows), the last five of level 0."""
+        return self._pyramid_loop("rpe_icp_pyramid_sdf_rgbd", pose12, iters, dist_thr, tol, cos_thr, use_normals, weight)
+
+    # ---- map volume term (Part 3): the volume term on the whole map -- the window plus the archived bricks -- inside a box
     def map_sdf_rows(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True, box=None) -> np.ndarray:
         """sdf_rows in the field of the MAP inside box = (lo, hi) in world voxels (multiples of 8; None: volume_map_bounds): bit for bit
         sdf_rows of a dense volume of the box holding the map's content (rpe_map_sdf_rows)."""
-        p = np.array(pose12, np.float64).reshape(12)
-        lo, hi = self._box(box)
-        h, w = getattr(self, "_frame_hw", (0, 0))
-        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
-        L.check(L.lib().rpe_map_sdf_rows(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(lo), _p(hi), _p(out)))
-        return out
+        return self._level_call("rpe_map_sdf_rows", True, pose12, level, float(dist_thr), float(cos_thr), int(use_normals), box=self._box(box))
 
     def map_sdf_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True, box=None) -> np.ndarray:
         """sdf_normal_eq on the map inside the box: the same 32 float64."""
-        p = np.array(pose12, np.float64).reshape(12)
-        lo, hi = self._box(box)
-        out = np.zeros(32, np.float64)
-        L.check(L.lib().rpe_map_sdf_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(cos_thr), int(use_normals), _p(lo), _p(hi), _p(out)))
-        return out
+        return self._level_call("rpe_map_sdf_normal_eq", False, pose12, level, float(dist_thr), float(cos_thr), int(use_normals),
+                                box=self._box(box))
 
     def icp_map_sdf(self, pose12, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True,
                     box=None):
         """icp_sdf on the map inside the box; the brick grid is built and uploaded once for all rounds.  Returns what icp_sdf returns."""
-        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
-        lo, hi = self._box(box)
-        L.check(L.lib().rpe_icp_map_sdf(self._h, C.byref(o), _p(lo), _p(hi), _p(p), C.byref(it), C.byref(step), C.byref(cost), C.byref(m)))
-        return p, it.value, step.value, cost.value, m.value
+        return self._loop("rpe_icp_map_sdf", pose12, max_iter, tol, dist_thr, cos_thr, use_normals, box=self._box(box))
 
     def icp_pyramid_map_sdf(self, pose12, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9, use_normals: bool = True,
                             box=None):
         """icp_pyramid_sdf on the map inside the box: the tracker of a moving window with the archive on (volume_follow -> volume_shift ->
         icp_pyramid_map_sdf -> volume_integrate).  Returns what icp_pyramid_sdf returns."""
-        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
-        lo, hi = self._box(box)
-        L.check(L.lib().rpe_icp_pyramid_map_sdf(self._h, C.byref(o), levels, _p(it_in), _p(thr), _p(lo), _p(hi), _p(p), _p(it_out), C.byref(step),
-                                                C.byref(cost), C.byref(m)))
-        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value
+        return self._pyramid_loop("rpe_icp_pyramid_map_sdf", pose12, iters, dist_thr, tol, cos_thr, use_normals, box=self._box(box))
 
     # ---- map volume colour term (Part 3): the volume colour term on the whole map -- TSDF and colour of the window plus the archived bricks
     def map_sdf_photo_rows(self, pose12, level: int = 0, dist_thr: float = 0.1, box=None) -> np.ndarray:
         """sdf_photo_rows against the MAP inside box = (lo, hi) in world voxels (multiples of 8; None: volume_map_bounds): bit for bit
         sdf_photo_rows of a dense volume and colour volume of the box holding the map's content (rpe_map_sdf_photo_rows)."""
-        p = np.array(pose12, np.float64).reshape(12)
-        lo, hi = self._box(box)
-        h, w = getattr(self, "_frame_hw", None) or (0, 0)
-        out = np.empty((7, max(1, (h >> max(level, 0)) * (w >> max(level, 0)))), np.float32)
-        L.check(L.lib().rpe_map_sdf_photo_rows(self._h, int(level), _p(p), float(dist_thr), _p(lo), _p(hi), _p(out)))
-        return out
+        return self._level_call("rpe_map_sdf_photo_rows", True, pose12, level, float(dist_thr), box=self._box(box))
 
     def map_sdf_photo_normal_eq(self, pose12, level: int = 0, dist_thr: float = 0.1, weight: float = 0.01, box=None) -> np.ndarray:
         """sdf_photo_normal_eq on the map inside the box: the same 32 float64."""
-        p = np.array(pose12, np.float64).reshape(12)
-        lo, hi = self._box(box)
-        out = np.zeros(32, np.float64)
-        L.check(L.lib().rpe_map_sdf_photo_normal_eq(self._h, int(level), _p(p), float(dist_thr), float(weight), _p(lo), _p(hi), _p(out)))
-        return out
+        return self._level_call("rpe_map_sdf_photo_normal_eq", False, pose12, level, float(dist_thr), float(weight), box=self._box(box))
 
     def icp_map_sdf_rgbd(self, pose12, weight: float = 0.01, max_iter: int = 10, tol: float = 1e-6, dist_thr: float = 0.1, cos_thr: float = 0.9,
                          use_normals: bool = True, box=None):
         """icp_sdf_rgbd on the map inside the box; the brick grid is built and uploaded once for both fetches and all rounds.  Returns
         what icp_sdf_rgbd returns."""
-        p, o, it, step, cost, m = self._icp_args(pose12, L.RES_P2PLANE, max_iter, tol, dist_thr, cos_thr, use_normals, 0, 1)
-        lo, hi = self._box(box)
-        pc, pm = C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_map_sdf_rgbd(self._h, C.byref(o), float(weight), _p(lo), _p(hi), _p(p), C.byref(it), C.byref(step), C.byref(cost),
-                                             C.byref(m), C.byref(pc), C.byref(pm)))
-        return p, it.value, step.value, cost.value, m.value, pc.value, pm.value
+        return self._loop("rpe_icp_map_sdf_rgbd", pose12, max_iter, tol, dist_thr, cos_thr, use_normals, weight, self._box(box))
 
     def icp_pyramid_map_sdf_rgbd(self, pose12, weight: float = 0.01, iters=(10, 5, 4), dist_thr=None, tol: float = 1e-6, cos_thr: float = 0.9,
                                  use_normals: bool = True, box=None):
         """icp_pyramid_sdf_rgbd on the map inside the box: the colour tracker of a moving window with the archive on (volume_follow ->
         volume_shift -> icp_pyramid_map_sdf_rgbd -> volume_integrate_color).  Returns what icp_pyramid_sdf_rgbd returns."""
-        p, levels, it_in, thr, o, it_out, step, cost, m = self._pyramid_args(pose12, iters, dist_thr, L.RES_P2PLANE, tol, cos_thr, use_normals, 0, 1)
-        lo, hi = self._box(box)
-        pc, pm = C.c_double(0), C.c_int64(0)
-        L.check(L.lib().rpe_icp_pyramid_map_sdf_rgbd(self._h, C.byref(o), float(weight), levels, _p(it_in), _p(thr), _p(lo), _p(hi), _p(p),
-                                                     _p(it_out), C.byref(step), C.byref(cost), C.byref(m), C.byref(pc), C.byref(pm)))
-        return p, tuple(int(i) for i in it_out), step.value, cost.value, m.value, pc.value, pm.value
+        return self._pyramid_loop("rpe_icp_pyramid_map_sdf_rgbd", pose12, iters, dist_thr, tol, cos_thr, use_normals, weight, self._box(box))
 
     # ---- features and relocalisation (Part 3): correspondences without a pose guess
     def features_detect(self, which: int = L.FEAT_FRAME, threshold: int = 12, max_keypoints: int = L.MAX_KEYPOINTS) -> int:

@@ -5,7 +5,7 @@ kind and what it holds.  Kernel units share device code in csrc/rpe_reduce.hpp a
 bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_sdf_rule.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp; each names one of its kernels
 with RPE_PRELOAD (csrc/rpe_kernels.h), through which rpe_create loads its code object.  Host units are the C-ABI side behind
 include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp lists them; csrc/rpe_devbuf.hpp owns their device memory,
-csrc/rpe_gn_host.hpp holds the Gauss-Newton step, round loop and coarse-to-fine walk of their host loops,
+csrc/rpe_gn_host.hpp holds the Gauss-Newton step, round loop, level driver and coarse-to-fine walk of their host loops,
 csrc/rpe_frontend_host.hpp what the Part 3 units share).  What each unit must satisfy is the gate table of tests/unit_gates.py.
 
 {units}
@@ -62,9 +62,8 @@ UNITS = [
     ("rpe_mesh_api.hip", "host", "Part 3: mesh extraction"),
     ("rpe_color_api.hip", "host", "Part 3: colour of frame, volume, model and mesh"),
     ("rpe_photo_api.hip", "host", "Part 3: photometric term beside ICP"),
-    ("rpe_sdf_api.hip", "host", "Part 3: the volume term, a frame tracked against the TSDF volume itself or against the whole map's"),
-    ("rpe_sdf_photo_api.hip", "host", "Part 3: the volume colour term, a photometric term against the colour volume beside the volume term, on the window or "
-                                      "on the whole map's two volumes"),
+    ("rpe_sdf_api.hip", "host", "Part 3: the volume term, a frame tracked against the TSDF volume itself, and the volume colour term, a photometric term "
+                                "against the colour volume beside it; each on the window or on the whole map's volumes"),
     ("rpe_feature_api.hip", "host", "Part 3: features and relocalisation"),
     ("rpe_keyframe_api.hip", "host", "Part 3: keyframes"),
     ("rpe_graph_api.hip", "host", "Part 3: the keyframe graph"),

@@ -628,6 +628,22 @@ __device__ __forceinline__ Finish late_finish_at(unsigned off) {
   return f;
 }
 __device__ __forceinline__ Finish late_finish() { return late_finish_at((unsigned)offsetof(SdfRoundArgs, fin)); }
+// The pose read from the kernarg segment with scalar loads (the segment is constant memory), where a loop trip needs it: for the round
+// kernels with one pixel per trip (late_pose, photo_late_pose, map_photo_late_pose name their offsets).  As a plain argument its twelve
+// scalars are live through the whole loop beside everything else the trip keeps in scalar registers, which is more than the 102 there
+// are.  The offset goes through an empty asm, as late_finish_at's does, so that the loads stay where they are written and the reads of
+// one trip are not merged
+__device__ __forceinline__ PoseF late_pose_at(unsigned off) {
+  typedef const __attribute__((address_space(4))) float* KernargFloats;
+  asm volatile("" : "+s"(off));
+  KernargFloats p = (KernargFloats)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+  PoseF T;
+#pragma unroll
+  for (int k = 0; k < 9; k++) T.R[k] = p[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) T.t[k] = p[9 + k];
+  return T;
+}
 
 // four waves per SIMD's worth of registers: 128
 template <int BLK>
@@ -665,6 +681,13 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(4))) void i
   reduce_and_finish<29, kNeLd, 0, BLK, false>(sums, late_finish());   // host-driven only: no device-side solve in this kernel
 }
 
+// the tail of the four rows kernels: {r, J[0..5]} of pixel i into the seven planes of rows, NaN where the pixel has no row
+__device__ __forceinline__ void store_row(float* __restrict__ rows, int64_t n, int64_t i, bool ok, float r, const float (&J)[6]) {
+  rows[i] = ok ? r : qnan();
+#pragma unroll
+  for (int k = 0; k < 6; k++) rows[(int64_t)(k + 1) * n + i] = ok ? J[k] : qnan();
+}
+
 __global__ __launch_bounds__(kSdfRowsBlock) void sdf_rows_kernel(const float* __restrict__ vmap, const float* __restrict__ nmap, int64_t n,
                                                                  const float* __restrict__ vol, VolumeGeometry G, SdfParams Q, PoseF T,
                                                                  float* __restrict__ rows) {
@@ -673,9 +696,7 @@ __global__ __launch_bounds__(kSdfRowsBlock) void sdf_rows_kernel(const float* __
   float r, J[6], nx = 0.f, ny = 0.f, nz = 0.f;
   if (Q.use_normals) { nx = nmap[3 * i]; ny = nmap[3 * i + 1]; nz = nmap[3 * i + 2]; }
   const bool ok = sdf_pixel(dense_corners(vol, G), G, T, Q, vmap[3 * i], vmap[3 * i + 1], vmap[3 * i + 2], nx, ny, nz, r, J);
-  rows[i] = ok ? r : qnan();
-#pragma unroll
-  for (int k = 0; k < 6; k++) rows[(int64_t)(k + 1) * n + i] = ok ? J[k] : qnan();
+  store_row(rows, n, i, ok, r, J);
 }
 
 SdfParams sdf_params(const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals) {
@@ -683,11 +704,12 @@ SdfParams sdf_params(const VolumeGeometry& G, float dist_thr, float cos_thr, int
   Q.gate = dist_thr; Q.c = cos_thr; Q.k = G.tr / G.s; Q.use_normals = use_normals;
   return Q;
 }
-PoseF sdf_pose(const double* p12) {
-  PoseF T;
-  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
-  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
-  return T;
+// the grid of a round launch of blk threads a workgroup: one item per thread while rt.max_blocks allows it, at least one workgroup
+// (an item: a group of 4 pixels for icp_sdf_kernel, a pixel for the round kernels with one pixel per trip)
+int round_grid(const ReduceTarget& rt, int64_t items, int blk) {
+  const int64_t full = (items + blk - 1) / blk;
+  const int grid = (int64_t)rt.max_blocks > full ? (int)full : rt.max_blocks;
+  return grid < 1 ? 1 : grid;
 }
 
 }  // namespace
@@ -695,14 +717,11 @@ PoseF sdf_pose(const double* p12) {
 hipError_t launch_icp_sdf(const float* vmap, const float* nmap, int64_t n, const float* vol, const VolumeGeometry& G, float dist_thr,
                           float cos_thr, int use_normals, const double* pose12, const ReduceTarget& rt, hipStream_t s) {
   const SdfParams Q = sdf_params(G, dist_thr, cos_thr, use_normals);
-  const PoseF T = sdf_pose(pose12);
+  const PoseF T = pose_f(pose12);
   const Finish fin = make_finish(rt);
   // geometry as the fused ICP round's: one pixel group per thread while the grid allows it
   const int blk = pick_block(rt);
-  const int64_t groups = (n + 3) / 4;
-  int grid = rt.max_blocks;
-  if ((int64_t)grid > (groups + blk - 1) / blk) grid = (int)((groups + blk - 1) / blk);
-  if (grid < 1) grid = 1;
+  const int grid = round_grid(rt, (n + 3) / 4, blk);
   if (blk == 512) hipLaunchKernelGGL((icp_sdf_kernel<512>), dim3(grid), dim3(512), 0, s, vmap, nmap, n, vol, G, Q, T, fin);
   else hipLaunchKernelGGL((icp_sdf_kernel<256>), dim3(grid), dim3(256), 0, s, vmap, nmap, n, vol, G, Q, T, fin);
   return hipGetLastError();
@@ -712,7 +731,7 @@ hipError_t launch_sdf_rows(const float* vmap, const float* nmap, int64_t n, cons
                            float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s) {
   const int64_t blocks = (n + kSdfRowsBlock - 1) / kSdfRowsBlock;
   hipLaunchKernelGGL(sdf_rows_kernel, dim3((unsigned)blocks), dim3(kSdfRowsBlock), 0, s, vmap, nmap, n, vol, G,
-                     sdf_params(G, dist_thr, cos_thr, use_normals), sdf_pose(pose12), rows);
+                     sdf_params(G, dist_thr, cos_thr, use_normals), pose_f(pose12), rows);
   return hipGetLastError();
 }
 
@@ -767,22 +786,9 @@ struct MapSdfRoundArgs { const float* vmap; const float* nmap; int64_t n; MapSdf
 static_assert(offsetof(MapSdfRoundArgs, fin) == 192 && sizeof(Finish) == 136, "late_finish_at: where the kernarg segment holds the reduction's argument");
 static_assert(offsetof(MapSdfRoundArgs, T) == 140 && sizeof(PoseF) == 48, "late_pose: where the kernarg segment holds the pose");
 
-// The pose read from the kernarg segment with scalar loads (the segment is constant memory), where a loop trip needs it.  As a plain
-// argument its twelve scalars are live through the whole loop beside view, geometry, gates and the exec masks of the fetch's nested
-// branches, which is more than the 102 there are (4 - 7 scalar spills, however the rest is arranged).  The offset goes through an empty
-// asm, as late_finish's does, so that the loads stay where they are written and the two of a trip are not merged
-__device__ __forceinline__ PoseF late_pose() {
-  typedef const __attribute__((address_space(4))) float* KernargFloats;
-  unsigned off = (unsigned)offsetof(MapSdfRoundArgs, T);
-  asm volatile("" : "+s"(off));
-  KernargFloats p = (KernargFloats)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
-  PoseF T;
-#pragma unroll
-  for (int k = 0; k < 9; k++) T.R[k] = p[k];
-#pragma unroll
-  for (int k = 0; k < 3; k++) T.t[k] = p[9 + k];
-  return T;
-}
+// late_pose_at for this kernel: beside view, geometry, gates and the exec masks of the fetch's nested branches the pose as a plain
+// argument costs 4 - 7 scalar spills, however the rest is arranged
+__device__ __forceinline__ PoseF late_pose() { return late_pose_at((unsigned)offsetof(MapSdfRoundArgs, T)); }
 
 template <int BLK>
 __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(4))) void icp_map_sdf_kernel(
@@ -842,9 +848,7 @@ __global__ __launch_bounds__(kSdfRowsBlock) void map_sdf_rows_kernel(const float
   float r, J[6], nx = 0.f, ny = 0.f, nz = 0.f;
   if (Q.use_normals) { nx = nmap[3 * i]; ny = nmap[3 * i + 1]; nz = nmap[3 * i + 2]; }
   const bool ok = sdf_pixel(map_sdf_corners{M}, G, T, Q, vmap[3 * i], vmap[3 * i + 1], vmap[3 * i + 2], nx, ny, nz, r, J);
-  rows[i] = ok ? r : qnan();
-#pragma unroll
-  for (int k = 0; k < 6; k++) rows[(int64_t)(k + 1) * n + i] = ok ? J[k] : qnan();
+  store_row(rows, n, i, ok, r, J);
 }
 
 MapSdfView sdf_view(const MapRayView& M) {
@@ -865,13 +869,11 @@ namespace round_node { RPE_PRELOAD(icp_map_sdf_kernel<256>); }
 hipError_t launch_icp_map_sdf(const float* vmap, const float* nmap, int64_t n, const MapRayView& M, const VolumeGeometry& G, float dist_thr,
                               float cos_thr, int use_normals, const double* pose12, const ReduceTarget& rt, hipStream_t s) {
   const SdfParams Q = sdf_params(G, dist_thr, cos_thr, use_normals);
-  const PoseF T = sdf_pose(pose12);
+  const PoseF T = pose_f(pose12);
   const Finish fin = make_finish(rt);
   const MapSdfView S = sdf_view(M);
   const int blk = pick_block(rt);   // one pixel per thread while the grid allows it
-  int grid = rt.max_blocks;
-  if ((int64_t)grid > (n + blk - 1) / blk) grid = (int)((n + blk - 1) / blk);
-  if (grid < 1) grid = 1;
+  const int grid = round_grid(rt, n, blk);
   if (blk == 512) hipLaunchKernelGGL((icp_map_sdf_kernel<512>), dim3(grid), dim3(512), 0, s, vmap, nmap, n, S, G, Q, T, fin);
   else hipLaunchKernelGGL((icp_map_sdf_kernel<256>), dim3(grid), dim3(256), 0, s, vmap, nmap, n, S, G, Q, T, fin);
   return hipGetLastError();
@@ -881,7 +883,7 @@ hipError_t launch_map_sdf_rows(const float* vmap, const float* nmap, int64_t n, 
                                float cos_thr, int use_normals, const double* pose12, float* rows, hipStream_t s) {
   const int64_t blocks = (n + kSdfRowsBlock - 1) / kSdfRowsBlock;
   hipLaunchKernelGGL(map_sdf_rows_kernel, dim3((unsigned)blocks), dim3(kSdfRowsBlock), 0, s, vmap, nmap, n, sdf_view(M), G,
-                     sdf_params(G, dist_thr, cos_thr, use_normals), sdf_pose(pose12), rows);
+                     sdf_params(G, dist_thr, cos_thr, use_normals), pose_f(pose12), rows);
   return hipGetLastError();
 }
 

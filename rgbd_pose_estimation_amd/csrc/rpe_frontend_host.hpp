@@ -15,12 +15,7 @@ inline int camera_of(const rpe_camera* cam, rpe::Camera* out) {
   out->width = cam->width; out->height = cam->height;
   return RPE_OK;
 }
-inline rpe::PoseF pose_f(const double* p12) {
-  rpe::PoseF T;
-  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
-  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
-  return T;
-}
+using rpe::pose_f;   // (rpe_kernels.h: the one pose cast, the launchers' too)
 // the solver slots a device-side producer writes (association, feature matches): the context's own storage, n columns, fp32
 // (rpe_frontend_api.hip)
 int claim_slots(rpe_context* c, int64_t n);
@@ -53,6 +48,27 @@ inline int pyramid_complaint(const char* who, int levels, const int* iters_per_l
     case kPyramidGate: return fail(RPE_ERR_ARG, "%s: bad distance gate at level %d", who, l);
     case kPyramidOk: break;
   }
+  return RPE_OK;
+}
+
+// ---- what the one-launch rounds and the rows calls of rpe_photo_api.hip and rpe_sdf_api.hip share
+// the round's record as wait_host left it in c->h_out: H | g | cost | weight into ne[0 .. 28], zeros behind
+inline void round_record(const rpe_context* c, double* ne) {
+  for (int i = 0; i < 32; i++) ne[i] = i < 29 ? c->h_out[i] : 0.0;
+}
+// the record of a photometric-only round as the ..._normal_eq calls return it: H | g of ne, the photometric cost and rows in the places
+// of the geometric ones, and the pivot floor for rpe_gn_solve (the rows' products are fp32)
+inline void photo_only_record(const double* ne, double pcost, double prows, double* out32) {
+  for (int i = 0; i < 32; i++) out32[i] = i < 27 ? ne[i] : 0.0;
+  out32[27] = pcost; out32[28] = prows;
+  out32[29] = rpe::pivot_floor(false);
+}
+// the tail of a rows call behind its launch (`launched`: what the launcher returned): the (7, n) rows down to the caller, one host wait
+inline int rows_download(rpe_context* c, const char* who, hipError_t launched, const float* d_rows, int64_t n, float* rows) {
+  hipError_t e = launched;
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, (size_t)n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(RPE_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   return RPE_OK;
 }
 
@@ -120,8 +136,8 @@ int map_box(const char* who, const rpe_context::Volume& V, const int64_t* lo, co
 // refuses a box of more than kMaxGrid bricks first
 constexpr int64_t kMaxGrid = (int64_t)1 << 24;
 void build_grid(const rpe_context::Volume& V, const int64_t b0[3], const int64_t nb[3], std::vector<unsigned char>& h, rpe::MapRayView& M);
-// the map's field inside the box (lo = NULL: the map's bounds), for the calls that track a frame against it (rpe_sdf_api.hip,
-// rpe_sdf_photo_api.hip): the state and box rules of rpe_volume_map_raycast, then the brick grid built and uploaded ONCE, for every fetch
+// the map's field inside the box (lo = NULL: the map's bounds), for the calls that track a frame against it (rpe_sdf_api.hip):
+// the state and box rules of rpe_volume_map_raycast, then the brick grid built and uploaded ONCE, for every fetch
 // and round of the call.  On success G is the virtual volume's geometry and M the view, both volumes and both planes of the pool
 // included (null where there is none).  Nothing but the volume's map list is written
 int map_field(rpe_context* c, const char* who, const int64_t* lo, const int64_t* hi, rpe::VolumeGeometry& G, rpe::MapRayView& M);

@@ -1,5 +1,6 @@
 // The host side of a Gauss-Newton solve, stated once for every loop of the library: the step (solve the 6x6 system, left-multiply the
-// pose by exp(delta), measure |delta|), the round loop around it, and the coarse-to-fine walk over pyramid levels.  Where a round's
+// pose by exp(delta), measure |delta|), the round loop around it, the driver of one level of the loops whose round is one launch, and
+// the coarse-to-fine walk over pyramid levels.  Where a round's
 // record comes from -- a launch and a host wait, a resident grid, the ranks' exchange -- is the caller's callable; so is every message.
 // This header includes no HIP header and no rpe_host.hpp: RPE_OK and RPE_MAX_LEVELS are the includer's (include/rgbd_pose_hip.h in the
 // library, two enumerators in tests/cpp/gn_host.cpp).
@@ -46,6 +47,40 @@ inline int gn_host_rounds(Round round, double rel_floor, double cost_scale, int 
     if (!gn_update(ne, rel_floor, pose12, &run->step)) return kGnRefused;
     if (run->step < tol) { run->it++; break; }
   }
+  return RPE_OK;
+}
+
+// ---- one level of a host-driven loop whose round is one launch (rpe_icp_rgbd, the volume term, the volume colour term and their
+// coarse-to-fine forms).  Where an entry point wants a level's figures, any of them null; cost2 / matched2 are the second term's, for a
+// round that carries one
+struct GnOut {
+  int* iters = nullptr; double* step = nullptr; double* cost = nullptr; int64_t* matched = nullptr;
+  double* cost2 = nullptr; int64_t* matched2 = nullptr;
+  // what a level of a coarse_to_fine walk reports: its rounds into `it`, everything else at the finest level only
+  GnOut at_level(bool fine, int* it) const {
+    GnOut o = fine ? *this : GnOut{};
+    o.iters = it;
+    return o;
+  }
+};
+// gn_host_rounds from round 0 over round(pose12, ne, second): second[0 .. 1] is the second term's cost and rows of the record, the
+// driver's own words, zero until a round writes them.  A refused system: out.iters = the refused round, nothing else is written, and
+// refused(round, weight, second term's rows) words the failure and gives the code.  A round's own non-zero code comes back with nothing
+// written.  Otherwise the figures of the last round run go into whichever outputs are there.
+template <class Round, class Refused>
+inline int gn_host_level(Round round, double rel_floor, int max_iter, double tol, double* pose12, const GnOut& out, Refused refused) {
+  GnRun run;
+  double second[2] = {0, 0};
+  const int rc = gn_host_rounds([&](const double* pose, double* ne) { return round(pose, ne, second); }, rel_floor, 1.0, max_iter, tol, pose12,
+                                &run);
+  if (rc == kGnRefused) {
+    if (out.iters) *out.iters = run.it;
+    return refused(run.it, run.weight, second[1]);
+  }
+  if (rc) return rc;
+  run.report(out.iters, out.step, out.cost, out.matched);
+  if (out.cost2) *out.cost2 = second[0];
+  if (out.matched2) *out.matched2 = (int64_t)second[1];
   return RPE_OK;
 }
 

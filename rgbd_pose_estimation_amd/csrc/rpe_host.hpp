@@ -11,10 +11,9 @@
 //   rpe_color_api.hip     Part 3: frame colour, the colour volume beside the TSDF, model and mesh colours
 //   rpe_register_api.hip  Part 3: colour registration (a separate colour camera reprojected onto the depth frame; kernels in rpe_register.hip)
 //   rpe_photo_api.hip     Part 3: photometric term beside ICP (model colour without a volume, photometric maps, RGB-D ICP)
-//   rpe_sdf_api.hip       Part 3: the volume term (a frame tracked against the TSDF volume itself, or against the whole map's through the
-//                         brick grid of rpe_mapmesh_api.hip; kernels in rpe_frontend.hip)
-//   rpe_sdf_photo_api.hip Part 3: the volume colour term (a photometric term against the colour volume beside the volume term,
-//                         on the window or on the whole map; kernels in rpe_sdf_photo.hpp and rpe_map_sdf_photo.hpp)
+//   rpe_sdf_api.hip       Part 3: the volume term (a frame tracked against the TSDF volume itself; kernels in rpe_frontend.hip) and the
+//                         volume colour term (a photometric term against the colour volume beside it; kernels in rpe_sdf_photo.hpp and
+//                         rpe_map_sdf_photo.hpp), each on the window or on the whole map through the brick grid of rpe_mapmesh_api.hip
 //   rpe_feature_api.hip   Part 3: features and relocalisation (keypoints, descriptors, matches into the solver slots, rpe_relocalize)
 //   rpe_keyframe_api.hip  Part 3: keyframes (the store of model-side features, the query over all of them, rpe_relocalize_keyframes)
 //   rpe_graph_api.hip     Part 3: the keyframe graph (edges of matches, the joint Gauss-Newton over all poses; state in rpe_graph.h)
@@ -29,8 +28,9 @@
 //                         brick of a box, window or archive; slots taken and released; kernel in rpe_mapfuse.hpp, compiled into rpe_frontend.hip)
 // Three headers beside this one: rpe_devbuf.hpp (rpeh::DevBuf<T>, the owner of every plain device allocation below: nothing else in the
 // host units calls hipMalloc / hipFree but rpe_dist.hip and the control-block probe of rpe_create), rpe_gn_host.hpp (the Gauss-Newton
-// step, round loop and coarse-to-fine walk of every host loop) and rpe_frontend_host.hpp (what the Part 3 units share: camera and pose
-// casts, the pyramid-level view, the solver slots, feature / match options, the relocalisers' common steps).
+// step, round loop, level driver and coarse-to-fine walk of every host loop) and rpe_frontend_host.hpp (what the Part 3 units share:
+// camera and pose casts, the pyramid-level view, the record and rows tails of the one-launch rounds, the solver slots, feature / match
+// options, the relocalisers' common steps).
 // Everything in namespace rpeh is internal to the library (hidden visibility).  There is NO CPU fallback anywhere behind this header.
 #pragma once
 #include "../../include/rgbd_pose_hip.h"
@@ -196,7 +196,7 @@ struct rpe_context {
     // (0 = not prepared: whatever replaces the frame's depth or colour, the model or the model colour resets it)
     rpeh::DevBuf<float> pint, pmap;
     int photo_levels = 0;
-    // volume colour term (rpe_sdf_photo_api.hip): its own intensity pyramid of the frame, all sint_levels levels of it (0 = not built:
+    // volume colour term (rpe_sdf_api.hip): its own intensity pyramid of the frame, all sint_levels levels of it (0 = not built:
     // whatever replaces the frame's depth or colour resets it, nothing else does)
     rpeh::DevBuf<float> sint;
     int sint_levels = 0;

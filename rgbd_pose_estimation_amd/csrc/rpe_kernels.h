@@ -221,6 +221,13 @@ hipError_t launch_prosac_order(const float* d_w, int n, int top_k, unsigned int*
 // ---- front end (rpe_frontend.hip): depth frame -> maps -> projective association; fp32 throughout
 struct Camera { float fx, fy, cx, cy; int width, height; };
 struct PoseF { float R[9]; float t[3]; };   // Xc = R Xw + t, R row-major
+// the C ABI's pose12 (R row-major | t, doubles) rounded to the kernels' fp32 pose: host units and launchers that take a pose12
+inline PoseF pose_f(const double* p12) {
+  PoseF T;
+  for (int i = 0; i < 9; i++) T.R[i] = (float)p12[i];
+  for (int i = 0; i < 3; i++) T.t[i] = (float)p12[9 + i];
+  return T;
+}
 // coarse-to-fine pyramid: level l is (width >> l) x (height >> l) pixels, stored at pixel offset off[l] of the concatenated maps
 // (off[l] is a multiple of 4: every level starts 16-byte aligned); block0 is set by the launchers
 constexpr int kMaxLevels = 4;

@@ -50,21 +50,9 @@ static_assert(offsetof(MapSdfPhotoRoundArgs, fin) == 216 && sizeof(Finish) == 13
 static_assert(offsetof(MapSdfPhotoRoundArgs, T) == 168 && sizeof(PoseF) == 48, "map_photo_late_pose: where the kernarg segment holds the pose");
 static_assert(offsetof(MapSdfPhotoRoundArgs, P) == 32 && sizeof(MapSdfPhotoView) == 80, "map_photo_late_view: where the kernarg segment holds the view");
 
-// The pose read from the kernarg segment with scalar loads where a loop trip needs it, as late_pose and photo_late_pose do and for
-// their reason: view, geometry, gates, seven pointers and the exec masks of the fetches' nested branches leave no room for twelve more
-// scalars through the whole loop
-__device__ __forceinline__ PoseF map_photo_late_pose() {
-  typedef const __attribute__((address_space(4))) float* KernargFloats;
-  unsigned off = (unsigned)offsetof(MapSdfPhotoRoundArgs, T);
-  asm volatile("" : "+s"(off));
-  KernargFloats p = (KernargFloats)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
-  PoseF T;
-#pragma unroll
-  for (int k = 0; k < 9; k++) T.R[k] = p[k];
-#pragma unroll
-  for (int k = 0; k < 3; k++) T.t[k] = p[9 + k];
-  return T;
-}
+// late_pose_at (rpe_frontend.hip) for this kernel, as late_pose and photo_late_pose and for their reason: view, geometry, gates, seven
+// pointers and the exec masks of the fetches' nested branches leave no room for twelve more scalars through the whole loop
+__device__ __forceinline__ PoseF map_photo_late_pose() { return late_pose_at((unsigned)offsetof(MapSdfPhotoRoundArgs, T)); }
 
 // The view read the same way in front of each of the two fetches: its 24 scalars are then live through one fetch, not through the loop
 __device__ __forceinline__ MapRayView map_photo_late_view() {
@@ -143,9 +131,7 @@ __global__ __launch_bounds__(kSdfRowsBlock) void map_sdf_photo_rows_kernel(const
   float r, J[6];
   const bool ok = sdf_photo_pixel(map_sdf_corners{M}, map_colour_corners{M}, G, T, gate, vmap[3 * i], vmap[3 * i + 1], vmap[3 * i + 2], fint[i],
                                   r, J);
-  rows[i] = ok ? r : qnan();
-#pragma unroll
-  for (int k = 0; k < 6; k++) rows[(int64_t)(k + 1) * n + i] = ok ? J[k] : qnan();
+  store_row(rows, n, i, ok, r, J);
 }
 
 MapSdfPhotoView photo_view(const MapRayView& M) {
@@ -165,13 +151,11 @@ hipError_t launch_icp_map_sdf_photo(const float* vmap, const float* nmap, const 
                                     const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals, float lam, int geometric,
                                     const double* pose12, const ReduceTarget& rt, hipStream_t s) {
   const SdfParams Q = sdf_params(G, dist_thr, cos_thr, use_normals);
-  const PoseF T = sdf_pose(pose12);
+  const PoseF T = pose_f(pose12);
   const Finish fin = make_finish(rt);
   const MapSdfPhotoView P = photo_view(M);
   const int blk = pick_block(rt);   // one pixel per thread while the grid allows it
-  int grid = rt.max_blocks;
-  if ((int64_t)grid > (n + blk - 1) / blk) grid = (int)((n + blk - 1) / blk);
-  if (grid < 1) grid = 1;
+  const int grid = round_grid(rt, n, blk);
 #define RPE_MAP_SDF_PHOTO_LAUNCH(GEO, B) \
   hipLaunchKernelGGL((icp_map_sdf_photo_kernel<GEO, B>), dim3(grid), dim3(B), 0, s, vmap, nmap, fint, n, P, G, Q, lam, T, fin)
   if (blk == 512) { if (geometric) RPE_MAP_SDF_PHOTO_LAUNCH(true, 512); else RPE_MAP_SDF_PHOTO_LAUNCH(false, 512); }
@@ -184,7 +168,7 @@ hipError_t launch_map_sdf_photo_rows(const float* vmap, const float* fint, int64
                                      float dist_thr, const double* pose12, float* rows, hipStream_t s) {
   const int64_t blocks = (n + kSdfRowsBlock - 1) / kSdfRowsBlock;
   hipLaunchKernelGGL(map_sdf_photo_rows_kernel, dim3((unsigned)blocks), dim3(kSdfRowsBlock), 0, s, vmap, fint, n, photo_view(M), G, dist_thr,
-                     sdf_pose(pose12), rows);
+                     pose_f(pose12), rows);
   return hipGetLastError();
 }
 

@@ -22,35 +22,25 @@ int photo_ready(rpe_context* c, int levels, const char* who) {
                 "model or model colour drops them)", who, F.photo_levels, levels);
   return RPE_OK;
 }
-// one round: launch, wait, the 32-double record of both terms in ne (cost and pairs the geometric ones), the photometric cost / pairs
+// one round: launch, wait, the 32-double record of both terms in ne (cost and pairs the geometric ones), second = the photometric
+// cost and pairs
 int rgbd_round(rpe_context* c, const PhotoLevel& lv, const rpe_icp_options* o, double dist_thr, float lam, int geometric,
-               const double* pose12, double* ne, double* pcost, double* ppairs) {
+               const double* pose12, double* ne, double* second) {
   HIP_TRY(rpe::launch_icp_photo(lv.f[0], lv.f[1], lv.fi, lv.n, lv.m[0], lv.m[1], lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr,
                                 o ? (float)o->cos_thr : 0.f, lam, geometric, pose12, collect_target(c), c->stream));
   int rc = wait_host(c, rpe::kNlLd);
   if (rc) return rc;
-  for (int i = 0; i < 32; i++) ne[i] = i < 29 ? c->h_out[i] : 0.0;
-  *pcost = c->h_out[29]; *ppairs = c->h_out[30];
+  round_record(c, ne);
+  second[0] = c->h_out[29]; second[1] = c->h_out[30];
   return RPE_OK;
 }
-// rpe_icp's host rounds on one level with the combined record
-int rgbd_level(rpe_context* c, const rpe_icp_options* o, int l, int max_iter, double dist_thr, float lam, double* pose12, int* iters_out,
-               double* last_step, double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched) {
+// the host rounds of one level with the combined record (rpe_gn_host.hpp gn_host_level); out.matched: the geometric pairs
+int rgbd_level(rpe_context* c, const rpe_icp_options* o, int l, int max_iter, double dist_thr, float lam, double* pose12, const GnOut& out) {
   const PhotoLevel lv = photo_level(c, l);
-  GnRun run;   // run.weight: the geometric pairs
-  double pcost = 0, ppairs = 0;
-  const int rc = gn_host_rounds([&](const double* pose, double* ne) { return rgbd_round(c, lv, o, dist_thr, lam, 1, pose, ne, &pcost, &ppairs); },
-                                rpe::pivot_floor(false), 1.0, max_iter, o->tol, pose12, &run);
-  if (rc == kGnRefused) {
-    if (iters_out) *iters_out = run.it;
-    return fail(RPE_ERR_DEGENERATE, "RGB-D ICP: normal equations are not positive definite at iteration %d (%g + %g pairs)", run.it, run.weight,
-                ppairs);
-  }
-  if (rc) return rc;
-  run.report(iters_out, last_step, final_cost, matched);
-  if (photo_cost) *photo_cost = pcost;
-  if (photo_matched) *photo_matched = (int64_t)ppairs;
-  return RPE_OK;
+  return gn_host_level([&](const double* pose, double* ne, double* second) { return rgbd_round(c, lv, o, dist_thr, lam, 1, pose, ne, second); },
+                       rpe::pivot_floor(false), max_iter, o->tol, pose12, out, [](int it, double pairs, double ppairs) {
+    return fail(RPE_ERR_DEGENERATE, "RGB-D ICP: normal equations are not positive definite at iteration %d (%g + %g pairs)", it, pairs, ppairs);
+  });
 }
 int rgbd_options(const rpe_icp_options* o, double photo_weight, const double* pose12, const char* who) {
   if (!o || !pose12 || !(o->dist_thr >= 0)) return fail(RPE_ERR_ARG, "%s: bad argument", who);
@@ -150,11 +140,9 @@ int rpe_photo_normal_eq(rpe_context* c, int level, const double* pose12, double 
   int rc = photo_ready(c, level + 1, "rpe_photo_normal_eq");
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  double ne[32], pcost = 0, ppairs = 0;
-  if ((rc = rgbd_round(c, photo_level(c, level), nullptr, dist_thr, (float)weight, 0, pose12, ne, &pcost, &ppairs))) return rc;
-  for (int i = 0; i < 32; i++) out32[i] = i < 27 ? ne[i] : 0.0;
-  out32[27] = pcost; out32[28] = ppairs;
-  out32[29] = rpe::pivot_floor(false);   // for rpe_gn_solve: the rows' products are fp32
+  double ne[32], second[2] = {0, 0};
+  if ((rc = rgbd_round(c, photo_level(c, level), nullptr, dist_thr, (float)weight, 0, pose12, ne, second))) return rc;
+  photo_only_record(ne, second[0], second[1], out32);
   return RPE_OK;
 }
 
@@ -167,11 +155,8 @@ int rpe_photo_rows(rpe_context* c, int level, const double* pose12, double dist_
   const PhotoLevel lv = photo_level(c, level);
   DevBuf<float> d_rows;
   if ((rc = d_rows.once(c, (size_t)lv.n * 7 * sizeof(float)))) return rc;
-  hipError_t e = rpe::launch_photo_rows(lv.f[0], lv.fi, lv.n, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr, pose12, d_rows, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, (size_t)lv.n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(RPE_ERR_HIP, "rpe_photo_rows: %s", hipGetErrorString(e));
-  return RPE_OK;
+  return rows_download(c, "rpe_photo_rows", rpe::launch_photo_rows(lv.f[0], lv.fi, lv.n, lv.pm, lv.mcam, pose_f(c->fe.mpose), (float)dist_thr,
+                                                                   pose12, d_rows, c->stream), d_rows, lv.n, rows);
 }
 
 int rpe_icp_rgbd(rpe_context* c, const rpe_icp_options* o, double photo_weight, double* pose12, int* iters_out, double* last_step,
@@ -183,8 +168,8 @@ int rpe_icp_rgbd(rpe_context* c, const rpe_icp_options* o, double photo_weight, 
   if (o->max_iter < 1) return fail(RPE_ERR_ARG, "rpe_icp_rgbd: max_iter >= 1");
   if ((rc = photo_ready(c, 1, "rpe_icp_rgbd"))) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  if ((rc = rgbd_level(c, o, 0, o->max_iter, o->dist_thr, (float)photo_weight, pose12, iters_out, last_step, final_cost, matched, photo_cost,
-                       photo_matched))) return rc;
+  if ((rc = rgbd_level(c, o, 0, o->max_iter, o->dist_thr, (float)photo_weight, pose12,
+                       {iters_out, last_step, final_cost, matched, photo_cost, photo_matched}))) return rc;
   // leave the pairs in the solver slots, under the returned pose (as a fused rpe_icp does)
   return rpe_associate(c, pose12, o->dist_thr, o->cos_thr, o->use_normals, nullptr);
 }
@@ -199,10 +184,10 @@ int rpe_icp_pyramid_rgbd(rpe_context* c, const rpe_icp_options* o, double photo_
   if ((rc = pyramid_complaint("rpe_icp_pyramid_rgbd", levels, iters_per_level, dist_thr_per_level))) return rc;
   if ((rc = photo_ready(c, levels, "rpe_icp_pyramid_rgbd"))) return rc;
   HIP_TRY(hipSetDevice(c->device));
+  const GnOut out{iters_out, last_step, final_cost, matched, photo_cost, photo_matched};
   rc = coarse_to_fine(levels, iters_per_level, dist_thr_per_level, o->dist_thr, iters_out,
                       [&](int l, int rounds, double gate, bool fine, int* it) {
-    return rgbd_level(c, o, l, rounds, gate, (float)photo_weight, pose12, it, fine ? last_step : nullptr, fine ? final_cost : nullptr,
-                      fine ? matched : nullptr, fine ? photo_cost : nullptr, fine ? photo_matched : nullptr);
+    return rgbd_level(c, o, l, rounds, gate, (float)photo_weight, pose12, out.at_level(fine, it));
   });
   if (rc) return rc;
   return rpe_associate(c, pose12, dist_thr_per_level ? dist_thr_per_level[0] : o->dist_thr, o->cos_thr, o->use_normals, nullptr);

@@ -122,21 +122,9 @@ struct SdfPhotoRoundArgs {
 static_assert(offsetof(SdfPhotoRoundArgs, fin) == 152 && sizeof(Finish) == 136, "late_finish_at: where the kernarg segment holds the reduction's argument");
 static_assert(offsetof(SdfPhotoRoundArgs, T) == 104 && sizeof(PoseF) == 48, "photo_late_pose: where the kernarg segment holds the pose");
 
-// The pose read from the kernarg segment with scalar loads where a loop trip needs it, as icp_map_sdf_kernel's late_pose does and for
-// its reason: as a plain argument its twelve scalars are live through the whole loop beside geometry, gates and six pointers, which is
-// more than the 102 there are (2 scalar spills, and the vector register that holds them is the 129th)
-__device__ __forceinline__ PoseF photo_late_pose() {
-  typedef const __attribute__((address_space(4))) float* KernargFloats;
-  unsigned off = (unsigned)offsetof(SdfPhotoRoundArgs, T);
-  asm volatile("" : "+s"(off));
-  KernargFloats p = (KernargFloats)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + off);
-  PoseF T;
-#pragma unroll
-  for (int k = 0; k < 9; k++) T.R[k] = p[k];
-#pragma unroll
-  for (int k = 0; k < 3; k++) T.t[k] = p[9 + k];
-  return T;
-}
+// late_pose_at (rpe_frontend.hip) for this kernel, as icp_map_sdf_kernel's late_pose and for its reason: beside geometry, gates and six
+// pointers the pose as a plain argument costs 2 scalar spills, and the vector register that holds them is the 129th
+__device__ __forceinline__ PoseF photo_late_pose() { return late_pose_at((unsigned)offsetof(SdfPhotoRoundArgs, T)); }
 
 // a row into the fp64 sums: H and g into the shared entries, the cost into its own.  A pixel without a row has r = 0 and J = 0
 __device__ __forceinline__ void add_row_f64(const float r, const float (&J)[6], double (&acc)[29], int cost) {
@@ -219,9 +207,7 @@ __global__ __launch_bounds__(kSdfRowsBlock) void sdf_photo_rows_kernel(const flo
   float r, J[6];
   const bool ok = sdf_photo_pixel(dense_corners(vol, G), dense_colour_corners(cvol, G), G, T, gate, vmap[3 * i], vmap[3 * i + 1],
                                   vmap[3 * i + 2], fint[i], r, J);
-  rows[i] = ok ? r : qnan();
-#pragma unroll
-  for (int k = 0; k < 6; k++) rows[(int64_t)(k + 1) * n + i] = ok ? J[k] : qnan();
+  store_row(rows, n, i, ok, r, J);
 }
 
 // a node per new kernel, beside the unit's own (one code object: whichever is touched first loads all of it)
@@ -234,13 +220,11 @@ hipError_t launch_icp_sdf_photo(const float* vmap, const float* nmap, const floa
                                 const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals, float lam, int geometric,
                                 const double* pose12, const ReduceTarget& rt, hipStream_t s) {
   const SdfParams Q = sdf_params(G, dist_thr, cos_thr, use_normals);
-  const PoseF T = sdf_pose(pose12);
+  const PoseF T = pose_f(pose12);
   const Finish fin = make_finish(rt);
   const uint2* cv = reinterpret_cast<const uint2*>(cvol);
   const int blk = pick_block(rt);   // one pixel per thread while the grid allows it
-  int grid = rt.max_blocks;
-  if ((int64_t)grid > (n + blk - 1) / blk) grid = (int)((n + blk - 1) / blk);
-  if (grid < 1) grid = 1;
+  const int grid = round_grid(rt, n, blk);
 #define RPE_SDF_PHOTO_LAUNCH(GEO, B) \
   hipLaunchKernelGGL((icp_sdf_photo_kernel<GEO, B>), dim3(grid), dim3(B), 0, s, vmap, nmap, fint, n, vol, cv, G, Q, lam, T, fin)
   if (blk == 512) { if (geometric) RPE_SDF_PHOTO_LAUNCH(true, 512); else RPE_SDF_PHOTO_LAUNCH(false, 512); }
@@ -253,7 +237,7 @@ hipError_t launch_sdf_photo_rows(const float* vmap, const float* fint, int64_t n
                                  const VolumeGeometry& G, float dist_thr, const double* pose12, float* rows, hipStream_t s) {
   const int64_t blocks = (n + kSdfRowsBlock - 1) / kSdfRowsBlock;
   hipLaunchKernelGGL(sdf_photo_rows_kernel, dim3((unsigned)blocks), dim3(kSdfRowsBlock), 0, s, vmap, fint, n, vol,
-                     reinterpret_cast<const uint2*>(cvol), G, dist_thr, sdf_pose(pose12), rows);
+                     reinterpret_cast<const uint2*>(cvol), G, dist_thr, pose_f(pose12), rows);
   return hipGetLastError();
 }
 

@@ -113,6 +113,64 @@ int main() {
     CHECK(plain.cost == 12 && scaled.cost == 2.5 * 12 && scaled.weight == plain.weight && scaled.it == plain.it);
     CHECK(same(&scaled.step, &plain.step, 1) && same(p, q, 12));
   }
+  // ---- gn_host_level: the level driver on the same scripted rounds, whose second term is cost 20 + k and rows 200 + k at round k
+  {
+    struct Words { int it = -1; double step = -1, cost = -1, cost2 = -1; int64_t matched = -1, matched2 = -1; };
+    auto all = [](Words& w) { return GnOut{&w.it, &w.step, &w.cost, &w.matched, &w.cost2, &w.matched2}; };
+    auto untouched = [](const Words& w) { return w.step == -1 && w.cost == -1 && w.cost2 == -1 && w.matched == -1 && w.matched2 == -1; };
+    int calls = 0, refusals = 0;
+    auto round = [&](const double*, double* ne, double* second) { shrinking(calls, ne); second[0] = 20 + calls; second[1] = 200 + calls; calls++; return 0; };
+    auto never = [&](int, double, double) { refusals++; return -9; };
+    double p[12], q[12], t = 0;
+    // a tol stop in round 3: every figure is that round's, the pose that of gn_host_rounds
+    std::memcpy(p, kStart, sizeof p); std::memcpy(q, kStart, sizeof q);
+    Words w;
+    CHECK(gn_host_level(round, kFloor, 50, 1e-3, p, all(w), never) == RPE_OK && calls == 4 && refusals == 0);
+    for (int k = 0; k < 4; k++) { double ne[32]; shrinking(k, ne); CHECK(by_hand(ne, q, &t)); }
+    CHECK(same(p, q, 12) && w.it == 4 && same(&w.step, &t, 1) && w.cost == 13 && w.matched == 103 && w.cost2 == 23 && w.matched2 == 203);
+    // outputs are written only where there is one: none at all; the rounds alone (a coarser level of a walk); all but the second term's
+    calls = 0;
+    CHECK(gn_host_level(round, kFloor, 2, 0.0, p, GnOut{}, never) == RPE_OK && calls == 2);
+    Words coarse, geo;
+    int it = -1;
+    calls = 0;
+    CHECK(gn_host_level(round, kFloor, 2, 0.0, p, all(coarse).at_level(false, &it), never) == RPE_OK && it == 2 && coarse.it == -1 && untouched(coarse));
+    calls = 0;
+    CHECK(gn_host_level(round, kFloor, 2, 0.0, p, GnOut{&geo.it, &geo.step, &geo.cost, &geo.matched}, never) == RPE_OK);
+    CHECK(geo.it == 2 && geo.step > 0 && geo.cost == 11 && geo.matched == 101 && geo.cost2 == -1 && geo.matched2 == -1);
+    Words fine;
+    calls = 0;
+    CHECK(gn_host_level(round, kFloor, 2, 0.0, p, all(fine).at_level(true, &it), never) == RPE_OK && it == 2 && fine.it == -1);
+    CHECK(fine.cost == 11 && fine.matched == 101 && fine.cost2 == 21 && fine.matched2 == 201);
+    // a round without a second term leaves the driver's zeros
+    Words plain;
+    calls = 0;
+    CHECK(gn_host_level([&](const double*, double* ne, double*) { shrinking(calls++, ne); return 0; }, kFloor, 2, 0.0, p, all(plain), never) == RPE_OK);
+    CHECK(plain.cost == 11 && plain.cost2 == 0 && plain.matched2 == 0);
+    // a system refused at round 2: iters = 2, no other output, and the hook has that round's weight and second-term rows; its code comes back
+    Words r;
+    int r_it = -1;
+    double r_weight = -1, r_rows2 = -1;
+    calls = 0;
+    std::memcpy(p, kStart, sizeof p); std::memcpy(q, kStart, sizeof q);
+    const int rc = gn_host_level([&](const double*, double* ne, double* second) {
+      shrinking(calls, ne);
+      second[0] = 20 + calls; second[1] = 200 + calls;
+      if (calls++ == 2) { for (int i = 0; i < 27; i++) ne[i] = 0; ne[27] = 7; ne[28] = 9; }
+      return 0;
+    }, kFloor, 50, 0.0, p, all(r), [&](int at, double weight, double rows2) { r_it = at; r_weight = weight; r_rows2 = rows2; return -42; });
+    CHECK(rc == -42 && calls == 3 && r.it == 2 && untouched(r) && r_it == 2 && r_weight == 9 && r_rows2 == 202);
+    for (int k = 0; k < 2; k++) { double ne[32]; shrinking(k, ne); CHECK(by_hand(ne, q, &t)); }
+    CHECK(same(p, q, 12));
+    CHECK(gn_host_level([&](const double*, double* ne, double*) { for (int i = 0; i < 32; i++) ne[i] = 0; return 0; }, kFloor, 5, 0.0, p, GnOut{},
+                        [&](int at, double, double) { return -40 - at; }) == -40);   // refused at once, nowhere to write: the hook's code still
+    // a round's own code at round 2 passes through: nothing reported, not even the rounds, and the hook is not asked
+    Words e;
+    calls = 0;
+    CHECK(gn_host_level([&](const double*, double* ne, double* second) { shrinking(calls, ne); second[0] = 1; second[1] = 2; return calls++ == 2 ? -77 : 0; },
+                        kFloor, 50, 0.0, p, all(e), never) == -77);
+    CHECK(calls == 3 && e.it == -1 && untouched(e) && refusals == 0);
+  }
   // ---- coarse_to_fine: coarsest first, a level without rounds skipped with a 0, per-level gates or the default, fine at level 0 only
   {
     struct Visit { int l, rounds; double gate; bool fine; };

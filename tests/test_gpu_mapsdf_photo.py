@@ -1,5 +1,5 @@
 """GPU: the map volume colour term (map_sdf_photo_rows_kernel / icp_map_sdf_photo_kernel of csrc/rpe_map_sdf_photo.hpp,
-rpe_sdf_photo_api.hip).  The rows are held BIT FOR BIT -- NaN for NaN -- to tests/mapsdf_photo_oracle.py and, independent of the oracle,
+rpe_sdf_api.hip).  The rows are held BIT FOR BIT -- NaN for NaN -- to tests/mapsdf_photo_oracle.py and, independent of the oracle,
 to the window's kernel: rpe_sdf_photo_rows of a second context that holds the dense virtual volume and colour volume of the box.  The
 record is held to its rounding bound, the combined round and the loops to the oracle's and the second context's, the wall walk of
 tests/mapsdf_photo_cases.py to its recorded figures, and the state rules to the union of the two terms'.  The maps are assembled on the

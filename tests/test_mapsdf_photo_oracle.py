@@ -143,7 +143,7 @@ def test_header_and_library_export_the_entry_points():
     text = open(os.path.join(UG.CSRC, "rpe_map_sdf_photo.hpp")).read()
     assert text.count("RPE_PRELOAD(") == 2                                        # one node per new kernel
     assert open(os.path.join(UG.CSRC, "rpe_sdf_photo.hpp")).read().rstrip().endswith('#include "rpe_map_sdf_photo.hpp"')
-    api = open(os.path.join(UG.CSRC, "rpe_sdf_api.hip")).read() + open(os.path.join(UG.CSRC, "rpe_sdf_photo_api.hip")).read()
+    api = open(os.path.join(UG.CSRC, "rpe_sdf_api.hip")).read()                   # the one host unit of both terms, window and map
     assert "build_grid(" not in api                                               # map_field lives once, beside build_grid
     assert open(os.path.join(UG.CSRC, "rpe_mapmesh_api.hip")).read().count("int rpeh::map_field(") == 1
 
@@ -164,7 +164,7 @@ def test_the_new_kernels_are_within_the_budget_taken():
 
 def test_the_round_kernel_finds_its_late_arguments_in_the_kernarg_segment(tmp_path):
     """icp_map_sdf_photo_kernel reads the view, the pose and the reduction's argument from the kernarg segment (rpe_map_sdf_photo.hpp
-    map_photo_late_view, map_photo_late_pose, late_finish_at), at the offsets of a struct that mirrors the argument list: the metadata
+    map_photo_late_view, map_photo_late_pose -- rpe_frontend.hip late_pose_at at its offset --, late_finish_at), at the offsets of a struct that mirrors the argument list: the metadata
     must hold the arguments exactly there"""
     UG.built()
     layouts = kernarg_layouts(tmp_path, "icp_map_sdf_photo_kernel")

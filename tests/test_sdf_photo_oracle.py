@@ -268,7 +268,9 @@ def test_header_and_library_export_the_entry_points():
                  "NOT gated"):
         assert what in block, what
     from rgbd_pose_estimation_amd import build as B
-    assert "rpe_sdf_photo_api.hip" in B.SOURCES and dict((s, k) for s, k, _ in B.UNITS)["rpe_sdf_photo_api.hip"] == "host"
+    # the host side is the volume term's unit, which states the four calls once for both terms: no unit of its own
+    assert "rpe_sdf_api.hip" in B.SOURCES and dict((s, k) for s, k, _ in B.UNITS)["rpe_sdf_api.hip"] == "host"
+    assert "rpe_sdf_photo_api.hip" not in B.SOURCES and not os.path.exists(os.path.join(UG.CSRC, "rpe_sdf_photo_api.hip"))
     src = open(os.path.join(UG.CSRC, "rpe_frontend.hip")).read()
     assert src.rstrip().endswith('#include "rpe_sdf_photo.hpp"')                   # compiled into the front end's unit: no new kernel unit
     text = open(os.path.join(UG.CSRC, "rpe_sdf_photo.hpp")).read()
@@ -307,8 +309,8 @@ def kernarg_layouts(tmp_path, kernel):
 
 
 def test_the_round_kernel_finds_its_late_arguments_in_the_kernarg_segment(tmp_path):
-    """icp_sdf_photo_kernel reads the pose and the reduction's argument from the kernarg segment (rpe_sdf_photo.hpp photo_late_pose,
-    late_finish_at), at the offsets of a struct that mirrors the argument list: the metadata must hold the arguments exactly there"""
+    """icp_sdf_photo_kernel reads the pose and the reduction's argument from the kernarg segment (rpe_frontend.hip late_pose_at and
+    late_finish_at, the pose's offset named by rpe_sdf_photo.hpp photo_late_pose), at the offsets of a struct that mirrors the argument list: the metadata must hold the arguments exactly there"""
     UG.built()
     layouts = kernarg_layouts(tmp_path, "icp_sdf_photo_kernel")
     assert len(layouts) == 4
