@@ -147,7 +147,8 @@ int rpe_gn_apply(const double* delta6, double* pose12);
  * IRLS weight on the residual-block norm s: Huber min(1, k/s) or Cauchy 1/(1 + (s/k)^2).  out32 as rpe_normal_eq, with
  * cost = sum scale*w*r^2 and the last entry = number-weighted count over all terms.  This is the single-kernel form of the
  * joint 2D-3D + 3D-3D + N-N objective the reference's nl_shinji_kneip_ls alternates over (:484-510). */
-enum { RPE_ROBUST_NONE = 0, RPE_ROBUST_HUBER = 1, RPE_ROBUST_CAUCHY = 2 };
+enum { RPE_ROBUST_NONE = 0, RPE_ROBUST_HUBER = 1, RPE_ROBUST_CAUCHY = 2,
+       RPE_ROBUST_TUKEY = 3 /* the volume terms only (rpe_sdf_set_robust): a term of this list with it is RPE_ERR_ARG */ };
 typedef struct { int kind; double scale; int robust; double robust_k; } rpe_term;
 int rpe_normal_eq_joint(rpe_context* ctx, int nterms, const rpe_term* terms, int flags, const double* pose12, double* out32);
 int rpe_gn_refine_joint(rpe_context* ctx, int nterms, const rpe_term* terms, int flags, double* pose12, int max_iter, double tol,
@@ -1316,6 +1317,44 @@ int rpe_icp_map_sdf_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double ph
 int rpe_icp_pyramid_map_sdf_rgbd(rpe_context* ctx, const rpe_icp_options* opt, double photo_weight, int levels, const int* iters_per_level,
                                  const double* dist_thr_per_level, const int64_t lo[3], const int64_t hi[3], double* pose12, int* iters_out,
                                  double* last_step, double* final_cost, int64_t* matched, double* photo_cost, int64_t* photo_matched);
+
+/* ---- Robust volume terms: an optional IRLS weight on the rows of the four volume terms ("Volume term", "Volume colour term", "Map volume
+ * term", "Map volume colour term").  Their gates are the only defence against depth the map does not explain -- a person, a moved chair,
+ * a door that has opened: a row 8 cm off passes a 10 cm gate at full weight and pulls the pose.  OFF by default; set once per context
+ * and then used by the four normal-equation calls and the eight loops.  The four rows calls are not affected: they return the
+ * unweighted r and J.
+ * The rule (csrc/rpe_sdf_robust_rule.hpp; tests/sdf_robust_oracle.py states it in numpy), followed bit for bit: fp32, the written
+ * order, no FMA contraction.  The weight w of a row with residual r and scale k -- r in metres for the geometric row, in UNSCALED
+ * intensity levels (before the photometric weight lam) for the photometric row:
+ *   RPE_ROBUST_HUBER:  s = fabsf(r);  w = s <= k ? 1.0f : k / s
+ *   RPE_ROBUST_TUKEY:  u = r / k;  q = 1.0f - u * u;  w = fabsf(r) < k ? q * q : 0.0f
+ * A weighted row contributes w J J^T to H, w J r to g and w r^2 to the cost entry of its term; a pixel without a row has no weight (0 in
+ * the sums, NaN in the hook below).  The row count still counts EVERY row that passed the gates, weight 0 included.  In the colour
+ * calls the geometric row is weighted with k; the photometric row with photo_k on its unscaled residual and then scaled by lam as
+ * before; photo_k = 0 leaves the photometric rows at weight 1.  The photometric-only record of rpe_sdf_photo_normal_eq /
+ * rpe_map_sdf_photo_normal_eq is weighted with photo_k.  The records' layout is unchanged, every sum is within 8 * 2^-24 of the sum of
+ * the magnitudes of its (weighted) products and the row counts are exact: the row and its weight are widened to fp64 (w J is exact
+ * there) and added with fp64 fused multiply-adds, one pixel per thread and loop trip, on the window too.  A round whose weights are all
+ * 0 ends as any round whose normal equations are not positive definite ends: RPE_ERR_DEGENERATE.
+ * With kind RPE_ROBUST_NONE every call launches exactly the kernels it launched before there was a weight and returns the same bits.
+ * What it is NOT.  No confidence weighting: rows are still not weighted by voxel weight (tried in the oracles: min(w, 4) / 4 moved a
+ * tracked pose by less than 3 % either way).  No scale estimation: k is the caller's, in the units of r, and does not follow the
+ * level or the round.  No Cauchy kernel.  The front-end ICP (rpe_icp, rpe_icp_rgbd and their pyramid forms) and the keyframe graph stay
+ * unweighted. */
+/* kind: RPE_ROBUST_NONE (off; k and photo_k are not read and read back as 0), RPE_ROBUST_HUBER or RPE_ROBUST_TUKEY; with a kind other
+ * than NONE k finite and >= 1e-6, photo_k 0 or finite and >= 1e-6.  RPE_ROBUST_CAUCHY, any other kind and any other scale are
+ * RPE_ERR_ARG and leave the setting as it was.  The setting is the context's: it survives new frames, volumes and shifts */
+int rpe_sdf_set_robust(rpe_context* ctx, int kind, double k, double photo_k);
+int rpe_sdf_robust(rpe_context* ctx, int* kind, double* k, double* photo_k);
+/* The tests' hook and a way to look at what the weight does: the plane of weights of the level, w_l*h_l floats, under the context's
+ * setting -- of the geometric rows (photo = 0: scale k, gates as rpe_sdf_rows') or of the photometric rows (photo = 1: scale photo_k,
+ * gate as rpe_sdf_photo_rows'; cos_thr and use_normals are not read; needs what the colour calls need).  NaN where the pixel has no
+ * row; 1 for every row with kind NONE or with photo = 1 and photo_k = 0.  The map form reads the map inside the box, as
+ * rpe_map_sdf_rows / rpe_map_sdf_photo_rows do.  Arguments, states and their codes are those of the rows calls */
+int rpe_sdf_robust_weights(rpe_context* ctx, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals, int photo,
+                           float* weights);
+int rpe_map_sdf_robust_weights(rpe_context* ctx, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals,
+                               int photo, const int64_t lo[3], const int64_t hi[3], float* weights);
 
 /* ---- Map fuse: the whole MAP rebuilt from the keyframes -- the window and the archived bricks.  rpe_volume_fuse_keyframes writes the
  * dense window only: after a loop closure the archived bricks, most of a walked map, would keep the surface fused at the drifted poses.

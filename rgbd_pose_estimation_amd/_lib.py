@@ -18,6 +18,7 @@ MOD_23, MOD_33, MOD_NN = 0, 1, 2
 USE_MASK, USE_WEIGHT, SKIP_INVALID = 1, 2, 4
 RES_P2P, RES_P2PLANE, RES_BEARING, RES_NORMAL, RES_REPROJ = 0, 1, 2, 3, 4
 ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY = 0, 1, 2
+ROBUST_TUKEY = 3        # the volume terms only (rpe_sdf_set_robust)
 VOTE_33, VOTE_23, VOTE_33_23, VOTE_NN_23, VOTE_NN_33, VOTE_NN_33_23, VOTE_23_MATRIX = 0, 1, 2, 3, 4, 5, 6
 SCORE_FAST, SCORE_EXACT = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1
@@ -67,6 +68,7 @@ SYMBOLS = [
     "rpe_volume_map_bounds", "rpe_volume_map_mesh", "rpe_volume_map_raycast",
     "rpe_map_sdf_rows", "rpe_map_sdf_normal_eq", "rpe_icp_map_sdf", "rpe_icp_pyramid_map_sdf",
     "rpe_map_sdf_photo_rows", "rpe_map_sdf_photo_normal_eq", "rpe_icp_map_sdf_rgbd", "rpe_icp_pyramid_map_sdf_rgbd",
+    "rpe_sdf_set_robust", "rpe_sdf_robust", "rpe_sdf_robust_weights", "rpe_map_sdf_robust_weights",
     "rpe_volume_map_fuse_keyframes",
     "rpe_host_random_elements", "rpe_host_prosac_samples", "rpe_host_update_num_iters", "rpe_host_sort_indexes", "rpe_host_kneip_main",
     "rpe_host_kneip", "rpe_host_nl_2p", "rpe_host_shinji", "rpe_host_se3_exp", "rpe_host_svd3", "rpe_host_calc_err",
@@ -330,6 +332,11 @@ def lib():
         L.rpe_icp_pyramid_map_sdf_rgbd.argtypes = [C.c_void_p, C.POINTER(RpeIcpOptions), C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p]
+        L.rpe_sdf_set_robust.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+        L.rpe_sdf_robust.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rpe_sdf_robust_weights.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]
+        L.rpe_map_sdf_robust_weights.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
         if hasattr(L, "rpe_run"):
             L.rpe_run.argtypes = [C.c_int, C.POINTER(RpeProblem), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_uint64,
                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -765,6 +765,38 @@ class Context:
         volume_shift -> icp_pyramid_map_sdf_rgbd -> volume_integrate_color).  Returns what icp_pyramid_sdf_rgbd returns."""
         return self._pyramid_loop("rpe_icp_pyramid_map_sdf_rgbd", pose12, iters, dist_thr, tol, cos_thr, use_normals, weight, self._box(box))
 
+    # ---- robust volume terms (Part 3): an IRLS weight on the rows of the four volume terms above, off by default
+    def sdf_set_robust(self, kind: int = L.ROBUST_NONE, k: float = 0.0, photo_k: float = 0.0):
+        """The robust weight of the normal-equation calls and loops of the volume terms, on the window and on the map: kind ROBUST_NONE
+        (off), ROBUST_HUBER or ROBUST_TUKEY; k the geometric row's scale in metres, photo_k the photometric row's in unscaled intensity
+        levels (0: photometric rows at weight 1).  The context's: it survives new frames, volumes and shifts (rpe_sdf_set_robust)."""
+        L.check(L.lib().rpe_sdf_set_robust(self._h, int(kind), float(k), float(photo_k)))
+        return self
+
+    def sdf_robust(self):
+        """(kind, k, photo_k) as set; (ROBUST_NONE, 0.0, 0.0) when off."""
+        kind, k, pk = C.c_int(0), C.c_double(0), C.c_double(0)
+        L.check(L.lib().rpe_sdf_robust(self._h, C.byref(kind), C.byref(k), C.byref(pk)))
+        return kind.value, k.value, pk.value
+
+    def _weights_call(self, name, pose12, level, dist_thr, cos_thr, use_normals, photo, box=()):
+        h, w = self._frame_hw or (0, 0)
+        out = np.empty(max(1, (h >> max(level, 0)) * (w >> max(level, 0))), np.float32)
+        L.check(getattr(L.lib(), name)(self._h, int(level), _p(np.array(pose12, np.float64).reshape(12)), float(dist_thr), float(cos_thr),
+                                       int(use_normals), int(photo), *map(_p, box), _p(out)))
+        return out
+
+    def sdf_robust_weights(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True,
+                           photo: bool = False) -> np.ndarray:
+        """(pixels,) float32: the weight of every frame pixel's row of the level under the setting of sdf_set_robust -- the geometric
+        rows' (gates as sdf_rows') or, with photo, the photometric rows' (gate as sdf_photo_rows').  NaN where the pixel has no row."""
+        return self._weights_call("rpe_sdf_robust_weights", pose12, level, dist_thr, cos_thr, use_normals, photo)
+
+    def map_sdf_robust_weights(self, pose12, level: int = 0, dist_thr: float = 0.1, cos_thr: float = 0.9, use_normals: bool = True,
+                               photo: bool = False, box=None) -> np.ndarray:
+        """sdf_robust_weights against the map inside the box (None: volume_map_bounds), as map_sdf_rows / map_sdf_photo_rows read it."""
+        return self._weights_call("rpe_map_sdf_robust_weights", pose12, level, dist_thr, cos_thr, use_normals, photo, self._box(box))
+
     # ---- features and relocalisation (Part 3): correspondences without a pose guess
     def features_detect(self, which: int = L.FEAT_FRAME, threshold: int = 12, max_keypoints: int = L.MAX_KEYPOINTS) -> int:
         """Detect and describe the keypoints of the frame's colour (FEAT_FRAME) or the model colour (FEAT_MODEL); returns their number."""

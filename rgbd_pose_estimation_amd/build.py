@@ -2,7 +2,7 @@
 
 hipcc cross-compiles without a GPU.  UNITS below is the manifest of the library: every compiled unit once, in link order, with its
 kind and what it holds.  Kernel units share device code in csrc/rpe_reduce.hpp and csrc/rpe_residuals.hpp and the front end's
-bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_sdf_rule.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp; each names one of its kernels
+bit-exact rules in csrc/rpe_volume_field.hpp, csrc/rpe_sdf_rule.hpp, csrc/rpe_sdf_robust_rule.hpp, csrc/rpe_mc_rules.hpp and csrc/rpe_feature_rules.hpp; each names one of its kernels
 with RPE_PRELOAD (csrc/rpe_kernels.h), through which rpe_create loads its code object.  Host units are the C-ABI side behind
 include/rgbd_pose_hip.h Part 2 / 3 (csrc/rpe_host.hpp lists them; csrc/rpe_devbuf.hpp owns their device memory,
 csrc/rpe_gn_host.hpp holds the Gauss-Newton step, round loop, level driver and coarse-to-fine walk of their host loops,
@@ -31,7 +31,8 @@ UNITS = [
     ("rpe_nl.hip", "kernel", "K1' moments, K5, publish kernels"),
     ("rpe_frontend.hip", "kernel", "depth-frame front end; the model maps raycast from the map; the volume term's rows and round, on the window and on the map; "
                                    "the keyframe list fused into the map's bricks (csrc/rpe_mapfuse.hpp); the volume colour term's rows and round (csrc/rpe_sdf_photo.hpp), "
-                                   "on the window and on the map (csrc/rpe_map_sdf_photo.hpp)"),
+                                   "on the window and on the map (csrc/rpe_map_sdf_photo.hpp); the robust rounds of the four volume terms and their weight hook "
+                                   "(csrc/rpe_sdf_robust.hpp)"),
     ("rpe_filter.hip", "kernel", "the bilateral depth filter in front of it"),
     ("rpe_volume.hip", "kernel", "TSDF volume: integrate, raycast"),
     ("rpe_mesh.hip", "kernel", "marching cubes over the volume"),

@@ -64,9 +64,10 @@ inline void photo_only_record(const double* ne, double pcost, double prows, doub
   out32[29] = rpe::pivot_floor(false);
 }
 // the tail of a rows call behind its launch (`launched`: what the launcher returned): the (7, n) rows down to the caller, one host wait
-inline int rows_download(rpe_context* c, const char* who, hipError_t launched, const float* d_rows, int64_t n, float* rows) {
+// (planes = 1: the plane of weights of the robust volume terms' hook)
+inline int rows_download(rpe_context* c, const char* who, hipError_t launched, const float* d_rows, int64_t n, float* rows, int planes = 7) {
   hipError_t e = launched;
-  if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, (size_t)n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, (size_t)n * planes * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(RPE_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   return RPE_OK;

@@ -294,6 +294,11 @@ struct rpe_context {
     bool mesh_is_map = false, map_color = false;
   } vol;
 
+  // robust volume terms (rpe_sdf_api.hip, rpe_sdf_set_robust): the weight on the rows of the four volume terms -- the kind (RPE_ROBUST_NONE:
+  // off), the geometric row's scale [m] and the photometric row's [unscaled levels; 0 = weight 1].  The context's: no frame, volume or
+  // shift resets it
+  struct SdfRobust { int kind = 0; double k = 0, photo_k = 0; } sdf_robust;
+
   rpe::DeviceArrays arrays() const {
     rpe::DeviceArrays A;
     for (int i = 0; i < RPE_NUM_ARRAYS; i++) A.a[i] = arr[i];

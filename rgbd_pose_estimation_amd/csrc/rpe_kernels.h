@@ -550,4 +550,25 @@ hipError_t launch_icp_map_sdf_photo(const float* vmap, const float* nmap, const 
                                     const double* pose12, const ReduceTarget& rt, hipStream_t s);
 hipError_t launch_map_sdf_photo_rows(const float* vmap, const float* fint, int64_t n, const MapRayView& M, const VolumeGeometry& G,
                                      float dist_thr, const double* pose12, float* rows, hipStream_t s);
+// ---- the robust volume terms (rpe_sdf_robust.hpp, compiled into rpe_frontend.hip; the weight's rule in rpe_sdf_robust_rule.hpp): the
+// four round launchers above with a robust weight on every row -- kind 1 (Huber) or 3 (Tukey), k the geometric row's scale [m], photo_k
+// the photometric row's [unscaled levels; 0: weight 1].  Records laid out as the unweighted launchers'; the row counts count every row
+constexpr int kRobustNone = 0, kRobustHuber = 1, kRobustTukey = 3;   // RPE_ROBUST_NONE / _HUBER / _TUKEY (rpe_sdf_api.hip asserts it)
+hipError_t launch_icp_sdf_robust(const float* vmap, const float* nmap, int64_t n, const float* vol, const VolumeGeometry& G, float dist_thr,
+                                 float cos_thr, int use_normals, int kind, float k, const double* pose12, const ReduceTarget& rt, hipStream_t s);
+hipError_t launch_icp_map_sdf_robust(const float* vmap, const float* nmap, int64_t n, const MapRayView& M, const VolumeGeometry& G,
+                                     float dist_thr, float cos_thr, int use_normals, int kind, float k, const double* pose12,
+                                     const ReduceTarget& rt, hipStream_t s);
+hipError_t launch_icp_sdf_photo_robust(const float* vmap, const float* nmap, const float* fint, int64_t n, const float* vol,
+                                       const unsigned short* cvol, const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals,
+                                       float lam, int geometric, int kind, float k, float photo_k, const double* pose12, const ReduceTarget& rt,
+                                       hipStream_t s);
+hipError_t launch_icp_map_sdf_photo_robust(const float* vmap, const float* nmap, const float* fint, int64_t n, const MapRayView& M,
+                                           const VolumeGeometry& G, float dist_thr, float cos_thr, int use_normals, float lam, int geometric,
+                                           int kind, float k, float photo_k, const double* pose12, const ReduceTarget& rt, hipStream_t s);
+// the tests' hook: out[i] = the weight of frame pixel i's row (photo != 0: the photometric row's; fint, cvol and the colour sources of M
+// are read only then), NaN where it has no row.  M = null: the dense window vol / cvol; else the map through M.  kind 0 or scale 0: 1
+hipError_t launch_sdf_robust_weights(const float* vmap, const float* nmap, const float* fint, int64_t n, const float* vol,
+                                     const unsigned short* cvol, const MapRayView* M, const VolumeGeometry& G, float dist_thr, float cos_thr,
+                                     int use_normals, int photo, int kind, float scale, const double* pose12, float* out, hipStream_t s);
 }  // namespace rpe

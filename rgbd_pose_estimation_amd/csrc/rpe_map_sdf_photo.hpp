@@ -173,3 +173,7 @@ hipError_t launch_map_sdf_photo_rows(const float* vmap, const float* fint, int64
 }
 
 }  // namespace rpe
+
+// the robust rounds of the four volume terms, as kernels of their own names, and the hook that writes a level's plane of weights
+// (include/rgbd_pose_hip.h Part 3, "Robust volume terms"): behind everything whose cell, corner fetches, rows and gates they share
+#include "rpe_sdf_robust.hpp"

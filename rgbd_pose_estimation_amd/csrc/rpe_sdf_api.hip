@@ -58,18 +58,30 @@ const float* intensity_of(rpe_context* c, bool colour, int l) { return colour ? 
 // of both terms (lam: the photometric weight; geometric = 0: of the photometric rows alone) and second = the photometric cost and rows
 int sdf_round(rpe_context* c, const Field& f, const Level& lv, const float* fint, bool colour, double dist_thr, double cos_thr, int use_normals,
               float lam, int geometric, const double* pose12, double* ne, double* second) {
-  if (colour && f.map)
-    HIP_TRY(rpe::launch_icp_map_sdf_photo(lv.f[0], lv.f[1], fint, lv.n, f.M, f.g, (float)dist_thr, (float)cos_thr, use_normals, lam, geometric,
-                                          pose12, collect_target(c), c->stream));
+  // the robust weight is the context's (rpe_sdf_set_robust); kind NONE launches exactly what there was before there was one
+  const auto& W = c->sdf_robust;
+  const float gate = (float)dist_thr, cosine = (float)cos_thr, k = (float)W.k, photo_k = (float)W.photo_k;
+  const rpe::ReduceTarget rt = collect_target(c);
+  if (W.kind != RPE_ROBUST_NONE) {
+    if (colour && f.map)
+      HIP_TRY(rpe::launch_icp_map_sdf_photo_robust(lv.f[0], lv.f[1], fint, lv.n, f.M, f.g, gate, cosine, use_normals, lam, geometric, W.kind, k,
+                                                   photo_k, pose12, rt, c->stream));
+    else if (colour)
+      HIP_TRY(rpe::launch_icp_sdf_photo_robust(lv.f[0], lv.f[1], fint, lv.n, c->vol.d, c->vol.cd, f.g, gate, cosine, use_normals, lam, geometric,
+                                               W.kind, k, photo_k, pose12, rt, c->stream));
+    else if (f.map)
+      HIP_TRY(rpe::launch_icp_map_sdf_robust(lv.f[0], lv.f[1], lv.n, f.M, f.g, gate, cosine, use_normals, W.kind, k, pose12, rt, c->stream));
+    else
+      HIP_TRY(rpe::launch_icp_sdf_robust(lv.f[0], lv.f[1], lv.n, c->vol.d, f.g, gate, cosine, use_normals, W.kind, k, pose12, rt, c->stream));
+  } else if (colour && f.map)
+    HIP_TRY(rpe::launch_icp_map_sdf_photo(lv.f[0], lv.f[1], fint, lv.n, f.M, f.g, gate, cosine, use_normals, lam, geometric, pose12, rt, c->stream));
   else if (colour)
-    HIP_TRY(rpe::launch_icp_sdf_photo(lv.f[0], lv.f[1], fint, lv.n, c->vol.d, c->vol.cd, f.g, (float)dist_thr, (float)cos_thr, use_normals, lam,
-                                      geometric, pose12, collect_target(c), c->stream));
+    HIP_TRY(rpe::launch_icp_sdf_photo(lv.f[0], lv.f[1], fint, lv.n, c->vol.d, c->vol.cd, f.g, gate, cosine, use_normals, lam, geometric, pose12, rt,
+                                      c->stream));
   else if (f.map)
-    HIP_TRY(rpe::launch_icp_map_sdf(lv.f[0], lv.f[1], lv.n, f.M, f.g, (float)dist_thr, (float)cos_thr, use_normals, pose12,
-                                    collect_target(c), c->stream));
+    HIP_TRY(rpe::launch_icp_map_sdf(lv.f[0], lv.f[1], lv.n, f.M, f.g, gate, cosine, use_normals, pose12, rt, c->stream));
   else
-    HIP_TRY(rpe::launch_icp_sdf(lv.f[0], lv.f[1], lv.n, c->vol.d, f.g, (float)dist_thr, (float)cos_thr, use_normals, pose12,
-                                collect_target(c), c->stream));
+    HIP_TRY(rpe::launch_icp_sdf(lv.f[0], lv.f[1], lv.n, c->vol.d, f.g, gate, cosine, use_normals, pose12, rt, c->stream));
   int rc = wait_host(c, colour ? rpe::kNlLd : rpe::kNeLd);
   if (rc) return rc;
   round_record(c, ne);
@@ -127,6 +139,28 @@ int rows_call(rpe_context* c, const Kind& K, const int64_t* lo, const int64_t* h
   return rows_download(c, K.who, e, d_rows, lv.n, rows);
 }
 
+// the hook of the robust volume terms: the plane of weights of the level's rows under the context's setting (photo: the photometric
+// rows', scale photo_k; else the geometric rows', scale k).  Checks and their order are rows_call's
+int weights_call(rpe_context* c, const Kind& K, const int64_t* lo, const int64_t* hi, int level, const double* pose12, double dist_thr,
+                 double cos_thr, int use_normals, float* weights) {
+  session_end(c);
+  if (!c || !pose12 || !weights || level < 0 || level >= RPE_MAX_LEVELS || !(dist_thr >= 0) || !lo != !hi)
+    return fail(RPE_ERR_ARG, "%s: bad argument (level 0 .. %d, dist_thr >= 0)", K.who, RPE_MAX_LEVELS - 1);
+  int rc = ready(c, K.colour, level + 1, K.who);
+  if (rc) return rc;
+  Field f;
+  if ((rc = field_of(c, K.who, K.box, lo, hi, f))) return rc;
+  const Level lv = level_of(c, level);
+  DevBuf<float> d_w;
+  if ((rc = d_w.once(c, (size_t)lv.n * sizeof(float)))) return rc;
+  const auto& W = c->sdf_robust;
+  const hipError_t e = rpe::launch_sdf_robust_weights(lv.f[0], lv.f[1], intensity_of(c, K.colour, level), lv.n, c->vol.d,
+                                                      K.colour ? (const unsigned short*)c->vol.cd : nullptr, f.map ? &f.M : nullptr, f.g,
+                                                      (float)dist_thr, (float)cos_thr, use_normals != 0, K.colour, W.kind,
+                                                      (float)(K.colour ? W.photo_k : W.k), pose12, d_w, c->stream);
+  return rows_download(c, K.who, e, d_w, lv.n, weights, 1);
+}
+
 int normal_eq_call(rpe_context* c, const Kind& K, const int64_t* lo, const int64_t* hi, int level, const double* pose12, double dist_thr,
                    double cos_thr, int use_normals, double weight, double* out32) {
   session_end(c);
@@ -180,6 +214,35 @@ int pyramid_call(rpe_context* c, const Kind& K, const int64_t* lo, const int64_t
 }  // namespace
 
 extern "C" {
+
+// ---- the robust weight of all sixteen: the context's setting, and the hook that shows a level's weights
+static_assert(RPE_ROBUST_NONE == rpe::kRobustNone && RPE_ROBUST_HUBER == rpe::kRobustHuber && RPE_ROBUST_TUKEY == rpe::kRobustTukey,
+              "the kernels' kinds are the C ABI's");
+int rpe_sdf_set_robust(rpe_context* c, int kind, double k, double photo_k) {
+  if (!c) return fail(RPE_ERR_ARG, "null context");
+  if (kind == RPE_ROBUST_CAUCHY) return fail(RPE_ERR_ARG, "rpe_sdf_set_robust: RPE_ROBUST_CAUCHY is not a kind of the volume terms (NONE, HUBER, TUKEY)");
+  if (kind != RPE_ROBUST_NONE && kind != RPE_ROBUST_HUBER && kind != RPE_ROBUST_TUKEY)
+    return fail(RPE_ERR_ARG, "rpe_sdf_set_robust: kind %d is none of RPE_ROBUST_NONE, RPE_ROBUST_HUBER, RPE_ROBUST_TUKEY", kind);
+  if (kind == RPE_ROBUST_NONE) { c->sdf_robust = {}; return RPE_OK; }
+  if (!(std::isfinite(k) && k >= 1e-6)) return fail(RPE_ERR_ARG, "rpe_sdf_set_robust: k must be finite and >= 1e-6");
+  if (!(photo_k == 0 || (std::isfinite(photo_k) && photo_k >= 1e-6)))
+    return fail(RPE_ERR_ARG, "rpe_sdf_set_robust: photo_k must be 0 (photometric rows at weight 1) or finite and >= 1e-6");
+  c->sdf_robust.kind = kind; c->sdf_robust.k = k; c->sdf_robust.photo_k = photo_k;
+  return RPE_OK;
+}
+int rpe_sdf_robust(rpe_context* c, int* kind, double* k, double* photo_k) {
+  if (!c || !kind || !k || !photo_k) return fail(RPE_ERR_ARG, "rpe_sdf_robust: bad argument");
+  *kind = c->sdf_robust.kind; *k = c->sdf_robust.k; *photo_k = c->sdf_robust.photo_k;
+  return RPE_OK;
+}
+int rpe_sdf_robust_weights(rpe_context* c, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals, int photo,
+                           float* weights) {
+  return weights_call(c, {"rpe_sdf_robust_weights", photo != 0, false}, nullptr, nullptr, level, pose12, dist_thr, cos_thr, use_normals, weights);
+}
+int rpe_map_sdf_robust_weights(rpe_context* c, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals, int photo,
+                               const int64_t lo[3], const int64_t hi[3], float* weights) {
+  return weights_call(c, {"rpe_map_sdf_robust_weights", photo != 0, true}, lo, hi, level, pose12, dist_thr, cos_thr, use_normals, weights);
+}
 
 // ---- the volume term on the window ...
 int rpe_sdf_rows(rpe_context* c, int level, const double* pose12, double dist_thr, double cos_thr, int use_normals, float* rows) {

@@ -581,6 +581,35 @@ class DepthFrontEnd {
     rows.resize(n);
     return rows;
   }
+  // ---- the robust volume terms: a Huber or Tukey weight on the rows of icpVolume / icpMap / icpVolumeColor / icpMapColor and their
+  // pyramid forms, against depth the map does not explain -- a person, a moved chair (rpe_sdf_set_robust).  Off by default; the
+  // front end's own setting, it survives new frames, volumes and shifts.  kind: RPE_ROBUST_NONE / _HUBER / _TUKEY; k: the geometric
+  // row's scale [m]; photo_k: the photometric row's [intensity levels, before the weight; 0: those rows at weight 1]
+  struct VolumeRobust { int kind = RPE_ROBUST_NONE; double k = 0.0, photo_k = 0.0; };
+  void setVolumeRobust(int kind, double k = 0.0, double photo_k = 0.0) {
+    check(rpe_sdf_set_robust(_ctx, kind, k, photo_k), "rpe_sdf_set_robust");
+  }
+  VolumeRobust volumeRobust() const {
+    VolumeRobust r;
+    check(rpe_sdf_robust(_ctx, &r.kind, &r.k, &r.photo_k), "rpe_sdf_robust");
+    return r;
+  }
+  // the weights of a level's rows under `pose` and the setting: of the geometric rows (gates of o) or, with photo, of the photometric
+  // rows (gate o.dist_thr); NaN where the pixel has no row.  map: against the whole map inside the box (both null: the bounds)
+  std::vector<float> volumeRobustWeights(const Pose& pose, int level = 0, const IcpOptions& o = IcpOptions(), bool photo = false,
+                                         bool map = false, const int64_t* lo = nullptr, const int64_t* hi = nullptr) const {
+    double p[12]; pose12(pose, p);
+    rpe_camera k;
+    check(rpe_frame_level_camera(_ctx, level, 0, &k), "rpe_frame_level_camera");
+    std::vector<float> w((size_t)k.width * k.height);
+    if (map)
+      check(rpe_map_sdf_robust_weights(_ctx, level, p, o.dist_thr, o.cos_thr, o.use_normals ? 1 : 0, photo ? 1 : 0, lo, hi, w.data()),
+            "rpe_map_sdf_robust_weights");
+    else
+      check(rpe_sdf_robust_weights(_ctx, level, p, o.dist_thr, o.cos_thr, o.use_normals ? 1 : 0, photo ? 1 : 0, w.data()),
+            "rpe_sdf_robust_weights");
+    return w;
+  }
   // keypoints and descriptors of the frame's colour (which = RPE_FEAT_FRAME) or of the model colour (RPE_FEAT_MODEL); returns their
   // number.  A new depth, colour, model or model colour drops the side's features
   int detectFeatures(int which, const FeatureOptions& o = FeatureOptions()) {
